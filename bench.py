@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Benchmark of the AMS student hot path on MI355X (contract: see README / DESIGN.md §measurement).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times exactly K steps, writes the outputs of the last timed step when --dump-outputs is given and
+prints the JSON line; every other leg below runs only with --full.
 
 With N > 1 and no WORLD_SIZE in the environment this process only LAUNCHES: it starts N fresh children (one rank per GPU, RCCL
 rendezvous on 127.0.0.1) before making any GPU call itself, waits for them and prints rank 0's JSON line.  Under torchrun
@@ -9,8 +12,9 @@ rendezvous on 127.0.0.1) before making any GPU call itself, waits for them and p
 
 Workload (BASELINE.json configs[1]): student inference only, 512x1024 synthetic video, frames resident in HBM as uint8 when the
 timed region starts.  One step = one pass of the hot path (frozen student forward + fused upsample/argmax -> int32 label maps) over
-one batch of --batch frames per GPU.  value = frames/s over all GPUs (replicas: no collective on this path).
-Extra legs on the same JSON line (none of them is `value`):
+one batch of --batch frames per GPU.  value = frames/s over all GPUs (replicas: no collective on this path), over the K timed steps.
+Extra legs on the same JSON line with --full (none of them is `value`):
+  spread         --windows - 1 more windows of K steps after the timed ones: min / max / median frames/s
   distill        configs[2]: the 8-frame fine-tune step (BN batch statistics, backward, Adam); N > 1: weak scaling (8 frames per GPU,
                  SyncBN + one gradient all-reduce through RCCL inside the engine) and `distill_strong` = configs[4]'s shape: the
                  global 8-frame batch split N ways
@@ -45,6 +49,7 @@ CI = [0, 1, 2, 10, 11, 13]          # exp 25 (Cityscapes) class subset, referenc
 BF16_MFMA_PEAK_TF = 2500.0          # dense bf16 matrix pipe (MI355X_MICROARCH.md)
 F32_MFMA_PEAK_TF = 157.3            # exact-f32 matrix pipe (v_mfma_f32_16x16x4_f32), MI355X_MICROARCH.md
 HBM_PEAK_GBS = 8000.0               # MI355X HBM3E spec (MI355X_MICROARCH.md); ~6300 GB/s is the measured copy ceiling
+DUMP_BYTES = 48 << 20               # --dump-outputs budget: 24 of the 32 frames of a 512x1024 step
 
 
 def parse_args():
@@ -52,7 +57,10 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--windows", type=int, default=5, help="timed windows of --steps steps each; value = the median window (spread reported)")
+    ap.add_argument("--full", action="store_true", help="also run every leg beside the headline (spread, latency, hipGraph, roofline, "
+                                                         "parity, bf16, fine-tune, stream, API, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the label maps of the last timed step to DIR/labels.npy (float32)")
+    ap.add_argument("--windows", type=int, default=5, help="--full: windows of --steps steps for the spread, the timed one included")
     ap.add_argument("--settle", type=float, default=0.3, help="seconds of untimed inference before the warm-up steps (plan choice + clocks)")
     ap.add_argument("--batch", type=int, default=32, help="frames per step per GPU (throughput saturates at ~24)")
     ap.add_argument("--height", type=int, default=512)
@@ -160,6 +168,17 @@ def algorithmic_bytes(H):
     return layerwise, blockfused
 
 
+def dump_outputs(out_dir, labels):
+    """--dump-outputs: the int32 label maps [B,H,W] the timed step returned, as float32 (class indices: exact) in out_dir/labels.npy.
+    When all B frames would exceed DUMP_BYTES, a fixed sample of whole frames is written (numpy default_rng(0), ascending order)."""
+    b = labels.shape[0]
+    k = min(b, DUMP_BYTES // (4 * labels[0].numel()))
+    assert k >= 1, "one label map exceeds the --dump-outputs budget"
+    pick = np.arange(b) if k == b else np.sort(np.random.default_rng(0).choice(b, k, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "labels.npy"), labels[torch.from_numpy(pick).to(labels.device)].cpu().numpy().astype(np.float32))
+
+
 def miou_of(conf):
     from ams_amd.utils import calculate_miou
     return float(np.nanmean(calculate_miou(np.asarray(conf, dtype=np.float64), nan=True)))
@@ -228,22 +247,29 @@ def main():
         torch.cuda.synchronize(dev)
     for _ in range(args.warmup):
         eng.predict(frames)
-    # `windows` timed windows of EXACTLY --steps steps, each bracketed by barrier + synchronize on both sides and maxed over the ranks;
-    # value = the MEDIAN window (one 67 ms window is at the mercy of a clock step or a host hiccup; the spread is in the line)
-    win_s = []
-    for _w in range(max(1, args.windows)):
+    # a window of EXACTLY --steps steps, bracketed by barrier + synchronize on both sides and maxed over the ranks
+    def timed_window():
         barrier()
         t0 = time.perf_counter()
         for _ in range(args.steps):
             out = eng.predict(frames)
         barrier()
-        win_s.append(max_over_ranks(time.perf_counter() - t0))
-    elapsed = float(np.median(win_s))
+        return max_over_ranks(time.perf_counter() - t0), out
+
+    elapsed, out = timed_window()
     fps = n_gpus * B * args.steps / elapsed
-    spread = {"windows": len(win_s), "steps_per_window": args.steps, "frames_per_sec_min": round(n_gpus * B * args.steps / max(win_s), 2),
-              "frames_per_sec_max": round(n_gpus * B * args.steps / min(win_s), 2),
-              "rel_spread": round((max(win_s) - min(win_s)) / elapsed, 4), "value_is": "median window"}
     checksum = int(out.sum().item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
+    # --full: more windows of the same step for the spread (one short window is at the mercy of a clock step or a host hiccup)
+    spread = None
+    if args.full:
+        win_s = [elapsed] + [timed_window()[0] for _w in range(args.windows - 1)]
+        med = float(np.median(win_s))
+        spread = {"windows": len(win_s), "steps_per_window": args.steps, "frames_per_sec_min": round(n_gpus * B * args.steps / max(win_s), 2),
+                  "frames_per_sec_max": round(n_gpus * B * args.steps / min(win_s), 2),
+                  "frames_per_sec_median": round(n_gpus * B * args.steps / med, 2),
+                  "rel_spread": round((max(win_s) - min(win_s)) / med, 4), "value_is": "the first window"}
 
     if args.only_timed:
         if dist is not None:
@@ -256,7 +282,7 @@ def main():
     # ---- latency mode + hipGraph replay (single GPU only: they say nothing about scaling) -------------------------
     fps_b1 = graph_fps = graph_fps_b1 = None
     b1_micro = {}
-    if n_gpus == 1:
+    if args.full and n_gpus == 1:
         one = frames[:1].contiguous()
         for _ in range(3):
             eng.predict(one)
@@ -315,7 +341,7 @@ def main():
     roofline = None
     kernels = {}
     layerwise_b, blockfused_b = algorithmic_bytes(H)
-    if not args.no_profile and rank == 0:
+    if args.full and not args.no_profile and rank == 0:
         hip.check(eng.lib.ams_student_profile(eng._h, 1))
         n_prof = min(args.steps, 5)
         for _ in range(n_prof):
@@ -420,7 +446,7 @@ def main():
 
     # ---- parity leg (rank 0, N = 1): HIP vs the CPU oracle at the benchmark's own size -----------------------------------
     parity = None
-    if not args.no_parity and rank == 0 and n_gpus == 1:
+    if args.full and not args.no_parity and rank == 0 and n_gpus == 1:
         from oracle.student_torch import StudentOracle
         torch.set_num_threads(min(os.cpu_count() or 1, 32))
         nf = 2
@@ -458,7 +484,7 @@ def main():
     # ---- bf16 variant (BASELINE.json configs[1] says "bf16"; SURVEY 8 d6: "bf16 path: label mismatch fraction + mIoU delta") ------
     # NOT the headline: one bf16 part per operand in the late 1x1 layers (plain bf16 products, f32 accumulate, f32 storage)
     bf16_leg = None
-    if not args.no_bf16 and rank == 0 and n_gpus == 1:
+    if args.full and not args.no_bf16 and rank == 0 and n_gpus == 1:
         lab_ref, cm_ref, _ = eng.predict_with_metric(frames, torch.from_numpy(labels_np[:B]).to(dev))
         hl, wl = eng.lowres
         low_ref = eng.logits_lowres.view(-1, hl, wl, 32)[:B, :, :, :19].clone()
@@ -532,7 +558,7 @@ def main():
     rccl_seen = None
     TB = args.train_batch
     n_train = max(3, min(args.steps, 10))
-    if not args.no_train:
+    if args.full and not args.no_train:
         teng = StudentEngine(CI, H, 2 * H, max_batch=TB, trainable=True, device=dev)
         teng.load_variables(W0)
         tf = torch.from_numpy(frames_np[:TB]).to(dev)
@@ -614,7 +640,7 @@ def main():
 
     # ---- stream leg: configs[2] as a workload (N = 1) / configs[3] (N > 1: one video and one student pair per GPU, no collective) ----
     stream = None
-    if not args.no_stream and not args.no_train:
+    if args.full and not args.no_stream and not args.no_train:
         fps_video = 30
         secs = args.stream_seconds
         clip_f, clip_l = synth.SyntheticVideo(H, 40, CI, seed=100 + rank).clip()
@@ -688,7 +714,7 @@ def main():
 
     # ---- API-level legs: what run.py would see (reference run.py:32-39 defaults, :309-313 per-phase timing, :422-423 the per-frame loop) ----
     infer_api = distill_api = None
-    if not args.no_api and rank == 0 and n_gpus == 1:
+    if args.full and not args.no_api and rank == 0 and n_gpus == 1:
         from collections import deque
         from ams_amd.semantic_network import SemanticNetwork, FrozenGraph
         cw = np.zeros((19, 1)); cw[CI] = 1
@@ -764,7 +790,7 @@ def main():
 
     # ---- CPU baseline legs: the oracle on the host cores (rank 0, N = 1 only) --------------------------------------------------
     cpu = None
-    if not args.no_cpu and rank == 0 and n_gpus == 1:
+    if args.full and not args.no_cpu and rank == 0 and n_gpus == 1:
         from oracle.student_torch import StudentOracle
         # PyTorch-CPU oversubscribes badly on very wide hosts (256 hardware threads: 55 s per frame); 32 threads is the
         # fastest setting measured on the GPU box, and `cores` reports the threads actually used
@@ -805,7 +831,7 @@ def main():
     if rank == 0:
         result = {
             "metric": "frames/sec student infer (DeeplabV3+MobileNetV2, 512x1024) + distill-steps/sec",
-            "value": round(fps, 2), "unit": "frames/s", "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup, "settle_s": args.settle,
+            "value": round(fps, 2), "unit": "frames/s", "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup, "settle_s": args.settle, "full": args.full,
             "ms_per_step": round(1e3 * elapsed / args.steps, 4), "spread": spread, "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "f32 (2xfp16 split products)", "data": "synthetic",
             "rccl_ranks": (rccl_seen[1] if rccl_seen else (1 if dist is None else None)),

@@ -3,12 +3,13 @@
 # -> gpurun_out/r03_*  (copied to profiles/ by hand after a look)
 parts=${@:-bench infer train pmc sq}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
+out=${BENCH_OUT:-out}; mkdir -p "$out"      # the full bench line (bench.py --full)
 stats() {  # <dir> <out.csv>
   s=$(find $1 -name "*kernel_stats.csv" | head -1); [ -n "$s" ] && cp $s $2
 }
 for part in $parts; do case $part in
 bench)
-  python3 bench.py > gpurun_out/r03_bench.json 2> gpurun_out/r03_bench.err ;;
+  python3 bench.py --full > "$out/r03_bench.json" 2> "$out/r03_bench.err" ;;
 infer)
   # the ONE-stream plan (what `roofline` prices per kernel) and the plan the headline times (two parts on two streams at 32 frames)
   rm -rf gpurun_out/p3i
@@ -32,7 +33,7 @@ pmc)
   rm -rf gpurun_out/pmc_r03t
   rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_r03t/fetch -o p -- python3 tools/train_loop.py 8 512 2 1 > gpurun_out/r03_pmc_train_fetch.log 2>&1
   rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_r03t/write -o p -- python3 tools/train_loop.py 8 512 2 1 > gpurun_out/r03_pmc_train_write.log 2>&1
-  alg=$(python3 -c "import json;print(json.loads(open('gpurun_out/r03_bench.json').read().strip().splitlines()[-1])['distill']['roofline']['alg_bytes_per_step'])" 2>/dev/null)
+  alg=$(python3 -c "import json;print(json.loads(open('$out/r03_bench.json').read().strip().splitlines()[-1])['distill']['roofline']['alg_bytes_per_step'])" 2>/dev/null)
   python3 tools/pmc_train_traffic.py gpurun_out/pmc_r03t 3 gpurun_out/r03_train_pmc_traffic.json $alg
   rm -rf gpurun_out/pmc_r03t gpurun_out/pmc_r03 ;;
 sq)

@@ -2,7 +2,8 @@
 # Round artefacts on the GPU box (repo root): full bench JSON, rocprofv3 kernel-trace summary of the timed inference loop
 # and of one fine-tune leg, PMC traffic passes.  usage: bash tools/profile_round.sh <tag>   -> gpurun_out/<tag>_*
 tag=${1:-rXX}
-python3 bench.py > gpurun_out/${tag}_bench.json 2> gpurun_out/${tag}_bench.err
+out=${BENCH_OUT:-out}; mkdir -p "$out"      # the full bench line (bench.py --full)
+python3 bench.py --full > "$out/${tag}_bench.json" 2> "$out/${tag}_bench.err"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 rm -rf gpurun_out/prof_$tag
 # kernel statistics of the ONE-stream plan: the launches the bench line prices per kernel (`roofline`); the headline runs the same kernels as

@@ -6,7 +6,7 @@ for b in 32 16; do
 for f in none 2,1,0,4,4,0 2,2,0,4,4,0 2,3,0,4,4,0 2,4,0,4,4,0 2,6,0,4,4,0 2,8,0,4,4,0; do
   if [ $f = none ]; then unset AMS_XDS_FORCE; else export AMS_XDS_FORCE=$f; fi
   echo -n "B=$b force=$f  "
-  AMS_DUAL_STREAM=0 python3 bench.py --batch $b --no-train --no-stream --no-api --no-cpu --no-parity --no-bf16 --dump-layers --steps 10 --windows 1 2>&1 | grep -v "^{" | grep "xdw_stream" | python3 -c "
+  AMS_DUAL_STREAM=0 python3 bench.py --full --batch $b --no-train --no-stream --no-api --no-cpu --no-parity --no-bf16 --dump-layers --steps 10 --windows 1 2>&1 | grep -v "^{" | grep "xdw_stream" | python3 -c "
 import sys,re
 a={}
 for l in sys.stdin:

@@ -6,5 +6,5 @@ export AMS_HIP_LIB=${AMS_HIP_LIB:-$(cd "$(dirname "$0")/.." && pwd)/ams_amd/liba
 [ -f "$AMS_HIP_LIB" ] || { echo "build it first: make -C ams_amd/csrc measure"; exit 1; }
 for a in 0 1 2 3 4 8 12 16 19 28 31; do
   echo -n "abl=$a  "
-  AMS_XWR_ABL=$a AMS_DUAL_STREAM=0 python3 bench.py --no-train --no-stream --no-api --no-cpu --no-parity --no-bf16 --dump-layers --steps 5 --windows 1 2>&1 | grep -v "^{" | grep xdw_wreg | head -1
+  AMS_XWR_ABL=$a AMS_DUAL_STREAM=0 python3 bench.py --full --no-train --no-stream --no-api --no-cpu --no-parity --no-bf16 --dump-layers --steps 5 --windows 1 2>&1 | grep -v "^{" | grep xdw_wreg | head -1
 done
