@@ -141,7 +141,11 @@ int ams_student_freeze(ams_student* s, void* stream) {
             RUN(launch_split_weights_f16(s->fparams + l.d.w_off + (int64_t)l.split_k0 * l.d.cout, l.d.cout, 1, K, l.d.cout, l.Kp, l.whf_mem,
                                          l.whf_mem + (size_t)l.d.cout * l.Kp, st));
     }
-    // fp16's range: a weight of 65520 or more has hi = inf, lo = -inf -> NaN logits.  Every freeze checks the frozen weights of the
+    // fp16's range: a weight of 65520 or more has hi = inf, lo = -inf -> NaN logits.  At the other end split1_f16 keeps 22 bits only
+    // while hi and lo are normal fp16 numbers (|w| >= 2^-14); below that every part is a multiple of 2^-24 and the pair's error is up to 2^-36
+    // absolute, so a layer whose weights ALL lie far below 1 (a legal checkpoint: its BN can scale them back up) would multiply at far worse than
+    // f32 level relative to its own scale.  A layer whose largest |w| is below 2^-10 has that floor at <= 2^-26 of its largest weight: below it
+    // the layer leaves the fp16 form too (tests/test_f16_split_cpu.py derives the bounds).  Every freeze checks the frozen weights of the
     // layers that hold fp16 panels (one small launch, one 4-byte-per-layer copy, one wait on `stream`: freeze is a phase boundary, not the hot
     // path) and a layer outside the range loses its fp16 form until a later freeze finds it inside again: it runs on three bf16 parts (f32's
     // range) like the fine-tune step.  Activations are not checked: see INTEGRATION.md "Range of the fp16 product form".
@@ -152,13 +156,14 @@ int ams_student_freeze(ams_student* s, void* stream) {
             LayerRt& l = s->L[i];
             l.whf = l.whf_mem;
             if (!l.whf_mem) continue;
-            const int64_t n = i == 1 ? 27 * 32 : (int64_t)l.d.cin * l.d.cout;
-            jobs.push_back(WeightRange{s->fparams + l.d.w_off, n});
+            // the weights the fp16 panels hold (concat_projection: not the image-pooling rows, which stay f32)
+            const int64_t n = i == 1 ? 27 * 32 : (int64_t)(l.d.cin - l.split_k0) * l.d.cout;
+            jobs.push_back(WeightRange{s->fparams + l.d.w_off + (int64_t)l.split_k0 * l.d.cout, n});
             which.push_back(i);
         }
         if (!jobs.empty()) {
             std::vector<int> over(jobs.size(), 0);
-            RUN(weights_beyond(jobs, 65504.f, reinterpret_cast<int*>(s->tmp_c), over.data(), st));
+            RUN(weights_beyond(jobs, 65504.f, 0x1p-10f, reinterpret_cast<int*>(s->tmp_c), over.data(), st));
             s->f16_fallback_layers = 0;
             for (size_t k = 0; k < jobs.size(); ++k)
                 if (over[k]) { s->L[which[k]].whf = nullptr; ++s->f16_fallback_layers; }

@@ -258,9 +258,16 @@ static int forward_frozen(ams_student* s, const void* frames, int dtype, const i
             bool wrote = false;
             if (stream_ok(i + 1) && s->xsplit && (size_t)a.M * a.N <= s->xsplit_plane) {
                 // the next block streams: its expand GEMM takes this result as bf16 parts, written here once instead of being
-                // split by every channel-chunk block there
-                a.ysplit = s->xsplit; a.ysplit_plane = a.M * a.N; a.ysplit_np = s->matmul_mode == AMS_MATMUL_SPLIT_BF16_X6 ? 3 : s->matmul_mode == AMS_MATMUL_BF16 ? 1 : 2;
-                a.ysplit_fmt = s->matmul_mode == AMS_MATMUL_SPLIT_F16 ? 1 : 0;
+                // split by every channel-chunk block there.  The format is the consumer's: fp16 pairs only where that expand layer runs the
+                // fp16 form (its panels survived the freeze's range check, Cin > 32).  An expand layer moved off the fp16 form gets no parts: the
+                // streaming kernel then splits f32 `x` itself, and a 160-channel block takes the unfused path (rare; its speed does not matter).
+                const LayerRt& ln = s->L[i + 1];
+                if (s->matmul_mode != AMS_MATMUL_SPLIT_F16) {
+                    a.ysplit = s->xsplit; a.ysplit_plane = a.M * a.N; a.ysplit_np = s->matmul_mode == AMS_MATMUL_SPLIT_BF16_X6 ? 3 : s->matmul_mode == AMS_MATMUL_BF16 ? 1 : 2;
+                    a.ysplit_fmt = 0;
+                } else if (ln.whf && ln.d.cin > 32) {
+                    a.ysplit = s->xsplit; a.ysplit_plane = a.M * a.N; a.ysplit_np = 2; a.ysplit_fmt = 1;
+                }
             }
             if (s->emulate_bf16_storage && l.px_out == (int64_t)s->h * s->w) a.ysplit = nullptr;      // the parts would be those of the unrounded result
             RUN(frozen_pointwise(s, i, a, st, &wrote));

@@ -367,9 +367,11 @@ int launch_ce_loss_grad(const float* logits, int ld, int B, int h, int w, const 
 // (utils/graph_utils.py:408: loss = sum(w ce) / sum(w))
 int launch_ce_combine(int B, int h, int w, const int32_t* cls, int K, int NC, const double* loss_and_count, const float* scratch,
                       float* dlogits, int ldd, hipStream_t st, float empty_val = 0.f);
-// freeze-time range check of the fp16 product form: over_host[j] = 1 when any |w| of job j is > limit or not finite.  Synchronises `st`.
+// freeze-time range check of the fp16 product form: over_host[j] = 1 when any |w| of job j is > limit or not finite, or when no |w| of job j
+// reaches `low` (every weight so small that its fp16 parts are subnormal: split1_f16 keeps 22 bits only for normal parts).  Synchronises `st`.
 struct WeightRange { const float* w; int64_t n; };
-int weights_beyond(const std::vector<WeightRange>& jobs, float limit, int* flags_dev /*>= jobs.size() ints + the job table*/, int* over_host, hipStream_t st);
+int weights_beyond(const std::vector<WeightRange>& jobs, float limit, float low, int* flags_dev /*>= jobs.size() ints + the job table*/, int* over_host,
+                   hipStream_t st);
 int launch_l2_regularizer(const float* p, float* g, const uint8_t* mask, int64_t n, int n_vars, float coef, double* part_scratch /*256 doubles*/,
                           double* loss, hipStream_t st);
 int launch_cross_confusion(const uint8_t* a, const uint8_t* b, int64_t n, const int32_t* lut /*[256] -> subset idx or -1*/,

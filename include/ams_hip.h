@@ -175,9 +175,10 @@ int ams_cross_confusion(const ams_student* s, const uint8_t* labels_dev, int64_t
 int ams_student_train_step(ams_student* s, const void* frames_dev, int32_t frames_dtype, const uint8_t* teacher_dev,
                            int32_t batch, float lr, const uint8_t* mask_dev, double* loss_dev, void* stream);
 
-/* Range of the default product form (AMS_MATMUL_SPLIT_F16): fp16 holds |x| < 65520.  ams_student_freeze checks the frozen weights of every layer
- * that has fp16 panels; a layer with a weight beyond 65504 (or a non-finite one) runs on three bf16 parts (f32's range) until a later freeze finds
- * it inside again — *n_layers = how many layers the last freeze moved.  Activations are not checked. */
+/* Range of the default product form (AMS_MATMUL_SPLIT_F16): fp16 holds |x| < 65520, and the two-part split keeps 22 bits only while its parts
+ * are normal fp16 numbers (|x| >= 2^-14).  ams_student_freeze checks the frozen weights of every layer that has fp16 panels; a layer with a weight
+ * beyond 65504 (or a non-finite one), or whose largest |w| is below 2^-10, runs on three bf16 parts (f32's range) until a later freeze finds it
+ * inside again — *n_layers = how many layers the last freeze moved.  Activations are not checked. */
 int ams_student_f16_fallback_layers(const ams_student* s, int32_t* n_layers);
 
 /* ---- create_student_v3's remaining kwargs (utils/graph_utils.py:338-339; run.py:150 leaves all three off) -------------------------------
@@ -324,8 +325,9 @@ enum { AMS_MATMUL_F32 = 0, AMS_MATMUL_SPLIT_BF16 = 1, AMS_MATMUL_SPLIT_BF16_X6 =
                                    their own: 3 MFMAs per 32 k instead of 6, and 4 bytes per value where parts are stored instead of 6 — the
                                    depthwise result of the stride-16 blocks is handed to the project GEMM as ready-made fp16 pairs at the bytes of
                                    f32.  Per product ~3 2^-22 against 2^-24: below the f32 accumulation error of these contractions (512x1024
-                                   logits 4e-5 from the f64 oracle, as the three-part form).  Operands must lie within fp16's range (|x| < 65504:
-                                   activations and weights of O(1)); the fine-tune step keeps the three-part bf16 form (its gradients span a range
+                                   logits 4e-5 from the f64 oracle, as the three-part form).  Operands must lie within fp16's range (|x| <= 65504, and
+                                   2^-14 or more for 22 bits: activations and weights of O(1); a layer's weights outside it move that layer to
+                                   three bf16 parts at freeze, see ams_student_f16_fallback_layers); the fine-tune step keeps the three-part bf16 form (its gradients span a range
                                    fp16 cannot hold). */,
        AMS_MATMUL_BF16 = 3 /* opt-in bf16 inference variant (BASELINE.json configs[1] says "bf16"): the same late layers with ONE bf16 part per
                               operand = plain bf16 products, f32 accumulate, 1 MFMA per 32 k.  Storage stays f32 and the early blocks stay
