@@ -423,6 +423,58 @@ int ams_pack_masked_fp16(const float* params_dev, const uint8_t* mask_dev, int64
     return launch_pack_fp16(params_dev, mask_dev, n, out_half_dev, n_out_dev, scratch_dev, (hipStream_t)stream);
 }
 
+// mask section of a descriptor table, or -1 if the table does not describe contiguous masks inside the arena (reason in the error)
+static int64_t delta_mask_bytes(const ams_student* s, const ams_delta_var* vars, int32_t n_vars) {
+    if (!vars || n_vars < 1 || n_vars > AMS_DELTA_MAX_VARS) { set_error("apply_delta: %d variables (1 .. %d)", n_vars, AMS_DELTA_MAX_VARS); return -1; }
+    int64_t mask = 0;
+    for (int32_t i = 0; i < n_vars; ++i) {
+        const ams_delta_var& d = vars[i];
+        const int64_t n_region = d.region == AMS_REGION_PARAMS ? (int64_t)s->cfg.n_trainable : d.region == AMS_REGION_STATS ? (int64_t)s->cfg.n_stats : -1;
+        if (n_region < 0) { set_error("apply_delta: variable %d: region %d is neither params nor stats", i, d.region); return -1; }
+        if (d.offset < 0 || d.count < 0 || d.offset > n_region - d.count) {
+            set_error("apply_delta: variable %d: elements [%lld, +%lld) outside its region of %lld", i, (long long)d.offset, (long long)d.count,
+                      (long long)n_region);
+            return -1;
+        }
+        if (d.mask_offset != mask) {
+            set_error("apply_delta: variable %d: mask at byte %lld, the masks before it end at %lld", i, (long long)d.mask_offset, (long long)mask);
+            return -1;
+        }
+        mask += (d.count + 7) / 8;
+    }
+    return mask;
+}
+
+size_t ams_student_apply_delta_scratch(const ams_delta_var* vars_host, int32_t n_vars) {
+    if (!vars_host || n_vars < 1 || n_vars > AMS_DELTA_MAX_VARS) return 0;
+    int64_t mask = 0;
+    for (int32_t i = 0; i < n_vars; ++i) mask += vars_host[i].count > 0 ? (vars_host[i].count + 7) / 8 : 0;
+    return (size_t)(4 * (int64_t)n_vars + delta_segments(mask));
+}
+
+int ams_student_apply_delta(ams_student* s, const uint8_t* payload_dev, int64_t payload_bytes, const ams_delta_var* vars_host,
+                            int32_t n_vars, int64_t* n_applied_dev, int32_t* status_dev, int64_t* scratch_dev, size_t scratch_elems,
+                            void* stream) {
+    AMS_REQUIRE(s && n_applied_dev && status_dev && scratch_dev, "apply_delta: null pointer");
+    AMS_REQUIRE(payload_bytes >= 0 && (payload_dev || payload_bytes == 0), "apply_delta: %lld payload bytes at %p", (long long)payload_bytes,
+                (const void*)payload_dev);
+    static_assert(sizeof(ams_delta_var) == 4 * sizeof(int64_t), "ams_delta_var: four int64 words");
+    const int64_t mask_bytes = delta_mask_bytes(s, vars_host, n_vars);
+    if (mask_bytes < 0) return AMS_E_INVALID;
+    const size_t need = 4 * (size_t)n_vars + (size_t)delta_segments(mask_bytes);
+    AMS_REQUIRE(scratch_elems >= need, "apply_delta: scratch too small (need %zu int64)", need);
+    hipStream_t st = (hipStream_t)stream;
+    // the table travels from a host copy the handle keeps until the upload has read it (no synchronisation on the stream's earlier work)
+    if (s->ev_delta) AMS_CHECK_HIP(hipEventSynchronize(s->ev_delta));
+    else RUN(create_sync_event(&s->ev_delta));
+    s->delta_vars.assign(vars_host, vars_host + n_vars);
+    ams_delta_var* vars_dev = reinterpret_cast<ams_delta_var*>(scratch_dev);
+    AMS_CHECK_HIP(hipMemcpyAsync(vars_dev, s->delta_vars.data(), n_vars * sizeof(ams_delta_var), hipMemcpyHostToDevice, st));
+    AMS_CHECK_HIP(hipEventRecord(s->ev_delta, st));
+    return launch_apply_delta(payload_dev, payload_bytes, vars_dev, n_vars, mask_bytes, s->params, (int64_t)s->cfg.n_trainable, s->stats,
+                              (int64_t)s->cfg.n_stats, scratch_dev + 4 * n_vars, n_applied_dev, status_dev, st);
+}
+
 // ---- kernel-level entry points -----------------------------------------------------------------------------
 int ams_k_stem_conv(const void* frames, int32_t frames_dtype, int32_t B, int32_t H, int32_t W, const float* w, int32_t cout,
                     const float* scale, const float* shift, int32_t act, float pixel_scale, float* y, void* stream) {

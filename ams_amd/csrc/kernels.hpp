@@ -348,6 +348,11 @@ int launch_round_bf16(float* p, int64_t n, hipStream_t st);       // x <- float(
 int launch_copy(float* dst, const float* src, int64_t n, hipStream_t st);
 size_t pack_fp16_scratch(int64_t n);
 int launch_pack_fp16(const float* p, const uint8_t* mask, int64_t n, uint16_t* out, int64_t* n_out, int64_t* counts, hipStream_t st);
+// k_delta.hip: the downlink delta decoded into params / stats (ams_student_apply_delta)
+int64_t delta_segments(int64_t mask_bytes);
+int launch_apply_delta(const uint8_t* payload, int64_t payload_bytes, const ams_delta_var* vars_dev, int n_vars, int64_t mask_bytes,
+                       float* params, int64_t n_params, float* stats, int64_t n_stats, int64_t* counts, int64_t* n_applied, int32_t* status,
+                       hipStream_t st);
 
 // ---- k_head.hip : fused upsample + argmax + metrics, CE gradient, phi-score confusion --------------------
 // per_frame != 0: conf [B][K][K] and loss [B][2] (one confusion matrix / loss pair per frame) instead of the batch totals

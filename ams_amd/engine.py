@@ -134,6 +134,13 @@ class StudentEngine:
         self._in_labels = torch.zeros(self.max_batch * self.height * self.width, dtype=torch.uint8).pin_memory()
         self._in_free = {}
         self._keepalive = []
+        # edge-side model updates (apply_delta): pinned staging + device buffer of the largest payload (created on first use), the status words,
+        # and the generation a GraphedPredict checks: it moves when a re-freeze after an update may have changed the fp16 fallback set
+        self._delta_host = self._delta_dev = self._delta_scratch = None
+        self._delta_words = torch.zeros(2, dtype=torch.int64, device=self.device)           # [values applied, status (int32)]
+        self._updated_since_freeze = False
+        self._fallback_layers = 0
+        self.generation = 0
         for name, opt in _ENV_OPTIONS.items():
             if name in os.environ:
                 hip.check(self.lib.ams_student_set_option(self._h, opt, int(os.environ[name])), "ams_student_set_option(%s)" % name)
@@ -360,6 +367,58 @@ class StudentEngine:
     def freeze(self) -> None:
         """Device-side server->edge hand-off (replaces save_to_frozen_graph + reload)."""
         hip.check(self.lib.ams_student_freeze(self._h, self._stream()), "ams_student_freeze")
+        before, self._fallback_layers = self._fallback_layers, self.f16_fallback_layers()
+        if self._updated_since_freeze and (before or self._fallback_layers):
+            # the frozen weights changed with layers in the fp16 fallback before or after: a graph captured earlier may hold the wrong
+            # kernel forms (the library reports how many layers fell back, not which: any set but the empty one counts as changed)
+            self.generation += 1
+        self._updated_since_freeze = False
+
+    def f16_fallback_layers(self) -> int:
+        """layers the last freeze moved off the fp16 product form (ams_student_f16_fallback_layers)"""
+        n = C.c_int32()
+        hip.check(self.lib.ams_student_f16_fallback_layers(self._h, C.byref(n)), "ams_student_f16_fallback_layers")
+        return int(n.value)
+
+    def apply_delta(self, payload, layout) -> int:
+        """Decode a downlink delta (``SemanticNetwork.delta_payload`` bytes of ``layout``, an ``ams_amd.delta.DeltaLayout``) into the unfolded
+        variables (``params`` / ``stats``) on the device; returns the number of values written.  ``payload``: bytes / uint8 array (through a
+        pinned staging buffer) or a uint8 device tensor.  A malformed payload raises AmsHipError and changes nothing.  The frozen snapshot is
+        not touched: call ``freeze`` to serve the update.  Synchronises the stream once (the status word)."""
+        if isinstance(payload, torch.Tensor):
+            assert payload.dtype == torch.uint8 and payload.device == self.arena.device, "payload: a uint8 tensor on the engine's device"
+            dev = payload.contiguous().view(-1)
+            n = int(dev.numel())
+        else:
+            a = np.frombuffer(payload, dtype=np.uint8) if isinstance(payload, (bytes, bytearray, memoryview)) else \
+                np.ascontiguousarray(payload, dtype=np.uint8).reshape(-1)
+            n = int(a.size)
+            if n > layout.max_payload_bytes:
+                raise hip.AmsHipError("delta payload rejected: %d bytes, the %s layout holds at most %d; the model is unchanged"
+                                      % (n, layout.kind, layout.max_payload_bytes))
+            if self._delta_host is None or self._delta_host.numel() < layout.max_payload_bytes:
+                self._delta_host = torch.empty(layout.max_payload_bytes, dtype=torch.uint8).pin_memory()
+                self._delta_dev = torch.empty(layout.max_payload_bytes, dtype=torch.uint8, device=self.device)
+            np.copyto(self._delta_host[:n].numpy(), a)          # (the previous update's copy out of this buffer ended with its status read)
+            self._delta_dev[:n].copy_(self._delta_host[:n], non_blocking=True)
+            dev = self._delta_dev
+        table = layout.table()
+        need = int(self.lib.ams_student_apply_delta_scratch(table, len(table)))
+        if self._delta_scratch is None or self._delta_scratch.numel() < need:
+            self._delta_scratch = torch.empty(need, dtype=torch.int64, device=self.device)
+        words = self._delta_words.data_ptr()
+        hip.check(self.lib.ams_student_apply_delta(self._h, C.c_void_p(dev.data_ptr()) if n else None, n, table, len(table),
+                                                   C.c_void_p(words), C.c_void_p(words + 8), C.c_void_p(self._delta_scratch.data_ptr()),
+                                                   self._delta_scratch.numel(), self._stream()), "ams_student_apply_delta")
+        w = self._delta_words.cpu().numpy()
+        applied, status = int(w[0]), int(w[1:].view(np.int32)[0])
+        if status != hip.DELTA_OK:
+            why = {hip.DELTA_BAD_SIZE: "its size does not match its mask (%d mask bytes + 2 per set bit): truncated, over-long or corrupted"
+                   % layout.mask_bytes, hip.DELTA_BAD_PADDING: "a padding bit after a variable's last element is set"}.get(status, "status %d" % status)
+            raise hip.AmsHipError("delta payload rejected (%d bytes, %s layout): %s; the model is unchanged" % (n, layout.kind, why))
+        if applied:
+            self._updated_since_freeze = True
+        return applied
 
     # ------------------------------------------------------------------ compute
     def predict(self, frames, mode: int = hip.MODE_FROZEN) -> torch.Tensor:
@@ -515,6 +574,7 @@ class GraphedPredict:
         assert 0 < batch <= engine.max_batch
         self.engine, self.batch, self.mode = engine, batch, mode
         dev = engine.device
+        self.generation = engine.generation
         self.frames = torch.zeros((batch, engine.height, engine.width, 3), dtype=torch.uint8, device=dev)
         self.labels = torch.empty((batch, engine.height, engine.width), dtype=torch.int32, device=dev)
         self._run()                                   # warm-up outside capture (lazy one-time initialisations)
@@ -529,6 +589,9 @@ class GraphedPredict:
                                             C.c_void_p(self.labels.data_ptr()), e._stream()), "ams_student_predict")
 
     def __call__(self, frames) -> torch.Tensor:
+        if self.engine.generation != self.generation:
+            raise hip.AmsHipError("GraphedPredict: a model update re-froze the engine with another fp16 fallback set than at capture "
+                                  "(the graph holds the kernel forms of that time); capture a new one")
         if not isinstance(frames, torch.Tensor):
             frames = torch.from_numpy(np.ascontiguousarray(frames))
         self.frames.copy_(frames, non_blocking=True)

@@ -65,6 +65,14 @@ class StudentConfig(C.Structure):
                 ("bn_eps_frozen", C.c_float), ("pixel_scale", C.c_float)]
 
 
+class DeltaVar(C.Structure):
+    """ams_delta_var: one variable of a downlink delta's layout (ams_amd/delta.py builds the table)."""
+    _fields_ = [("region", C.c_int32), ("reserved", C.c_int32), ("offset", C.c_int64), ("count", C.c_int64), ("mask_offset", C.c_int64)]
+
+
+DELTA_OK, DELTA_BAD_SIZE, DELTA_BAD_PADDING = 0, 1, 2
+DELTA_MAX_VARS = 1024
+
 ALLREDUCE_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int32)
 
 _vp, _i32, _i64, _f32, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
@@ -106,6 +114,8 @@ SIGNATURES = {
     "ams_student_set_adam_step": (C.c_int, [_vp, _i64]),
     "ams_pack_masked_fp16": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
     "ams_pack_masked_fp16_scratch": (_sz, [_i64]),
+    "ams_student_apply_delta": (C.c_int, [_vp, _vp, _i64, C.POINTER(DeltaVar), _i32, _vp, _vp, _vp, _sz, _vp]),
+    "ams_student_apply_delta_scratch": (_sz, [C.POINTER(DeltaVar), _i32]),
     "ams_k_stem_conv": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _f32, _vp, _vp]),
     "ams_k_depthwise3x3": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp]),
     "ams_k_pointwise": (C.c_int, [_vp, _i64, _i32, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp]),

@@ -40,7 +40,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 from .exp_configs import class_weights, coco_class_converter, is_coco, test_length
-from .semantic_network import SemanticNetwork
+from .semantic_network import FrozenGraph, SemanticNetwork
 from .synth import SyntheticVideo
 from .utils import calculate_miou, choose_frames, resize_linear, resize_nearest, string_class_iou
 
@@ -86,6 +86,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--sampling", default="reference", choices=["reference", "per_second"],
                    help="uplink sampling: 'reference' = run.py:115/175 (send_rate = send_period / fps is the fraction of the bucket "
                         "that is uploaded), 'per_second' = send_rate counts frames per second (fps / send_period)")
+    p.add_argument("--edge_from_delta", action="store_true",
+                   help="score the edge model the downlink payload produces (extra flag): the server also writes each event's raw payload "
+                        "(<label>_<second>_delta.bin), and the edge keeps its network and applies that payload to the initial model "
+                        "(--no_restore: to its previous model) on the device instead of reloading the server's full f32 model")
     p.add_argument("--horizon_k1s", default="16,32,64,128,256,512", help="horizon mode: training-window lengths in seconds (reference: hard-coded)")
     p.add_argument("--horizon_k2", type=int, default=256, help="horizon mode: evaluation window in seconds (reference: 256)")
     p.add_argument("--horizon_points", type=int, default=3, help="horizon mode: number of evaluation points (reference: 3)")
@@ -311,6 +315,10 @@ def train_model(ctx: Context, train_start, train_end, sampling_period, gpu_id, r
                 f.write(payload)
             with gzip.open(save_dir + '_mask.dat.gz', 'wb', compresslevel=9) as f:
                 f.write(payload)
+            if getattr(FLAGS, "edge_from_delta", False):
+                # _mask.dat above carries the PREVIOUS event's label (as in the reference): the edge finds this event's payload by its own time
+                with open(ctx.save_dir(run_label + "_%d" % second) + "_delta.bin", 'wb') as f:
+                    f.write(payload)
             curr_update = os.path.getsize(save_dir + '_mask.dat.gz') * 8
             down_bw_per_period.append(curr_update)
             update_count += 1
@@ -350,6 +358,9 @@ def infer_output(ctx: Context, inf_start, inf_end, gpu_id, run_label, gt_path, e
     t_infer = 0.0
     depth = int(getattr(FLAGS, "edge_pipeline", 1))
     in_flight = deque()               # tickets of submitted frames (depth >= 2), oldest first
+    from_delta = bool(getattr(FLAGS, "edge_from_delta", False))
+    base_variables = None             # --edge_from_delta: the model the edge loaded first (what the server restores before each event)
+    update_s = []                     # --edge_from_delta: host wall time of each edge update (payload in -> model re-frozen)
 
     def record(result, n_done):
         _labels, conf_mat_, _, miou_, loss_ = result
@@ -372,11 +383,25 @@ def infer_output(ctx: Context, inf_start, inf_end, gpu_id, run_label, gt_path, e
                 done += 1
                 record(res, done)
             save_dir = ctx.save_dir(run_label + "_%d" % (i // fps))
-            if semantic_network is not None:
-                semantic_network.close_model()
-            kw = {"pipeline_depth": depth} if depth > 1 else {}
-            semantic_network = ctx.network_cls(meta_dir=save_dir + "_final", class_weights_exp=class_weights(exp_num),
-                                               height=FLAGS.height, gpu_id=gpu_id, mem_frac=1, frozen=True, **kw)
+            if from_delta and semantic_network is not None:
+                # the edge keeps its network and applies what the downlink carried; an event that published the current model unchanged
+                # (empty replay memory) sent no payload, and the edge keeps its model
+                if os.path.exists(save_dir + "_delta.bin"):
+                    with open(save_dir + "_delta.bin", "rb") as f:
+                        payload = f.read()
+                    t0 = time.time()
+                    semantic_network.apply_delta(payload, FLAGS.train_strategy, None if FLAGS.no_restore else base_variables)
+                    update_s.append(time.time() - t0)
+            else:
+                if semantic_network is not None:
+                    semantic_network.close_model()
+                kw = {"pipeline_depth": depth} if depth > 1 else {}
+                if from_delta:
+                    with open(save_dir + "_final.pb", "rb") as f:
+                        kw["frozen_graph"] = FrozenGraph.ParseFromString(f.read())
+                    base_variables = kw["frozen_graph"].variables
+                semantic_network = ctx.network_cls(meta_dir=save_dir + "_final", class_weights_exp=class_weights(exp_num),
+                                                   height=FLAGS.height, gpu_id=gpu_id, mem_frac=1, frozen=True, **kw)
         frame, gt_frame = _to_size(*ctx.source.read(i), ctx.size, ctx.ingest)
         t0 = time.time()
         if depth > 1:
@@ -403,7 +428,13 @@ def infer_output(ctx: Context, inf_start, inf_end, gpu_id, run_label, gt_path, e
     if semantic_network is not None:
         semantic_network.close_model()
     n = max(1, inf_end_frame - inf_start * fps)
-    return {"frames": n, "frames_per_sec": n / max(t_infer, 1e-9), "mean_miou": float(np.nanmean(miou_s))}
+    summary = {"frames": n, "frames_per_sec": n / max(t_infer, 1e-9), "mean_miou": float(np.nanmean(miou_s))}
+    if from_delta:
+        summary["edge_updates"] = len(update_s)
+        summary["edge_update_ms"] = 1000.0 * float(np.mean(update_s)) if update_s else float("nan")
+        print_process("%d edge updates from the downlink payload, %.2f ms each (mean host wall time)"
+                      % (summary["edge_updates"], summary["edge_update_ms"]), inf_end / 1.0)
+    return summary
 
 
 def event_times(flags, length: int) -> List[int]:
@@ -418,6 +449,8 @@ def main(argv: Optional[List[str]] = None, network_cls=None):
     assert not flags.enable_ATR or flags.enable_ASR, 'ASR must be enabled for ATR to work'
     assert not flags.enable_ASR or flags.mode == 'simple', 'ASR can only be used in simple mode'
     assert not flags.enable_ATR or flags.mode == 'simple', 'ATR can only be used in simple mode'
+    assert not flags.edge_from_delta or flags.mode in ('simple', 'early', 'pretrained'), \
+        '--edge_from_delta needs an edge that starts from the server\'s initial model (simple, early or pretrained mode)'
     os.makedirs(flags.output_dir, exist_ok=True)
     ctx = Context(flags, network_cls)
     vid_num, length = ctx.vid_num, ctx.length

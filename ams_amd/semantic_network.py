@@ -26,6 +26,7 @@ import numpy as np
 import torch
 
 from . import coord_masks, hip
+from .delta import delta_layout
 from .engine import StudentEngine
 from .utils import calculate_miou, colormap, mini_batch
 from .weights import load_npy
@@ -476,6 +477,39 @@ class SemanticNetwork(object):
                 assert p_.shape == m_.shape
                 payload += p_[m_].astype(np.float16).tobytes()
         return bytes(payload)
+
+    def apply_delta(self, payload, train_strategy, base_variables=None) -> int:
+        """The edge half of the downlink (an addition: the reference's edge reloads the server's full model, run.py:401-411): decode a
+        ``delta_payload`` of a server running ``train_strategy`` into this network's variables on the device and, on a frozen instance,
+        re-freeze (which repeats the fp16 range check).  ``base_variables`` (a {name: array} dict, e.g. the initial model's) are loaded
+        first, so that the update lands on the model the server started from; None applies it to the current model.  Returns the number of
+        values applied.  A malformed payload raises AmsHipError and leaves the model as it was (including a base loaded for it).
+
+        Frames submitted with ``predict_with_metric_async`` before this call are answered by the old model, frames submitted after it by the
+        new one: the queued ones are launched and fetched first."""
+        layout = delta_layout(self.engine.spec, train_strategy)
+        with self.process_lock:
+            if self.frozen:
+                if self._queued:
+                    self._launch_queued()
+                self._fetch_pending()
+            eng = self.engine
+            saved = None
+            if base_variables is not None:
+                saved = (eng.params.clone(), eng.stats.clone())
+                eng.load_variables(base_variables)
+                eng._updated_since_freeze = True
+            try:
+                n = eng.apply_delta(payload, layout)
+            except hip.AmsHipError:
+                if saved is not None:
+                    eng.params.copy_(saved[0])
+                    eng.stats.copy_(saved[1])
+                    eng._updated_since_freeze = False
+                raise
+            if self.frozen:
+                eng.freeze()
+        return n
 
     def get_train_mask(self, train_strategy):
         """Coordinate-descent masks (SemanticNetwork.py:302-669): dict variable name -> bool array, or None."""

@@ -355,6 +355,40 @@ int ams_pack_masked_fp16(const float* params_dev, const uint8_t* mask_dev, int64
 /* int64 elements of caller-owned device scratch the call above needs (segment counts; nothing is allocated inside) */
 size_t ams_pack_masked_fp16_scratch(int64_t n);
 
+/* ---- the same delta applied on the edge: replaces reading the payload of run.py:316-328 and the model reload of run.py:401-411 -----------
+ * One descriptor per variable of the payload's layout, in layout order: where its elements live (AMS_REGION_PARAMS or AMS_REGION_STATS,
+ * element offset, element count) and where its packed mask bits start in the payload.  Masks are contiguous: mask_offset of the first
+ * variable is 0 and each next one starts ceil(count / 8) bytes later; their sum is the mask section, the fp16 values follow it. */
+typedef struct ams_delta_var {
+    int32_t region;          /* AMS_REGION_PARAMS or AMS_REGION_STATS */
+    int32_t reserved;        /* 0 */
+    int64_t offset;          /* first element inside the region */
+    int64_t count;           /* elements */
+    int64_t mask_offset;     /* byte offset of the variable's mask bits in the payload */
+} ams_delta_var;
+
+#define AMS_DELTA_MAX_VARS 1024
+
+/* status word written by ams_student_apply_delta */
+enum {
+    AMS_DELTA_OK = 0,
+    AMS_DELTA_BAD_SIZE = 1,      /* payload bytes != mask bytes + 2 x set mask bits (truncated, over-long or a corrupted mask) */
+    AMS_DELTA_BAD_PADDING = 2    /* a padding bit after a variable's last element is set */
+};
+
+/* Decodes payload_dev (payload_bytes device bytes, any alignment) into the student's unfolded variables: every masked element gets
+ * float(its fp16 value), bit-exactly; every other element keeps its bits.  The payload is validated on the device first and a payload that
+ * fails writes nothing: *status_dev (int32) = AMS_DELTA_*, *n_applied_dev (int64) = values written (0 unless AMS_DELTA_OK).  Neither is
+ * read back here: the caller reads them once the stream has run.  The frozen snapshot is not touched: ams_student_freeze re-freezes.
+ * vars_host (n_vars <= AMS_DELTA_MAX_VARS) is checked against the arena on the host; scratch_dev holds
+ * ams_student_apply_delta_scratch(vars_host, n_vars) int64.  Three launches on `stream` (delta_count_kernel, delta_scan_kernel,
+ * delta_apply_kernel) after a copy of the table; no allocation, no synchronisation. */
+int ams_student_apply_delta(ams_student* s, const uint8_t* payload_dev, int64_t payload_bytes, const ams_delta_var* vars_host,
+                            int32_t n_vars, int64_t* n_applied_dev, int32_t* status_dev, int64_t* scratch_dev, size_t scratch_elems,
+                            void* stream);
+/* int64 elements of device scratch ams_student_apply_delta needs for this table (0 if the table is malformed) */
+size_t ams_student_apply_delta_scratch(const ams_delta_var* vars_host, int32_t n_vars);
+
 /* =====================================================================================================
  * Kernel-level entry points.  Same kernels the engine launches, exposed one by one so that tests/ can
  * check each against the oracle (SURVEY.md §4 test pyramid level 1).  x/y/... are device pointers.
