@@ -259,7 +259,6 @@ static inline int sync_doubles(const SyncCtx* sc, double* p, size_t n, hipStream
 // ---- engine_forward.hip ----------------------------------------------------------------------------------
 bool split_pays(const PwArgs& a);
 int live_pointwise(ams_student* s, const PwArgs& a, hipStream_t st);
-int frozen_pointwise(ams_student* s, int layer, PwArgs a, hipStream_t st, bool* wrote_parts = nullptr, bool force_split = false);
 bool train_recompute_block(const ams_student* s, int i);
 bool dw_fused_train(const ams_student* s, int i, int B);
 bool stem_fused_train(const ams_student* s);

@@ -32,6 +32,20 @@ static int bn_backward(ams_student* s, LayerRt& l, const float* da, int64_t M_lo
     return AMS_OK;
 }
 
+// The BN-backward coefficients (cA, cB, cC) and dgamma / dbeta of layer l from the partial rows [rows][stride] a kernel left (sum dy | sum dy xhat
+// first in each row): one launch on a single rank, through the cross-rank sum of l.bsums otherwise
+static int bn_bwd_from_partials(ams_student* s, LayerRt& l, const float* part, int rows, int64_t stride, double n_global, const SyncCtx* sc,
+                                hipStream_t st) {
+    const float* gamma = s->params + l.d.gamma_off;
+    float *dgamma = s->grads + l.d.gamma_off, *dbeta = s->grads + l.d.beta_off;
+    if (!sc || !sc->cb)
+        return launch_bn_bwd_finalize_partials(part, rows, stride, l.d.cout, l.bsums, n_global, gamma, l.mean, l.rstd, l.cA, l.cB, l.cC, dgamma, dbeta, st);
+    RUN(launch_partials_to_sums(part, rows, stride, l.d.cout, l.bsums, st));
+    RUN(launch_bn_param_grads(l.bsums, l.d.cout, dgamma, dbeta, st));
+    RUN(sync_doubles(sc, l.bsums, 2 * (size_t)l.d.cout, st));
+    return launch_bn_bwd_coef(l.bsums, n_global, l.d.cout, gamma, l.mean, l.rstd, l.cA, l.cB, l.cC, nullptr, nullptr, st);
+}
+
 // xa: the layer whose BN + activation the x operand still needs (x = its raw output z): WgArgs x_mode 1
 static int pw_wgrad(ams_student* s, const float* x, int ldx, int K, const float* dy, int ldy, int N, int64_t M, float* dw,
                     hipStream_t st, float* scratch = nullptr, const LayerRt* xa = nullptr) {
@@ -194,16 +208,7 @@ int backward(ams_student* s, const void* frames, int dtype, const uint8_t* teach
         if (fused_rows > 0) {
             // the depthwise input-gradient kernel of the layer behind this one already applied the activation's derivative and left the
             // partial sums (launch_depthwise_dgrad_bn): second stage of the reduction, then dz = A dy + B + C z
-            const double n_l = (double)global_B * l.px_out;
-            if (!sc || !sc->cb) {
-                RUN(launch_bn_bwd_finalize_partials(fused_buf, fused_rows, fused_stride, l.d.cout, l.bsums, n_l, P + l.d.gamma_off, l.mean,
-                                                    l.rstd, l.cA, l.cB, l.cC, G + l.d.gamma_off, G + l.d.beta_off, st));
-            } else {
-                RUN(launch_partials_to_sums(fused_buf, fused_rows, fused_stride, l.d.cout, l.bsums, st));
-                RUN(launch_bn_param_grads(l.bsums, l.d.cout, G + l.d.gamma_off, G + l.d.beta_off, st));
-                RUN(sync_doubles(sc, l.bsums, 2 * (size_t)l.d.cout, st));
-                RUN(launch_bn_bwd_coef(l.bsums, n_l, l.d.cout, P + l.d.gamma_off, l.mean, l.rstd, l.cA, l.cB, l.cC, nullptr, nullptr, st));
-            }
+            RUN(bn_bwd_from_partials(s, l, fused_buf, fused_rows, fused_stride, (double)global_B * l.px_out, sc, st));
             // the depthwise layer's weight gradient came with the same rows (taps behind the two sums)
             if (fused_dw && !(fused_buf != s->scratch &&
                               deferred.add(fused_buf + 2 * (int64_t)l.d.cout, fused_rows, 9 * (int64_t)l.d.cout, G + s->L[i + 1].d.w_off, fused_stride)))
@@ -232,16 +237,7 @@ int backward(ams_student* s, const void* frames, int dtype, const uint8_t* teach
             RUNK(i, 4.0 * ((double)B * (le.px_in * le.d.cin + l.px_out * l.d.cout)),
                  launch_xdw_bwd_reduce(x, B, le.Hin, le.Win, le.d.cin, P + le.d.w_off, le.d.cout, le.scale, le.shift, le.mean, le.rstd, le.d.act,
                                        P + l.d.w_off, l.d.stride, dz, s->xt_scratch, &rows, &stride, st));
-            const double n_e = (double)global_B * le.px_out;
-            if (!sc || !sc->cb) {
-                RUN(launch_bn_bwd_finalize_partials(s->xt_scratch, rows, stride, le.d.cout, le.bsums, n_e, P + le.d.gamma_off, le.mean, le.rstd,
-                                                    le.cA, le.cB, le.cC, G + le.d.gamma_off, G + le.d.beta_off, st));
-            } else {
-                RUN(launch_partials_to_sums(s->xt_scratch, rows, stride, le.d.cout, le.bsums, st));
-                RUN(launch_bn_param_grads(le.bsums, le.d.cout, G + le.d.gamma_off, G + le.d.beta_off, st));
-                RUN(sync_doubles(sc, le.bsums, 2 * (size_t)le.d.cout, st));
-                RUN(launch_bn_bwd_coef(le.bsums, n_e, le.d.cout, P + le.d.gamma_off, le.mean, le.rstd, le.cA, le.cB, le.cC, nullptr, nullptr, st));
-            }
+            RUN(bn_bwd_from_partials(s, le, s->xt_scratch, rows, stride, (double)global_B * le.px_out, sc, st));
             const float* skip = (i + 1 <= s->n_backbone && s->L[i + 1].d.residual_from == i - 2) ? s->L[i + 1].da : nullptr;
             // the block input is the previous block's project layer (BN, no activation): the first half of ITS BN backward rides on the
             // dx pass (sum dx, sum dx xhat as one partial row per block), the separate pass over (dx, z) disappears
@@ -290,16 +286,7 @@ int backward(ams_student* s, const void* frames, int dtype, const uint8_t* teach
             RUNK(i, 4.0 * B * l.px_out * l.d.cout,
                  launch_xdw_bwd_reduce_stem(frames, dtype, B, c.height, c.width, c.pixel_scale, P + le.d.w_off, le.scale, le.shift, le.mean, le.rstd,
                                             le.d.act, P + l.d.w_off, dz, s->xt_scratch, &rows, &stride, st));
-            const double n_e = (double)global_B * le.px_out;
-            if (!sc || !sc->cb) {
-                RUN(launch_bn_bwd_finalize_partials(s->xt_scratch, rows, stride, le.d.cout, le.bsums, n_e, P + le.d.gamma_off, le.mean, le.rstd,
-                                                    le.cA, le.cB, le.cC, G + le.d.gamma_off, G + le.d.beta_off, st));
-            } else {
-                RUN(launch_partials_to_sums(s->xt_scratch, rows, stride, le.d.cout, le.bsums, st));
-                RUN(launch_bn_param_grads(le.bsums, le.d.cout, G + le.d.gamma_off, G + le.d.beta_off, st));
-                RUN(sync_doubles(sc, le.bsums, 2 * (size_t)le.d.cout, st));
-                RUN(launch_bn_bwd_coef(le.bsums, n_e, le.d.cout, P + le.d.gamma_off, le.mean, le.rstd, le.cA, le.cB, le.cC, nullptr, nullptr, st));
-            }
+            RUN(bn_bwd_from_partials(s, le, s->xt_scratch, rows, stride, (double)global_B * le.px_out, sc, st));
             float* reduced = s->xt_scratch + (int64_t)rows * stride;
             RUN(launch_reduce_splits(s->xt_scratch + 2 * 32, rows, 9 * 32, G + l.d.w_off, st, stride));
             RUN(launch_reduce_splits(s->xt_scratch + 11 * 32, rows, 32 * 32 + 32 * 32 + 32, reduced, st, stride));

@@ -42,309 +42,420 @@ int live_pointwise(ams_student* s, const PwArgs& a, hipStream_t st) {
     return launch_pointwise_split3(a, p0, p0 + plane, p0 + 2 * plane, Kp, st);
 }
 
-// frozen 1x1 layer: late layers (few rows, wide K/N: matrix-pipe bound) go through the split-bf16 kernel
-int frozen_pointwise(ams_student* s, int layer, PwArgs a, hipStream_t st, bool* wrote_parts, bool force_split) {
-    const LayerRt& l = s->L[layer];
-    const bool split = s->matmul_mode != AMS_MATMUL_F32 && l.whi && (split_pays(a) || (force_split && a.K % 8 == 0 && a.K >= 32));
-    // the bf16 parts of the result (a.ysplit) exist only when the split kernel runs with a vector epilogue
-    const bool parts = split && a.ysplit && pointwise_split_writes_parts(a);
-    if (!parts) a.ysplit = nullptr;
-    if (wrote_parts) *wrote_parts = parts;
-    if (split && s->matmul_mode == AMS_MATMUL_SPLIT_F16 && l.whf && pointwise_f16_applies(a))
-        RUNK(layer, pw_bytes(a), launch_pointwise_split_f16(a, l.whf, (int64_t)l.d.cout * l.Kp, l.Kp, st));
-    else if (a.x_fmt != 0) { set_error("frozen_pointwise: layer %d was handed fp16 pairs but does not run the fp16 product", layer); return AMS_E_STATE; }
-    else if (split && s->matmul_mode == AMS_MATMUL_SPLIT_F16) RUNK(layer, pw_bytes(a), launch_pointwise_split3(a, l.whi, l.wlo, l.wlo3, l.Kp, st));
-    else if (split && s->matmul_mode == AMS_MATMUL_SPLIT_BF16_X6) RUNK(layer, pw_bytes(a), launch_pointwise_split3(a, l.whi, l.wlo, l.wlo3, l.Kp, st));
-    else if (split && s->matmul_mode == AMS_MATMUL_BF16) RUNK(layer, pw_bytes(a), launch_pointwise_split1(a, l.whi, l.Kp, st));
-    else if (split) RUNK(layer, pw_bytes(a), launch_pointwise_split(a, l.whi, l.wlo, l.Kp, st));
-    else RUNK(layer, pw_bytes(a), launch_pointwise(a, st));
-    return AMS_OK;
-}
-
 // =======================================================================================================
 // frozen inference (BN folded; what the edge device runs)
 // =======================================================================================================
-static int forward_frozen(ams_student* s, const void* frames, int dtype, const int Bfull, hipStream_t st) {
+// The buffers one pass may use: the whole student's, or frames b0 .. b0 + bp - 1 of each (all are sized for max_batch frames).
+struct FrozenView {
+    float* act[4];                             // ping-pong pool
+    uint16_t* xsplit; size_t xsplit_plane;     // parts of a stride-16 block's input, and the elements one part plane holds here
+    float *pooled, *pool_a, *img_bias, *logits, *scratch;
+    const void* frames; int B;                 // the frames of the pass
+    int reserved;                              // act[reserved] holds the late section's input for ALL sub-batches: never a target (-1: none)
+};
+static FrozenView view_whole(const ams_student* s, const void* frames, int B) {
+    return {{s->act[0], s->act[1], s->act[2], s->act[3]}, s->xsplit, s->xsplit_plane, s->pooled, s->pool_a, s->img_bias, s->logits, s->scratch, frames, B, -1};
+}
+// frames b0 .. b0 + bp - 1 of the late section: the same activation buffers for every sub-batch (the input of all of them in
+// act[input_i]), the head's outputs in their place
+static FrozenView view_late(const ams_student* s, FrozenView v, int b0, int bp, int input_i) {
+    v.pooled += (size_t)b0 * s->L[s->iPool].d.cin;
+    v.pool_a += (size_t)b0 * s->L[s->iPool].d.cout;
+    v.img_bias += (size_t)b0 * s->L[s->iProj].d.cout;
+    v.logits += (size_t)b0 * s->h * s->w * 32;
+    v.B = bp; v.reserved = input_i;
+    return v;
+}
+// frames b0 .. b0 + bp - 1 of `frames` in their own slice of every buffer (one part of forward_frozen_dual)
+static FrozenView view_slice(const ams_student* s, const void* frames, int dtype, int b0, int bp) {
     const ams_student_config& c = s->cfg;
-    int B = Bfull;                             // frames of the current pass: the whole batch, or one sub-batch of the late section
-    const float* P = s->fparams;
-    float* cur = s->act[0];
-    int cur_i = 0;
-    int i = 2;
-    {
-        LayerRt& l = s->L[1];
-        LayerRt& ld = s->L[2];
-        LayerRt& lj = s->L[3];
-        const double in_bytes = (double)B * c.height * c.width * 3 * (dtype == AMS_DT_U8 ? 1 : 4);
-        if (s->fuse_first_block && s->n_backbone >= 3 && l.d.cout == 32 && ld.d.role == AMS_ROLE_DEPTHWISE && ld.d.cin == 32 &&
-            ld.d.stride == 1 && ld.d.rate == 1 && lj.d.role == AMS_ROLE_PROJECT && lj.d.cin == 32 && lj.d.cout == 16 &&
-            !lj.d.residual_from) {
-            // stem + depthwise + project of the first block in one kernel: the 32-channel half-resolution tensor stays in LDS
-            const double bytes = in_bytes + 4.0 * B * lj.px_out * lj.d.cout + 4.0 * (27 * 32 + 9 * 32 + 32 * 16);
-            if (s->fuse_first_block >= 2)
-                RUNK(3, bytes, launch_first_block_tiles(frames, dtype, B, c.height, c.width, c.pixel_scale, P + l.d.w_off, l.fscale, l.fshift,
-                                                        l.d.act, P + ld.d.w_off, ld.fscale, ld.fshift, ld.d.act, P + lj.d.w_off, lj.fscale,
-                                                        lj.fshift, lj.d.act, cur, st, l.blk_vecs));
-            else {
-                const bool h16 = s->block_x6 && s->matmul_mode == AMS_MATMUL_SPLIT_F16 && l.whf && lj.whf && lj.Kp == 32;
-                const bool x6 = !h16 && s->block_x6 && s->matmul_mode != AMS_MATMUL_F32 && l.whi;
-                RUNK(3, bytes, launch_first_block(frames, dtype, B, c.height, c.width, c.pixel_scale, P + l.d.w_off, l.fscale, l.fshift,
-                                                  l.d.act, P + ld.d.w_off, ld.fscale, ld.fshift, ld.d.act, P + lj.d.w_off, lj.fscale,
-                                                  lj.fshift, lj.d.act, cur, st, x6 ? l.whi : nullptr, 32 * 32, h16 ? l.whf : nullptr, 32 * 32,
-                                                  h16 ? lj.whf : nullptr, (int64_t)lj.d.cout * lj.Kp));
-            }
-            i = 4;
-        } else {
-            const double bytes = in_bytes + 4.0 * B * l.px_out * l.d.cout;
-            RUNK(1, bytes, launch_stem(frames, dtype, B, c.height, c.width, P + l.d.w_off, l.d.cout, l.fscale, l.fshift, l.d.act,
-                                       c.pixel_scale, cur, st));
+    FrozenView v = view_late(s, view_whole(s, (const char*)frames + (size_t)b0 * c.height * c.width * 3 * (dtype == AMS_DT_U8 ? 1 : 4), bp), b0, bp, -1);
+    for (int k = 0; k < 4; ++k) v.act[k] += (size_t)b0 * (s->act_elems / c.max_batch);
+    if (v.xsplit) { v.xsplit += 3 * (s->xsplit_plane / c.max_batch) * b0; v.xsplit_plane = (s->xsplit_plane / c.max_batch) * bp; }
+    v.scratch += image_colsum_scratch(b0, s->L[s->iPool].d.cin);
+    return v;
+}
+
+// bf16 / fp16 parts of a block input in FrozenView::xsplit, as the project GEMM in front of a streamed block leaves them
+struct PartsFmt { int np = 0, fmt = 0; };      // np 0: none; PwArgs::ysplit_np / ysplit_fmt
+// where a pass stands: the next layer, its input (in act[cur_i]) and what else exists of that input
+struct Cursor { int i; const float* cur; int cur_i; PartsFmt parts; };
+
+static int other(const FrozenView& v, int avoid0, int avoid1) {
+    for (int k = 0; k < 4; ++k) if (k != avoid0 && k != avoid1 && k != v.reserved) return k;
+    return -1;
+}
+
+// ---- the plan of one inverted-residual block: decided before any launch of that block, by plan_block alone ----------------------------
+enum PwForm { PW_F32, PW_BF16_1, PW_BF16_2, PW_BF16_3, PW_F16 };      // products of a 1x1 layer: exact f32 | 1, 2, 3 bf16 parts | two fp16 parts
+enum BlockForm { BLOCK_WHOLE,                  // k_block.hip
+                 BLOCK_TILED,                  // k_expand_dw.hip, then the project GEMM
+                 BLOCK_STREAM, BLOCK_WREG,     // k_xdw_stream.hip | k_xdw_wreg.hip, then the project GEMM
+                 BLOCK_LAYERS };               // layer by layer
+struct BlockPlan {
+    BlockForm form = BLOCK_LAYERS;
+    bool expand = false;                       // the block opens with an expand layer (the first block does not)
+    bool h16 = false, x6 = false;              // whole block: expand + project on fp16 parts | expand on three bf16 parts
+    int np = 0; const uint16_t* wparts = nullptr; int64_t wplane = 0;      // streamed: the expand layer's product form and panels
+    PartsFmt in;                               // streamed: the block input also comes as parts
+    PwForm expand_form = PW_F32;               // layer by layer
+    bool dw_project = false;                   // layer by layer: depthwise + project as launch_dw_project
+    bool d_h2i = false;                        // the depthwise result reaches the project GEMM as fp16 pairs (PwArgs::x_fmt 1)
+    PwForm project_form = PW_F32;
+    PartsFmt out;                              // what the project GEMM leaves in xsplit for the next block
+};
+
+// arguments of the backbone's 1x1 layer `layer` over B frames; `res`: the block input, where the layer adds it.  The planner asks with
+// null tensors: the kernel choice depends on the shape and on whether a residual is added, not on where anything lies
+static PwArgs layer_args(const ams_student* s, int layer, int B, const float* x, float* y, const float* res) {
+    const LayerRt& l = s->L[layer];
+    PwArgs a = pw_args(x, (int64_t)B * l.px_in, l.d.cin, l.d.cin, s->fparams + l.d.w_off, l.d.cout, y, l.d.cout);
+    a.scale = l.fscale; a.shift = l.fshift; a.act = l.d.act;
+    if (l.d.role == AMS_ROLE_PROJECT && l.d.residual_from) { a.res = res; a.ldr = l.d.cout; }
+    return a;
+}
+
+// frozen 1x1 layer: late layers (few rows, wide K/N: matrix-pipe bound) go through the split kernels, in the matmul mode's form; a layer
+// whose fp16 panels did not survive the freeze's range check runs three bf16 parts.  `streamable`: see plan_block
+static PwForm pointwise_form(const ams_student* s, int layer, const PwArgs& a, bool streamable) {
+    const LayerRt& l = s->L[layer];
+    if (s->matmul_mode == AMS_MATMUL_F32 || !l.whi || !(split_pays(a) || (streamable && a.K % 8 == 0 && a.K >= 32))) return PW_F32;
+    switch (s->matmul_mode) {
+        case AMS_MATMUL_SPLIT_F16: return l.whf && pointwise_f16_applies(a) ? PW_F16 : PW_BF16_3;
+        case AMS_MATMUL_SPLIT_BF16_X6: return PW_BF16_3;
+        case AMS_MATMUL_BF16: return PW_BF16_1;
+        default: return PW_BF16_2;
+    }
+}
+
+// layer k starts a block whose expand + depthwise run as the streaming kernel (stride-16 blocks, split-bf16 modes, a few
+// frames: below that the launch cannot fill the chip)
+static bool stream_ok(const ams_student* s, int B, int k) {
+    if (!(s->fuse_expand_dw_stream && k + 1 <= s->n_backbone && s->L[k].d.role == AMS_ROLE_EXPAND && s->L[k + 1].d.role == AMS_ROLE_DEPTHWISE &&
+          (int64_t)B * s->L[k].px_in >= s->stream_min_rows && (int64_t)s->L[k + 1].px_out * s->L[k + 1].d.cout * 4 < 0x7fffffffLL &&
+          expand_dw_stream_supported(s->L[k].d.cin, s->L[k].d.cout, s->L[k + 1].d.stride, s->L[k + 1].d.rate)))
+        return false;
+    // stride 2 on the streaming kernel is correct and tested but measured no faster than the tiled kernel (the expand runs at
+    // full resolution either way: 412 vs 376 us on the first such block) — only with option value 2
+    if (s->L[k + 1].d.stride != 1 && s->fuse_expand_dw_stream < 2) return false;
+    if (s->L[k].d.cin <= 32) return true;                        // exact-f32 form: any matmul mode
+    return s->matmul_mode != AMS_MATMUL_F32 && s->L[k].whi && s->L[k].Kp == s->L[k].d.cin;
+}
+// `np` of the streaming launchers for expand layer k
+// (Cin <= 32 streams on the exact-f32 form whatever the mode: no fp16 parts there, so no fp16-pair hand-over of d either)
+static int stream_np(const ams_student* s, int k) {
+    if (s->matmul_mode == AMS_MATMUL_SPLIT_F16 && s->L[k].whf && s->L[k].d.cin > 32) return AMS_NP_F16;
+    return s->matmul_mode == AMS_MATMUL_SPLIT_BF16_X6 || s->matmul_mode == AMS_MATMUL_SPLIT_F16 ? 3 : s->matmul_mode == AMS_MATMUL_BF16 ? 1 : 2;
+}
+// ... and the parts of its input it can take ready-made.  The format is the consumer's: fp16 pairs only where that expand layer runs the fp16
+// form (its panels survived the freeze's range check, Cin > 32).  An expand layer moved off the fp16 form gets no parts: the streaming kernel
+// then splits f32 `x` itself, and a 160-channel block takes the unfused path (rare; its speed does not matter).
+static PartsFmt stream_parts(const ams_student* s, int k) {
+    PartsFmt f;
+    const int np = stream_np(s, k);
+    if (np == AMS_NP_F16) { f.np = 2; f.fmt = 1; }
+    else if (s->matmul_mode != AMS_MATMUL_SPLIT_F16) f.np = np;
+    return f;
+}
+
+// The plan of the block that starts at layer i, for the frames of view v, when the block before it left `in` in xsplit.  Launches nothing.
+static BlockPlan plan_block(const ams_student* s, const FrozenView& v, int i, PartsFmt in) {
+    BlockPlan p;
+    const int B = v.B, nb = s->n_backbone;
+    const auto role = [&](int k) { return k <= nb ? s->L[k].d.role : -1; };
+    p.expand = role(i) == AMS_ROLE_EXPAND;
+    const int id = i + (p.expand ? 1 : 0), ij = id + 1;       // the depthwise and the project layer
+    const LayerRt& le = s->L[i];
+    const LayerRt& ld = s->L[id];
+    const LayerRt& lj = s->L[ij];
+    if (s->fuse_block && p.expand && role(id) == AMS_ROLE_DEPTHWISE && role(ij) == AMS_ROLE_PROJECT &&
+        (!lj.d.residual_from || lj.d.residual_from == i - 1) &&
+        block_fused_supported(le.d.cin, le.d.cout, lj.d.cout, ld.d.stride, ld.d.rate, lj.d.residual_from != 0)) {
+        // early blocks: only the block input and output touch HBM (k_block.hip)
+        p.form = BLOCK_WHOLE;
+        // three-part split products for the expand layer when K >= 24 (not in the exact-f32 mode; the one- and two-part modes
+        // concern the late layers only: the early blocks keep f32-level products there too)
+        // fp16 form (AMS_MATMUL_SPLIT_F16): expand (any K, 16 included) and project products as 3 fp16 MFMAs each
+        p.h16 = s->block_x6 && s->matmul_mode == AMS_MATMUL_SPLIT_F16 && le.whf && lj.whf && le.Kp == 32;
+        p.x6 = !p.h16 && s->block_x6 && s->matmul_mode != AMS_MATMUL_F32 && le.whi && le.Kp == 32 && le.d.cin > 16;
+        return p;
+    }
+    // a 160-channel block streams only on ready-made parts (k_xdw_wreg.hip), or with option value 2
+    if (stream_ok(s, B, i) && (le.d.cin <= 96 || in.np || s->fuse_expand_dw_stream >= 2)) {
+        // stride-16 blocks: expand + depthwise streamed through an LDS ring, split-bf16 products (bit-identical to the two
+        // kernels it replaces); the 6x-expanded tensor is never written
+        // 160 -> 960: expand weights in registers, the operand staged once per block in LDS (k_xdw_wreg.hip); with 30 channel
+        // chunks the LDS-weight form is bound by its passes over the operand
+        p.form = le.d.cin > 96 && in.np ? BLOCK_WREG : BLOCK_STREAM;
+        p.in = in;
+        p.np = stream_np(s, i);
+        p.h16 = p.np == AMS_NP_F16;
+        p.wparts = p.h16 ? le.whf : le.whi;
+        p.wplane = p.h16 ? (int64_t)le.d.cout * le.Kp : (int64_t)(le.wlo - le.whi);
+    } else if (s->fuse_expand_dw && p.expand && role(id) == AMS_ROLE_DEPTHWISE &&
+               expand_dw_supported(le.d.cin, le.d.cout, ld.d.stride, ld.d.rate) &&
+               (s->fuse_expand_dw >= 2 || le.d.cin <= 24 || ld.d.stride == 2)) {
+        // expand + depthwise in one kernel: the 6x-expanded tensor stays in LDS
+        p.form = BLOCK_TILED;
+    } else {
+        if (p.expand) {
+            // an expand layer the streaming kernel can take forms its products the same way when it runs alone (split bf16), so
+            // that the result does not depend on batch size or on AMS_OPT_FUSE_EXPAND_DW_STREAM
+            const bool streamable = role(id) == AMS_ROLE_DEPTHWISE && le.Kp == le.d.cin && le.d.cin >= 64 &&
+                                    expand_dw_stream_supported(le.d.cin, le.d.cout, ld.d.stride, ld.d.rate);
+            p.expand_form = pointwise_form(s, i, layer_args(s, i, B, nullptr, nullptr, nullptr), streamable);
+        }
+        if (s->fuse_dw_project && s->matmul_mode == AMS_MATMUL_SPLIT_BF16 &&   /* two-part split only */ role(id) == AMS_ROLE_DEPTHWISE &&
+            role(ij) == AMS_ROLE_PROJECT && lj.whi && (int64_t)B * ld.px_out < 32768 && (int64_t)B * ld.px_out >= 256 &&
+            lj.Kp == ld.d.cin && dw_project_supported(ld.d.cin, lj.d.cout, ld.d.stride, ld.d.rate)) {
+            // depthwise + project in one kernel (split-bf16 GEMM that computes its own operand): d never reaches HBM
+            p.dw_project = true;
+            return p;
         }
     }
-    int reserved = -1;                         // buffer that holds the late section's input for ALL sub-batches: never a target there
-    auto other = [&](int avoid0, int avoid1) { for (int k = 0; k < 4; ++k) if (k != avoid0 && k != avoid1 && k != reserved) return k; return -1; };
-    // layer k starts a block whose expand + depthwise run as the streaming kernel (stride-16 blocks, split-bf16 modes, a few
-    // frames: below that the launch cannot fill the chip)
-    auto stream_ok = [&](int k) {
-        if (!(s->fuse_expand_dw_stream && k + 1 <= s->n_backbone && s->L[k].d.role == AMS_ROLE_EXPAND && s->L[k + 1].d.role == AMS_ROLE_DEPTHWISE &&
-              (int64_t)B * s->L[k].px_in >= s->stream_min_rows && (int64_t)s->L[k + 1].px_out * s->L[k + 1].d.cout * 4 < 0x7fffffffLL &&
-              expand_dw_stream_supported(s->L[k].d.cin, s->L[k].d.cout, s->L[k + 1].d.stride, s->L[k + 1].d.rate)))
-            return false;
-        // stride 2 on the streaming kernel is correct and tested but measured no faster than the tiled kernel (the expand runs at
-        // full resolution either way: 412 vs 376 us on the first such block) — only with option value 2
-        if (s->L[k + 1].d.stride != 1 && s->fuse_expand_dw_stream < 2) return false;
-        if (s->L[k].d.cin <= 32) return true;                        // exact-f32 form: any matmul mode
-        return s->matmul_mode != AMS_MATMUL_F32 && s->L[k].whi && s->L[k].Kp == s->L[k].d.cin;
-    };
-    const uint16_t* cur_parts = nullptr;       // `cur` as bf16 parts (s->xsplit), when the GEMM that produced it wrote them
+    if (role(ij) != AMS_ROLE_PROJECT) return p;                  // a malformed table: the launch code reports it
+    const PwArgs a = layer_args(s, ij, B, nullptr, nullptr, s->fparams);
+    p.project_form = pointwise_form(s, ij, a, false);
+    // fp16 form: the depthwise result goes to the project GEMM as fp16 pairs (PwArgs::x_fmt 1) when that GEMM runs the fp16 product
+    p.d_h2i = (p.form == BLOCK_STREAM || p.form == BLOCK_WREG) && p.h16 && p.project_form == PW_F16 && ld.d.cout % 8 == 0 && !s->emulate_bf16_storage;
+    // the next block streams: its expand GEMM takes this result as parts, written here once instead of being split by every
+    // channel-chunk block there — when the GEMM chosen has the vector epilogue that writes them, and they fit
+    if (stream_ok(s, B, ij + 1) && v.xsplit && (size_t)a.M * a.N <= v.xsplit_plane && p.project_form != PW_F32 && pointwise_split_writes_parts(a) &&
+        !(s->emulate_bf16_storage && lj.px_out == (int64_t)s->h * s->w))       // (the parts would be those of the unrounded result)
+        p.out = stream_parts(s, ij + 1);
+    return p;
+}
+
+// one frozen 1x1 layer in the form planned for it
+static int frozen_pointwise(ams_student* s, int layer, const PwArgs& a, PwForm form, hipStream_t st) {
+    const LayerRt& l = s->L[layer];
+    if (a.x_fmt != 0 && form != PW_F16) { set_error("frozen_pointwise: layer %d was handed fp16 pairs but does not run the fp16 product", layer); return AMS_E_STATE; }
+    switch (form) {
+        case PW_F16: RUNK(layer, pw_bytes(a), launch_pointwise_split_f16(a, l.whf, (int64_t)l.d.cout * l.Kp, l.Kp, st)); break;
+        case PW_BF16_3: RUNK(layer, pw_bytes(a), launch_pointwise_split3(a, l.whi, l.wlo, l.wlo3, l.Kp, st)); break;
+        case PW_BF16_2: RUNK(layer, pw_bytes(a), launch_pointwise_split(a, l.whi, l.wlo, l.Kp, st)); break;
+        case PW_BF16_1: RUNK(layer, pw_bytes(a), launch_pointwise_split1(a, l.whi, l.Kp, st)); break;
+        case PW_F32: RUNK(layer, pw_bytes(a), launch_pointwise(a, st)); break;
+    }
+    return AMS_OK;
+}
+
+// ---- the launches: each form builds its arguments from the plan and advances the cursor ------------------------------------------------
+static int run_first_block(ams_student* s, const FrozenView& v, int dtype, Cursor& c, hipStream_t st) {
+    const ams_student_config& cf = s->cfg;
+    const float* P = s->fparams;
+    const int B = v.B;
+    float* y = v.act[0];
+    const LayerRt& l = s->L[1];
+    const LayerRt& ld = s->L[2];
+    const LayerRt& lj = s->L[3];
+    const double in_bytes = (double)B * cf.height * cf.width * 3 * (dtype == AMS_DT_U8 ? 1 : 4);
+    c.i = 2;
+    if (s->fuse_first_block && s->n_backbone >= 3 && l.d.cout == 32 && ld.d.role == AMS_ROLE_DEPTHWISE && ld.d.cin == 32 &&
+        ld.d.stride == 1 && ld.d.rate == 1 && lj.d.role == AMS_ROLE_PROJECT && lj.d.cin == 32 && lj.d.cout == 16 &&
+        !lj.d.residual_from) {
+        // stem + depthwise + project of the first block in one kernel: the 32-channel half-resolution tensor stays in LDS
+        const double bytes = in_bytes + 4.0 * B * lj.px_out * lj.d.cout + 4.0 * (27 * 32 + 9 * 32 + 32 * 16);
+        if (s->fuse_first_block >= 2)
+            RUNK(3, bytes, launch_first_block_tiles(v.frames, dtype, B, cf.height, cf.width, cf.pixel_scale, P + l.d.w_off, l.fscale, l.fshift,
+                                                    l.d.act, P + ld.d.w_off, ld.fscale, ld.fshift, ld.d.act, P + lj.d.w_off, lj.fscale,
+                                                    lj.fshift, lj.d.act, y, st, l.blk_vecs));
+        else {
+            const bool h16 = s->block_x6 && s->matmul_mode == AMS_MATMUL_SPLIT_F16 && l.whf && lj.whf && lj.Kp == 32;
+            const bool x6 = !h16 && s->block_x6 && s->matmul_mode != AMS_MATMUL_F32 && l.whi;
+            RUNK(3, bytes, launch_first_block(v.frames, dtype, B, cf.height, cf.width, cf.pixel_scale, P + l.d.w_off, l.fscale, l.fshift,
+                                              l.d.act, P + ld.d.w_off, ld.fscale, ld.fshift, ld.d.act, P + lj.d.w_off, lj.fscale,
+                                              lj.fshift, lj.d.act, y, st, x6 ? l.whi : nullptr, 32 * 32, h16 ? l.whf : nullptr, 32 * 32,
+                                              h16 ? lj.whf : nullptr, (int64_t)lj.d.cout * lj.Kp));
+        }
+        c.i = 4;
+    } else {
+        const double bytes = in_bytes + 4.0 * B * l.px_out * l.d.cout;
+        RUNK(1, bytes, launch_stem(v.frames, dtype, B, cf.height, cf.width, P + l.d.w_off, l.d.cout, l.fscale, l.fshift, l.d.act,
+                                   cf.pixel_scale, y, st));
+    }
+    c.cur = y; c.cur_i = 0; c.parts = PartsFmt();
+    return AMS_OK;
+}
+
+// the project GEMM (+ block input) on the depthwise result d = act[d_i]; the block is done
+static int run_project(ams_student* s, const FrozenView& v, Cursor& c, const BlockPlan& p, int ij, const float* d, int d_i, hipStream_t st) {
+    const LayerRt& l = s->L[ij];
+    AMS_REQUIRE(l.d.role == AMS_ROLE_PROJECT, "engine: expected project at layer %d", ij);
+    const int o = other(v, c.cur_i, d_i);
+    PwArgs a = layer_args(s, ij, v.B, d, v.act[o], c.cur);
+    a.x_fmt = p.d_h2i ? 1 : 0;
+    if (p.out.np) { a.ysplit = v.xsplit; a.ysplit_plane = a.M * a.N; a.ysplit_np = p.out.np; a.ysplit_fmt = p.out.fmt; }
+    RUN(frozen_pointwise(s, ij, a, p.project_form, st));
+    if (s->emulate_bf16_storage && l.px_out == (int64_t)s->h * s->w)
+        RUN(launch_round_bf16(v.act[o], (int64_t)v.B * l.px_out * l.d.cout, st));            // block input as bf16 storage would hold it
+    c.cur = v.act[o]; c.cur_i = o; c.i = ij + 1; c.parts = p.out;
+    return AMS_OK;
+}
+
+static int run_block_whole(ams_student* s, const FrozenView& v, Cursor& c, const BlockPlan& p, hipStream_t st) {
+    const float* P = s->fparams;
+    const int B = v.B, i = c.i;
+    const LayerRt& le = s->L[i];
+    const LayerRt& ld = s->L[i + 1];
+    const LayerRt& lj = s->L[i + 2];
+    const int o = other(v, c.cur_i, -1);
+    const bool res = lj.d.residual_from != 0;
+    const double bytes = 4.0 * ((double)B * (le.px_in * le.d.cin * (res ? 2 : 1) + lj.px_out * lj.d.cout) + (double)le.d.cin * le.d.cout +
+                                9.0 * ld.d.cin + (double)lj.d.cin * lj.d.cout);
+    // algorithmic FLOPs (no halo, no padding): the kernel is bound by the exact-f32 matrix pipe, not by HBM
+    const double fl_e = 2.0 * B * (double)le.px_in * le.d.cin * le.d.cout, fl_p = 2.0 * B * (double)lj.px_out * lj.d.cin * lj.d.cout;
+    s->prof_flops = 2.0 * B * (double)ld.px_out * 9.0 * ld.d.cin + (p.h16 ? 0.0 : fl_p) + (p.x6 || p.h16 ? 0.0 : fl_e);
+    s->prof_flops_x6 = p.h16 ? fl_e + fl_p : p.x6 ? fl_e : 0.0;
+    RUNK(i + 2, bytes, launch_block_fused(c.cur, B, le.Hin, le.Win, le.d.cin, P + le.d.w_off, le.fscale, le.fshift, le.d.act, le.d.cout,
+                                          P + ld.d.w_off, ld.d.stride, ld.fscale, ld.fshift, ld.d.act, P + lj.d.w_off, lj.fscale, lj.fshift,
+                                          lj.d.act, lj.d.cout, res, v.act[o], st, le.blk_vecs, p.x6 ? le.whi : nullptr,
+                                          (int64_t)(le.wlo - le.whi), p.h16 ? le.whf : nullptr, (int64_t)le.d.cout * le.Kp, p.h16 ? lj.whf : nullptr,
+                                          (int64_t)lj.d.cout * lj.Kp, lj.Kp));
+    c.cur = v.act[o]; c.cur_i = o; c.i = i + 3; c.parts = PartsFmt();
+    return AMS_OK;
+}
+
+// expand + depthwise in one kernel (tiled or streamed), then the project GEMM
+static int run_block_expand_dw(ams_student* s, const FrozenView& v, Cursor& c, const BlockPlan& p, hipStream_t st) {
+    const float* P = s->fparams;
+    const int B = v.B, i = c.i;
+    const LayerRt& le = s->L[i];
+    const LayerRt& ld = s->L[i + 1];
+    const int o = other(v, c.cur_i, -1);
+    const double bytes = 4.0 * ((double)B * (le.px_in * le.d.cin + ld.px_out * ld.d.cout) + (double)le.d.cin * le.d.cout + 9.0 * ld.d.cin);
+    const uint16_t* x_parts = p.in.np ? v.xsplit : nullptr;
+    const int64_t xplane = (int64_t)B * le.px_in * le.d.cin;
+    if (p.form == BLOCK_TILED)
+        RUNK(i + 1, bytes, launch_expand_dw(c.cur, B, le.Hin, le.Win, le.d.cin, P + le.d.w_off, le.fscale, le.fshift, le.d.act, le.d.cout,
+                                            P + ld.d.w_off, ld.d.stride, ld.d.rate, ld.fscale, ld.fshift, ld.d.act, v.act[o], st));
+    else if (p.form == BLOCK_WREG)
+        RUNK(i + 1, bytes, launch_expand_dw_wreg(x_parts, xplane, B, le.Hin, le.Win, le.d.cin, p.wparts, p.wplane, p.np, le.fscale,
+                                                 le.fshift, le.d.act, le.d.cout, P + ld.d.w_off, ld.d.rate, ld.fscale, ld.fshift, ld.d.act,
+                                                 v.act[o], st, p.d_h2i ? 1 : 0));
+    else
+        RUNK(i + 1, bytes, launch_expand_dw_stream(c.cur, x_parts, xplane, B, le.Hin, le.Win, le.d.cin, P + le.d.w_off, p.wparts, p.wplane, p.np, le.fscale,
+                                                   le.fshift, le.d.act, le.d.cout, P + ld.d.w_off, ld.d.stride, ld.d.rate, ld.fscale, ld.fshift, ld.d.act,
+                                                   v.act[o], st, p.d_h2i ? 1 : 0));
+    if (p.form != BLOCK_TILED && s->emulate_bf16_storage && ld.px_out == (int64_t)s->h * s->w)
+        RUN(launch_round_bf16(v.act[o], (int64_t)B * ld.px_out * ld.d.cout, st));          // d as bf16 storage would hold it
+    return run_project(s, v, c, p, i + 2, v.act[o], o, st);
+}
+
+static int run_block_layers(ams_student* s, const FrozenView& v, Cursor& c, const BlockPlan& p, hipStream_t st) {
+    const float* P = s->fparams;
+    const int B = v.B;
+    int i = c.i;
+    const float* x = c.cur;
+    int x_i = c.cur_i;
+    if (p.expand) {
+        const int o = other(v, c.cur_i, -1);
+        RUN(frozen_pointwise(s, i, layer_args(s, i, B, x, v.act[o], nullptr), p.expand_form, st));
+        x = v.act[o]; x_i = o; ++i;
+    }
+    const LayerRt& l = s->L[i];
+    AMS_REQUIRE(l.d.role == AMS_ROLE_DEPTHWISE, "engine: expected depthwise at layer %d", i);
+    const int o = other(v, c.cur_i, x_i);
+    if (p.dw_project) {
+        const LayerRt& lpj = s->L[i + 1];
+        const PwArgs a = layer_args(s, i + 1, B, nullptr, v.act[o], c.cur);
+        const double bytes = 4.0 * ((double)B * (l.px_in * l.d.cin + lpj.px_out * lpj.d.cout * (a.res ? 2 : 1)) +
+                                    (double)lpj.d.cin * lpj.d.cout + 9.0 * l.d.cin);
+        RUNK(i + 1, bytes, launch_dw_project(x, B, l.Hin, l.Win, l.d.cin, P + l.d.w_off, l.d.rate, l.fscale, l.fshift, l.d.act, a,
+                                             lpj.whi, lpj.wlo, lpj.Kp, st));
+        c.cur = v.act[o]; c.cur_i = o; c.i = i + 2; c.parts = PartsFmt();
+        return AMS_OK;
+    }
+    RUNK(i, dw_bytes(l, B), launch_depthwise(x, B, l.Hin, l.Win, l.d.cin, P + l.d.w_off, l.d.stride, l.d.rate, l.fscale,
+                                             l.fshift, l.d.act, v.act[o], st));
+    if (s->emulate_bf16_storage && l.px_out == (int64_t)s->h * s->w)
+        RUN(launch_round_bf16(v.act[o], (int64_t)B * l.px_out * l.d.cout, st));
+    return run_project(s, v, c, p, i + 1, v.act[o], o, st);
+}
+
+// blocks from the cursor up to layer i_stop: [expand] -> depthwise -> project (+ block input) each
+static int run_blocks(ams_student* s, const FrozenView& v, Cursor& c, int i_stop, hipStream_t st) {
+    while (c.i <= s->n_backbone && c.i < i_stop) {
+        const BlockPlan p = plan_block(s, v, c.i, c.parts);
+        switch (p.form) {
+            case BLOCK_WHOLE: RUN(run_block_whole(s, v, c, p, st)); break;
+            case BLOCK_TILED: case BLOCK_STREAM: case BLOCK_WREG: RUN(run_block_expand_dw(s, v, c, p, st)); break;
+            case BLOCK_LAYERS: RUN(run_block_layers(s, v, c, p, st)); break;
+        }
+    }
+    return AMS_OK;
+}
+
+// the head on the backbone's result c.cur (the frames of the view)
+static int run_head(ams_student* s, const FrozenView& v, const Cursor& c, hipStream_t st) {
+    const float* P = s->fparams;
+    const LayerRt& lp = s->L[s->iPool]; const LayerRt& la = s->L[s->iAspp]; const LayerRt& lc = s->L[s->iProj]; const LayerRt& ll = s->L[s->iLogits];
+    const int B = v.B;
+    const int64_t HW = (int64_t)s->h * s->w, M = (int64_t)B * HW;
+    // The image-pooling branch (global mean -> 1x1 + BN + ReLU -> its share of concat_projection as a per-image bias) is three
+    // latency-bound launches on a handful of rows (58 us at 32 frames, 22 us at one).  With overlap_head it runs on the side stream
+    // beside the aspp0 GEMM and joins before concat_projection (off by default, see the flag).
+    const bool fork = s->overlap_head && !s->prof.on;
+    hipStream_t ps = st;
+    if (fork) {
+        if (!s->side) RUN(create_side_stream(&s->side));
+        if (!s->ev_fork) RUN(create_sync_event(&s->ev_fork));
+        if (!s->ev_head) RUN(create_sync_event(&s->ev_head));
+        AMS_CHECK_HIP(hipEventRecord(s->ev_fork, st));
+        AMS_CHECK_HIP(hipStreamWaitEvent(s->side, s->ev_fork, 0));
+        ps = s->side;
+    }
+    RUNK(s->iPool, 4.0 * M * lp.d.cin, launch_global_mean(c.cur, B, HW, lp.d.cin, v.pooled, v.scratch, ps));
+    {   // image_pooling conv + BN + ReLU on the pooled vector
+        PwArgs a = pw_args(v.pooled, B, lp.d.cin, lp.d.cin, P + lp.d.w_off, lp.d.cout, v.pool_a, lp.d.cout);
+        a.scale = lp.fscale; a.shift = lp.fshift; a.act = lp.d.act;
+        RUNK(s->iPool, pw_bytes(a), launch_pointwise(a, ps));
+        // the broadcast pool branch enters concat_projection as a per-image bias: W_proj[0:256]^T . pool
+        PwArgs b = pw_args(v.pool_a, B, lp.d.cout, lp.d.cout, P + lc.d.w_off, lc.d.cout, v.img_bias, lc.d.cout);
+        RUNK(s->iProj, pw_bytes(b), launch_pointwise(b, ps));
+    }
+    if (fork) AMS_CHECK_HIP(hipEventRecord(s->ev_head, s->side));
+    const int o1 = other(v, c.cur_i, -1), o2 = other(v, c.cur_i, o1);
+    PwArgs a = pw_args(c.cur, M, la.d.cin, la.d.cin, P + la.d.w_off, la.d.cout, v.act[o1], la.d.cout);
+    a.scale = la.fscale; a.shift = la.fshift; a.act = la.d.act;
+    RUN(frozen_pointwise(s, s->iAspp, a, pointwise_form(s, s->iAspp, a, false), st));
+    if (fork) AMS_CHECK_HIP(hipStreamWaitEvent(st, s->ev_head, 0));
+    PwArgs b = pw_args(v.act[o1], M, la.d.cout, la.d.cout, P + lc.d.w_off + (int64_t)lp.d.cout * lc.d.cout, lc.d.cout,
+                       v.act[o2], lc.d.cout);
+    b.img_bias = v.img_bias; b.rows_per_img = HW; b.scale = lc.fscale; b.shift = lc.fshift; b.act = lc.d.act;
+    RUN(frozen_pointwise(s, s->iProj, b, pointwise_form(s, s->iProj, b, false), st));
+    PwArgs d = pw_args(v.act[o2], M, lc.d.cout, lc.d.cout, P + ll.d.w_off, ll.d.cout, v.logits, 32);
+    d.shift = P + ll.d.gamma_off;      // biases
+    RUN(frozen_pointwise(s, s->iLogits, d, pointwise_form(s, s->iLogits, d, false), st));
+    return AMS_OK;
+}
+
+// One pass over the frames of view v.  Of the student it writes the profiler's records and the side stream / events that overlap_head
+// creates on first use; every buffer comes from the view.
+static int forward_frozen(ams_student* s, const FrozenView& v, int dtype, hipStream_t st) {
+    Cursor c;
+    RUN(run_first_block(s, v, dtype, c, st));
     // The output-stride-16 section (blocks 7-16 and the head) can run in sub-batches: its largest tensor, the depthwise result of
     // the 960-channel blocks, is 264 MB at 32 frames — written by one kernel, read by the next, and larger than the 256 MB Infinity
     // Cache.  At 16 frames the writer/reader pairs of that section meet in the cache (and every sub-batch reuses the same addresses).
     int i_late = s->n_backbone + 1;
     for (int k = 2; k <= s->n_backbone; ++k)
         if (s->L[k].d.role == AMS_ROLE_EXPAND && s->L[k].px_in == (int64_t)s->h * s->w) { i_late = k; break; }
-    const int sub = (s->late_subbatch > 0 && Bfull > s->late_subbatch && i_late <= s->n_backbone) ? s->late_subbatch : Bfull;
-    auto run_blocks = [&](int i_stop) -> int {
-    while (i <= s->n_backbone && i < i_stop) {
-        // one inverted-residual block: [expand] -> depthwise -> project (+ block input)
-        const float* block_in = cur;
-        const float* x = cur;
-        int x_i = cur_i;
-        bool d_h2i = false;                    // x (the depthwise result) is stored as fp16 pairs (PwArgs::x_fmt 1)
-        if (s->fuse_block && i + 2 <= s->n_backbone && s->L[i].d.role == AMS_ROLE_EXPAND && s->L[i + 1].d.role == AMS_ROLE_DEPTHWISE &&
-            s->L[i + 2].d.role == AMS_ROLE_PROJECT && (!s->L[i + 2].d.residual_from || s->L[i + 2].d.residual_from == i - 1) &&
-            block_fused_supported(s->L[i].d.cin, s->L[i].d.cout, s->L[i + 2].d.cout, s->L[i + 1].d.stride, s->L[i + 1].d.rate,
-                                  s->L[i + 2].d.residual_from != 0)) {
-            // early blocks: only the block input and output touch HBM (k_block.hip)
-            LayerRt& le = s->L[i];
-            LayerRt& ld = s->L[i + 1];
-            LayerRt& lj = s->L[i + 2];
-            const int o = other(cur_i, -1);
-            const bool res = lj.d.residual_from != 0;
-            const double bytes = 4.0 * ((double)B * (le.px_in * le.d.cin * (res ? 2 : 1) + lj.px_out * lj.d.cout) + (double)le.d.cin * le.d.cout +
-                                        9.0 * ld.d.cin + (double)lj.d.cin * lj.d.cout);
-            // algorithmic FLOPs (no halo, no padding): the kernel is bound by the exact-f32 matrix pipe, not by HBM
-            // three-part split products for the expand layer when K >= 24 (not in the exact-f32 mode; the one- and two-part modes
-            // concern the late layers only: the early blocks keep f32-level products there too)
-            // fp16 form (AMS_MATMUL_SPLIT_F16): expand (any K, 16 included) and project products as 3 fp16 MFMAs each
-            const bool h16 = s->block_x6 && s->matmul_mode == AMS_MATMUL_SPLIT_F16 && le.whf && lj.whf && le.Kp == 32;
-            const bool x6 = !h16 && s->block_x6 && s->matmul_mode != AMS_MATMUL_F32 && le.whi && le.Kp == 32 && le.d.cin > 16;
-            const double fl_e = 2.0 * B * (double)le.px_in * le.d.cin * le.d.cout, fl_p = 2.0 * B * (double)lj.px_out * lj.d.cin * lj.d.cout;
-            s->prof_flops = 2.0 * B * (double)ld.px_out * 9.0 * ld.d.cin + (h16 ? 0.0 : fl_p) + (x6 || h16 ? 0.0 : fl_e);
-            s->prof_flops_x6 = h16 ? fl_e + fl_p : x6 ? fl_e : 0.0;
-            RUNK(i + 2, bytes, launch_block_fused(cur, B, le.Hin, le.Win, le.d.cin, P + le.d.w_off, le.fscale, le.fshift, le.d.act, le.d.cout,
-                                                  P + ld.d.w_off, ld.d.stride, ld.fscale, ld.fshift, ld.d.act, P + lj.d.w_off, lj.fscale, lj.fshift,
-                                                  lj.d.act, lj.d.cout, res, s->act[o], st, le.blk_vecs, x6 ? le.whi : nullptr,
-                                                  (int64_t)(le.wlo - le.whi), h16 ? le.whf : nullptr, (int64_t)le.d.cout * le.Kp, h16 ? lj.whf : nullptr,
-                                                  (int64_t)lj.d.cout * lj.Kp, lj.Kp));
-            cur = s->act[o]; cur_i = o; i += 3;
-            cur_parts = nullptr;
-            continue;
-        }
-        const bool stream_here = stream_ok(i) && (s->L[i].d.cin <= 96 || cur_parts || s->fuse_expand_dw_stream >= 2);
-        if (!stream_here && s->fuse_expand_dw && s->L[i].d.role == AMS_ROLE_EXPAND && i + 1 <= s->n_backbone &&
-            s->L[i + 1].d.role == AMS_ROLE_DEPTHWISE &&
-            expand_dw_supported(s->L[i].d.cin, s->L[i].d.cout, s->L[i + 1].d.stride, s->L[i + 1].d.rate) &&
-            (s->fuse_expand_dw >= 2 || s->L[i].d.cin <= 24 || s->L[i + 1].d.stride == 2)) {
-            // expand + depthwise in one kernel: the 6x-expanded tensor stays in LDS
-            LayerRt& le = s->L[i];
-            LayerRt& ld = s->L[i + 1];
-            const int o = other(cur_i, -1);
-            const double bytes = 4.0 * ((double)B * (le.px_in * le.d.cin + ld.px_out * ld.d.cout) + (double)le.d.cin * le.d.cout + 9.0 * ld.d.cin);
-            RUNK(i + 1, bytes, launch_expand_dw(x, B, le.Hin, le.Win, le.d.cin, P + le.d.w_off, le.fscale, le.fshift, le.d.act, le.d.cout,
-                                                P + ld.d.w_off, ld.d.stride, ld.d.rate, ld.fscale, ld.fshift, ld.d.act, s->act[o], st));
-            x = s->act[o]; x_i = o; i += 2;
-        } else if (stream_here) {
-            // stride-16 blocks: expand + depthwise streamed through an LDS ring, split-bf16 products (bit-identical to the two
-            // kernels it replaces); the 6x-expanded tensor is never written
-            LayerRt& le = s->L[i];
-            LayerRt& ld = s->L[i + 1];
-            const int o = other(cur_i, -1);
-            // (Cin <= 32 streams on the exact-f32 form whatever the mode: no fp16 parts there, so no fp16-pair hand-over of d either)
-            const bool h16 = s->matmul_mode == AMS_MATMUL_SPLIT_F16 && le.whf && le.d.cin > 32;
-            const int np = h16 ? AMS_NP_F16 : s->matmul_mode == AMS_MATMUL_SPLIT_BF16_X6 || s->matmul_mode == AMS_MATMUL_SPLIT_F16 ? 3 : s->matmul_mode == AMS_MATMUL_BF16 ? 1 : 2;
-            const uint16_t* wparts = h16 ? le.whf : le.whi;
-            const int64_t wplane = h16 ? (int64_t)le.d.cout * le.Kp : (int64_t)(le.wlo - le.whi);
-            // fp16 form: the depthwise result goes to the project GEMM as fp16 pairs (PwArgs::x_fmt 1) when that GEMM will run the fp16 product
-            d_h2i = false;
-            if (h16 && i + 2 <= s->n_backbone && s->L[i + 2].d.role == AMS_ROLE_PROJECT && s->L[i + 2].whf && ld.d.cout % 8 == 0 && !s->emulate_bf16_storage) {
-                const LayerRt& lj = s->L[i + 2];
-                PwArgs pj = pw_args(nullptr, (int64_t)B * lj.px_in, lj.d.cin, lj.d.cin, nullptr, lj.d.cout, nullptr, lj.d.cout);
-                d_h2i = split_pays(pj) && pointwise_f16_applies(pj);
-            }
-            const double bytes = 4.0 * ((double)B * (le.px_in * le.d.cin + ld.px_out * ld.d.cout) + (double)le.d.cin * le.d.cout + 9.0 * ld.d.cin);
-            const int64_t xplane = (int64_t)B * le.px_in * le.d.cin;
-            if (le.d.cin > 96 && cur_parts)
-                // 160 -> 960: expand weights in registers, the operand staged once per block in LDS (k_xdw_wreg.hip); with 30 channel
-                // chunks the LDS-weight form is bound by its passes over the operand
-                RUNK(i + 1, bytes, launch_expand_dw_wreg(cur_parts, xplane, B, le.Hin, le.Win, le.d.cin, wparts, wplane, np, le.fscale,
-                                                         le.fshift, le.d.act, le.d.cout, P + ld.d.w_off, ld.d.rate, ld.fscale, ld.fshift, ld.d.act,
-                                                         s->act[o], st, d_h2i ? 1 : 0));
-            else
-                RUNK(i + 1, bytes, launch_expand_dw_stream(x, cur_parts, xplane, B, le.Hin, le.Win, le.d.cin, P + le.d.w_off, wparts, wplane, np, le.fscale,
-                                                           le.fshift, le.d.act, le.d.cout, P + ld.d.w_off, ld.d.stride, ld.d.rate, ld.fscale, ld.fshift, ld.d.act,
-                                                           s->act[o], st, d_h2i ? 1 : 0));
-            x = s->act[o]; x_i = o; i += 2;
-            if (s->emulate_bf16_storage && ld.px_out == (int64_t)s->h * s->w)
-                RUN(launch_round_bf16(s->act[o], (int64_t)B * ld.px_out * ld.d.cout, st));          // d as bf16 storage would hold it
-        } else {
-        if (s->L[i].d.role == AMS_ROLE_EXPAND) {
-            LayerRt& l = s->L[i];
-            const int o = other(cur_i, -1);
-            PwArgs a = pw_args(x, (int64_t)B * l.px_in, l.d.cin, l.d.cin, P + l.d.w_off, l.d.cout, s->act[o], l.d.cout);
-            a.scale = l.fscale; a.shift = l.fshift; a.act = l.d.act;
-            // an expand layer the streaming kernel can take forms its products the same way when it runs alone (split bf16), so
-            // that the result does not depend on batch size or on AMS_OPT_FUSE_EXPAND_DW_STREAM
-            const bool streamable = i + 1 <= s->n_backbone && s->L[i + 1].d.role == AMS_ROLE_DEPTHWISE && l.Kp == l.d.cin && l.d.cin >= 64 &&
-                                    expand_dw_stream_supported(l.d.cin, l.d.cout, s->L[i + 1].d.stride, s->L[i + 1].d.rate);
-            RUN(frozen_pointwise(s, i, a, st, nullptr, streamable));
-            x = s->act[o]; x_i = o; ++i;
-        }
-        {
-            LayerRt& l = s->L[i];
-            AMS_REQUIRE(l.d.role == AMS_ROLE_DEPTHWISE, "engine: expected depthwise at layer %d", i);
-            LayerRt& lpj = s->L[i + 1];
-            if (s->fuse_dw_project && s->matmul_mode == AMS_MATMUL_SPLIT_BF16 &&   /* two-part split only */ i + 1 <= s->n_backbone &&
-                lpj.d.role == AMS_ROLE_PROJECT && lpj.whi && (int64_t)B * l.px_out < 32768 && (int64_t)B * l.px_out >= 256 &&
-                lpj.Kp == l.d.cin && dw_project_supported(l.d.cin, lpj.d.cout, l.d.stride, l.d.rate)) {
-                // depthwise + project in one kernel (split-bf16 GEMM that computes its own operand): d never reaches HBM
-                const int o = other(cur_i, x_i);
-                PwArgs a = pw_args(nullptr, (int64_t)B * lpj.px_in, lpj.d.cin, lpj.d.cin, P + lpj.d.w_off, lpj.d.cout, s->act[o], lpj.d.cout);
-                a.scale = lpj.fscale; a.shift = lpj.fshift; a.act = lpj.d.act;
-                if (lpj.d.residual_from) { a.res = block_in; a.ldr = lpj.d.cout; }
-                const double bytes = 4.0 * ((double)B * (l.px_in * l.d.cin + lpj.px_out * lpj.d.cout * (a.res ? 2 : 1)) +
-                                            (double)lpj.d.cin * lpj.d.cout + 9.0 * l.d.cin);
-                RUNK(i + 1, bytes, launch_dw_project(x, B, l.Hin, l.Win, l.d.cin, P + l.d.w_off, l.d.rate, l.fscale, l.fshift, l.d.act, a,
-                                                     lpj.whi, lpj.wlo, lpj.Kp, st));
-                cur = s->act[o]; cur_i = o; i += 2;
-                cur_parts = nullptr;
-                continue;
-            }
-            const int o = other(cur_i, x_i);
-            RUNK(i, dw_bytes(l, B), launch_depthwise(x, B, l.Hin, l.Win, l.d.cin, P + l.d.w_off, l.d.stride, l.d.rate, l.fscale,
-                                                     l.fshift, l.d.act, s->act[o], st));
-            if (s->emulate_bf16_storage && l.px_out == (int64_t)s->h * s->w)
-                RUN(launch_round_bf16(s->act[o], (int64_t)B * l.px_out * l.d.cout, st));
-            x = s->act[o]; x_i = o; ++i;
-        }
-        }
-        {
-            LayerRt& l = s->L[i];
-            AMS_REQUIRE(l.d.role == AMS_ROLE_PROJECT, "engine: expected project at layer %d", i);
-            const int o = other(cur_i, x_i);
-            PwArgs a = pw_args(x, (int64_t)B * l.px_in, l.d.cin, l.d.cin, P + l.d.w_off, l.d.cout, s->act[o], l.d.cout);
-            a.scale = l.fscale; a.shift = l.fshift; a.act = l.d.act;
-            if (l.d.residual_from) { a.res = block_in; a.ldr = l.d.cout; }
-            a.x_fmt = d_h2i ? 1 : 0;
-            bool wrote = false;
-            if (stream_ok(i + 1) && s->xsplit && (size_t)a.M * a.N <= s->xsplit_plane) {
-                // the next block streams: its expand GEMM takes this result as bf16 parts, written here once instead of being
-                // split by every channel-chunk block there.  The format is the consumer's: fp16 pairs only where that expand layer runs the
-                // fp16 form (its panels survived the freeze's range check, Cin > 32).  An expand layer moved off the fp16 form gets no parts: the
-                // streaming kernel then splits f32 `x` itself, and a 160-channel block takes the unfused path (rare; its speed does not matter).
-                const LayerRt& ln = s->L[i + 1];
-                if (s->matmul_mode != AMS_MATMUL_SPLIT_F16) {
-                    a.ysplit = s->xsplit; a.ysplit_plane = a.M * a.N; a.ysplit_np = s->matmul_mode == AMS_MATMUL_SPLIT_BF16_X6 ? 3 : s->matmul_mode == AMS_MATMUL_BF16 ? 1 : 2;
-                    a.ysplit_fmt = 0;
-                } else if (ln.whf && ln.d.cin > 32) {
-                    a.ysplit = s->xsplit; a.ysplit_plane = a.M * a.N; a.ysplit_np = 2; a.ysplit_fmt = 1;
-                }
-            }
-            if (s->emulate_bf16_storage && l.px_out == (int64_t)s->h * s->w) a.ysplit = nullptr;      // the parts would be those of the unrounded result
-            RUN(frozen_pointwise(s, i, a, st, &wrote));
-            cur_parts = wrote ? s->xsplit : nullptr;
-            cur = s->act[o]; cur_i = o; ++i;
-            if (s->emulate_bf16_storage && l.px_out == (int64_t)s->h * s->w)
-                RUN(launch_round_bf16(s->act[o], (int64_t)B * l.px_out * l.d.cout, st));            // block input as bf16 storage would hold it
-        }
+    if (!(s->late_subbatch > 0 && v.B > s->late_subbatch && i_late <= s->n_backbone)) {
+        RUN(run_blocks(s, v, c, s->n_backbone + 1, st));
+        return run_head(s, v, c, st);
     }
-    return AMS_OK;
-    };
-    // ---- head -------------------------------------------------------------------------------------------
-    LayerRt& lp = s->L[s->iPool]; LayerRt& la = s->L[s->iAspp]; LayerRt& lc = s->L[s->iProj]; LayerRt& ll = s->L[s->iLogits];
-    const int64_t HW = (int64_t)s->h * s->w;
-    auto run_head = [&](int B0) -> int {       // frames B0 .. B0 + B - 1 of the batch
-        const int64_t M = (int64_t)B * HW;
-        float* pooled = s->pooled + (int64_t)B0 * lp.d.cin;
-        float* pool_a = s->pool_a + (int64_t)B0 * lp.d.cout;
-        float* img_bias = s->img_bias + (int64_t)B0 * lc.d.cout;
-        // The image-pooling branch (global mean -> 1x1 + BN + ReLU -> its share of concat_projection as a per-image bias) is three
-        // latency-bound launches on a handful of rows (58 us at 32 frames, 22 us at one).  With overlap_head it runs on the side stream
-        // beside the aspp0 GEMM and joins before concat_projection (off by default, see the flag).
-        const bool fork = s->overlap_head && !s->prof.on;
-        hipStream_t ps = st;
-        if (fork) {
-            if (!s->side) RUN(create_side_stream(&s->side));
-            if (!s->ev_fork) RUN(create_sync_event(&s->ev_fork));
-            if (!s->ev_head) RUN(create_sync_event(&s->ev_head));
-            AMS_CHECK_HIP(hipEventRecord(s->ev_fork, st));
-            AMS_CHECK_HIP(hipStreamWaitEvent(s->side, s->ev_fork, 0));
-            ps = s->side;
-        }
-        RUNK(s->iPool, 4.0 * M * lp.d.cin, launch_global_mean(cur, B, HW, lp.d.cin, pooled, s->scratch, ps));
-        {   // image_pooling conv + BN + ReLU on the pooled vector
-            PwArgs a = pw_args(pooled, B, lp.d.cin, lp.d.cin, P + lp.d.w_off, lp.d.cout, pool_a, lp.d.cout);
-            a.scale = lp.fscale; a.shift = lp.fshift; a.act = lp.d.act;
-            RUNK(s->iPool, pw_bytes(a), launch_pointwise(a, ps));
-            // the broadcast pool branch enters concat_projection as a per-image bias: W_proj[0:256]^T . pool
-            PwArgs b = pw_args(pool_a, B, lp.d.cout, lp.d.cout, P + lc.d.w_off, lc.d.cout, img_bias, lc.d.cout);
-            RUNK(s->iProj, pw_bytes(b), launch_pointwise(b, ps));
-        }
-        if (fork) AMS_CHECK_HIP(hipEventRecord(s->ev_head, s->side));
-        const int o1 = other(cur_i, -1), o2 = other(cur_i, o1);
-        PwArgs a = pw_args(cur, M, la.d.cin, la.d.cin, P + la.d.w_off, la.d.cout, s->act[o1], la.d.cout);
-        a.scale = la.fscale; a.shift = la.fshift; a.act = la.d.act;
-        RUN(frozen_pointwise(s, s->iAspp, a, st));
-        if (fork) AMS_CHECK_HIP(hipStreamWaitEvent(st, s->ev_head, 0));
-        PwArgs b = pw_args(s->act[o1], M, la.d.cout, la.d.cout, P + lc.d.w_off + (int64_t)lp.d.cout * lc.d.cout, lc.d.cout,
-                           s->act[o2], lc.d.cout);
-        b.img_bias = img_bias; b.rows_per_img = HW; b.scale = lc.fscale; b.shift = lc.fshift; b.act = lc.d.act;
-        RUN(frozen_pointwise(s, s->iProj, b, st));
-        PwArgs d = pw_args(s->act[o2], M, lc.d.cout, lc.d.cout, P + ll.d.w_off, ll.d.cout, s->logits + (int64_t)B0 * HW * 32, 32);
-        d.shift = P + ll.d.gamma_off;      // biases
-        RUN(frozen_pointwise(s, s->iLogits, d, st));
-        return AMS_OK;
-    };
-    if (sub >= Bfull) {
-        RUN(run_blocks(s->n_backbone + 1));
-        return run_head(0);
-    }
-    RUN(run_blocks(i_late));                   // early section: the whole batch
-    float* late_in = cur;
-    const int late_in_i = cur_i;
+    RUN(run_blocks(s, v, c, i_late, st));      // early section: the whole batch
     const int64_t late_in_frame = s->L[i_late].px_in * s->L[i_late].d.cin;
-    reserved = late_in_i;
-    for (int B0 = 0; B0 < Bfull; B0 += sub) {
-        B = Bfull - B0 < sub ? Bfull - B0 : sub;
-        cur = late_in + (int64_t)B0 * late_in_frame;
-        cur_i = late_in_i;
-        cur_parts = nullptr;
-        i = i_late;
-        RUN(run_blocks(s->n_backbone + 1));
-        RUN(run_head(B0));
+    for (int b0 = 0; b0 < v.B; b0 += s->late_subbatch) {
+        const int bp = v.B - b0 < s->late_subbatch ? v.B - b0 : s->late_subbatch;
+        const FrozenView lv = view_late(s, v, b0, bp, c.cur_i);
+        Cursor lc = {i_late, c.cur + (int64_t)b0 * late_in_frame, c.cur_i, PartsFmt()};
+        RUN(run_blocks(s, lv, lc, s->n_backbone + 1, st));
+        RUN(run_head(s, lv, lc, st));
     }
     return AMS_OK;
 }
-
 
 // =======================================================================================================
 // live forward: training-mode BN.  z = raw conv output, batch statistics -> (scale, shift), a = act(z*scale+shift)(+res)
@@ -402,35 +513,41 @@ size_t red_rows_bound(int64_t M) {
     return tiled > streaming ? tiled : streaming;
 }
 
+// what finishing a training-mode BN layer takes besides its sums: their centre (shifted sums: moving_mean is a good, rank-identical
+// centre), 1 - decay and the moving statistics to update
+struct BnEma { const float* center; float omd; float *mm, *mv; };
+static BnEma bn_ema(const ams_student* s, const LayerRt& l, bool update_ema) {
+    return {s->stats + l.d.mean_off, 1.0f - s->cfg.bn_decay, update_ema ? s->stats + l.d.mean_off : nullptr, update_ema ? s->stats + l.d.var_off : nullptr};
+}
+// (scale, shift, mean, rstd) of layer l from the partial rows [rows][stride] a kernel left (sum | sum of squares first in each row): one
+// launch on a single rank, through the cross-rank sum of l.fsums otherwise
+static int bn_from_partials(ams_student* s, LayerRt& l, const BnEma& e, const float* part, int rows, int64_t stride, double n_global,
+                            const SyncCtx* sc, hipStream_t st) {
+    const float *gamma = s->params + l.d.gamma_off, *beta = s->params + l.d.beta_off;
+    if (!sc || !sc->cb)
+        return launch_bn_fwd_finalize_partials(part, rows, stride, l.d.cout, l.fsums, n_global, e.center, gamma, beta, l.d.bn_eps, e.omd, e.mm, e.mv,
+                                               l.scale, l.shift, l.mean, l.rstd, st);
+    RUN(launch_partials_to_sums(part, rows, stride, l.d.cout, l.fsums, st));
+    RUN(sync_doubles(sc, l.fsums, 2 * (size_t)l.d.cout, st));
+    return launch_bn_finalize(l.fsums, n_global, l.d.cout, e.center, gamma, beta, l.d.bn_eps, e.omd, e.mm, e.mv, l.scale, l.shift, l.mean, l.rstd, st);
+}
+
 // pre_rows > 0: the kernel that wrote l.z already left the statistics' partial rows [pre_rows][2][C] in s->scratch
 static int bn_train(ams_student* s, LayerRt& l, int64_t M_local, double n_global, bool update_ema, const SyncCtx* sc,
                     const float* res, hipStream_t st, int pre_rows = 0, bool act_pass = true) {
-    const ams_student_config& c = s->cfg;
-    const float* center = s->stats + l.d.mean_off;       // shifted sums: moving_mean is a good, rank-identical centre
-    const float omd = 1.0f - c.bn_decay;
-    float* mm = update_ema ? s->stats + l.d.mean_off : nullptr;
-    float* mv = update_ema ? s->stats + l.d.var_off : nullptr;
+    const BnEma e = bn_ema(s, l, update_ema);
     if (pre_rows > 0) {
-        if (!sc || !sc->cb) {
-            RUN(launch_bn_fwd_finalize_partials(s->scratch, pre_rows, 2 * (int64_t)l.d.cout, l.d.cout, l.fsums, n_global, center,
-                                                s->params + l.d.gamma_off, s->params + l.d.beta_off, l.d.bn_eps, omd, mm, mv, l.scale, l.shift,
-                                                l.mean, l.rstd, st));
-        } else {
-            RUN(launch_partials_to_sums(s->scratch, pre_rows, 2 * (int64_t)l.d.cout, l.d.cout, l.fsums, st));
-            RUN(sync_doubles(sc, l.fsums, 2 * (size_t)l.d.cout, st));
-            RUN(launch_bn_finalize(l.fsums, n_global, l.d.cout, center, s->params + l.d.gamma_off, s->params + l.d.beta_off, l.d.bn_eps, omd,
-                                   mm, mv, l.scale, l.shift, l.mean, l.rstd, st));
-        }
+        RUN(bn_from_partials(s, l, e, s->scratch, pre_rows, 2 * (int64_t)l.d.cout, n_global, sc, st));
     } else if (!sc || !sc->cb) {
         // no cross-rank sum between the statistics and their use: the reduction's second stage finishes the BN arithmetic
         RUNK(0, 4.0 * M_local * l.d.cout,
-             launch_colstats_bn(l.z, M_local, l.d.cout, center, l.fsums, s->scratch, n_global, s->params + l.d.gamma_off,
-                                s->params + l.d.beta_off, l.d.bn_eps, omd, mm, mv, l.scale, l.shift, l.mean, l.rstd, st));
+             launch_colstats_bn(l.z, M_local, l.d.cout, e.center, l.fsums, s->scratch, n_global, s->params + l.d.gamma_off,
+                                s->params + l.d.beta_off, l.d.bn_eps, e.omd, e.mm, e.mv, l.scale, l.shift, l.mean, l.rstd, st));
     } else {
-        RUNK(0, 4.0 * M_local * l.d.cout, launch_colstats(l.z, M_local, l.d.cout, center, l.fsums, s->scratch, st));
+        RUNK(0, 4.0 * M_local * l.d.cout, launch_colstats(l.z, M_local, l.d.cout, e.center, l.fsums, s->scratch, st));
         RUN(sync_doubles(sc, l.fsums, 2 * (size_t)l.d.cout, st));
-        RUN(launch_bn_finalize(l.fsums, n_global, l.d.cout, center, s->params + l.d.gamma_off, s->params + l.d.beta_off, l.d.bn_eps, omd,
-                               mm, mv, l.scale, l.shift, l.mean, l.rstd, st));
+        RUN(launch_bn_finalize(l.fsums, n_global, l.d.cout, e.center, s->params + l.d.gamma_off, s->params + l.d.beta_off, l.d.bn_eps, e.omd,
+                               e.mm, e.mv, l.scale, l.shift, l.mean, l.rstd, st));
     }
     if (!act_pass) return AMS_OK;              // the consumer applies scale / shift / activation on its own loads of z
     RUNK(0, 4.0 * M_local * l.d.cout * (res ? 3 : 2), launch_bn_act(l.z, M_local, l.d.cout, l.scale, l.shift, l.d.act, res, l.a, st));
@@ -475,10 +592,7 @@ int forward_live(ams_student* s, const void* frames, int dtype, int B, int globa
             // early block: neither z_e nor a_e is written.  Statistics of z_e = x . W_e straight from x, then the inference kernel
             // expand + BN + ReLU6 + depthwise with the batch statistics -> the depthwise layer's raw output
             LayerRt& ld = s->L[i + 1];
-            const float* center = s->stats + l.d.mean_off;
-            const float omd = 1.0f - c.bn_decay;
-            float* mm = update_ema ? s->stats + l.d.mean_off : nullptr;
-            float* mv = update_ema ? s->stats + l.d.var_off : nullptr;
+            const BnEma e = bn_ema(s, l, update_ema);
             const double n_e = (double)global_B * l.px_out;
             if (s->train_recompute >= 2 && l.xx64 && s->xx_scratch && l.d.cin <= 32 &&
                 xx_stats_scratch_doubles((int64_t)B * l.px_in, l.d.cin) <= s->xx_scratch_doubles) {
@@ -487,27 +601,18 @@ int forward_live(ams_student* s, const void* frames, int dtype, int B, int globa
                 const int KP = (l.d.cin + 15) / 16 * 16;
                 RUNK(i, 4.0 * B * l.px_in * l.d.cin, launch_xx_gram(x, (int64_t)B * l.px_in, l.d.cin, s->xx_scratch, l.xx64, l.xx_g0, st));
                 RUN(sync_doubles(sc, l.xx64, (size_t)KP * KP + KP, st));
-                RUN(launch_expand_stats(l.xx64, l.d.cin, P + l.d.w_off, l.d.cout, n_e, center, s->params + l.d.gamma_off, s->params + l.d.beta_off,
-                                        l.d.bn_eps, omd, mm, mv, l.scale, l.shift, l.mean, l.rstd, l.fsums, st));
+                RUN(launch_expand_stats(l.xx64, l.d.cin, P + l.d.w_off, l.d.cout, n_e, e.center, s->params + l.d.gamma_off, s->params + l.d.beta_off,
+                                        l.d.bn_eps, e.omd, e.mm, e.mv, l.scale, l.shift, l.mean, l.rstd, l.fsums, st));
             } else {
             int rows = 0;
             int64_t fstride = 0;
             RUNK(i, 4.0 * B * l.px_in * l.d.cin,
-                 launch_xdw_fwd_stats(x, B, l.Hin, l.Win, l.d.cin, P + l.d.w_off, l.d.cout, center, s->xt_scratch, &rows, &fstride, st));
+                 launch_xdw_fwd_stats(x, B, l.Hin, l.Win, l.d.cin, P + l.d.w_off, l.d.cout, e.center, s->xt_scratch, &rows, &fstride, st));
             {   // sums of x and x x^T over this rank's pixels, kept for the expand weight gradient
                 const int KP = (l.d.cin + 15) / 16 * 16;
                 RUN(launch_reduce_splits(s->xt_scratch + 2 * (int64_t)l.d.cout, rows, (int64_t)KP * KP + KP, l.xx_g0, st, fstride));
             }
-            if (!sc || !sc->cb) {
-                RUN(launch_bn_fwd_finalize_partials(s->xt_scratch, rows, fstride, l.d.cout, l.fsums, n_e, center,
-                                                    s->params + l.d.gamma_off, s->params + l.d.beta_off, l.d.bn_eps, omd, mm, mv, l.scale,
-                                                    l.shift, l.mean, l.rstd, st));
-            } else {
-                RUN(launch_partials_to_sums(s->xt_scratch, rows, fstride, l.d.cout, l.fsums, st));
-                RUN(sync_doubles(sc, l.fsums, 2 * (size_t)l.d.cout, st));
-                RUN(launch_bn_finalize(l.fsums, n_e, l.d.cout, center, s->params + l.d.gamma_off, s->params + l.d.beta_off, l.d.bn_eps, omd,
-                                       mm, mv, l.scale, l.shift, l.mean, l.rstd, st));
-            }
+            RUN(bn_from_partials(s, l, e, s->xt_scratch, rows, fstride, n_e, sc, st));
             }
             // ... which leaves the statistics of that raw output behind as one partial row per tile (no separate pass over z_d)
             int d_rows = 0;
@@ -585,33 +690,6 @@ int check_call(const ams_student* s, const void* frames, int dtype, int batch) {
     return AMS_OK;
 }
 
-// A slice of the student's frozen-inference buffers: frames b0 .. b0 + bp - 1 of every activation / head buffer (all sized for max_batch
-// frames).  While the guard lives, forward_frozen works inside that slice; the pointers come back whatever way the scope is left.
-struct SliceGuard {
-    ams_student* s;
-    float* act0[4]; uint16_t* xs0; size_t xp0; float *pooled0, *pool_a0, *img_bias0, *logits0, *scratch0;
-    SliceGuard(ams_student* s_, int b0, int bp) : s(s_) {
-        const ams_student_config& c = s->cfg;
-        for (int k = 0; k < 4; ++k) act0[k] = s->act[k];
-        xs0 = s->xsplit; xp0 = s->xsplit_plane;
-        pooled0 = s->pooled; pool_a0 = s->pool_a; img_bias0 = s->img_bias; logits0 = s->logits; scratch0 = s->scratch;
-        const LayerRt& lp = s->L[s->iPool]; const LayerRt& lc = s->L[s->iProj];
-        const size_t per_frame = s->act_elems / c.max_batch;
-        for (int k = 0; k < 4; ++k) s->act[k] = act0[k] + (size_t)b0 * per_frame;
-        if (xs0) { s->xsplit = xs0 + 3 * (xp0 / c.max_batch) * b0; s->xsplit_plane = (xp0 / c.max_batch) * bp; }
-        s->pooled = pooled0 + (size_t)b0 * lp.d.cin;
-        s->pool_a = pool_a0 + (size_t)b0 * lp.d.cout;
-        s->img_bias = img_bias0 + (size_t)b0 * lc.d.cout;
-        s->logits = logits0 + (size_t)b0 * s->h * s->w * 32;
-        s->scratch = scratch0 + image_colsum_scratch(b0, lp.d.cin);
-    }
-    ~SliceGuard() {
-        for (int k = 0; k < 4; ++k) s->act[k] = act0[k];
-        s->xsplit = xs0; s->xsplit_plane = xp0;
-        s->pooled = pooled0; s->pool_a = pool_a0; s->img_bias = img_bias0; s->logits = logits0; s->scratch = scratch0;
-    }
-};
-
 // Frozen inference as two to four parts on as many streams: the parts run the same layer sequence side by side (part 0 on the caller's
 // stream, the others on streams the student owns; one fork and one join per step), each in its own slice of every activation buffer.
 // A launch of this network rarely fills the chip to the end — tails of 1.05- or 2.1-round grids, latency-bound chains on a few blocks
@@ -629,15 +707,13 @@ static bool ensure_part_streams(ams_student* s, int nparts, hipStream_t st) {
     return true;
 }
 
-static int forward_frozen_dual(ams_student* s, const void* frames, int dtype, int batch, hipStream_t st, int nparts = 2) {
-    const ams_student_config& c = s->cfg;
-    if (nparts < 2) nparts = 2;
+// nparts <= 1: the one-stream plan
+static int forward_frozen_dual(ams_student* s, const void* frames, int dtype, int batch, hipStream_t st, int nparts) {
     if (nparts > 4) nparts = 4;
     if (nparts > batch) nparts = batch;
-    if (nparts < 2 || !ensure_part_streams(s, nparts, st)) return forward_frozen(s, frames, dtype, batch, st);
+    if (nparts < 2 || !ensure_part_streams(s, nparts, st)) return forward_frozen(s, view_whole(s, frames, batch), dtype, st);
     AMS_REQUIRE(s->ev_fork_dual && s->part_stream[nparts - 2] && s->part_done[nparts - 2], "dual plan: part streams were not created");
     AMS_CHECK_HIP(hipEventRecord(s->ev_fork_dual, st));
-    const size_t frame_bytes = (size_t)c.height * c.width * 3 * (dtype == AMS_DT_U8 ? 1 : 4);
     int rc = AMS_OK;
     int b0 = 0, forked = 0;
     for (int p = 0; p < nparts && !rc; ++p) {
@@ -647,10 +723,7 @@ static int forward_frozen_dual(ams_student* s, const void* frames, int dtype, in
             if (hipStreamWaitEvent(ps, s->ev_fork_dual, 0) != hipSuccess) { set_error("dual plan: fork failed"); rc = AMS_E_HIP; break; }
             forked = p;
         }
-        {
-            SliceGuard slice(s, b0, bp);
-            rc = forward_frozen(s, (const char*)frames + (size_t)b0 * frame_bytes, dtype, bp, ps);
-        }
+        rc = forward_frozen(s, view_slice(s, frames, dtype, b0, bp), dtype, ps);
         b0 += bp;
     }
     // join every stream that was forked, error or not: no part may still be writing the student's buffers after the return
@@ -677,13 +750,10 @@ static int dual_parts_static(int batch) {
 int run_forward(ams_student* s, const void* frames, int dtype, int batch, int mode, hipStream_t st) {
     if (mode == AMS_MODE_FROZEN) {
         if (!s->frozen_ready) { set_error("predict: ams_student_freeze has not been called"); return AMS_E_STATE; }
-        if (s->dual_stream == 0 || s->prof.on || s->late_subbatch != 0 || batch < 2) return forward_frozen(s, frames, dtype, batch, st);
-        if (s->dual_stream >= 2) return batch >= s->dual_stream ? forward_frozen_dual(s, frames, dtype, batch, st, s->dual_parts) : forward_frozen(s, frames, dtype, batch, st);
-        if (!s->dual_autotune) {
-            const int n = dual_parts_static(batch);
-            return n > 1 ? forward_frozen_dual(s, frames, dtype, batch, st, n) : forward_frozen(s, frames, dtype, batch, st);
-        }
-        if (batch < 16) return forward_frozen(s, frames, dtype, batch, st);
+        if (s->dual_stream == 0 || s->prof.on || s->late_subbatch != 0 || batch < 2) return forward_frozen_dual(s, frames, dtype, batch, st, 1);
+        if (s->dual_stream >= 2) return forward_frozen_dual(s, frames, dtype, batch, st, batch >= s->dual_stream ? s->dual_parts : 1);
+        if (!s->dual_autotune) return forward_frozen_dual(s, frames, dtype, batch, st, dual_parts_static(batch));
+        if (batch < 16) return forward_frozen_dual(s, frames, dtype, batch, st, 1);
         auto it = s->dual_choice.find(batch);
         if (it == s->dual_choice.end()) {
             // AMS_OPT_DUAL_AUTOTUNE (opt-in; this branch synchronises the host): the first call with this batch size times the one-stream
@@ -691,7 +761,7 @@ int run_forward(ams_student* s, const void* frames, int dtype, int batch, int mo
             // multi-part plan only when it wins by more than the timing noise, and finishes with a pass of the chosen plan
             hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
             (void)hipStreamIsCapturing(st, &cap);
-            if (cap != hipStreamCaptureStatusNone) return forward_frozen(s, frames, dtype, batch, st);      // no timing inside a capture
+            if (cap != hipStreamCaptureStatusNone) return forward_frozen_dual(s, frames, dtype, batch, st, 1);      // no timing inside a capture
             hipEvent_t e0 = nullptr, e1 = nullptr;
             AMS_CHECK_HIP(hipEventCreate(&e0));
             if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); set_error("autotune: hipEventCreate failed"); return AMS_E_HIP; }
@@ -701,10 +771,10 @@ int run_forward(ams_student* s, const void* frames, int dtype, int batch, int mo
             const int max_parts = batch >= 32 ? 4 : batch >= 24 ? 3 : 2;       // parts of at least 8 frames
             for (int n = 1; n <= max_parts && !rc && he == hipSuccess; ++n) {
                 float t[3] = {0.f, 0.f, 0.f};
-                rc = n > 1 ? forward_frozen_dual(s, frames, dtype, batch, st, n) : forward_frozen(s, frames, dtype, batch, st);      // warm-up
+                rc = forward_frozen_dual(s, frames, dtype, batch, st, n);      // warm-up
                 for (int rep = 0; rep < 3 && !rc && he == hipSuccess; ++rep) {
                     he = hipEventRecord(e0, st);
-                    rc = n > 1 ? forward_frozen_dual(s, frames, dtype, batch, st, n) : forward_frozen(s, frames, dtype, batch, st);
+                    rc = forward_frozen_dual(s, frames, dtype, batch, st, n);
                     if (he == hipSuccess) he = hipEventRecord(e1, st);
                     if (he == hipSuccess) he = hipEventSynchronize(e1);
                     if (he == hipSuccess) he = hipEventElapsedTime(&t[rep], e0, e1);
@@ -721,7 +791,7 @@ int run_forward(ams_student* s, const void* frames, int dtype, int batch, int mo
                 if (ms[n] < 0.985f * ms[1] && (best == 1 || ms[n] < ms[best])) best = n;
             it = s->dual_choice.emplace(batch, best).first;
         }
-        return it->second > 1 ? forward_frozen_dual(s, frames, dtype, batch, st, it->second) : forward_frozen(s, frames, dtype, batch, st);
+        return forward_frozen_dual(s, frames, dtype, batch, st, it->second);
     }
     if (mode == AMS_MODE_LIVE) return forward_live(s, frames, dtype, batch, batch, /*update_ema=*/false, nullptr, st);
     set_error("predict: unknown mode %d", mode);
