@@ -88,3 +88,41 @@ def build_mask(train_strategy: str, coord_frac: float, shapes: Dict[str, tuple])
         else:
             out[k] = np.zeros(s, dtype=bool)
     return out
+
+
+# ---- coord_desc_auto: np.percentile's threshold from two order statistics ------------------------------------------------------------------
+# The reference cuts at np.percentile(changes, 100 * (1 - coord_frac)) over the float32 changes (SemanticNetwork.py:267-271).  With the default
+# 'linear' method NumPy forms the virtual index (n - 1) * (q / float32(100)) in FLOAT32 (the divisor takes the array's dtype), interpolates
+# between the order statistics around it in float32 and returns a float32.  The device path finds those two order statistics
+# (ams_select_changed); the two functions below repeat NumPy's expressions on them, operand for operand, so that the cut has np.percentile's
+# bits (tests/test_select_cpu.py holds them to np.percentile itself).
+def _virtual_index(n: int, q):
+    quantile = np.asanyarray(np.true_divide(q, np.float32(100)))
+    return np.asanyarray((int(n) - 1) * quantile)
+
+
+def percentile_rank(n: int, q) -> int:
+    """0-based rank k of the lower order statistic ``np.percentile(x, q)`` reads from a float32 array of ``n`` elements; the upper one is
+    rank k + 1, or k again at the top end."""
+    assert n > 0
+    virtual = _virtual_index(n, q)
+    if virtual >= n - 1:
+        return n - 1
+    return int(np.floor(virtual))
+
+
+def percentile_cut(a, b, n: int, q, nan_count: int = 0) -> np.float32:
+    """``np.percentile(x, q)`` of a float32 array of ``n`` elements, given a = its element of rank ``percentile_rank(n, q)`` (ascending), b = the
+    element of the next rank (a again at the top end) and the number of NaNs in it (any NaN makes the percentile NaN)."""
+    if nan_count > 0:
+        return np.float32(np.nan)
+    virtual = _virtual_index(n, q)
+    # at the top end both neighbours are the last element and NumPy takes gamma from its index, -1 (b - a is 0 there)
+    previous = np.asanyarray(-1, dtype=virtual.dtype) if virtual >= n - 1 else np.floor(virtual)
+    gamma = np.asanyarray(virtual - previous, dtype=virtual.dtype)
+    a, b = np.float32(a), np.float32(b)
+    with np.errstate(invalid="ignore", over="ignore"):
+        diff = np.subtract(b, a)
+        cut = np.asanyarray(np.add(a, diff * gamma))
+        np.subtract(b, diff * (1 - gamma), out=cut, where=gamma >= 0.5, casting="unsafe", dtype=type(cut.dtype))
+    return np.float32(cut[()])

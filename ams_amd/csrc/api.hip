@@ -424,20 +424,20 @@ int ams_pack_masked_fp16(const float* params_dev, const uint8_t* mask_dev, int64
 }
 
 // mask section of a descriptor table, or -1 if the table does not describe contiguous masks inside the arena (reason in the error)
-static int64_t delta_mask_bytes(const ams_student* s, const ams_delta_var* vars, int32_t n_vars) {
-    if (!vars || n_vars < 1 || n_vars > AMS_DELTA_MAX_VARS) { set_error("apply_delta: %d variables (1 .. %d)", n_vars, AMS_DELTA_MAX_VARS); return -1; }
+static int64_t delta_mask_bytes(const ams_student* s, const ams_delta_var* vars, int32_t n_vars, const char* what = "apply_delta") {
+    if (!vars || n_vars < 1 || n_vars > AMS_DELTA_MAX_VARS) { set_error("%s: %d variables (1 .. %d)", what, n_vars, AMS_DELTA_MAX_VARS); return -1; }
     int64_t mask = 0;
     for (int32_t i = 0; i < n_vars; ++i) {
         const ams_delta_var& d = vars[i];
         const int64_t n_region = d.region == AMS_REGION_PARAMS ? (int64_t)s->cfg.n_trainable : d.region == AMS_REGION_STATS ? (int64_t)s->cfg.n_stats : -1;
-        if (n_region < 0) { set_error("apply_delta: variable %d: region %d is neither params nor stats", i, d.region); return -1; }
+        if (n_region < 0) { set_error("%s: variable %d: region %d is neither params nor stats", what, i, d.region); return -1; }
         if (d.offset < 0 || d.count < 0 || d.offset > n_region - d.count) {
-            set_error("apply_delta: variable %d: elements [%lld, +%lld) outside its region of %lld", i, (long long)d.offset, (long long)d.count,
+            set_error("%s: variable %d: elements [%lld, +%lld) outside its region of %lld", what, i, (long long)d.offset, (long long)d.count,
                       (long long)n_region);
             return -1;
         }
         if (d.mask_offset != mask) {
-            set_error("apply_delta: variable %d: mask at byte %lld, the masks before it end at %lld", i, (long long)d.mask_offset, (long long)mask);
+            set_error("%s: variable %d: mask at byte %lld, the masks before it end at %lld", what, i, (long long)d.mask_offset, (long long)mask);
             return -1;
         }
         mask += (d.count + 7) / 8;
@@ -473,6 +473,56 @@ int ams_student_apply_delta(ams_student* s, const uint8_t* payload_dev, int64_t 
     AMS_CHECK_HIP(hipEventRecord(s->ev_delta, st));
     return launch_apply_delta(payload_dev, payload_bytes, vars_dev, n_vars, mask_bytes, s->params, (int64_t)s->cfg.n_trainable, s->stats,
                               (int64_t)s->cfg.n_stats, scratch_dev + 4 * n_vars, n_applied_dev, status_dev, st);
+}
+
+size_t ams_select_changed_scratch(int64_t n) { return n > 0 ? select_scratch() : 0; }
+
+int ams_select_changed(const float* after_dev, const float* before_dev, int64_t n, int64_t k, ams_select_result* result_dev,
+                       int64_t* scratch_dev, size_t scratch_elems, void* stream) {
+    AMS_REQUIRE(after_dev && before_dev && result_dev && scratch_dev, "select_changed: null pointer");
+    AMS_REQUIRE(n > 0 && n < ((int64_t)1 << 31) && k >= 0 && k < n, "select_changed: rank %lld of %lld elements (0 <= k < n < 2^31)", (long long)k,
+                (long long)n);
+    AMS_REQUIRE(((uintptr_t)result_dev & 7) == 0 && ((uintptr_t)after_dev & 3) == 0 && ((uintptr_t)before_dev & 3) == 0, "select_changed: misaligned pointer");
+    AMS_REQUIRE(scratch_elems >= select_scratch(), "select_changed: scratch too small (need %zu int64)", select_scratch());
+    return launch_select_changed(after_dev, before_dev, n, k, result_dev, scratch_dev, (hipStream_t)stream);
+}
+
+int ams_select_apply(float* params_dev, const float* before_dev, int64_t n, float cut, uint8_t* mask_dev, int64_t* n_kept_dev, void* stream) {
+    AMS_REQUIRE(params_dev && before_dev && mask_dev && n_kept_dev && n > 0, "select_apply: bad argument");
+    AMS_REQUIRE(((uintptr_t)n_kept_dev & 7) == 0 && ((uintptr_t)params_dev & 3) == 0 && ((uintptr_t)before_dev & 3) == 0, "select_apply: misaligned pointer");
+    return launch_select_apply(params_dev, before_dev, n, cut, mask_dev, n_kept_dev, (hipStream_t)stream);
+}
+
+size_t ams_student_encode_delta_scratch(const ams_delta_var* vars_host, int32_t n_vars) {
+    if (!vars_host || n_vars < 1 || n_vars > AMS_DELTA_MAX_VARS) return 0;
+    int64_t mask = 0;
+    for (int32_t i = 0; i < n_vars; ++i) mask += vars_host[i].count > 0 ? (vars_host[i].count + 7) / 8 : 0;
+    return (size_t)(5 * (int64_t)n_vars + 2 + encode_segments(mask));
+}
+
+int ams_student_encode_delta(ams_student* s, const uint8_t* mask_dev, const ams_delta_var* vars_host, int32_t n_vars, uint8_t* payload_dev,
+                             int64_t payload_cap, int64_t* payload_bytes_dev, int64_t* scratch_dev, size_t scratch_elems, void* stream) {
+    AMS_REQUIRE(s && payload_dev && payload_bytes_dev && scratch_dev, "encode_delta: null pointer");
+    const int64_t mask_bytes = delta_mask_bytes(s, vars_host, n_vars, "encode_delta");
+    if (mask_bytes < 0) return AMS_E_INVALID;
+    AMS_REQUIRE(payload_cap >= mask_bytes, "encode_delta: room for %lld bytes, the mask section alone has %lld", (long long)payload_cap,
+                (long long)mask_bytes);
+    const size_t table = 5 * (size_t)n_vars + 1;
+    const size_t need = table + 1 + (size_t)encode_segments(mask_bytes);
+    AMS_REQUIRE(scratch_elems >= need, "encode_delta: scratch too small (need %zu int64)", need);
+    hipStream_t st = (hipStream_t)stream;
+    // as in apply_delta: the table (descriptors, then each variable's first element in layout order) travels from a host copy the handle keeps
+    if (s->ev_encode) AMS_CHECK_HIP(hipEventSynchronize(s->ev_encode));
+    else RUN(create_sync_event(&s->ev_encode));
+    s->encode_table.resize(table);
+    memcpy(s->encode_table.data(), vars_host, n_vars * sizeof(ams_delta_var));
+    int64_t first = 0;
+    for (int32_t i = 0; i < n_vars; ++i) { s->encode_table[4 * (size_t)n_vars + i] = first; first += vars_host[i].count; }
+    s->encode_table[table - 1] = first;
+    AMS_CHECK_HIP(hipMemcpyAsync(scratch_dev, s->encode_table.data(), table * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    AMS_CHECK_HIP(hipEventRecord(s->ev_encode, st));
+    return launch_encode_delta(mask_dev, scratch_dev, n_vars, mask_bytes, s->params, s->stats, scratch_dev + table, payload_dev, payload_cap,
+                               payload_bytes_dev, st);
 }
 
 // ---- kernel-level entry points -----------------------------------------------------------------------------

@@ -107,6 +107,8 @@ struct ams_student {
     hipEvent_t ev_tp = nullptr;
     std::vector<ams_delta_var> delta_vars;                       // ams_student_apply_delta: the descriptor table the last call uploaded, kept
     hipEvent_t ev_delta = nullptr;                               // alive until its upload (ev_delta) has read it
+    std::vector<int64_t> encode_table;                           // ams_student_encode_delta: the same for its table (descriptors + element starts)
+    hipEvent_t ev_encode = nullptr;
     float* dlogits = nullptr;
     float* ce_scratch = nullptr;       // unnormalised CE gradient planes of the one-pass loss kernel (k_head.hip)
     // fine-tune step of the early blocks without their 6x-expanded tensors (k_xdw_train.hip): AMS_OPT_TRAIN_RECOMPUTE, default on
@@ -172,6 +174,7 @@ struct ams_student {
         if (ev_xt) (void)hipEventDestroy(ev_xt);
         if (ev_tp) (void)hipEventDestroy(ev_tp);
         if (ev_delta) (void)hipEventDestroy(ev_delta);
+        if (ev_encode) (void)hipEventDestroy(ev_encode);
     }
     float* scratch = nullptr; size_t scratch_floats = 0;
     float* tmp_c = nullptr;          // [1024] small per-channel temp

@@ -13,6 +13,7 @@
 //                       of the variables' mask offsets held in LDS
 #include "common.hpp"
 #include "kernels.hpp"
+#include "block_scan.hpp"
 
 #include <hip/hip_fp16.h>
 
@@ -20,7 +21,7 @@ namespace ams {
 
 namespace {
 
-constexpr int DELTA_THREADS = 256;
+constexpr int DELTA_THREADS = BLOCK_SCAN_THREADS;
 constexpr int64_t DELTA_SEG = 8 * DELTA_THREADS;          // mask bytes per segment: 8 per thread
 
 // mask bytes [b, b + 8) clipped at e, as one word in element order: bit 63 = bit 7 of byte b
@@ -29,33 +30,6 @@ __device__ inline uint64_t mask_word(const uint8_t* p, int64_t b, int64_t e) {
     uint64_t w = 0;
     for (int k = 0; k < 8; ++k) w = (w << 8) | (uint64_t)(b + k < e ? p[b + k] : 0);
     return w;
-}
-
-__device__ inline int64_t block_sum(int64_t v, int64_t* sh) {
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = DELTA_THREADS / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-        __syncthreads();
-    }
-    const int64_t r = sh[0];
-    __syncthreads();
-    return r;
-}
-
-// exclusive prefix of v over the block's threads (Hillis-Steele in LDS; 256 entries)
-__device__ inline int64_t block_exclusive_scan(int64_t v, int64_t* sh) {
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = 1; o < DELTA_THREADS; o <<= 1) {
-        const int64_t add = (int)threadIdx.x >= o ? sh[threadIdx.x - o] : 0;
-        __syncthreads();
-        sh[threadIdx.x] += add;
-        __syncthreads();
-    }
-    const int64_t r = sh[threadIdx.x] - v;
-    __syncthreads();
-    return r;
 }
 
 }  // namespace

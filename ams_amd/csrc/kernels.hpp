@@ -353,6 +353,14 @@ int64_t delta_segments(int64_t mask_bytes);
 int launch_apply_delta(const uint8_t* payload, int64_t payload_bytes, const ams_delta_var* vars_dev, int n_vars, int64_t mask_bytes,
                        float* params, int64_t n_params, float* stats, int64_t n_stats, int64_t* counts, int64_t* n_applied, int32_t* status,
                        hipStream_t st);
+// k_select.hip: the server half of a model update: coordinates chosen by their change, the roll-back, the downlink delta encoded
+size_t select_scratch();
+int launch_select_changed(const float* after, const float* before, int64_t n, int64_t k, ams_select_result* result, int64_t* scratch,
+                          hipStream_t st);
+int launch_select_apply(float* params, const float* before, int64_t n, float cut, uint8_t* mask, int64_t* n_kept, hipStream_t st);
+int64_t encode_segments(int64_t mask_bytes);
+int launch_encode_delta(const uint8_t* mask, const int64_t* table_dev, int n_vars, int64_t mask_bytes, const float* params, const float* stats,
+                        int64_t* work, uint8_t* payload, int64_t cap, int64_t* payload_bytes, hipStream_t st);
 
 // ---- k_head.hip : fused upsample + argmax + metrics, CE gradient, phi-score confusion --------------------
 // per_frame != 0: conf [B][K][K] and loss [B][2] (one confusion matrix / loss pair per frame) instead of the batch totals

@@ -13,7 +13,7 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 import torch
 
-from . import hip
+from . import coord_masks, hip
 from .spec import (BN_DECAY, BN_EPS_FROZEN, PIXEL_SCALE, Layer, StudentSpec, build_spec)
 from . import weights as W
 
@@ -140,6 +140,9 @@ class StudentEngine:
         self._delta_words = torch.zeros(2, dtype=torch.int64, device=self.device)           # [values applied, status (int32)]
         self._updated_since_freeze = False
         self._fallback_layers = 0
+        # server-side model updates (select_changed, encode_delta): scratch (created on first use), [a, b | NaN changes | kept | payload bytes]
+        self._select_scratch = self._encode_scratch = None
+        self._select_words = torch.zeros(4, dtype=torch.int64, device=self.device)
         self.generation = 0
         for name, opt in _ENV_OPTIONS.items():
             if name in os.environ:
@@ -419,6 +422,57 @@ class StudentEngine:
         if applied:
             self._updated_since_freeze = True
         return applied
+
+    # ------------------------------------------------------------------ server-side model updates (k_select.hip)
+    def snapshot_params(self) -> torch.Tensor:
+        """A device copy of the trainable arena: the ``before`` of ``select_changed``."""
+        return self.params.clone()
+
+    def select_changed(self, before: torch.Tensor, frac: float):
+        """coord_desc_auto's selection on the device (reference SemanticNetwork.py:263-288): keeps the coordinates whose |params - before| lies
+        above ``np.percentile(changes, 100 * (1 - frac))`` and sets the others back to ``before``.  Returns (mask uint8 [n_trainable] on the
+        device, the number kept as an int64 device tensor of one element).  The two order statistics the percentile interpolates between
+        come back to the host (16 bytes, the one synchronisation) and the threshold is formed there with NumPy's arithmetic
+        (``coord_masks.percentile_cut``), so it has np.percentile's bits; Adam moments and statistics are not touched."""
+        n = self.spec.n_trainable
+        assert before.dtype == torch.float32 and before.numel() == n and before.device == self.arena.device
+        q = 100 * (1 - frac)
+        k = coord_masks.percentile_rank(n, q)
+        if self._select_scratch is None:
+            self._select_scratch = torch.empty(int(self.lib.ams_select_changed_scratch(n)), dtype=torch.int64, device=self.device)
+        words = self._select_words
+        hip.check(self.lib.ams_select_changed(C.c_void_p(self.params.data_ptr()), C.c_void_p(before.data_ptr()), n, k, C.c_void_p(words.data_ptr()),
+                                              C.c_void_p(self._select_scratch.data_ptr()), self._select_scratch.numel(), self._stream()),
+                  "ams_select_changed")
+        w = words[:2].cpu().numpy()
+        a, b = w[:1].view(np.float32)
+        cut = coord_masks.percentile_cut(a, b, n, q, int(w[1]))
+        mask = torch.empty(n, dtype=torch.uint8, device=self.device)
+        hip.check(self.lib.ams_select_apply(C.c_void_p(self.params.data_ptr()), C.c_void_p(before.data_ptr()), n, float(cut),
+                                            C.c_void_p(mask.data_ptr()), C.c_void_p(words.data_ptr() + 16), self._stream()), "ams_select_apply")
+        return mask, words[2:3].clone()
+
+    def encode_delta(self, layout, mask: Optional[torch.Tensor] = None, cap: Optional[int] = None) -> torch.Tensor:
+        """The downlink delta of ``layout`` (an ``ams_amd.delta.DeltaLayout``) encoded on the device from the current variables: the bytes of
+        ``SemanticNetwork.delta_payload`` as a uint8 device tensor (what ``apply_delta`` accepts).  ``mask``: uint8 on the device, one entry per
+        element in layout order (the trainable layout: arena order), None = every element.  ``cap``: bytes of the output buffer (default: the
+        layout's largest payload); a payload beyond it raises AmsHipError with nothing written.  Synchronises once (the payload's size)."""
+        if mask is not None:
+            assert mask.dtype == torch.uint8 and mask.numel() == layout.n_elements and mask.device == self.arena.device
+        table = layout.table()
+        need = int(self.lib.ams_student_encode_delta_scratch(table, len(table)))
+        if self._encode_scratch is None or self._encode_scratch.numel() < need:
+            self._encode_scratch = torch.empty(need, dtype=torch.int64, device=self.device)
+        cap = layout.max_payload_bytes if cap is None else int(cap)
+        out = torch.empty(cap, dtype=torch.uint8, device=self.device)
+        size = self._select_words.data_ptr() + 24
+        hip.check(self.lib.ams_student_encode_delta(self._h, C.c_void_p(mask.data_ptr()) if mask is not None else None, table, len(table),
+                                                    C.c_void_p(out.data_ptr()), cap, C.c_void_p(size), C.c_void_p(self._encode_scratch.data_ptr()),
+                                                    self._encode_scratch.numel(), self._stream()), "ams_student_encode_delta")
+        nbytes = int(self._select_words[3].item())
+        if nbytes > cap:
+            raise hip.AmsHipError("encode_delta: the payload has %d bytes, the buffer %d; nothing was written" % (nbytes, cap))
+        return out[:nbytes]
 
     # ------------------------------------------------------------------ compute
     def predict(self, frames, mode: int = hip.MODE_FROZEN) -> torch.Tensor:

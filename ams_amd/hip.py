@@ -116,6 +116,11 @@ SIGNATURES = {
     "ams_pack_masked_fp16_scratch": (_sz, [_i64]),
     "ams_student_apply_delta": (C.c_int, [_vp, _vp, _i64, C.POINTER(DeltaVar), _i32, _vp, _vp, _vp, _sz, _vp]),
     "ams_student_apply_delta_scratch": (_sz, [C.POINTER(DeltaVar), _i32]),
+    "ams_select_changed": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _sz, _vp]),
+    "ams_select_changed_scratch": (_sz, [_i64]),
+    "ams_select_apply": (C.c_int, [_vp, _vp, _i64, _f32, _vp, _vp, _vp]),
+    "ams_student_encode_delta": (C.c_int, [_vp, _vp, C.POINTER(DeltaVar), _i32, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "ams_student_encode_delta_scratch": (_sz, [C.POINTER(DeltaVar), _i32]),
     "ams_k_stem_conv": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _f32, _vp, _vp]),
     "ams_k_depthwise3x3": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp]),
     "ams_k_pointwise": (C.c_int, [_vp, _i64, _i32, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp]),

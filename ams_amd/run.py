@@ -39,6 +39,7 @@ from typing import List, Optional, Tuple
 
 import numpy as np
 
+from .delta import delta_layout
 from .exp_configs import class_weights, coco_class_converter, is_coco, test_length
 from .semantic_network import FrozenGraph, SemanticNetwork
 from .synth import SyntheticVideo
@@ -90,6 +91,9 @@ def build_parser() -> argparse.ArgumentParser:
                    help="score the edge model the downlink payload produces (extra flag): the server also writes each event's raw payload "
                         "(<label>_<second>_delta.bin), and the edge keeps its network and applies that payload to the initial model "
                         "(--no_restore: to its previous model) on the device instead of reloading the server's full f32 model")
+    p.add_argument("--device_masks", action="store_true",
+                   help="server: choose coord_desc_auto's coordinates, keep the masks and encode the downlink payload on the device (extra "
+                        "flag; same files and numbers)")
     p.add_argument("--horizon_k1s", default="16,32,64,128,256,512", help="horizon mode: training-window lengths in seconds (reference: hard-coded)")
     p.add_argument("--horizon_k2", type=int, default=256, help="horizon mode: evaluation window in seconds (reference: 256)")
     p.add_argument("--horizon_points", type=int, default=3, help="horizon mode: number of evaluation points (reference: 3)")
@@ -237,7 +241,8 @@ def train_model(ctx: Context, train_start, train_end, sampling_period, gpu_id, r
                                        lr=FLAGS.lr, mem_frac=1, coord_frac=float(FLAGS.coord_fraction),
                                        train_biases_only=False, regularize=False,
                                        masked_gradients=FLAGS.train_strategy not in ['full_model'],
-                                       cross_miou_compat=FLAGS.enable_ASR, initial_variables=ctx.initial_variables)
+                                       cross_miou_compat=FLAGS.enable_ASR, initial_variables=ctx.initial_variables,
+                                       **({"device_masks": True} if getattr(FLAGS, "device_masks", False) else {}))
     save_dir = ctx.save_dir(run_label + "_%d" % train_start)
     semantic_network.save_to_frozen_graph(save_dir + "_final")
     print_process("Saved model to %s_final.pb" % save_dir, 0)
@@ -310,7 +315,10 @@ def train_model(ctx: Context, train_start, train_end, sampling_period, gpu_id, r
             print("Training for %d iterations took %d ms!!!" % (FLAGS.iter, train_ms[-1]))
             # model delta on the downlink: packed mask bits + masked parameters as fp16, gzip -9 (run.py:316-336)
             payload = semantic_network.delta_payload()          # value part gathered + cast to fp16 on the device
-            full_size = sum(val.size for val in semantic_network.curr_mask)
+            if getattr(FLAGS, "device_masks", False):          # the same number from the layout: curr_mask stays on the device
+                full_size = delta_layout(semantic_network.engine.spec, FLAGS.train_strategy).n_elements
+            else:
+                full_size = sum(val.size for val in semantic_network.curr_mask)
             with open(save_dir + '_mask.dat', 'wb') as f:
                 f.write(payload)
             with gzip.open(save_dir + '_mask.dat.gz', 'wb', compresslevel=9) as f:

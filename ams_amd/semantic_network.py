@@ -11,6 +11,7 @@ Deliberate differences (all listed in INTEGRATION.md):
     gamma/beta, moving statistics; reference utils/graph_utils.py:52-126) is the same, the bytes are not.
   * ``infer`` / ``train_step`` aliases are added (BASELINE.json north-star names).
   * per-iteration loss printing is off unless ``verbose=True`` (each print forces a device sync).
+  * ``device_masks=True`` keeps the server side of a model update on the device (coordinate selection, masks, the delta's bytes); same results.
 """
 from __future__ import annotations
 
@@ -26,6 +27,7 @@ import numpy as np
 import torch
 
 from . import coord_masks, hip
+from . import weights as W
 from .delta import delta_layout
 from .engine import StudentEngine
 from .utils import calculate_miou, colormap, mini_batch
@@ -118,6 +120,8 @@ class SemanticNetwork(object):
         max_batch = kwargs.pop("max_batch", None)
         # frozen only: depth of the asynchronous single-call pipeline (predict_with_metric_async / collect); 1 = off
         self.pipeline_depth = int(kwargs.pop("pipeline_depth", 1))
+        # training only: masks, coord_desc_auto's selection and the delta's bytes stay on the device (same results; see _train, delta_payload)
+        self.device_masks = bool(kwargs.pop("device_masks", False)) and not frozen
         assert 1 <= self.pipeline_depth <= 4, "pipeline_depth must be 1 .. 4"
         assert not kwargs, "unknown arguments: %s" % sorted(kwargs)
 
@@ -171,6 +175,64 @@ class SemanticNetwork(object):
                 need = self.engine.arena_bytes
                 self.engine.close()
                 raise MemoryError("the student's arena (%.2f GB) exceeds mem_frac = %g of the device's %.1f GB" % (need / 1e9, self._mem_frac, total / 1e9))
+
+    # ------------------------------------------------------------------ mask / curr_mask / train_params
+    # Plain attributes on the host path.  With device_masks=True a phase leaves them on the device (``_held``: the phase's device mask and a
+    # device copy of the variables at its end) and the first read brings them to the host, with the values, types and shapes of the host path.
+    def _lazy(name):
+        def get(self):
+            if name not in self.__dict__:
+                self._materialise(name)
+            return self.__dict__.get(name)
+
+        def put(self, value):
+            self.__dict__[name] = value
+            if name == "mask" and value is None:
+                self.__dict__.pop("_auto_mask_dev", None)
+
+        return property(get, put)
+
+    mask = _lazy("mask")
+    curr_mask = _lazy("curr_mask")
+    train_params = _lazy("train_params")
+    del _lazy
+
+    def _materialise(self, name):
+        spec = self.engine.spec
+        if name == "mask":                                    # coord_desc_auto's selection, kept for keep_mask=True
+            kept = self.__dict__.get("_auto_mask_dev")
+            if kept is not None:
+                flat = kept.cpu().numpy().astype(bool)
+                self.__dict__["mask"] = {v.name: flat[v.offset:v.offset + v.size].reshape(v.shape) for v in spec.trainable}
+            return
+        held = self.__dict__.get("_held")
+        if held is None:
+            return
+        if held["mask"] is not None:                          # a coord_desc_* phase: the trainable variables in arena order
+            if name == "curr_mask":
+                flat = held["mask"].cpu().numpy().astype(bool)
+                value = [flat[v.offset:v.offset + v.size].reshape(v.shape) for v in spec.trainable]
+            else:
+                flat = held["params"].cpu().numpy()
+                value = [flat[v.offset:v.offset + v.size].reshape(v.shape) for v in spec.trainable]
+        else:                                                 # full_model: every variable, all-ones masks
+            every = W.unpack(spec, held["params"].cpu().numpy(), held["stats"].cpu().numpy())
+            value = [every[k] for k in every.keys()] if name == "train_params" else [np.ones_like(every[k], dtype=bool) for k in every.keys()]
+        self.__dict__[name] = value
+
+    def _hold_phase(self, train_strategy, mask_dev):
+        """End of a device_masks phase: what curr_mask / train_params / delta_payload are made from, without a copy to the host."""
+        eng = self.engine
+        held = self.__dict__.get("_held") or {"params": torch.empty_like(eng.params), "stats": None}
+        held["params"].copy_(eng.params)
+        if mask_dev is None:
+            if held["stats"] is None:
+                held["stats"] = torch.empty_like(eng.stats)
+            held["stats"].copy_(eng.stats)
+        held["mask"], held["strategy"] = mask_dev, train_strategy
+        self.__dict__["_held"] = held
+        self.__dict__.pop("curr_mask", None)
+        self.__dict__.pop("train_params", None)
 
     # ------------------------------------------------------------------ variables (SaveHelper semantics)
     def _restore_dict(self, variables: Dict[str, np.ndarray]) -> None:
@@ -379,8 +441,13 @@ class SemanticNetwork(object):
         ctx["fill_thr"] = fill_thr                  # joined by train_with_deque's finally, whatever happens below
         fill_thr.start()
 
-        _before, train_mask_ = self.get_train_mask(train_strategy)
-        mask_dev = self._mask_to_device(train_mask_) if train_mask_ is not None else None
+        on_device = getattr(self, "device_masks", False)
+        before_dev = None
+        if on_device:
+            before_dev, mask_dev = self._device_train_mask(train_strategy)
+        else:
+            _before, train_mask_ = self.get_train_mask(train_strategy)
+            mask_dev = self._mask_to_device(train_mask_) if train_mask_ is not None else None
         losses = []
         t_phase = time.time()
         for it in range(num_of_iterations):
@@ -406,7 +473,16 @@ class SemanticNetwork(object):
                 ls = loss_dev.cpu().numpy()
                 print('Loss is %.3f at iteration %d and took %.1f ms' % (ls[0] / max(ls[1], 1), it,
                                                                          (time.time() - t1) * 1000.0))
-            if train_strategy == 'coord_desc_auto':
+            if on_device:
+                if it == 0 and before_dev is not None:
+                    # the same selection on the device: two order statistics of |delta w| come back, the threshold is np.percentile's
+                    mask_dev, kept = self.engine.select_changed(before_dev, self.coord_frac)
+                    before_dev = None
+                    if self.verbose:
+                        print("Using auto mode, Training %.3f%% of variables" % (100 * int(kept.item()) / mask_dev.numel()))
+                    self.__dict__.pop("mask", None)
+                    self.__dict__["_auto_mask_dev"] = mask_dev
+            elif train_strategy == 'coord_desc_auto':
                 if it == 0 and self.mask is None:
                     # derive the mask from the first step's |delta w|: keep the top coord_frac, roll back the rest
                     _after = self._model_vars()
@@ -432,6 +508,10 @@ class SemanticNetwork(object):
         self.last_losses = [float(s / c) if c > 0 else float("nan") for s, c in stacked]
         self._last_train_ms = (time.time() - t_phase) * 1000.0
 
+        if on_device:
+            self._hold_phase(train_strategy, mask_dev)
+            return
+        self.__dict__.pop("_held", None)
         _after_train = self._model_vars()
         if 'coord_desc_' in train_strategy:
             names = [v.name for v in self.engine.spec.trainable]
@@ -440,6 +520,22 @@ class SemanticNetwork(object):
         else:
             self.train_params = [_after_train[k] for k in _after_train.keys()]
             self.curr_mask = [np.ones_like(_after_train[k], dtype=bool) for k in _after_train.keys()]
+
+    def _device_train_mask(self, train_strategy):
+        """device_masks=True: (snapshot of the trainable arena or None, device mask or None) for a phase.  coord_desc_auto starts from an
+        all-ones mask and a snapshot, or from the mask the previous phase selected (keep_mask=True); the table / Bernoulli strategies draw
+        their masks on the host as ever (their random numbers are part of the contract) and upload them once."""
+        if train_strategy == 'full_model':
+            return None, None
+        if train_strategy == 'coord_desc_auto':
+            kept = self.__dict__.get("_auto_mask_dev")
+            if kept is not None:
+                return None, kept
+            if self.__dict__.get("mask") is not None:          # a mask assigned by the caller
+                return None, self._mask_to_device(self.__dict__["mask"])
+            return self.engine.snapshot_params(), torch.ones(self.engine.spec.n_trainable, dtype=torch.uint8, device=self.engine.device)
+        _before, train_mask_ = self.get_train_mask(train_strategy)
+        return None, self._mask_to_device(train_mask_)
 
     def _consume_staged(self, staged):
         """Make the compute stream wait for a staged batch's copy; returns its device tensors."""
@@ -453,11 +549,22 @@ class SemanticNetwork(object):
         labels_dev.record_stream(compute)
         return frames_dev, labels_dev
 
-    def delta_payload(self) -> bytes:
+    def delta_payload(self, device: bool = False):
         """The downlink model delta of reference run.py:316-336 as bytes: per variable ``np.packbits(mask.flatten())``, then
         per variable the masked parameters as fp16.  Under the coordinate-descent strategies (``train_params`` = the
         trainable variables, in arena order) the value part is gathered and cast on the device by ``ams_pack_masked_fp16``;
-        otherwise (``full_model``: every model variable incl. BN statistics) it is the reference's host loop."""
+        otherwise (``full_model``: every model variable incl. BN statistics) it is the reference's host loop.
+
+        After a ``device_masks=True`` phase the whole payload, mask bits included, is encoded on the device from the phase's device mask and the
+        engine's current variables (``ams_student_encode_delta``; call it before the model changes again, as run.py does) and comes to the
+        host in one copy.  ``device=True`` returns the payload as a uint8 device tensor instead, which ``apply_delta`` accepts."""
+        held = self.__dict__.get("_held")
+        if held is not None:
+            with self.process_lock:
+                dev = self.engine.encode_delta(delta_layout(self.engine.spec, held["strategy"]), held["mask"])
+                return dev if device else dev.cpu().numpy().tobytes()
+        if device:
+            return torch.from_numpy(np.frombuffer(self.delta_payload(), dtype=np.uint8).copy()).to(self.engine.device)
         assert self.curr_mask is not None and self.train_params is not None, "no training phase has run yet"
         payload = bytearray()
         for val in self.curr_mask:

@@ -389,6 +389,44 @@ int ams_student_apply_delta(ams_student* s, const uint8_t* payload_dev, int64_t 
 /* int64 elements of device scratch ams_student_apply_delta needs for this table (0 if the table is malformed) */
 size_t ams_student_apply_delta_scratch(const ams_delta_var* vars_host, int32_t n_vars);
 
+/* ---- the server half of a model update: coordinates chosen by how far the first step moved them, the others rolled back, and the
+ * delta encoded, all on the device.  Every result equals the host code it replaces bit for bit. --------------------------------------------
+ *
+ * The order statistics np.percentile interpolates between (replaces SemanticNetwork.py:267-271: the model fetched twice, 164
+ * abs(after - before) arrays concatenated and partitioned).  change[i] = fabsf(after[i] - before[i]); *result_dev receives a = the change
+ * of rank k (0-based, ascending), b = the change of rank k + 1 (a again when k + 1 == n) and the number of NaN changes (which sort last, as
+ * in np.sort).  The threshold itself is formed on the host from these 16 bytes with NumPy's arithmetic (ams_amd/coord_masks.py:
+ * percentile_rank, percentile_cut).  0 <= k < n < 2^31; result_dev 8-byte aligned; after / before any float alignment.  A memset and eight
+ * launches on `stream` (three histogram + scan passes of a radix select, select_tail_kernel, select_finish_kernel); no allocation, no
+ * synchronisation; scratch_dev holds ams_select_changed_scratch(n) int64. */
+typedef struct ams_select_result {
+    float a;
+    float b;
+    int64_t nan_count;
+} ams_select_result;
+int ams_select_changed(const float* after_dev, const float* before_dev, int64_t n, int64_t k, ams_select_result* result_dev,
+                       int64_t* scratch_dev, size_t scratch_elems, void* stream);
+size_t ams_select_changed_scratch(int64_t n);
+
+/* The mask and the roll-back (replaces SemanticNetwork.py:276-287): mask_dev[i] = fabsf(params[i] - before[i]) > cut as uint8 0 / 1,
+ * params_dev[i] keeps its value where the mask is set and becomes before_dev[i] elsewhere, *n_kept_dev (int64) = set mask entries.
+ * cut = NaN keeps nothing and rolls everything back (np.percentile's answer when a change is NaN).  Adam moments and BN statistics are not
+ * part of it.  One launch after a memset of the count; 16 bytes per lane when params / before are 16-byte and mask_dev 4-byte aligned. */
+int ams_select_apply(float* params_dev, const float* before_dev, int64_t n, float cut, uint8_t* mask_dev, int64_t* n_kept_dev, void* stream);
+
+/* The downlink delta written on the device (replaces the host loop of run.py:316-336; the inverse of ams_student_apply_delta, over the
+ * same descriptor table): payload_dev receives, per variable, np.packbits of its mask, then the masked elements of every variable as
+ * little-endian fp16 (round to nearest even, +-inf beyond 65504, as ams_pack_masked_fp16), read from the student's params / stats.
+ * mask_dev: uint8 0 / non-0 per element in layout order (for the trainable layout: arena order), NULL = every element.
+ * *payload_bytes_dev (int64) = the payload's size.  If that exceeds payload_cap nothing is written to payload_dev at all and the caller,
+ * who reads the word once the stream has run, sees payload_bytes > payload_cap.  payload_cap below the mask section is refused at once.
+ * Three launches (encode_kernel<false>, encode_scan_kernel, encode_kernel<true>) after a copy of the table; no allocation, no
+ * synchronisation; scratch_dev holds ams_student_encode_delta_scratch(vars_host, n_vars) int64. */
+int ams_student_encode_delta(ams_student* s, const uint8_t* mask_dev, const ams_delta_var* vars_host, int32_t n_vars, uint8_t* payload_dev,
+                             int64_t payload_cap, int64_t* payload_bytes_dev, int64_t* scratch_dev, size_t scratch_elems, void* stream);
+/* int64 elements of device scratch ams_student_encode_delta needs for this table (0 if the table is malformed) */
+size_t ams_student_encode_delta_scratch(const ams_delta_var* vars_host, int32_t n_vars);
+
 /* =====================================================================================================
  * Kernel-level entry points.  Same kernels the engine launches, exposed one by one so that tests/ can
  * check each against the oracle (SURVEY.md §4 test pyramid level 1).  x/y/... are device pointers.
