@@ -230,6 +230,29 @@ int ams_cross_confusion(const ams_student* s, const uint8_t* labels_dev, int64_t
                                   (hipStream_t)stream);
 }
 
+int ams_cross_confusion_pairs(const ams_student* s, const uint8_t* label_slots_dev, int64_t label_slot_stride, int32_t capacity, int64_t n_pixels,
+                              const int32_t* pairs_dev, const int32_t* pairs_host, int32_t n_pairs, int64_t* conf_mats_dev, void* stream) {
+    AMS_REQUIRE(s, "cross_confusion_pairs: null student");
+    int32_t lut[256];
+    for (int i = 0; i < 256; ++i) lut[i] = -1;
+    for (int k = 0; k < s->cfg.n_selected; ++k) lut[s->cfg.class_indices[k]] = k;
+    return launch_cross_confusion_pairs(label_slots_dev, label_slot_stride, capacity, n_pixels, pairs_dev, pairs_host, n_pairs, lut, s->cfg.n_selected,
+                                        conf_mats_dev, (hipStream_t)stream);
+}
+
+int ams_replay_gather(const uint8_t* frame_slots_dev, int64_t frame_slot_stride, const uint8_t* label_slots_dev, int64_t label_slot_stride,
+                      int32_t capacity, int32_t src_h, int32_t src_w, const ams_replay_sample* samples_dev, const ams_replay_sample* samples_host,
+                      int32_t batch, int32_t H, int32_t W, uint8_t* frames_out_dev, uint8_t* labels_out_dev, void* stream) {
+    return launch_replay_gather(frame_slots_dev, frame_slot_stride, label_slots_dev, label_slot_stride, capacity, src_h, src_w, samples_dev,
+                                samples_host, batch, H, W, frames_out_dev, labels_out_dev, (hipStream_t)stream);
+}
+
+int ams_replay_gather_f32(const float* slots_dev, int64_t slot_stride, int32_t capacity, int32_t th, int32_t tw, int32_t channels,
+                          const ams_replay_sample* samples_dev, const ams_replay_sample* samples_host, int32_t batch, float* out_dev, void* stream) {
+    return launch_replay_gather_rows(slots_dev, slot_stride, capacity, th, tw, channels, samples_dev, samples_host, batch, out_dev,
+                                     (hipStream_t)stream);
+}
+
 int ams_student_train_step_dp(ams_student* s, const void* frames_dev, int32_t frames_dtype, const uint8_t* teacher_dev,
                               int32_t batch, int32_t global_batch, float lr, const uint8_t* mask_dev, double* loss_dev,
                               ams_allreduce_cb cb, void* user, void* stream) {

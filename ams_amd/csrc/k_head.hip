@@ -5,10 +5,9 @@
 // SemanticNetwork.py:96-115).  The backward kernel is the exact transpose: every low-resolution logit gathers
 // (softmax - onehot)/N from the full-resolution pixels it was interpolated into, in a fixed order.
 #include "kernels.hpp"
+#include "cross_conf.hpp"
 
 namespace ams {
-
-constexpr int kMaxK = 32;
 
 struct HeadGeom {
     int B, h, w, ld, K, H, W, NC;
@@ -40,11 +39,6 @@ struct SoftTeacher {
     const float* t;
     int th, tw, ld;
     float sy, sx;
-};
-
-struct ClassTable {
-    int32_t idx[kMaxK];      // selected class ids
-    int32_t lut[256];        // teacher id -> subset index, -1 = ignored
 };
 
 // KMAX > 0: K <= KMAX and the K horizontally interpolated values of the two source rows live in registers while the thread walks
@@ -602,15 +596,7 @@ int launch_ce_combine(int B, int h, int w, const int32_t* cls, int K, int NC, co
 __global__ __launch_bounds__(256) void cross_conf_kernel(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b, int64_t n,
                                                          ClassTable ct, int K, unsigned long long* __restrict__ conf) {
     __shared__ int s_conf[kMaxK * kMaxK];
-    for (int e = threadIdx.x; e < K * K; e += blockDim.x) s_conf[e] = 0;
-    __syncthreads();
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const int ka = ct.lut[a[i]], kb = ct.lut[b[i]];
-        if (ka >= 0 && kb >= 0) atomicAdd(&s_conf[ka * K + kb], 1);
-    }
-    __syncthreads();
-    for (int e = threadIdx.x; e < K * K; e += blockDim.x)
-        if (s_conf[e]) atomicAdd(&conf[e], (unsigned long long)s_conf[e]);
+    cross_conf_block(a, b, n, ct, K, conf, s_conf);
 }
 
 // lut: HOST pointer, 256 entries (teacher id -> subset index or -1)

@@ -13,25 +13,11 @@
 // float roundings above.)
 #include "common.hpp"
 #include "kernels.hpp"
+#include "resize_taps.hpp"
 
 namespace ams {
 
 struct IngestGeom { int Hs, Ws, H, W, C, swap_rb, mode2x; double sy, sx; };
-
-// one axis of cv::resize's tap table
-__device__ __forceinline__ void fixed_tap(int d, double step, int n_in, bool zero_at_border, int& t0, int& t1, int& w0, int& w1) {
-    float f = (float)(((double)d + 0.5) * step - 0.5);
-    int s = (int)floorf(f);
-    f = f - (float)s;
-    if (zero_at_border && (s < 0 || s >= n_in - 1)) {
-        s = s < 0 ? 0 : n_in - 1;
-        f = 0.f;
-    }
-    t0 = s < 0 ? 0 : (s > n_in - 1 ? n_in - 1 : s);
-    t1 = s + 1 < 0 ? 0 : (s + 1 > n_in - 1 ? n_in - 1 : s + 1);
-    w0 = __float2int_rn((1.f - f) * 2048.f);       // cvRound: nearest, halves to even
-    w1 = __float2int_rn(f * 2048.f);
-}
 
 template <int MODE>       // 0: nearest, 1: linear (fixed point), 2: exact 2x box average, 3: copy
 __global__ __launch_bounds__(256) void resize_u8_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, IngestGeom g) {

@@ -1,0 +1,189 @@
+// The server's replay memory on the device (reference run.py:136-137 frame_memory / label_memory, utils/utils.py:129-185 mini_batch): a ring
+// of uint8 frame / label slots in HBM, and one launch that builds a mini-batch from it.
+//
+//   replay_gather_kernel          per batch entry (blockIdx.z) a descriptor {slot, th, tw, top, left, flip}: the crop [top, top + H) x
+//                                 [left, left + W) of cv2.resize(frame, (tw, th)) [INTER_LINEAR] / cv2.resize(label, ..., INTER_NEAREST),
+//                                 mirrored when flip.  A tap table depends on the output index alone, so the taps are evaluated at
+//                                 (top + y, left + x) and the rescaled frame is never formed.  The cases of launch_resize_u8, per sample:
+//                                 equal sizes copy, an exact 2x down-scale is the box average, anything else the 11-bit fixed-point bilinear
+//                                 form (resize_taps.hpp).  The case is uniform per sample: the branch is on blockIdx.z, not per lane.
+//                                 The copy case, what a scale list of [1] over frames at the network size hits on every step, is byte
+//                                 traffic: 16 bytes per lane where the row pitches, the crop origin and the bases allow it.
+//   replay_gather_rows_kernel     whole f32 slots (the cached teacher logits of the drawn frames) by the same table
+//   cross_confusion_pairs_kernel  the K x K phi-score confusion matrices of n pairs of label slots in one launch (blockIdx.z = the pair)
+//
+// Every descriptor is checked on the host before the launch (api.hip); the kernels check it again against the sizes they are given and
+// skip a sample that fails, so that a table that changed between the two cannot reach outside the slots.
+#include "common.hpp"
+#include "kernels.hpp"
+#include "resize_taps.hpp"
+#include "cross_conf.hpp"
+
+namespace ams {
+
+struct ReplayGeom {
+    int capacity, Hs, Ws, H, W, B;
+    int64_t frame_stride, label_stride;          // bytes from one slot to the next
+    int vec;                                     // pitches and bases allow 16-byte accesses
+};
+
+__device__ __forceinline__ bool replay_sample_ok(const ams_replay_sample& d, const ReplayGeom& g) {
+    return d.slot >= 0 && d.slot < g.capacity && d.th > 0 && d.tw > 0 && d.top >= 0 && d.left >= 0 && d.top <= d.th - g.H && d.left <= d.tw - g.W;
+}
+
+__global__ __launch_bounds__(256) void replay_gather_kernel(const uint8_t* __restrict__ frame_slots, const uint8_t* __restrict__ label_slots,
+                                                            const ams_replay_sample* __restrict__ samples, ReplayGeom g,
+                                                            uint8_t* __restrict__ frames_out, uint8_t* __restrict__ labels_out) {
+    const int b = blockIdx.z, oy = blockIdx.y;
+    const ams_replay_sample d = samples[b];
+    if (!replay_sample_ok(d, g)) return;
+    const uint8_t* fsrc = frame_slots + (int64_t)d.slot * g.frame_stride;
+    const uint8_t* lsrc = label_slots + (int64_t)d.slot * g.label_stride;
+    uint8_t* fdst = frames_out + ((int64_t)b * g.H + oy) * g.W * 3;
+    uint8_t* ldst = labels_out + ((int64_t)b * g.H + oy) * g.W;
+    const bool same = d.th == g.Hs && d.tw == g.Ws;
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+
+    if (same && g.vec && !d.flip && (d.left & 15) == 0) {
+        // whole rows of bytes: the frame row's 16-byte pieces first, the label row's behind them
+        const int fc = g.W * 3 / 16, lc = g.W / 16;
+        const uint8_t* frow = fsrc + ((int64_t)(d.top + oy) * g.Ws + d.left) * 3;
+        const uint8_t* lrow = lsrc + (int64_t)(d.top + oy) * g.Ws + d.left;
+        for (int c = t; c < fc + lc; c += gridDim.x * blockDim.x) {
+            if (c < fc) reinterpret_cast<uint4*>(fdst)[c] = reinterpret_cast<const uint4*>(frow)[c];
+            else reinterpret_cast<uint4*>(ldst)[c - fc] = reinterpret_cast<const uint4*>(lrow)[c - fc];
+        }
+        return;
+    }
+
+    if (t >= g.W) return;
+    const int cy = d.top + oy, cx = d.left + (d.flip ? g.W - 1 - t : t);          // the pixel of the rescaled image
+    uint8_t* fout = fdst + (int64_t)t * 3;
+    if (same) {
+        const uint8_t* p = fsrc + ((int64_t)cy * g.Ws + cx) * 3;
+        fout[0] = p[0]; fout[1] = p[1]; fout[2] = p[2];
+        ldst[t] = lsrc[(int64_t)cy * g.Ws + cx];
+        return;
+    }
+    const double sy = cv_step(g.Hs, d.th), sx = cv_step(g.Ws, d.tw);
+    ldst[t] = lsrc[(int64_t)nearest_tap(cy, sy, g.Hs) * g.Ws + nearest_tap(cx, sx, g.Ws)];
+    if (g.Hs == 2 * d.th && g.Ws == 2 * d.tw) {
+        const uint8_t* p0 = fsrc + ((int64_t)(2 * cy) * g.Ws + 2 * cx) * 3;
+        const uint8_t* p1 = p0 + (int64_t)g.Ws * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) fout[c] = (uint8_t)(((int)p0[c] + (int)p0[3 + c] + (int)p1[c] + (int)p1[3 + c] + 2) >> 2);
+        return;
+    }
+    int y0, y1, x0, x1, b0, b1, a0, a1;
+    fixed_tap(cy, sy, g.Hs, false, y0, y1, b0, b1);
+    fixed_tap(cx, sx, g.Ws, true, x0, x1, a0, a1);
+    const uint8_t* p00 = fsrc + ((int64_t)y0 * g.Ws + x0) * 3;
+    const uint8_t* p01 = fsrc + ((int64_t)y0 * g.Ws + x1) * 3;
+    const uint8_t* p10 = fsrc + ((int64_t)y1 * g.Ws + x0) * 3;
+    const uint8_t* p11 = fsrc + ((int64_t)y1 * g.Ws + x1) * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+        fout[c] = fixed_blend((int)p00[c] * a0 + (int)p01[c] * a1, (int)p10[c] * a0 + (int)p11[c] * a1, b0, b1);
+}
+
+__global__ __launch_bounds__(256) void replay_gather_rows_kernel(const float* __restrict__ slots, int64_t slot_stride, int capacity,
+                                                                 const ams_replay_sample* __restrict__ samples, int64_t n, int vec,
+                                                                 float* __restrict__ out) {
+    const int b = blockIdx.z;
+    const int slot = samples[b].slot;
+    if (slot < 0 || slot >= capacity) return;
+    const float* src = slots + (int64_t)slot * slot_stride;
+    float* dst = out + (int64_t)b * n;
+    const int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x, step = (int64_t)gridDim.x * blockDim.x;
+    if (vec) {
+        for (int64_t i = t; i < (n >> 2); i += step) st4(dst + 4 * i, ld4(src + 4 * i));
+    } else {
+        for (int64_t i = t; i < n; i += step) dst[i] = src[i];
+    }
+}
+
+__global__ __launch_bounds__(256) void cross_confusion_pairs_kernel(const uint8_t* __restrict__ label_slots, int64_t label_stride, int capacity,
+                                                                    const int32_t* __restrict__ pairs, int64_t n, ClassTable ct, int K,
+                                                                    unsigned long long* __restrict__ conf) {
+    __shared__ int s_conf[kMaxK * kMaxK];
+    const int p = blockIdx.z;
+    const int sa = pairs[2 * p], sb = pairs[2 * p + 1];
+    if (sa < 0 || sa >= capacity || sb < 0 || sb >= capacity) return;         // (the same for every thread of the block)
+    cross_conf_block(label_slots + (int64_t)sa * label_stride, label_slots + (int64_t)sb * label_stride, n, ct, K, conf + (int64_t)p * K * K, s_conf);
+}
+
+static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// samples_host: the table the caller uploaded to samples_dev, checked here before anything is launched
+int launch_replay_gather(const uint8_t* frame_slots, int64_t frame_stride, const uint8_t* label_slots, int64_t label_stride, int capacity, int Hs,
+                         int Ws, const ams_replay_sample* samples_dev, const ams_replay_sample* samples_host, int B, int H, int W,
+                         uint8_t* frames_out, uint8_t* labels_out, hipStream_t st) {
+    AMS_REQUIRE(frame_slots && label_slots && samples_dev && samples_host && frames_out && labels_out, "replay_gather: null pointer");
+    AMS_REQUIRE(capacity > 0 && Hs > 0 && Ws > 0 && H > 0 && W > 0 && B > 0 && B <= 65535 && H <= 65535, "replay_gather: bad geometry %dx%d -> %d x %dx%d, %d slots",
+                Hs, Ws, B, H, W, capacity);
+    AMS_REQUIRE(frame_stride >= (int64_t)Hs * Ws * 3 && label_stride >= (int64_t)Hs * Ws, "replay_gather: slot strides %lld / %lld below a %dx%d frame",
+                (long long)frame_stride, (long long)label_stride, Hs, Ws);
+    for (int b = 0; b < B; ++b) {
+        const ams_replay_sample& d = samples_host[b];
+        AMS_REQUIRE(d.slot >= 0 && d.slot < capacity, "replay_gather: sample %d draws slot %d of %d", b, d.slot, capacity);
+        AMS_REQUIRE(d.th > 0 && d.tw > 0 && d.th - H >= 0 && d.tw - W >= 0, "replay_gather: sample %d: a %dx%d crop of a %dx%d image (negative slack)", b, H, W,
+                    d.th, d.tw);
+        AMS_REQUIRE(d.top >= 0 && d.left >= 0 && d.top <= d.th - H && d.left <= d.tw - W, "replay_gather: sample %d: crop origin (%d, %d) outside %dx%d", b,
+                    d.top, d.left, d.th, d.tw);
+    }
+    ReplayGeom g;
+    g.capacity = capacity; g.Hs = Hs; g.Ws = Ws; g.H = H; g.W = W; g.B = B;
+    g.frame_stride = frame_stride; g.label_stride = label_stride;
+    g.vec = W % 16 == 0 && Ws % 16 == 0 && frame_stride % 16 == 0 && label_stride % 16 == 0 && aligned16(frame_slots) && aligned16(label_slots) &&
+            aligned16(frames_out) && aligned16(labels_out);
+    note_kernel("replay_gather_kernel");
+    hipLaunchKernelGGL(replay_gather_kernel, dim3(cdiv(W, 256), H, B), dim3(256), 0, st, frame_slots, label_slots, samples_dev, g, frames_out,
+                       labels_out);
+    AMS_CHECK_LAUNCH();
+    return AMS_OK;
+}
+
+int launch_replay_gather_rows(const float* slots, int64_t slot_stride, int capacity, int th, int tw, int C, const ams_replay_sample* samples_dev,
+                              const ams_replay_sample* samples_host, int B, float* out, hipStream_t st) {
+    AMS_REQUIRE(slots && samples_dev && samples_host && out, "replay_gather_f32: null pointer");
+    AMS_REQUIRE(capacity > 0 && th > 0 && tw > 0 && C > 0 && B > 0 && B <= 65535, "replay_gather_f32: bad geometry %d x %dx%dx%d, %d slots", B, th, tw, C, capacity);
+    const int64_t n = (int64_t)th * tw * C;
+    AMS_REQUIRE(slot_stride >= n, "replay_gather_f32: slot stride %lld below %lld elements", (long long)slot_stride, (long long)n);
+    for (int b = 0; b < B; ++b) {
+        const ams_replay_sample& d = samples_host[b];
+        AMS_REQUIRE(d.slot >= 0 && d.slot < capacity, "replay_gather_f32: sample %d draws slot %d of %d", b, d.slot, capacity);
+        // soft targets follow frames that are taken as they are: no rescale / crop / flip of teacher logits is defined
+        AMS_REQUIRE(d.top == 0 && d.left == 0 && d.flip == 0, "replay_gather_f32: sample %d is cropped or flipped (%d, %d, %d)", b, d.top, d.left, d.flip);
+    }
+    const int vec = n % 4 == 0 && slot_stride % 4 == 0 && aligned16(slots) && aligned16(out) ? 1 : 0;
+    int64_t gx = cdiv64(vec ? n / 4 : n, 256 * 4);
+    gx = gx < 1 ? 1 : gx > 1024 ? 1024 : gx;
+    note_kernel("replay_gather_rows_kernel");
+    hipLaunchKernelGGL(replay_gather_rows_kernel, dim3((int)gx, 1, B), dim3(256), 0, st, slots, slot_stride, capacity, samples_dev, n, vec, out);
+    AMS_CHECK_LAUNCH();
+    return AMS_OK;
+}
+
+// lut: HOST pointer, 256 entries (teacher id -> subset index or -1); conf [n_pairs][K][K] overwritten
+int launch_cross_confusion_pairs(const uint8_t* label_slots, int64_t label_stride, int capacity, int64_t n, const int32_t* pairs_dev,
+                                 const int32_t* pairs_host, int n_pairs, const int32_t* lut, int K, int64_t* conf, hipStream_t st) {
+    AMS_REQUIRE(label_slots && pairs_dev && pairs_host && conf, "cross_confusion_pairs: null pointer");
+    AMS_REQUIRE(K > 0 && K <= kMaxK, "cross_confusion_pairs: K=%d out of range", K);
+    AMS_REQUIRE(capacity > 0 && n > 0 && label_stride >= n && n_pairs > 0 && n_pairs <= 65535, "cross_confusion_pairs: bad geometry (%d pairs, %d slots)", n_pairs,
+                capacity);
+    for (int p = 0; p < 2 * n_pairs; ++p)
+        AMS_REQUIRE(pairs_host[p] >= 0 && pairs_host[p] < capacity, "cross_confusion_pairs: pair %d names slot %d of %d", p / 2, pairs_host[p], capacity);
+    ClassTable ct;
+    for (int i = 0; i < 256; ++i) ct.lut[i] = lut[i];
+    for (int k = 0; k < kMaxK; ++k) ct.idx[k] = 0;
+    AMS_CHECK_HIP(hipMemsetAsync(conf, 0, sizeof(int64_t) * K * K * n_pairs, st));
+    int grid = (int)cdiv64(n, 256 * 16);
+    grid = grid < 1 ? 1 : grid > 2048 ? 2048 : grid;
+    note_kernel("cross_confusion_pairs_kernel");
+    hipLaunchKernelGGL(cross_confusion_pairs_kernel, dim3(grid, 1, n_pairs), dim3(256), 0, st, label_slots, label_stride, capacity, pairs_dev, n, ct, K,
+                       (unsigned long long*)conf);
+    AMS_CHECK_LAUNCH();
+    return AMS_OK;
+}
+
+}  // namespace ams

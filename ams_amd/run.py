@@ -94,6 +94,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--device_masks", action="store_true",
                    help="server: choose coord_desc_auto's coordinates, keep the masks and encode the downlink payload on the device (extra "
                         "flag; same files and numbers)")
+    p.add_argument("--device_memory", action="store_true",
+                   help="server: keep the replay memory on the device and sample mini-batches from it there (extra flag; needs a GPU; composes "
+                        "with --gpu_ingest and --device_masks; same files and numbers)")
     p.add_argument("--horizon_k1s", default="16,32,64,128,256,512", help="horizon mode: training-window lengths in seconds (reference: hard-coded)")
     p.add_argument("--horizon_k2", type=int, default=256, help="horizon mode: evaluation window in seconds (reference: 256)")
     p.add_argument("--horizon_points", type=int, default=3, help="horizon mode: number of evaluation points (reference: 3)")
@@ -235,6 +238,10 @@ def train_model(ctx: Context, train_start, train_end, sampling_period, gpu_id, r
     map_coco = coco_class_converter() if is_coco(exp_num) else None
     mem = max(1, int(FLAGS.memory_len / sampling_period * fps))
     frame_memory, label_memory = deque(maxlen=mem), deque(maxlen=mem)
+    device_memory = None
+    if getattr(FLAGS, "device_memory", False):
+        from .replay import DeviceReplayMemory
+        device_memory = DeviceReplayMemory(mem, ctx.size[0], ctx.size[1], "cuda:%s" % gpu_id)
 
     semantic_network = ctx.network_cls(meta_dir=FLAGS.student_checkpoint, class_weights_exp=class_weights(exp_num),
                                        height=FLAGS.height, gpu_id=gpu_id, scale=[1], mini_batch_size=FLAGS.batch_size,
@@ -264,18 +271,27 @@ def train_model(ctx: Context, train_start, train_end, sampling_period, gpu_id, r
             size_images = 0.0
             for fr, label in zip(frames_chosen, labels_chosen):
                 fr, label_resized = _to_size(fr, label, ctx.size, ctx.ingest)
-                fr, label_resized = _host(fr), _host(label_resized)       # the replay memory lives on the host
-                if map_coco is not None:
-                    label_resized = map_coco[label_resized]
-                frame_memory.append(fr)
-                label_memory.append(label_resized)
+                if device_memory is not None:
+                    # the replay memory lives on the device: what --gpu_ingest produced there stays there; the host copy of the frame below
+                    # is emulation accounting only
+                    if map_coco is not None:
+                        label_resized = map_coco[_host(label_resized)]
+                    device_memory.append(fr, label_resized)
+                    fr = _host(fr)
+                else:
+                    fr, label_resized = _host(fr), _host(label_resized)       # the replay memory lives on the host
+                    if map_coco is not None:
+                        label_resized = map_coco[label_resized]
+                    frame_memory.append(fr)
+                    label_memory.append(label_resized)
                 size_images += len(zlib.compress(fr.tobytes(), 6)) / 1024     # stand-in for the PNG size
             frame_label_bucket.clear()
             sample_per_period.append(len(frames_chosen))
             num_unseen_frames += len(frames_chosen)
             up_bw_per_period.append(size_images * 8)
 
-        if second in save_range and len(frame_memory) == 0:
+        n_memory = len(device_memory) if device_memory is not None else len(frame_memory)
+        if second in save_range and n_memory == 0:
             # nothing has been uploaded yet (e.g. a horizon window shorter than the upload period): the model of this event
             # time is the current one, published unchanged
             print_process("No samples in memory at %d s: publishing the current model unchanged" % second, second)
@@ -284,11 +300,14 @@ def train_model(ctx: Context, train_start, train_end, sampling_period, gpu_id, r
             model_save_times.append(float(second))
         elif second in save_range:
             phi = float("nan")
-            if FLAGS.enable_ASR and len(label_memory) > 1:
+            if FLAGS.enable_ASR and n_memory > 1:
                 # phi-score over the frames that arrived since the last update -> sampling rate (run.py:279-290)
-                i_start = max(0, len(label_memory) - num_unseen_frames - 1)
-                cross = [semantic_network.calc_cross_miou(np.array([label_memory[k], label_memory[k + 1]]))[2]
-                         for k in range(i_start, len(label_memory) - 1)]
+                i_start = max(0, n_memory - num_unseen_frames - 1)
+                if device_memory is not None:
+                    cross = [r[2] for r in device_memory.cross_miou_pairs(semantic_network, i_start)]       # one launch, one copy
+                else:
+                    cross = [semantic_network.calc_cross_miou(np.array([label_memory[k], label_memory[k + 1]]))[2]
+                             for k in range(i_start, len(label_memory) - 1)]
                 if cross:
                     phi = float(np.mean(cross))
                     send_rate = float(np.clip(send_rate - 0.2 * np.tanh((np.mean(cross) - 0.6) * 20), 0.1, 1))
@@ -310,7 +329,10 @@ def train_model(ctx: Context, train_start, train_end, sampling_period, gpu_id, r
             if not FLAGS.no_restore:
                 semantic_network.restore_initial()
             t1 = time.time()
-            semantic_network.train_with_deque(frame_memory, label_memory, FLAGS.iter, FLAGS.train_strategy)
+            if device_memory is not None:
+                semantic_network.train_with_deque(device_memory, None, FLAGS.iter, FLAGS.train_strategy)
+            else:
+                semantic_network.train_with_deque(frame_memory, label_memory, FLAGS.iter, FLAGS.train_strategy)
             train_ms.append(1000 * (time.time() - t1))
             print("Training for %d iterations took %d ms!!!" % (FLAGS.iter, train_ms[-1]))
             # model delta on the downlink: packed mask bits + masked parameters as fp16, gzip -9 (run.py:316-336)

@@ -12,6 +12,8 @@ Deliberate differences (all listed in INTEGRATION.md):
   * ``infer`` / ``train_step`` aliases are added (BASELINE.json north-star names).
   * per-iteration loss printing is off unless ``verbose=True`` (each print forces a device sync).
   * ``device_masks=True`` keeps the server side of a model update on the device (coordinate selection, masks, the delta's bytes); same results.
+  * ``train_with_deque`` also takes an ``ams_amd.replay.DeviceReplayMemory`` in place of the two deques: the replay memory and its sampler on
+    the device, no helper thread; ``flip=True`` (the reference passes False) is reachable on that path.
 """
 from __future__ import annotations
 
@@ -30,6 +32,7 @@ from . import coord_masks, hip
 from . import weights as W
 from .delta import delta_layout
 from .engine import StudentEngine
+from .replay import DeviceReplayMemory, draw_samples
 from .utils import calculate_miou, colormap, mini_batch
 from .weights import load_npy
 
@@ -122,6 +125,8 @@ class SemanticNetwork(object):
         self.pipeline_depth = int(kwargs.pop("pipeline_depth", 1))
         # training only: masks, coord_desc_auto's selection and the delta's bytes stay on the device (same results; see _train, delta_payload)
         self.device_masks = bool(kwargs.pop("device_masks", False)) and not frozen
+        # training from a DeviceReplayMemory only: mini_batch's flip augmentation (the reference passes flip=False, SemanticNetwork.py:687)
+        self.flip = bool(kwargs.pop("flip", False))
         assert 1 <= self.pipeline_depth <= 4, "pipeline_depth must be 1 .. 4"
         assert not kwargs, "unknown arguments: %s" % sorted(kwargs)
 
@@ -364,10 +369,24 @@ class SemanticNetwork(object):
                          keep_mask=False, teacher_logits_deque=None):
         """``teacher_logits_deque`` (soft_teacher=True only; the reference's _train never feeds teacher_labels_logits_pl, so its soft graph cannot
         run through this method at all): the cached teacher logits of the replay memory, one f32 [th, tw, TOTAL_CLASSES] array per frame of
-        ``frame_deque``; a mini-batch takes the logits of the frames it drew."""
+        ``frame_deque``; a mini-batch takes the logits of the frames it drew.
+
+        ``frame_deque`` may be an ``ams_amd.replay.DeviceReplayMemory`` (``label_deque`` and ``teacher_logits_deque`` are then None; with
+        ``soft_teacher=True`` the logits come from the memory).  That path starts no helper thread and uses no pinned staging: the calling
+        thread draws the phase's descriptors (``replay.draw_samples``, all iterations), uploads them once, and per iteration launches the gather
+        on the engine's stream into one resident batch buffer before the same ``engine.train_step``; everything after the step is shared with
+        the host path.  Order of the random draws: the sample descriptors of the whole phase FIRST, then ``get_train_mask``.  On the host path
+        that order is a race between the sampler thread and ``get_train_mask`` (in the reference too), so the two paths are bit-identical,
+        given equal seeds, for the strategies whose mask draws nothing: ``full_model`` and ``coord_desc_auto``."""
         assert not self.frozen, "Can't train frozen graph!!!"
-        assert (teacher_logits_deque is not None) == bool(getattr(self, "soft_teacher", False)), \
-            "teacher_logits_deque goes with soft_teacher=True (and is required then)"
+        on_memory = isinstance(frame_deque, DeviceReplayMemory)
+        if on_memory:
+            assert label_deque is None and teacher_logits_deque is None, "a DeviceReplayMemory carries its labels and teacher logits itself"
+            assert (frame_deque.logits_shape is not None) == bool(getattr(self, "soft_teacher", False)), \
+                "soft_teacher=True goes with a memory constructed with logits_shape (and needs one)"
+        else:
+            assert (teacher_logits_deque is not None) == bool(getattr(self, "soft_teacher", False)), \
+                "teacher_logits_deque goes with soft_teacher=True (and is required then)"
         if teacher_logits_deque is not None:
             assert len(teacher_logits_deque) == len(frame_deque), "one teacher-logit array per frame of the replay memory"
         if not keep_mask:
@@ -379,11 +398,14 @@ class SemanticNetwork(object):
         ctx = self._helpers = {"abort": threading.Event(), "error": None}
         batch_thr = None
         try:
-            batch_deque = deque()
-            batch_thr = threading.Thread(target=self._guarded, args=(ctx, self._fill_batch, batch_deque, frame_deque, label_deque,
-                                                                     num_of_iterations, teacher_logits_deque))
-            batch_thr.start()
-            self._train(batch_deque, num_of_iterations, train_strategy)
+            if on_memory:
+                self._train(frame_deque, num_of_iterations, train_strategy)
+            else:
+                batch_deque = deque()
+                batch_thr = threading.Thread(target=self._guarded, args=(ctx, self._fill_batch, batch_deque, frame_deque, label_deque,
+                                                                         num_of_iterations, teacher_logits_deque))
+                batch_thr.start()
+                self._train(batch_deque, num_of_iterations, train_strategy)
         finally:
             ctx["abort"].set()                      # after a clean phase the helpers have returned already; after an error this stops them
             if batch_thr is not None:
@@ -437,9 +459,13 @@ class SemanticNetwork(object):
     def _train(self, batch_deque, num_of_iterations, train_strategy):
         signal_deque = deque()
         ctx = getattr(self, "_helpers", None) or {"abort": threading.Event(), "error": None}
-        fill_thr = threading.Thread(target=self._guarded, args=(ctx, self._fill_queue, batch_deque, num_of_iterations, signal_deque))
-        ctx["fill_thr"] = fill_thr                  # joined by train_with_deque's finally, whatever happens below
-        fill_thr.start()
+        plan = fill_thr = None
+        if isinstance(batch_deque, DeviceReplayMemory):
+            plan = self._replay_plan(batch_deque, num_of_iterations)        # the phase's draws, before get_train_mask; no helper thread
+        else:
+            fill_thr = threading.Thread(target=self._guarded, args=(ctx, self._fill_queue, batch_deque, num_of_iterations, signal_deque))
+            ctx["fill_thr"] = fill_thr                  # joined by train_with_deque's finally, whatever happens below
+            fill_thr.start()
 
         on_device = getattr(self, "device_masks", False)
         before_dev = None
@@ -452,7 +478,7 @@ class SemanticNetwork(object):
         t_phase = time.time()
         for it in range(num_of_iterations):
             staged = None
-            while staged is None:
+            while staged is None and plan is None:
                 try:
                     staged = signal_deque.popleft()
                 except IndexError:
@@ -460,10 +486,13 @@ class SemanticNetwork(object):
                         return
                     time.sleep(self.THREAD_SLEEP_INTERVAL)
             t1 = time.time()
-            frames_dev, labels_dev = self._consume_staged(staged)
-            logits_dev = staged[3] if len(staged) > 3 else None
-            if logits_dev is not None:
-                logits_dev.record_stream(torch.cuda.current_stream(self.engine.device))
+            if plan is not None:
+                frames_dev, labels_dev, logits_dev = plan.batch(it)       # one launch on this stream into the resident batch buffer
+            else:
+                frames_dev, labels_dev = self._consume_staged(staged)
+                logits_dev = staged[3] if len(staged) > 3 else None
+                if logits_dev is not None:
+                    logits_dev.record_stream(torch.cuda.current_stream(self.engine.device))
             if logits_dev is not None:
                 loss_dev = self.engine.train_step(frames_dev, labels_dev, self.lr, mask_dev, teacher_logits=logits_dev)
             else:
@@ -501,7 +530,8 @@ class SemanticNetwork(object):
                     self._restore_dict(_combine)
                     self.mask = train_mask_
                     mask_dev = self._mask_to_device(train_mask_)
-        fill_thr.join()
+        if fill_thr is not None:
+            fill_thr.join()
         if ctx["error"] is not None:
             return
         stacked = torch.stack(losses).cpu().numpy() if losses else np.zeros((0, 2))
@@ -536,6 +566,17 @@ class SemanticNetwork(object):
             return self.engine.snapshot_params(), torch.ones(self.engine.spec.n_trainable, dtype=torch.uint8, device=self.engine.device)
         _before, train_mask_ = self.get_train_mask(train_strategy)
         return None, self._mask_to_device(train_mask_)
+
+    def _replay_plan(self, memory, num_of_iterations):
+        """A phase on a DeviceReplayMemory: mini_batch's draws for every iteration, on the calling thread, uploaded once."""
+        crop = [self.height, self.height * 2]
+        # soft targets follow the frames a batch drew: only where frames are taken as they are (no rescale / crop of the logits is defined)
+        assert memory.logits_shape is None or (list(self.scale) == [1] and (memory.src_h, memory.src_w) == tuple(crop)), \
+            "teacher logits need frames and labels at the network size and scale == [1]"
+        samples = draw_samples(len(memory), (memory.src_h, memory.src_w), crop, self.scale, self.mini_batch_size, num_of_iterations,
+                               flip=getattr(self, "flip", False))
+        assert memory.logits_shape is None or all(tuple(d[1:]) == (memory.src_h, memory.src_w, 0, 0, 0) for d in samples.reshape(-1, 6))
+        return memory.plan(samples, crop[0], crop[1])
 
     def _consume_staged(self, staged):
         """Make the compute stream wait for a staged batch's copy; returns its device tensors."""

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define AMS_ABI_VERSION 3
+#define AMS_ABI_VERSION 4
 
 enum {
     AMS_OK = 0,
@@ -426,6 +426,45 @@ int ams_student_encode_delta(ams_student* s, const uint8_t* mask_dev, const ams_
                              int64_t payload_cap, int64_t* payload_bytes_dev, int64_t* scratch_dev, size_t scratch_elems, void* stream);
 /* int64 elements of device scratch ams_student_encode_delta needs for this table (0 if the table is malformed) */
 size_t ams_student_encode_delta_scratch(const ams_delta_var* vars_host, int32_t n_vars);
+
+/* ---- the server's replay memory on the device (replaces run.py:136-137 frame_memory / label_memory, two host deques, and the sampling of
+ * utils/utils.py:129-185 mini_batch from them).  The memory is a ring of `capacity` slots the caller owns: slot p of the frames is uint8
+ * [src_h, src_w, 3] at frame_slots_dev + p * frame_slot_stride, of the labels uint8 [src_h, src_w] at label_slots_dev + p * label_slot_stride
+ * (strides in bytes; multiples of 16 with 16-byte aligned bases and src_w, W multiples of 16 let the copy case move 16 bytes per lane).
+ *
+ * One descriptor per batch entry, drawn on the host with the host generators (ams_amd/replay.py: draw_samples): the entry is the crop
+ * [top, top + H) x [left, left + W) of cv2.resize(frame, (tw, th)) [INTER_LINEAR, OpenCV's 8-bit fixed-point arithmetic as in
+ * ams_ingest_resize_u8] and of cv2.resize(label, (tw, th), INTER_NEAREST), with the columns mirrored when flip != 0 (np.flip(axis=1)):
+ * utils/utils.py:165-183, bit for bit, without forming the rescaled frame. */
+typedef struct ams_replay_sample {
+    int32_t slot;        /* physical slot in the ring */
+    int32_t th, tw;      /* size of the rescaled image the crop is cut from: int(src_h*factor), int(src_w*factor) */
+    int32_t top, left;   /* crop origin inside it */
+    int32_t flip;        /* mirror the columns (np.flip(axis=1)) */
+} ams_replay_sample;
+
+/* A mini-batch in one launch (replaces utils/utils.py:129-185 and the pinned staging + upload of the batch): frames_out_dev uint8
+ * [batch, H, W, 3], labels_out_dev uint8 [batch, H, W].  samples_dev is the table the kernel reads; samples_host is the same table on the
+ * host, checked before the launch: a slot outside the capacity, negative slack (th < H or tw < W) or a crop outside (th, tw) is refused
+ * with AMS_E_INVALID and nothing is launched.  One launch (replay_gather_kernel); no allocation, no synchronisation. */
+int ams_replay_gather(const uint8_t* frame_slots_dev, int64_t frame_slot_stride, const uint8_t* label_slots_dev, int64_t label_slot_stride,
+                      int32_t capacity, int32_t src_h, int32_t src_w, const ams_replay_sample* samples_dev, const ams_replay_sample* samples_host,
+                      int32_t batch, int32_t H, int32_t W, uint8_t* frames_out_dev, uint8_t* labels_out_dev, void* stream);
+
+/* The cached teacher logits of the frames a batch drew (replaces the np.stack + pin_memory + upload of the soft-teacher batch; the reference
+ * feeds teacher_labels_logits_pl per batch, utils/graph_utils.py:359): slot p is f32 [th, tw, channels] at slots_dev + p * slot_stride
+ * (stride in elements), out_dev f32 [batch, th, tw, channels].  Whole slots only: a descriptor with a crop origin or a flip is refused (no
+ * rescale or crop of teacher logits is defined).  One launch (replay_gather_rows_kernel); no allocation, no synchronisation. */
+int ams_replay_gather_f32(const float* slots_dev, int64_t slot_stride, int32_t capacity, int32_t th, int32_t tw, int32_t channels,
+                          const ams_replay_sample* samples_dev, const ams_replay_sample* samples_host, int32_t batch, float* out_dev, void* stream);
+
+/* The phi-score confusion matrices of n_pairs pairs of label slots at once (replaces the loop of run.py:287-291 over calc_cross_miou,
+ * SemanticNetwork.py:124-139: one upload and one synchronising read per pair): pair i is (pairs[2i], pairs[2i + 1]) = (before, after)
+ * physical slots, conf_mats_dev int64 [n_pairs][K][K] overwritten with the integers ams_cross_confusion gives pair by pair.  pairs_host
+ * is checked against the capacity before the launch.  A memset and one launch (cross_confusion_pairs_kernel); no allocation, no
+ * synchronisation. */
+int ams_cross_confusion_pairs(const ams_student* s, const uint8_t* label_slots_dev, int64_t label_slot_stride, int32_t capacity, int64_t n_pixels,
+                              const int32_t* pairs_dev, const int32_t* pairs_host, int32_t n_pairs, int64_t* conf_mats_dev, void* stream);
 
 /* =====================================================================================================
  * Kernel-level entry points.  Same kernels the engine launches, exposed one by one so that tests/ can

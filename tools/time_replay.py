@@ -1,0 +1,165 @@
+"""Time a training phase fed from the host replay memory (two deques, sampler and stager threads, pinned staging: the default) against the
+same phase fed from a DeviceReplayMemory (ams_amd/replay.py, k_replay.hip), alternating in one process on one GPU.
+
+Host clock around ``train_with_deque`` (which ends with the read-back of the losses, so the stream is drained), medians of --reps phases after
+--warmup, p10 / p90 beside them, at 512 x 1024, batch 8, 20 iterations:
+
+  a  hard labels, scale [1]                       (what run.py runs)
+  b  soft_teacher with teacher logits at the label size
+  c  scale [1, 1.25, 1.5]                         (the host path falls to utils.mini_batch)
+
+Both paths start every phase from the same seeds, so they train on the same draws.  The baseline of every ratio is the host path timed in
+the same run.  Beside them: HIP-event times of the gather launch alone (copy case, bilinear case; stream otherwise idle), and the ASR event
+with 10 label pairs as the loop over calc_cross_miou against one cross_miou_pairs call (host clock).  Writes one JSON (--out) and prints it.
+Cases b and c are slow on the host path (seconds per phase): --reps_b / --reps_c set their own counts, recorded in the JSON.
+
+    python tools/time_replay.py [--cases a,b,c,gather,asr] [--reps 50] [--warmup 5] [--out out/time_replay.json]
+"""
+import argparse
+import json
+import os
+import random
+import sys
+import time
+from collections import deque
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+
+from ams_amd import exp_configs, spec as S, synth, weights as Wt  # noqa: E402
+from ams_amd.replay import DeviceReplayMemory, draw_samples  # noqa: E402
+from ams_amd.semantic_network import SemanticNetwork  # noqa: E402
+
+CI = [0, 1, 2, 10, 11, 13]
+
+
+def stats(xs):
+    xs = np.asarray(xs, np.float64)
+    return {"median": float(np.median(xs)), "mean": float(xs.mean()), "min": float(xs.min()), "max": float(xs.max()),
+            "p10": float(np.percentile(xs, 10)), "p90": float(np.percentile(xs, 90)), "n": int(xs.size)}
+
+
+def seed(k):
+    np.random.seed(k)
+    random.seed(k)
+
+
+def time_phases(net, host_args, mem, iters, reps, warmup):
+    """host path and device path alternate; returns their per-phase wall times in ms"""
+    dev = net.engine.device
+    host_ms, dev_ms = [], []
+    for r in range(warmup + reps):
+        for path in ("host", "device"):
+            seed(100 + r)
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            if path == "host":
+                net.train_with_deque(host_args[0], host_args[1], iters, "full_model", teacher_logits_deque=host_args[2])
+            else:
+                net.train_with_deque(mem, None, iters, "full_model")
+            torch.cuda.synchronize(dev)
+            ms = (time.perf_counter() - t0) * 1e3
+            if r >= warmup:
+                (host_ms if path == "host" else dev_ms).append(ms)
+    out = {"host_ms": stats(host_ms), "device_ms": stats(dev_ms)}
+    out["host_over_device"] = out["host_ms"]["median"] / out["device_ms"]["median"]
+    return out
+
+
+def time_gather(mem, H, scale, batch, reps, warmup):
+    dev = mem.device
+    st = torch.cuda.current_stream(dev)
+    seed(7)
+    plan = mem.plan(draw_samples(len(mem), (mem.src_h, mem.src_w), [H, 2 * H], scale, batch, warmup + reps), H, 2 * H)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    us = []
+    for r in range(warmup + reps):
+        torch.cuda.synchronize(dev)
+        e0.record(st)
+        plan.batch(r)
+        e1.record(st)
+        torch.cuda.synchronize(dev)
+        if r >= warmup:
+            us.append(e0.elapsed_time(e1) * 1e3)
+    return stats(us)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--height", type=int, default=512)
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--slots", type=int, default=12)
+    ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--reps_b", type=int, default=None)
+    ap.add_argument("--reps_c", type=int, default=None)
+    ap.add_argument("--cases", default="a,b,c,gather,asr")
+    ap.add_argument("--out", default="out/time_replay.json")
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "time_replay needs the GPU"
+    cases = a.cases.split(",")
+    H = a.height
+    W0 = Wt.synthetic_weights(S.build_spec(), seed=0)
+    frames, labels = synth.SyntheticVideo(H, a.slots, CI, seed=3).clip()
+    frames, labels = [np.ascontiguousarray(f) for f in frames], [np.ascontiguousarray(l) for l in labels]
+    net = SemanticNetwork("unused", class_weights_exp=exp_configs.class_weights(25), height=H, scale=[1], mini_batch_size=a.batch, lr=1e-3,
+                          initial_variables=W0)
+    dev = net.engine.device
+    mem = DeviceReplayMemory(a.slots, H, 2 * H, dev)
+    for f, l in zip(frames, labels):
+        mem.append(f, l)
+    host = (deque(frames), deque(labels), None)
+    result = {"height": H, "width": 2 * H, "batch": a.batch, "iterations": a.iters, "slots": a.slots, "warmup": a.warmup,
+              "device": torch.cuda.get_device_name(dev), "memory_bytes": mem.nbytes}
+    if "a" in cases:
+        net.scale = [1]
+        result["a_hard_scale1"] = time_phases(net, host, mem, a.iters, a.reps, a.warmup)
+    if "c" in cases:
+        net.scale = [1, 1.25, 1.5]
+        result["c_multi_scale"] = time_phases(net, host, mem, a.iters, a.reps_c or a.reps, a.warmup)
+        net.scale = [1]
+    if "gather" in cases:
+        result["gather_copy_us"] = time_gather(mem, H, [1], a.batch, a.reps, a.warmup)
+        result["gather_bilinear_us"] = time_gather(mem, H, [1.25], a.batch, a.reps, a.warmup)
+    if "asr" in cases:
+        pairs = min(10, a.slots - 1)
+        loop_ms, call_ms = [], []
+        for r in range(a.warmup + a.reps):
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            first = len(mem) - 1 - pairs
+            want = [net.calc_cross_miou(np.array([labels[k], labels[k + 1]]))[2] for k in range(first, len(mem) - 1)]
+            t1 = time.perf_counter()
+            got = [x[2] for x in mem.cross_miou_pairs(net, first)]
+            t2 = time.perf_counter()
+            assert len(got) == pairs and np.array_equal(want, got, equal_nan=True)
+            if r >= a.warmup:
+                loop_ms.append((t1 - t0) * 1e3)
+                call_ms.append((t2 - t1) * 1e3)
+        result["asr_pairs"] = pairs
+        result["asr_loop_ms"], result["asr_one_call_ms"] = stats(loop_ms), stats(call_ms)
+        result["asr_loop_over_one_call"] = result["asr_loop_ms"]["median"] / result["asr_one_call_ms"]["median"]
+    if "b" in cases:
+        rng = np.random.default_rng(5)
+        tl = [rng.standard_normal((H, 2 * H, 19)).astype(np.float32) for _ in range(a.slots)]
+        soft_mem = DeviceReplayMemory(a.slots, H, 2 * H, dev, logits_shape=(H, 2 * H, 19))
+        for f, l, t in zip(frames, labels, tl):
+            soft_mem.append(f, l, t)
+        net.soft_teacher = True
+        net.engine.set_soft_teacher(True)
+        result["b_soft_teacher_full_size"] = time_phases(net, (host[0], host[1], deque(tl)), soft_mem, a.iters, a.reps_b or a.reps, a.warmup)
+        result["b_soft_teacher_full_size"]["memory_bytes"] = soft_mem.nbytes
+    result["note"] = ("*_ms: host clock around train_with_deque, stream drained before and after, host path and device path alternating with equal "
+                      "seeds; gather_*_us: HIP events around the one launch, stream otherwise idle; asr_*: host clock, results compared")
+    net.close_model()
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(result, f, indent=1)
+    print(json.dumps(result, indent=1))
+
+
+if __name__ == "__main__":
+    main()
