@@ -253,6 +253,13 @@ int ams_replay_gather_f32(const float* slots_dev, int64_t slot_stride, int32_t c
                                      (hipStream_t)stream);
 }
 
+size_t ams_render_table_bytes(void) { return AMS_RENDER_TABLE_BYTES; }
+
+int ams_render_views(const uint8_t* frames_dev, const void* student_dev, int32_t student_dtype, const uint8_t* teacher_dev, int32_t batch, int32_t H,
+                     int32_t W, int32_t K, const uint8_t* tables_dev, const ams_render_out* out, void* stream) {
+    return launch_render_views(frames_dev, student_dev, student_dtype, teacher_dev, batch, H, W, K, tables_dev, out, (hipStream_t)stream);
+}
+
 int ams_student_train_step_dp(ams_student* s, const void* frames_dev, int32_t frames_dtype, const uint8_t* teacher_dev,
                               int32_t batch, int32_t global_batch, float lr, const uint8_t* mask_dev, double* loss_dev,
                               ams_allreduce_cb cb, void* user, void* stream) {

@@ -401,4 +401,9 @@ int launch_cross_confusion_pairs(const uint8_t* label_slots, int64_t label_strid
                                  const int32_t* pairs_host, int n_pairs, const int32_t* lut /*[256] -> subset idx or -1*/, int K, int64_t* conf,
                                  hipStream_t st);
 
+// ---- k_render.hip : the edge's pictures on the device: up to six RGB views of a batch in one launch ----
+// student: uint8 or int32 [B,H,W] (AMS_DT_U8 / AMS_DT_I32); tables: the device block of AMS_RENDER_TABLE_BYTES; out: NULL = view not wanted
+int launch_render_views(const uint8_t* frames, const void* student, int student_dtype, const uint8_t* teacher, int B, int H, int W, int K,
+                        const uint8_t* tables, const ams_render_out* out, hipStream_t st);
+
 }  // namespace ams

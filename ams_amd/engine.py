@@ -536,6 +536,10 @@ class StudentEngine:
                   self._out_dev[meta:meta + px * 4].view(torch.int32).view(b, self.height, self.width))
         return labels, conf, loss
 
+    def last_inputs(self):
+        """(frames, teacher labels or None) of the last ``predict_frames`` as the device tensors the pass read (kept alive until the next one)."""
+        return self._keepalive[0], self._keepalive[1]
+
     def fetch_frames(self, labels_only: bool = False):
         """(labels [B,H,W] int32, conf [B,K,K] int64, loss [B,2] f64) of the last ``predict_frames`` as fresh ndarrays: one copy, one sync.
         (``labels_only``, or a pass without teacher labels: conf and loss are None and only the label bytes cross PCIe.)"""

@@ -13,7 +13,7 @@ from pathlib import Path
 _HERE = Path(__file__).resolve().parent
 LIB_PATH = _HERE / "libams_hip.so"
 
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 # enums of include/ams_hip.h
 ROLE_STEM, ROLE_EXPAND, ROLE_DEPTHWISE, ROLE_PROJECT, ROLE_POOL_CONV, ROLE_ASPP, ROLE_CONCAT_PROJ, ROLE_LOGITS = range(8)
@@ -70,6 +70,15 @@ class DeltaVar(C.Structure):
     _fields_ = [("region", C.c_int32), ("reserved", C.c_int32), ("offset", C.c_int64), ("count", C.c_int64), ("mask_offset", C.c_int64)]
 
 
+class RenderOut(C.Structure):
+    """ams_render_out: the six views of ams_render_views, device pointers (None = not wanted), in the order of RENDER_VIEWS."""
+    _fields_ = [("colour_student", C.c_void_p), ("overlay_student", C.c_void_p), ("colour_teacher", C.c_void_p), ("overlay_teacher", C.c_void_p),
+                ("ignore_mask", C.c_void_p), ("cross_mask", C.c_void_p)]
+
+
+RENDER_VIEWS = tuple(f[0] for f in RenderOut._fields_)
+RENDER_TABLE_BYTES = 1120
+
 DELTA_OK, DELTA_BAD_SIZE, DELTA_BAD_PADDING = 0, 1, 2
 DELTA_MAX_VARS = 1024
 
@@ -97,6 +106,8 @@ SIGNATURES = {
     "ams_cross_confusion_pairs": (C.c_int, [_vp, _vp, _i64, _i32, _i64, _vp, _vp, _i32, _vp, _vp]),
     "ams_replay_gather": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "ams_replay_gather_f32": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp]),
+    "ams_render_table_bytes": (_sz, []),
+    "ams_render_views": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, C.POINTER(RenderOut), _vp]),
     "ams_student_train_step": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _f32, _vp, _vp, _vp]),
     "ams_student_train_step_dp": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _f32, _vp, _vp, ALLREDUCE_CB, _vp, _vp]),
     "ams_comm_unique_id": (C.c_int, [_vp, _sz]),

@@ -19,10 +19,15 @@ committed; the defects listed in SURVEY.md Appendix D are resolved towards their
     contents (hence the fine-tuned models) differ between the two settings; INTEGRATION.md lists them;
   * samples are uploaded every ``train_period`` seconds (the reference's last ``train_model`` argument, run.py:600-601);
   * a training event that finds the replay memory empty still publishes the current model for that time, so that the edge
-    has a model to load (the reference would fail inside ``mini_batch``).
+    has a model to load (the reference would fail inside ``mini_batch``);
+  * ``--save_pic`` (run.py:441-454): the reference unpacks the ``(colour, overlay)`` pair of ``colorize`` / ``colorize_teacher`` into swapped
+    names, so its ``overlay_*.png`` files hold the bare colour maps and its ``output_*.png`` files the overlays; here the ``overlay_*`` files
+    hold the overlays.  The reference rewrites ``<results>_<second>_*.png`` at every frame (``second = i / fps`` after ``i`` advanced), so only
+    the last frame of each label survives; here only those frames are painted and written.  ``cross_ignore`` raises IndexError on a teacher id
+    from the class count on (255 = unlabelled in the synthetic clips); the pictures count such a pixel as ignored, as the metric does.
 Out of scope (networking emulation / reporting): H.264 uplink through ffmpeg (``--compress_uplink``
 is rejected), PNG-exact uplink byte counts (zlib-deflated frame size is logged instead), the matplotlib plots.
-Video comes from a ``FrameSource``: there is no OpenCV here, so ``--input_video`` is either
+Video comes from a ``FrameSource``: there is no OpenCV here (pictures are written by ``ams_amd.png``), so ``--input_video`` is either
 ``synthetic:<NUM>-<name>[:seconds=S][:fps=F]`` (procedural clip) or a directory holding
 ``frame_%06d.npy`` (RGB uint8) and ``gt_%06d.npy`` files.
 """
@@ -39,6 +44,7 @@ from typing import List, Optional, Tuple
 
 import numpy as np
 
+from . import png
 from .delta import delta_layout
 from .exp_configs import class_weights, coco_class_converter, is_coco, test_length
 from .semantic_network import FrozenGraph, SemanticNetwork
@@ -97,6 +103,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--device_memory", action="store_true",
                    help="server: keep the replay memory on the device and sample mini-batches from it there (extra flag; needs a GPU; composes "
                         "with --gpu_ingest and --device_masks; same files and numbers)")
+    p.add_argument("--device_render", action="store_true",
+                   help="edge: paint the --save_pic views on the device right behind the inference pass and copy them to the host once per "
+                        "written frame (extra flag; needs --save_pic and a GPU; composes with --gpu_ingest, --edge_pipeline and "
+                        "--edge_from_delta; same files)")
     p.add_argument("--horizon_k1s", default="16,32,64,128,256,512", help="horizon mode: training-window lengths in seconds (reference: hard-coded)")
     p.add_argument("--horizon_k2", type=int, default=256, help="horizon mode: evaluation window in seconds (reference: 256)")
     p.add_argument("--horizon_points", type=int, default=3, help="horizon mode: number of evaluation points (reference: 3)")
@@ -202,6 +212,33 @@ class Context:
         ck = self.flags.student_checkpoint.replace(":", "_").split("/")
         return os.path.join(self.flags.output_dir, "%s_%s_%s_%d" % (prepend, video, ck[-2] if len(ck) > 1 else ck[-1],
                                                                     self.flags.height))
+
+
+PICTURES = ("cross_mask", "ignore_mask", "overlay_teacher", "output_teacher", "output_student", "overlay_student", "frame", "label_student")
+
+
+def write_pictures(prefix: str, semantic_network, frame, gt_frame, label_student, views=None) -> None:
+    """The eight files of reference run.py:443-454 under ``prefix`` (RGB in the file, as cv2.imwrite leaves it after RGB2BGR).  ``views``: host
+    arrays [1,H,W,3] by view name, painted on the device (--device_render); None: the host helpers paint."""
+    frame, gt_frame = _host(frame), _host(gt_frame)
+    if views is not None:
+        v = {k: a[0] for k, a in views.items()}
+        cross_mask, ignore_mask = v["cross_mask"], v["ignore_mask"]
+        output_teacher, overlay_teacher = v["colour_teacher"], v["overlay_teacher"]
+        output_student, overlay_student = v["colour_student"], v["overlay_student"]
+    else:
+        # cross_ignore indexes its take table with the teacher ids and raises on one from the class count on (255 = unlabelled): such a pixel
+        # is ignored (white / black), as the metric and the device path count it; the helper sees a valid id there and its answer is replaced
+        known = gt_frame < len(semantic_network.take_array)
+        cross_mask, ignore_mask = semantic_network.cross_ignore(label_teacher=np.where(known, gt_frame, 0), label_student=label_student)
+        ignore_mask[~known] = 255
+        cross_mask[~known] = 0
+        output_teacher, overlay_teacher = semantic_network.colorize_teacher(label=gt_frame, frame=frame)
+        output_student, overlay_student = semantic_network.colorize(label=label_student, frame=frame)
+    images = (cross_mask, ignore_mask, overlay_teacher, output_teacher, output_student, overlay_student, frame,
+              np.asarray(label_student).astype(np.uint8))
+    for name, image in zip(PICTURES, images):
+        png.write(prefix + name + ".png", image)
 
 
 def print_process(str_log, curr_time):
@@ -391,6 +428,26 @@ def infer_output(ctx: Context, inf_start, inf_end, gpu_id, run_label, gt_path, e
     from_delta = bool(getattr(FLAGS, "edge_from_delta", False))
     base_variables = None             # --edge_from_delta: the model the edge loaded first (what the server restores before each event)
     update_s = []                     # --edge_from_delta: host wall time of each edge update (payload in -> model re-frozen)
+    save_pic = bool(getattr(FLAGS, "save_pic", False))
+    device_render = bool(getattr(FLAGS, "device_render", False))
+    views = None
+    if device_render:
+        from .render import VIEWS as views
+    held = {}                         # --save_pic, depth >= 2: ticket -> (advanced frame index, frame, label) of the frames that get pictures
+
+    def pictured(i_next):
+        """--save_pic: does the frame after which ``i`` became ``i_next`` keep its files?  (the last frame of each label ``i_next // fps``)"""
+        return save_pic and ((i_next + 1) % fps == 0 or i_next == inf_end_frame)
+
+    def pictures(i_next, frame, gt_frame, result, rendered):
+        write_pictures(final_save_dir + "_%d_" % (i_next // fps), semantic_network, frame, gt_frame, result[0][0],
+                       rendered.host() if rendered is not None else None)
+
+    def collect(ticket):
+        res = semantic_network.collect(ticket)
+        if ticket in held:
+            pictures(*held.pop(ticket), res, semantic_network.take_rendered(ticket) if device_render else None)
+        return res
 
     def record(result, n_done):
         _labels, conf_mat_, _, miou_, loss_ = result
@@ -408,7 +465,7 @@ def infer_output(ctx: Context, inf_start, inf_end, gpu_id, run_label, gt_path, e
         if i / fps in load_times:
             while in_flight:                           # the frames still in flight belong to the model that is about to be replaced
                 t0 = time.time()
-                res = semantic_network.collect(in_flight.popleft())
+                res = collect(in_flight.popleft())
                 t_infer += time.time() - t0
                 done += 1
                 record(res, done)
@@ -434,20 +491,30 @@ def infer_output(ctx: Context, inf_start, inf_end, gpu_id, run_label, gt_path, e
                                                    height=FLAGS.height, gpu_id=gpu_id, mem_frac=1, frozen=True, **kw)
         frame, gt_frame = _to_size(*ctx.source.read(i), ctx.size, ctx.ingest)
         t0 = time.time()
+        rendered = None
         if depth > 1:
-            in_flight.append(semantic_network.predict_with_metric_async(_batch1(frame), _batch1(gt_frame)))
+            if pictured(i + 1):
+                render_kw = {"render": views} if device_render else {}
+                in_flight.append(semantic_network.predict_with_metric_async(_batch1(frame), _batch1(gt_frame), **render_kw))
+                held[in_flight[-1]] = (i + 1, frame, gt_frame)
+            else:
+                in_flight.append(semantic_network.predict_with_metric_async(_batch1(frame), _batch1(gt_frame)))
             # up to two passes of `depth` frames in flight: the one on the GPU and the one being filled
-            res = semantic_network.collect(in_flight.popleft()) if len(in_flight) >= 2 * depth else None
+            res = collect(in_flight.popleft()) if len(in_flight) >= 2 * depth else None
+        elif device_render and pictured(i + 1):
+            *res, rendered = semantic_network.predict_rendered(_batch1(frame), _batch1(gt_frame), views)
         else:
             res = semantic_network.predict_with_metric(_batch1(frame), _batch1(gt_frame))
         t_infer += time.time() - t0
         i += 1
+        if depth == 1 and pictured(i):
+            pictures(i, frame, gt_frame, res, rendered)
         if res is not None:
             done += 1
             record(res, done)
     while in_flight:
         t0 = time.time()
-        res = semantic_network.collect(in_flight.popleft())
+        res = collect(in_flight.popleft())
         t_infer += time.time() - t0
         done += 1
         record(res, done)
@@ -481,6 +548,7 @@ def main(argv: Optional[List[str]] = None, network_cls=None):
     assert not flags.enable_ATR or flags.mode == 'simple', 'ATR can only be used in simple mode'
     assert not flags.edge_from_delta or flags.mode in ('simple', 'early', 'pretrained'), \
         '--edge_from_delta needs an edge that starts from the server\'s initial model (simple, early or pretrained mode)'
+    assert not flags.device_render or flags.save_pic, '--device_render paints the pictures of --save_pic: pass both'
     os.makedirs(flags.output_dir, exist_ok=True)
     ctx = Context(flags, network_cls)
     vid_num, length = ctx.vid_num, ctx.length

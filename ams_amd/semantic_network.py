@@ -14,6 +14,9 @@ Deliberate differences (all listed in INTEGRATION.md):
   * ``device_masks=True`` keeps the server side of a model update on the device (coordinate selection, masks, the delta's bytes); same results.
   * ``train_with_deque`` also takes an ``ams_amd.replay.DeviceReplayMemory`` in place of the two deques: the replay memory and its sampler on
     the device, no helper thread; ``flip=True`` (the reference passes False) is reachable on that path.
+  * ``colorize`` / ``colorize_teacher`` / ``cross_ignore`` also take torch device tensors and then paint on the device (k_render.hip) and return
+    device tensors; ``predict_rendered`` and ``predict_with_metric_async(..., render=)`` / ``take_rendered`` paint right behind the inference pass.
+    On the device a label out of range gives defined output where the host helpers raise IndexError (ams_amd/render.py).
 """
 from __future__ import annotations
 
@@ -32,6 +35,7 @@ from . import coord_masks, hip
 from . import weights as W
 from .delta import delta_layout
 from .engine import StudentEngine
+from .render import VIEWS as RENDER_VIEWS, DeviceRenderer
 from .replay import DeviceReplayMemory, draw_samples
 from .utils import calculate_miou, colormap, mini_batch
 from .weights import load_npy
@@ -152,6 +156,7 @@ class SemanticNetwork(object):
             self._queued = []              # (ticket, frame, label) not yet launched
             self._pending = []             # tickets of the pass that is running on the GPU (its results are still on the device)
             self._ready = {}               # ticket -> result, after a pass was fetched
+            self._rendered = {}            # ticket -> views painted behind its pass (predict_with_metric_async(render=...))
             self._tickets = 0
         else:
             self.engine = StudentEngine(self.class_indices_graph, self.height, 2 * self.height,
@@ -320,16 +325,50 @@ class SemanticNetwork(object):
             self.process_lock.release()
         return labels_student, conf_mat_, iou_, miou_, loss_
 
+    def predict_rendered(self, frames, labels_teacher=None, views=RENDER_VIEWS):
+        """One inference pass and one render launch behind it on the same stream (an addition; the reference paints on the host after the
+        call, run.py:441-454).  The launch reads the pass's uint8 label view, the frames and the teacher labels where they are on the device.
+        Returns what ``predict_with_metric`` returns (``predict_input`` when ``labels_teacher`` is None: the labels alone), bit for bit, plus a
+        ``RenderedViews`` dict: view name -> uint8 device tensor [B,H,W,3] (``.host()``: all of them in one copy)."""
+        self.process_lock.acquire()
+        try:
+            self._drain_async()
+            labels_dev, _conf, _loss = self.engine.predict_frames(frames, labels_teacher, self._mode(), u8=True)
+            frames_dev, teacher_dev = self.engine.last_inputs()
+            rendered = self._get_renderer().render(frames_dev, labels_dev, teacher_dev, views)      # before anything else writes the label view
+            labels_student, confs, losses = self.engine.fetch_frames()
+            assert labels_student.shape == tuple(frames.shape[:-1] if hasattr(frames, 'shape') else np.shape(frames)[:-1])
+            if labels_teacher is None:
+                return labels_student, rendered
+            conf_mat_ = confs.sum(axis=0).astype(np.float64)
+            ls = losses.sum(axis=0)
+            loss_ = np.float32(ls[0] / ls[1]) if ls[1] > 0 else np.float32(np.nan)
+            iou_ = calculate_miou(conf_mat_, nan=True)
+            miou_ = np.nanmean(iou_)
+        finally:
+            self.process_lock.release()
+        return labels_student, conf_mat_, iou_, miou_, loss_, rendered
+
+    def _get_renderer(self):
+        """The render tables of this network, built and uploaded once."""
+        r = self.__dict__.get("_renderer")
+        if r is None:
+            r = self.__dict__["_renderer"] = DeviceRenderer(self.color_map_reduced_, colormap(), self.take_array, self.TOTAL_CLASSES,
+                                                            self.engine.device)
+        return r
+
     # The edge's per-frame call, pipeline_depth frames at a time (an addition: the reference's call is synchronous).  A one-frame forward is
     # ~45 dependent launches that leave most of the chip idle (0.49 ms); two frames in one pass take 0.59 ms, three 0.68 ms.  Submitted
     # frames wait until pipeline_depth of them are there (or until one of them is collected), then run as ONE pass with per-frame metrics
     # (ams_student_predict_frames).  Each frame's result is what predict_with_metric returns for it, bit for bit.
-    def predict_with_metric_async(self, frames, labels_teacher):
+    # ``render=views`` paints that frame's views right behind its pass, before the next pass overwrites the engine's label view (same stream);
+    # ``take_rendered(ticket)`` hands them over, ``collect`` keeps its 5-tuple.
+    def predict_with_metric_async(self, frames, labels_teacher, render=None):
         assert self.frozen and self.pipeline_depth > 1, "construct the frozen network with pipeline_depth >= 2"
         assert np.shape(frames)[0] == 1 and np.shape(labels_teacher)[0] == 1, "one frame per call"
         with self.process_lock:
             self._tickets += 1
-            self._queued.append((self._tickets, frames, labels_teacher))
+            self._queued.append((self._tickets, frames, labels_teacher, tuple(render) if render else None))
             if len(self._queued) >= self.pipeline_depth:
                 self._launch_queued()
             return self._tickets
@@ -352,8 +391,13 @@ class SemanticNetwork(object):
         frames = cat(q[1] for q in self._queued)
         labels = cat(q[2] for q in self._queued)
         self._pending = [q[0] for q in self._queued]
+        wanted = [(k, q[0], q[3]) for k, q in enumerate(self._queued) if q[3]]
         self._queued = []
-        self.engine.predict_frames(frames, labels, self._mode(), u8=True)     # returns at once: the pass runs while the caller goes on (labels leave as uint8)
+        labels_dev, _conf, _loss = self.engine.predict_frames(frames, labels, self._mode(), u8=True)     # returns at once: the pass runs while the caller goes on (labels leave as uint8)
+        if wanted:
+            frames_dev, teacher_dev = self.engine.last_inputs()
+            for k, ticket, views in wanted:       # enqueued behind the pass and before the next one, which overwrites the label view
+                self._rendered[ticket] = self._get_renderer().render(frames_dev[k:k + 1], labels_dev[k:k + 1], teacher_dev[k:k + 1], views)
 
     def collect(self, ticket):
         with self.process_lock:
@@ -363,6 +407,15 @@ class SemanticNetwork(object):
                     self._launch_queued()
                 self._fetch_pending()
             return self._ready.pop(ticket)
+
+    def take_rendered(self, ticket):
+        """The views of a frame submitted with ``render=``: a ``RenderedViews`` dict of device tensors [1,H,W,3] (once per ticket; before or
+        after ``collect``).  A frame that is still queued is launched first."""
+        with self.process_lock:
+            if ticket not in self._rendered and any(q[0] == ticket and q[3] for q in self._queued):
+                self._launch_queued()
+            assert ticket in self._rendered, "no views were requested for this ticket (or they were taken already)"
+            return self._rendered.pop(ticket)
 
     # ------------------------------------------------------------------ training
     def train_with_deque(self, frame_deque, label_deque, num_of_iterations, train_strategy='full_model',
@@ -836,13 +889,31 @@ class SemanticNetwork(object):
     def close_model(self):
         self.engine.close()
 
-    # ------------------------------------------------------------------ visualisation helpers (NumPy only)
+    # ------------------------------------------------------------------ visualisation helpers
     # Same signatures and return conventions as the reference (SemanticNetwork.py:719-755); bodies are this build's own:
     # palettes are looked up through one helper, the 50/50 overlay is integer arithmetic (cv2.addWeighted rounds half
     # to even on the float sum; so does _overlay), and the disagreement picture is built from boolean planes.
+    # Routed by input type: host arrays take the NumPy bodies and return ndarrays; torch tensors are painted by k_render.hip on the engine's
+    # device and return device tensors, equal bit for bit for labels in range (out of range: ams_amd/render.py).
     def _check_hw(self, arr, channels=None, what="array"):
         want = (self.height, 2 * self.height) + (() if channels is None else (channels,))
-        assert arr.shape == want, "%s must be %s, got %s" % (what, want, arr.shape)
+        assert tuple(arr.shape) == want, "%s must be %s, got %s" % (what, want, tuple(arr.shape))
+
+    @staticmethod
+    def _on_device(*arrays):
+        return any(isinstance(a, torch.Tensor) for a in arrays)
+
+    def _predict_device(self, frame):
+        """Labels of one device frame as an int32 device tensor [H, W]; nothing goes through the host."""
+        with self.process_lock:
+            self._drain_async()
+            return self.engine.predict(frame[None], self._mode())[0]
+
+    def _render_one(self, views, frame=None, student=None, teacher=None):
+        b1 = lambda x: None if x is None else (x[None] if isinstance(x, torch.Tensor) else np.asarray(x)[None])     # noqa: E731
+        with self.process_lock:
+            out = self._get_renderer().render(b1(frame), b1(student), b1(teacher), views)
+        return [out[v][0] for v in views]
 
     @staticmethod
     def _overlay(frame, colours):
@@ -859,6 +930,13 @@ class SemanticNetwork(object):
         assert frame is not None or label is not None, "At least a label or frame must be given"
         if frame is not None:
             self._check_hw(frame, 3, "frame")
+        if self._on_device(frame, label):
+            if label is None:
+                label = self._predict_device(frame)
+            self._check_hw(label, None, "label")
+            if frame is None:
+                return self._render_one(("colour_student",), student=label)[0]
+            return tuple(self._render_one(("colour_student", "overlay_student"), frame=frame, student=label))
         if label is None:
             label = self.predict_input(frame[None])[0]
         self._check_hw(label, None, "label")
@@ -868,6 +946,10 @@ class SemanticNetwork(object):
         if frame is not None:
             self._check_hw(frame, 3, "frame")
         self._check_hw(label, None, "label")
+        if self._on_device(frame, label):
+            if frame is None:
+                return self._render_one(("colour_teacher",), teacher=label)[0]
+            return tuple(self._render_one(("colour_teacher", "overlay_teacher"), frame=frame, teacher=label))
         return self._paint(colormap(), label, frame)
 
     def cross_ignore(self, label_teacher, label_student=None, frame_student=None):
@@ -876,6 +958,11 @@ class SemanticNetwork(object):
         assert label_student is not None or frame_student is not None, \
             "At least a label or frame from student must be given"
         self._check_hw(label_teacher, None, "label_teacher")
+        if self._on_device(label_teacher, label_student, frame_student):
+            if label_student is None:
+                label_student = self._predict_device(frame_student if isinstance(frame_student, torch.Tensor) else torch.from_numpy(frame_student))
+            self._check_hw(label_student, None, "label_student")
+            return tuple(self._render_one(("cross_mask", "ignore_mask"), student=label_student, teacher=label_teacher))
         if label_student is None:
             label_student = self.predict_input(frame_student[None])[0]
         self._check_hw(label_student, None, "label_student")

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define AMS_ABI_VERSION 4
+#define AMS_ABI_VERSION 5
 
 enum {
     AMS_OK = 0,
@@ -465,6 +465,47 @@ int ams_replay_gather_f32(const float* slots_dev, int64_t slot_stride, int32_t c
  * synchronisation. */
 int ams_cross_confusion_pairs(const ams_student* s, const uint8_t* label_slots_dev, int64_t label_slot_stride, int32_t capacity, int64_t n_pixels,
                               const int32_t* pairs_dev, const int32_t* pairs_host, int32_t n_pairs, int64_t* conf_mats_dev, void* stream);
+
+/* ---- the edge's pictures on the device (replaces the NumPy bodies of SemanticNetwork.py:719-755 colorize / colorize_teacher / cross_ignore
+ * for callers whose frame and labels are on the device already, and feeds run.py:441-454 --save_pic).  Six RGB uint8 views [batch, H, W, 3]:
+ *
+ *   colour_student    reduced palette [student]                     (student: index into the K-class subset)
+ *   overlay_student   the 50/50 blend of the frame and colour_student
+ *   colour_teacher    full palette [teacher]                        (teacher: dataset class id; all 256 rows exist, rows >= 19 are black)
+ *   overlay_teacher   the 50/50 blend of the frame and colour_teacher
+ *   ignore_mask       white where take[teacher] == 0, black elsewhere (as in the reference, subset index 0 doubles as "ignored")
+ *   cross_mask        reduced palette [take[teacher]] where not ignored and take[teacher] != student, black elsewhere
+ *
+ * The blend is integer: t = f + c; h = t >> 1; h += (t & 1) & (h & 1) (half to even, what cv2.addWeighted gives on the float sum).
+ *
+ * The table block (AMS_RENDER_TABLE_BYTES bytes on the device; ams_amd/render.py: build_tables makes it once per network): the full palette
+ * uint8 [256][3], the reduced palette uint8 [32][3] (rows from K on zero), the take table uint8 [256] (teacher id -> subset index, zero for
+ * an id outside the subset and from the dataset's class count on).
+ *
+ * Labels out of range give defined output: a student label outside [0, K) paints black; a teacher id from the dataset's class count on counts
+ * as ignored (white in ignore_mask, black in cross_mask, black in colour_teacher), where the host helper raises IndexError.  The metric of
+ * ams_student_predict_with_metric ignores such an id as well (its class table maps every id outside the subset to "ignored"). */
+#define AMS_RENDER_TABLE_BYTES 1120
+
+typedef struct ams_render_out {          /* device pointers, uint8 [batch, H, W, 3]; NULL = the view is not wanted and costs nothing */
+    uint8_t* colour_student;
+    uint8_t* overlay_student;
+    uint8_t* colour_teacher;
+    uint8_t* overlay_teacher;
+    uint8_t* ignore_mask;
+    uint8_t* cross_mask;
+} ams_render_out;
+
+/* AMS_RENDER_TABLE_BYTES of the library that is loaded */
+size_t ams_render_table_bytes(void);
+
+/* frames_dev uint8 [batch, H, W, 3]; student_dev uint8 or int32 [batch, H, W] (student_dtype AMS_DT_U8 / AMS_DT_I32); teacher_dev uint8
+ * [batch, H, W].  An input that no requested view reads may be NULL.  Stateless; one launch (render_views_kernel), no allocation, no
+ * synchronisation.  With W a multiple of 16 and every pointer 16-byte aligned a lane moves 16 pixels with 16-byte accesses.
+ * Refused with AMS_E_INVALID before anything is launched (no output is touched): batch, H or W <= 0 (or batch, H above 65535), K outside
+ * [1, 32], another student_dtype, tables_dev NULL, no view requested, a requested view whose input is NULL. */
+int ams_render_views(const uint8_t* frames_dev, const void* student_dev, int32_t student_dtype, const uint8_t* teacher_dev, int32_t batch, int32_t H,
+                     int32_t W, int32_t K, const uint8_t* tables_dev, const ams_render_out* out, void* stream);
 
 /* =====================================================================================================
  * Kernel-level entry points.  Same kernels the engine launches, exposed one by one so that tests/ can
