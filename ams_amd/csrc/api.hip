@@ -221,6 +221,14 @@ int ams_student_predict_frames_u8(ams_student* s, const void* frames_dev, int32_
                                   /*per_frame=*/1, /*labels_u8=*/1);
 }
 
+int ams_student_confidence(ams_student* s, int32_t batch, const uint8_t* teacher_dev, uint8_t* conf_u8, float* conf_f32, int64_t* stats, void* stream) {
+    AMS_REQUIRE(s, "confidence: null student");
+    AMS_REQUIRE(batch >= 1 && batch <= s->cfg.max_batch, "confidence: batch %d outside 1..%d", batch, s->cfg.max_batch);
+    const ams_student_config& c = s->cfg;
+    return launch_upsample_confidence(s->logits, 32, batch, s->h, s->w, c.class_indices, c.n_selected, c.height, c.width, teacher_dev, c.num_classes,
+                                      conf_u8, conf_f32, stats, (hipStream_t)stream);
+}
+
 int ams_cross_confusion(const ams_student* s, const uint8_t* labels_dev, int64_t n_pixels, int64_t* conf_mat_dev, void* stream) {
     AMS_REQUIRE(s && labels_dev && conf_mat_dev && n_pixels > 0, "cross_confusion: bad argument");
     int32_t lut[256];
@@ -759,6 +767,12 @@ int ams_k_upsample_argmax(const float* logits, int32_t B, int32_t h, int32_t w, 
     return launch_upsample_argmax(logits, NC, B, h, w, class_idx_host, K, H, W, teacher, NC, labels_out, conf_mat, loss,
                                   (hipStream_t)stream);
 }
+
+int ams_k_upsample_confidence(const float* logits, int32_t B, int32_t h, int32_t w, int32_t NC, const int32_t* class_idx_host, int32_t K,
+                              int32_t H, int32_t W, const uint8_t* teacher, uint8_t* conf_u8, float* conf_f32, int64_t* stats, void* stream) {
+    return launch_upsample_confidence(logits, NC, B, h, w, class_idx_host, K, H, W, teacher, NC, conf_u8, conf_f32, stats, (hipStream_t)stream);
+}
+size_t ams_confidence_stats_len(void) { return (size_t)confidence_stats_len(); }
 
 int ams_k_ce_grad(const float* logits, int32_t B, int32_t h, int32_t w, int32_t NC, const int32_t* class_idx_host, int32_t K, int32_t H,
                   int32_t W, const uint8_t* teacher, const double* loss_and_count_dev, float* dlogits, void* stream) {

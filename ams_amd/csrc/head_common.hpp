@@ -1,0 +1,60 @@
+// Geometry and interpolation arithmetic shared by the output-head kernels (k_head.hip, k_confidence.hip): every kernel that walks the
+// full-resolution pixels forms a pixel's K interpolated logits with these functions, in this order, so they all see the same bits.
+#pragma once
+#include "kernels.hpp"
+#include "cross_conf.hpp"
+
+namespace ams {
+
+struct HeadGeom {
+    int B, h, w, ld, K, H, W, NC;
+    int per_frame;         // metrics per frame: conf [B][K][K], loss [B][2] instead of the batch totals
+    int labels_u8;         // the label map as uint8 [B][H][W] through the same pointer (K <= 32 fits a byte: a quarter of the device -> host bytes)
+    float sy, sx;          // (h-1)/(H-1), (w-1)/(W-1) as f32 (TF: CalculateResizeScale with align_corners)
+};
+
+__device__ __forceinline__ void src_tap(int dst, float scale, int n_in, int& lo, int& hi, float& t) {
+    const float src = __fmul_rn((float)dst, scale);
+    const float fl = floorf(src);
+    lo = (int)fl;
+    hi = lo + 1 < n_in ? lo + 1 : n_in - 1;
+    t = __fsub_rn(src, fl);
+}
+
+// v = top + (bot - top) * ty,  top = tl + (tr - tl) * tx   (unfused, like the TF CPU kernel / the oracle)
+__device__ __forceinline__ float bilerp(float tl, float tr, float bl, float br, float tx, float ty) {
+    const float top = __fadd_rn(tl, __fmul_rn(__fsub_rn(tr, tl), tx));
+    const float bot = __fadd_rn(bl, __fmul_rn(__fsub_rn(br, bl), tx));
+    return __fadd_rn(top, __fmul_rn(__fsub_rn(bot, top), ty));
+}
+
+static inline int fill_class_table(const int32_t* cls_host, int K, int NC, ClassTable* ct) {
+    AMS_REQUIRE(K > 0 && K <= kMaxK, "head: K=%d out of range (1..%d)", K, kMaxK);
+    for (int i = 0; i < 256; ++i) ct->lut[i] = -1;
+    for (int k = 0; k < kMaxK; ++k) ct->idx[k] = 0;
+    for (int k = 0; k < K; ++k) {
+        AMS_REQUIRE(cls_host[k] >= 0 && cls_host[k] < NC && cls_host[k] < 256, "head: class id %d out of range", cls_host[k]);
+        ct->idx[k] = cls_host[k];
+        ct->lut[cls_host[k]] = k;
+    }
+    return AMS_OK;
+}
+
+static inline HeadGeom head_geom(int ld, int B, int h, int w, int K, int H, int W, int NC) {
+    HeadGeom g;
+    g.B = B; g.h = h; g.w = w; g.ld = ld; g.K = K; g.H = H; g.W = W; g.NC = NC; g.per_frame = 0; g.labels_u8 = 0;
+    g.sy = H > 1 ? (float)(h - 1) / (float)(H - 1) : 0.f;
+    g.sx = W > 1 ? (float)(w - 1) / (float)(W - 1) : 0.f;
+    return g;
+}
+
+// the grid of the kernels that walk down columns: (column strips of 256, row bands, frames).  32 bands per column strip and image, fewer
+// rows per band when that leaves the chip short of blocks
+static inline dim3 head_band_grid(int B, int H, int W) {
+    int rows_y = H < 32 ? H : 32;
+    while (rows_y < H && (int64_t)cdiv(W, 256) * rows_y * B < 2048) rows_y *= 2;
+    if (rows_y > H) rows_y = H;
+    return dim3(cdiv(W, 256), rows_y, B);
+}
+
+}  // namespace ams

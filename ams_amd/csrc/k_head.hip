@@ -4,32 +4,9 @@
 // confusion matrix and the masked cross-entropy sums (reference utils/graph_utils.py:373-408,
 // SemanticNetwork.py:96-115).  The backward kernel is the exact transpose: every low-resolution logit gathers
 // (softmax - onehot)/N from the full-resolution pixels it was interpolated into, in a fixed order.
-#include "kernels.hpp"
-#include "cross_conf.hpp"
+#include "head_common.hpp"
 
 namespace ams {
-
-struct HeadGeom {
-    int B, h, w, ld, K, H, W, NC;
-    int per_frame;         // metrics per frame: conf [B][K][K], loss [B][2] instead of the batch totals
-    int labels_u8;         // the label map as uint8 [B][H][W] through the same pointer (K <= 32 fits a byte: a quarter of the device -> host bytes)
-    float sy, sx;          // (h-1)/(H-1), (w-1)/(W-1) as f32 (TF: CalculateResizeScale with align_corners)
-};
-
-__device__ __forceinline__ void src_tap(int dst, float scale, int n_in, int& lo, int& hi, float& t) {
-    const float src = __fmul_rn((float)dst, scale);
-    const float fl = floorf(src);
-    lo = (int)fl;
-    hi = lo + 1 < n_in ? lo + 1 : n_in - 1;
-    t = __fsub_rn(src, fl);
-}
-
-// v = top + (bot - top) * ty,  top = tl + (tr - tl) * tx   (unfused, like the TF CPU kernel / the oracle)
-__device__ __forceinline__ float bilerp(float tl, float tr, float bl, float br, float tx, float ty) {
-    const float top = __fadd_rn(tl, __fmul_rn(__fsub_rn(tr, tl), tx));
-    const float bot = __fadd_rn(bl, __fmul_rn(__fsub_rn(br, bl), tx));
-    return __fadd_rn(top, __fmul_rn(__fsub_rn(bot, top), ty));
-}
 
 // Soft-teacher targets (create_student_v3 with soft_teacher=True, utils/graph_utils.py:359, 375-376, 403-404): teacher logits
 // [B][th][tw][ld] f32 fed through teacher_labels_logits_pl; the target of a pixel is softmax(gather(teacher_logits, class_weights)).  th x tw is
@@ -140,26 +117,6 @@ __global__ __launch_bounds__(256) void upsample_argmax_kernel(const float* __res
     }
 }
 
-static int fill_class_table(const int32_t* cls_host, int K, int NC, ClassTable* ct) {
-    AMS_REQUIRE(K > 0 && K <= kMaxK, "head: K=%d out of range (1..%d)", K, kMaxK);
-    for (int i = 0; i < 256; ++i) ct->lut[i] = -1;
-    for (int k = 0; k < kMaxK; ++k) ct->idx[k] = 0;
-    for (int k = 0; k < K; ++k) {
-        AMS_REQUIRE(cls_host[k] >= 0 && cls_host[k] < NC && cls_host[k] < 256, "head: class id %d out of range", cls_host[k]);
-        ct->idx[k] = cls_host[k];
-        ct->lut[cls_host[k]] = k;
-    }
-    return AMS_OK;
-}
-
-static HeadGeom head_geom(int ld, int B, int h, int w, int K, int H, int W, int NC) {
-    HeadGeom g;
-    g.B = B; g.h = h; g.w = w; g.ld = ld; g.K = K; g.H = H; g.W = W; g.NC = NC; g.per_frame = 0; g.labels_u8 = 0;
-    g.sy = H > 1 ? (float)(h - 1) / (float)(H - 1) : 0.f;
-    g.sx = W > 1 ? (float)(w - 1) / (float)(W - 1) : 0.f;
-    return g;
-}
-
 // cls: HOST pointer to the K selected class ids (they travel to the kernel by value)
 int launch_upsample_argmax(const float* logits, int ld, int B, int h, int w, const int32_t* cls, int K, int H, int W,
                            const uint8_t* teacher, int NC, int32_t* labels, int64_t* conf, double* loss, hipStream_t st, int per_frame, int labels_u8) {
@@ -176,11 +133,7 @@ int launch_upsample_argmax(const float* logits, int ld, int B, int h, int w, con
     g.per_frame = per_frame;
     g.labels_u8 = labels_u8;
     note_kernel("upsample_argmax_kernel");
-    // bands of consecutive rows per block: 32 per column strip and image, fewer rows per band when that leaves the chip short of blocks
-    int rows_y = H < 32 ? H : 32;
-    while (rows_y < H && (int64_t)cdiv(W, 256) * rows_y * B < 2048) rows_y *= 2;
-    if (rows_y > H) rows_y = H;
-    const dim3 grid(cdiv(W, 256), rows_y, B);
+    const dim3 grid = head_band_grid(B, H, W);      // bands of consecutive rows per block
     if (K <= 8)
         hipLaunchKernelGGL(upsample_argmax_kernel<8>, grid, dim3(256), 0, st, logits, g, ct, teacher, labels, (unsigned long long*)conf, loss);
     else

@@ -390,6 +390,12 @@ int launch_l2_regularizer(const float* p, float* g, const uint8_t* mask, int64_t
 int launch_cross_confusion(const uint8_t* a, const uint8_t* b, int64_t n, const int32_t* lut /*[256] -> subset idx or -1*/,
                            int K, int64_t* conf, hipStream_t st);
 
+// ---- k_confidence.hip : the student's per-pixel certainty (max softmax) and its statistics, the same walk as upsample_argmax ----
+// conf_u8 [B][H][W], conf_f32 [B][H][W], stats [B][confidence_stats_len()] (layout: include/ams_hip.h); each may be null
+int confidence_stats_len();
+int launch_upsample_confidence(const float* logits, int ld, int B, int h, int w, const int32_t* cls, int K, int H, int W, const uint8_t* teacher,
+                               int NC, uint8_t* conf_u8, float* conf_f32, int64_t* stats, hipStream_t st);
+
 // ---- k_replay.hip : the replay memory on the device: a mini-batch in one launch, cached teacher logits, the phi-score pairs ----
 // samples_host / pairs_host: the host copies of the device tables, checked before anything is launched
 int launch_replay_gather(const uint8_t* frame_slots, int64_t frame_stride, const uint8_t* label_slots, int64_t label_stride, int capacity, int Hs,

@@ -562,6 +562,24 @@ class StudentEngine:
             labels = host[meta:n].view(np.int32).reshape(b, self.height, self.width).copy()
         return labels, conf, loss
 
+    def confidence(self, teacher=None, f32: bool = False, batch: Optional[int] = None):
+        """The student's certainty about the frames of the LAST pass (k_confidence.hip; one launch on the current stream, nothing is
+        synchronised): (uint8 map [B,H,W] = rint(p * 255), f32 map [B,H,W] or None, int64 statistics [B, confidence.STATS_LEN]) as fresh
+        device tensors, p = the largest softmax value over the selected classes.  ``teacher``: uint8 labels [B,H,W] (host array or device
+        tensor) for the calibration fields of the statistics, None = the label-free fields only.  ``batch``: frames of that pass (default:
+        those of the last ``predict_frames``).  Call it before the next pass, which overwrites the low-resolution logits it reads."""
+        b = int(batch if batch is not None else self._frames_b)
+        assert 0 < b <= self.max_batch, "confidence: no pass to read (batch %d outside 1..%d)" % (b, self.max_batch)
+        lab = self._labels_to_device(teacher, b) if teacher is not None else None
+        n = int(self.lib.ams_confidence_stats_len())
+        conf_u8 = torch.empty((b, self.height, self.width), dtype=torch.uint8, device=self.device)
+        conf_f32 = torch.empty((b, self.height, self.width), dtype=torch.float32, device=self.device) if f32 else None
+        stats = torch.empty((b, n), dtype=torch.int64, device=self.device)
+        hip.check(self.lib.ams_student_confidence(self._h, b, C.c_void_p(lab.data_ptr()) if lab is not None else None,
+                                                  C.c_void_p(conf_u8.data_ptr()), C.c_void_p(conf_f32.data_ptr()) if f32 else None,
+                                                  C.c_void_p(stats.data_ptr()), self._stream()), "ams_student_confidence")
+        return conf_u8, conf_f32, stats
+
     def cross_confusion(self, labels_pair) -> torch.Tensor:
         a = np.asarray(labels_pair)
         assert a.shape[0] == 2

@@ -13,7 +13,7 @@ from pathlib import Path
 _HERE = Path(__file__).resolve().parent
 LIB_PATH = _HERE / "libams_hip.so"
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 # enums of include/ams_hip.h
 ROLE_STEM, ROLE_EXPAND, ROLE_DEPTHWISE, ROLE_PROJECT, ROLE_POOL_CONV, ROLE_ASPP, ROLE_CONCAT_PROJ, ROLE_LOGITS = range(8)
@@ -78,6 +78,7 @@ class RenderOut(C.Structure):
 
 RENDER_VIEWS = tuple(f[0] for f in RenderOut._fields_)
 RENDER_TABLE_BYTES = 1120
+CONFIDENCE_BINS = 32          # AMS_CONFIDENCE_BINS
 
 DELTA_OK, DELTA_BAD_SIZE, DELTA_BAD_PADDING = 0, 1, 2
 DELTA_MAX_VARS = 1024
@@ -102,6 +103,7 @@ SIGNATURES = {
     "ams_student_predict_with_metric": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "ams_student_predict_frames": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "ams_student_predict_frames_u8": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "ams_student_confidence": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "ams_cross_confusion": (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
     "ams_cross_confusion_pairs": (C.c_int, [_vp, _vp, _i64, _i32, _i64, _vp, _vp, _i32, _vp, _vp]),
     "ams_replay_gather": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
@@ -153,6 +155,8 @@ SIGNATURES = {
     "ams_k_global_mean_scratch": (_sz, [_i32, _i32]),
     "ams_k_upsample_argmax": (C.c_int, [_vp, _i32, _i32, _i32, _i32, C.POINTER(_i32), _i32, _i32, _i32, _vp, _vp, _vp,
                                         _vp, _vp]),
+    "ams_k_upsample_confidence": (C.c_int, [_vp, _i32, _i32, _i32, _i32, C.POINTER(_i32), _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "ams_confidence_stats_len": (_sz, []),
     "ams_k_ce_grad": (C.c_int, [_vp, _i32, _i32, _i32, _i32, C.POINTER(_i32), _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ams_k_ce_loss_grad": (C.c_int, [_vp, _i32, _i32, _i32, _i32, C.POINTER(_i32), _i32, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ams_k_ce_loss_grad_scratch": (_sz, [_i32, _i32, _i32, _i32]),

@@ -45,6 +45,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 from . import png
+from .confidence import NB as CONFIDENCE_BINS
 from .delta import delta_layout
 from .exp_configs import class_weights, coco_class_converter, is_coco, test_length
 from .semantic_network import FrozenGraph, SemanticNetwork
@@ -107,6 +108,12 @@ def build_parser() -> argparse.ArgumentParser:
                    help="edge: paint the --save_pic views on the device right behind the inference pass and copy them to the host once per "
                         "written frame (extra flag; needs --save_pic and a GPU; composes with --gpu_ingest, --edge_pipeline and "
                         "--edge_from_delta; same files)")
+    p.add_argument("--edge_confidence", action="store_true",
+                   help="edge: also compute the student's own certainty (per-pixel softmax maximum) right behind every inference pass and log it "
+                        "(extra flag; needs a GPU network): <results>_confidence.npy [frames, 3] = mean confidence, share of pixels below 0.5, "
+                        "expected calibration error against the teacher; <results>_reliability.npy [frames, 3, 32] = valid pixels, hits and "
+                        "summed confidence (x 2^20) per confidence bin; with --save_pic one grey confidence.png per pictured frame.  Every other "
+                        "file is unchanged; composes with --gpu_ingest, --edge_pipeline, --edge_from_delta and --device_render")
     p.add_argument("--horizon_k1s", default="16,32,64,128,256,512", help="horizon mode: training-window lengths in seconds (reference: hard-coded)")
     p.add_argument("--horizon_k2", type=int, default=256, help="horizon mode: evaluation window in seconds (reference: 256)")
     p.add_argument("--horizon_points", type=int, default=3, help="horizon mode: number of evaluation points (reference: 3)")
@@ -433,20 +440,33 @@ def infer_output(ctx: Context, inf_start, inf_end, gpu_id, run_label, gt_path, e
     views = None
     if device_render:
         from .render import VIEWS as views
+    edge_confidence = bool(getattr(FLAGS, "edge_confidence", False))
+    conf_rows, reliability = [], []   # --edge_confidence: per frame (mean, low_fraction(0.5), ECE) and (hist_valid, hist_hit, bin_sum)
     held = {}                         # --save_pic, depth >= 2: ticket -> (advanced frame index, frame, label) of the frames that get pictures
 
     def pictured(i_next):
         """--save_pic: does the frame after which ``i`` became ``i_next`` keep its files?  (the last frame of each label ``i_next // fps``)"""
         return save_pic and ((i_next + 1) % fps == 0 or i_next == inf_end_frame)
 
-    def pictures(i_next, frame, gt_frame, result, rendered):
+    def pictures(i_next, frame, gt_frame, result, rendered, confidence=None):
         write_pictures(final_save_dir + "_%d_" % (i_next // fps), semantic_network, frame, gt_frame, result[0][0],
                        rendered.host() if rendered is not None else None)
+        if confidence is not None:                     # after the reference's eight: the certainty map, grey (255 = sure)
+            png.write(final_save_dir + "_%d_confidence.png" % (i_next // fps), confidence.host()[0])
+
+    def log_confidence(confidence):
+        st = confidence.stats[0]
+        conf_rows.append((st.mean, st.low_fraction(0.5), st.ece))
+        reliability.append(np.stack([st.hist_valid, st.hist_hit, st.bin_sum]))
 
     def collect(ticket):
         res = semantic_network.collect(ticket)
+        confidence = None
+        if edge_confidence:
+            confidence = semantic_network.take_confidence(ticket)
+            log_confidence(confidence)
         if ticket in held:
-            pictures(*held.pop(ticket), res, semantic_network.take_rendered(ticket) if device_render else None)
+            pictures(*held.pop(ticket), res, semantic_network.take_rendered(ticket) if device_render else None, confidence)
         return res
 
     def record(result, n_done):
@@ -491,24 +511,32 @@ def infer_output(ctx: Context, inf_start, inf_end, gpu_id, run_label, gt_path, e
                                                    height=FLAGS.height, gpu_id=gpu_id, mem_frac=1, frozen=True, **kw)
         frame, gt_frame = _to_size(*ctx.source.read(i), ctx.size, ctx.ingest)
         t0 = time.time()
-        rendered = None
+        rendered = confidence = None
         if depth > 1:
+            more_kw = {"confidence": True} if edge_confidence else {}
             if pictured(i + 1):
                 render_kw = {"render": views} if device_render else {}
-                in_flight.append(semantic_network.predict_with_metric_async(_batch1(frame), _batch1(gt_frame), **render_kw))
+                in_flight.append(semantic_network.predict_with_metric_async(_batch1(frame), _batch1(gt_frame), **render_kw, **more_kw))
                 held[in_flight[-1]] = (i + 1, frame, gt_frame)
             else:
-                in_flight.append(semantic_network.predict_with_metric_async(_batch1(frame), _batch1(gt_frame)))
+                in_flight.append(semantic_network.predict_with_metric_async(_batch1(frame), _batch1(gt_frame), **more_kw))
             # up to two passes of `depth` frames in flight: the one on the GPU and the one being filled
             res = collect(in_flight.popleft()) if len(in_flight) >= 2 * depth else None
         elif device_render and pictured(i + 1):
-            *res, rendered = semantic_network.predict_rendered(_batch1(frame), _batch1(gt_frame), views)
+            if edge_confidence:
+                *res, rendered, confidence = semantic_network.predict_rendered(_batch1(frame), _batch1(gt_frame), views, confidence=True)
+            else:
+                *res, rendered = semantic_network.predict_rendered(_batch1(frame), _batch1(gt_frame), views)
+        elif edge_confidence:
+            *res, confidence = semantic_network.predict_with_confidence(_batch1(frame), _batch1(gt_frame))
         else:
             res = semantic_network.predict_with_metric(_batch1(frame), _batch1(gt_frame))
         t_infer += time.time() - t0
         i += 1
+        if confidence is not None:
+            log_confidence(confidence)
         if depth == 1 and pictured(i):
-            pictures(i, frame, gt_frame, res, rendered)
+            pictures(i, frame, gt_frame, res, rendered, confidence)
         if res is not None:
             done += 1
             record(res, done)
@@ -522,6 +550,9 @@ def infer_output(ctx: Context, inf_start, inf_end, gpu_id, run_label, gt_path, e
     np.save('%s_mioucats.npy' % final_save_dir, miou_cats)
     np.save('%s_mious.npy' % final_save_dir, miou_s)
     np.save('%s_mioumems.npy' % final_save_dir, miou_mem_s)
+    if edge_confidence:
+        np.save('%s_confidence.npy' % final_save_dir, np.asarray(conf_rows, dtype=np.float64).reshape(-1, 3))
+        np.save('%s_reliability.npy' % final_save_dir, np.asarray(reliability, dtype=np.int64).reshape(-1, 3, CONFIDENCE_BINS))
     if semantic_network is not None:
         semantic_network.close_model()
     n = max(1, inf_end_frame - inf_start * fps)
@@ -549,6 +580,9 @@ def main(argv: Optional[List[str]] = None, network_cls=None):
     assert not flags.edge_from_delta or flags.mode in ('simple', 'early', 'pretrained'), \
         '--edge_from_delta needs an edge that starts from the server\'s initial model (simple, early or pretrained mode)'
     assert not flags.device_render or flags.save_pic, '--device_render paints the pictures of --save_pic: pass both'
+    assert not flags.edge_confidence or hasattr(network_cls or SemanticNetwork, "predict_with_confidence"), \
+        '--edge_confidence needs a network that computes the student\'s confidence on the GPU (predict_with_confidence): %s has none' \
+        % (network_cls or SemanticNetwork).__name__
     os.makedirs(flags.output_dir, exist_ok=True)
     ctx = Context(flags, network_cls)
     vid_num, length = ctx.vid_num, ctx.length

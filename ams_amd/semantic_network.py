@@ -17,6 +17,9 @@ Deliberate differences (all listed in INTEGRATION.md):
   * ``colorize`` / ``colorize_teacher`` / ``cross_ignore`` also take torch device tensors and then paint on the device (k_render.hip) and return
     device tensors; ``predict_rendered`` and ``predict_with_metric_async(..., render=)`` / ``take_rendered`` paint right behind the inference pass.
     On the device a label out of range gives defined output where the host helpers raise IndexError (ams_amd/render.py).
+  * ``predict_with_confidence`` / ``predict_probabilities`` / ``predict_with_metric_async(..., confidence=True)`` + ``take_confidence`` expose
+    the student graph's ``probabilities_reduced`` (the per-pixel softmax maximum) and its statistics, computed right behind the inference pass
+    (k_confidence.hip, ams_amd/confidence.py).
 """
 from __future__ import annotations
 
@@ -32,6 +35,7 @@ import numpy as np
 import torch
 
 from . import coord_masks, hip
+from .confidence import Confidence, ConfidenceStats
 from . import weights as W
 from .delta import delta_layout
 from .engine import StudentEngine
@@ -157,6 +161,7 @@ class SemanticNetwork(object):
             self._pending = []             # tickets of the pass that is running on the GPU (its results are still on the device)
             self._ready = {}               # ticket -> result, after a pass was fetched
             self._rendered = {}            # ticket -> views painted behind its pass (predict_with_metric_async(render=...))
+            self._confident = {}           # ticket -> (confidence map, its pass's statistics rows, frame index) (..._async(confidence=True))
             self._tickets = 0
         else:
             self.engine = StudentEngine(self.class_indices_graph, self.height, 2 * self.height,
@@ -325,21 +330,28 @@ class SemanticNetwork(object):
             self.process_lock.release()
         return labels_student, conf_mat_, iou_, miou_, loss_
 
-    def predict_rendered(self, frames, labels_teacher=None, views=RENDER_VIEWS):
+    def predict_rendered(self, frames, labels_teacher=None, views=RENDER_VIEWS, confidence=False):
         """One inference pass and one render launch behind it on the same stream (an addition; the reference paints on the host after the
         call, run.py:441-454).  The launch reads the pass's uint8 label view, the frames and the teacher labels where they are on the device.
         Returns what ``predict_with_metric`` returns (``predict_input`` when ``labels_teacher`` is None: the labels alone), bit for bit, plus a
-        ``RenderedViews`` dict: view name -> uint8 device tensor [B,H,W,3] (``.host()``: all of them in one copy)."""
+        ``RenderedViews`` dict: view name -> uint8 device tensor [B,H,W,3] (``.host()``: all of them in one copy).  ``confidence=True``: the
+        confidence launch of ``predict_with_confidence`` behind the same pass too, its ``Confidence`` as one more element at the end."""
         self.process_lock.acquire()
         try:
             self._drain_async()
             labels_dev, _conf, _loss = self.engine.predict_frames(frames, labels_teacher, self._mode(), u8=True)
             frames_dev, teacher_dev = self.engine.last_inputs()
             rendered = self._get_renderer().render(frames_dev, labels_dev, teacher_dev, views)      # before anything else writes the label view
+            more = ()
+            if confidence:
+                conf_map, _f32, stats_dev = self.engine.confidence(teacher_dev)
+                stats_host = self._confidence_rows(stats_dev)
             labels_student, confs, losses = self.engine.fetch_frames()
+            if confidence:
+                more = (Confidence(conf_map, [ConfidenceStats(r, self.class_count) for r in stats_host.numpy().copy()]),)
             assert labels_student.shape == tuple(frames.shape[:-1] if hasattr(frames, 'shape') else np.shape(frames)[:-1])
             if labels_teacher is None:
-                return labels_student, rendered
+                return (labels_student, rendered) + more
             conf_mat_ = confs.sum(axis=0).astype(np.float64)
             ls = losses.sum(axis=0)
             loss_ = np.float32(ls[0] / ls[1]) if ls[1] > 0 else np.float32(np.nan)
@@ -347,7 +359,49 @@ class SemanticNetwork(object):
             miou_ = np.nanmean(iou_)
         finally:
             self.process_lock.release()
-        return labels_student, conf_mat_, iou_, miou_, loss_, rendered
+        return (labels_student, conf_mat_, iou_, miou_, loss_, rendered) + more
+
+    def predict_with_confidence(self, frames, labels_teacher=None):
+        """One inference pass and one confidence launch behind it on the same stream: the student graph's ``probabilities_reduced``
+        (utils/graph_utils.py:388-389), which the reference builds and no caller of it fetches.  Returns what ``predict_with_metric`` returns
+        (``predict_input`` when ``labels_teacher`` is None: the labels alone), bit for bit, plus a ``Confidence``: ``.map`` the uint8 device
+        tensor [B,H,W] = rint(p * 255) and ``.stats`` one ``ConfidenceStats`` per frame (calibration fields only with teacher labels)."""
+        self.process_lock.acquire()
+        try:
+            self._drain_async()
+            self.engine.predict_frames(frames, labels_teacher, self._mode(), u8=True)
+            conf_map, _f32, stats_dev = self.engine.confidence(self.engine.last_inputs()[1])      # before anything else overwrites the logits
+            stats_host = self._confidence_rows(stats_dev)          # leaves with the pass's results: fetch_frames synchronises once for both
+            labels_student, confs, losses = self.engine.fetch_frames()
+            confidence = Confidence(conf_map, [ConfidenceStats(r, self.class_count) for r in stats_host.numpy().copy()])
+            assert labels_student.shape == tuple(frames.shape[:-1] if hasattr(frames, 'shape') else np.shape(frames)[:-1])
+            if labels_teacher is None:
+                return labels_student, confidence
+            conf_mat_ = confs.sum(axis=0).astype(np.float64)
+            ls = losses.sum(axis=0)
+            loss_ = np.float32(ls[0] / ls[1]) if ls[1] > 0 else np.float32(np.nan)
+            iou_ = calculate_miou(conf_mat_, nan=True)
+            miou_ = np.nanmean(iou_)
+        finally:
+            self.process_lock.release()
+        return labels_student, conf_mat_, iou_, miou_, loss_, confidence
+
+    def _confidence_rows(self, stats_dev):
+        """the statistics rows on their way to a pinned host block (asynchronous: valid after the stream's next synchronisation)"""
+        block = self.__dict__.get("_confidence_host")
+        if block is None:
+            block = self.__dict__["_confidence_host"] = torch.empty((self.engine.max_batch, stats_dev.shape[1]), dtype=torch.int64).pin_memory()
+        view = block[:stats_dev.shape[0]]
+        view.copy_(stats_dev, non_blocking=True)
+        return view
+
+    def predict_probabilities(self, frames):
+        """``student['probabilities_reduced']`` of the reference's graph: f32 ndarray [B,H,W], per pixel the largest softmax value over the
+        selected classes."""
+        with self.process_lock:
+            self._drain_async()
+            self.engine.predict_frames(frames, None, self._mode(), u8=True)
+            return self.engine.confidence(None, f32=True)[1].cpu().numpy()
 
     def _get_renderer(self):
         """The render tables of this network, built and uploaded once."""
@@ -362,13 +416,14 @@ class SemanticNetwork(object):
     # frames wait until pipeline_depth of them are there (or until one of them is collected), then run as ONE pass with per-frame metrics
     # (ams_student_predict_frames).  Each frame's result is what predict_with_metric returns for it, bit for bit.
     # ``render=views`` paints that frame's views right behind its pass, before the next pass overwrites the engine's label view (same stream);
-    # ``take_rendered(ticket)`` hands them over, ``collect`` keeps its 5-tuple.
-    def predict_with_metric_async(self, frames, labels_teacher, render=None):
+    # ``take_rendered(ticket)`` hands them over, ``collect`` keeps its 5-tuple.  ``confidence=True`` works the same way: one confidence launch over
+    # the pass's frames behind it, ``take_confidence(ticket)`` hands that frame's ``Confidence`` over.
+    def predict_with_metric_async(self, frames, labels_teacher, render=None, confidence=False):
         assert self.frozen and self.pipeline_depth > 1, "construct the frozen network with pipeline_depth >= 2"
         assert np.shape(frames)[0] == 1 and np.shape(labels_teacher)[0] == 1, "one frame per call"
         with self.process_lock:
             self._tickets += 1
-            self._queued.append((self._tickets, frames, labels_teacher, tuple(render) if render else None))
+            self._queued.append((self._tickets, frames, labels_teacher, tuple(render) if render else None, bool(confidence)))
             if len(self._queued) >= self.pipeline_depth:
                 self._launch_queued()
             return self._tickets
@@ -392,12 +447,18 @@ class SemanticNetwork(object):
         labels = cat(q[2] for q in self._queued)
         self._pending = [q[0] for q in self._queued]
         wanted = [(k, q[0], q[3]) for k, q in enumerate(self._queued) if q[3]]
+        certain = [(k, q[0]) for k, q in enumerate(self._queued) if q[4]]
         self._queued = []
         labels_dev, _conf, _loss = self.engine.predict_frames(frames, labels, self._mode(), u8=True)     # returns at once: the pass runs while the caller goes on (labels leave as uint8)
         if wanted:
             frames_dev, teacher_dev = self.engine.last_inputs()
             for k, ticket, views in wanted:       # enqueued behind the pass and before the next one, which overwrites the label view
                 self._rendered[ticket] = self._get_renderer().render(frames_dev[k:k + 1], labels_dev[k:k + 1], teacher_dev[k:k + 1], views)
+        if certain:                               # one launch over the whole pass, behind it and before the next one overwrites the logits
+            conf_map, _f32, stats_dev = self.engine.confidence(self.engine.last_inputs()[1])
+            rows = {"dev": stats_dev, "host": None}
+            for k, ticket in certain:
+                self._confident[ticket] = (conf_map[k:k + 1], rows, k)
 
     def collect(self, ticket):
         with self.process_lock:
@@ -416,6 +477,18 @@ class SemanticNetwork(object):
                 self._launch_queued()
             assert ticket in self._rendered, "no views were requested for this ticket (or they were taken already)"
             return self._rendered.pop(ticket)
+
+    def take_confidence(self, ticket):
+        """The ``Confidence`` of a frame submitted with ``confidence=True``: map [1,H,W] on the device, one ``ConfidenceStats`` (once per
+        ticket; before or after ``collect``).  A frame that is still queued is launched first."""
+        with self.process_lock:
+            if ticket not in self._confident and any(q[0] == ticket and q[4] for q in self._queued):
+                self._launch_queued()
+            assert ticket in self._confident, "no confidence was requested for this ticket (or it was taken already)"
+            conf_map, rows, k = self._confident.pop(ticket)
+            if rows["host"] is None:
+                rows["host"] = rows["dev"].cpu().numpy()          # the pass's rows, once for all its tickets
+            return Confidence(conf_map, [ConfidenceStats(rows["host"][k], self.class_count)])
 
     # ------------------------------------------------------------------ training
     def train_with_deque(self, frame_deque, label_deque, num_of_iterations, train_strategy='full_model',
@@ -887,6 +960,9 @@ class SemanticNetwork(object):
             pb_file.write(graph_def.SerializeToString())
 
     def close_model(self):
+        if self.frozen:                   # views and confidence maps nobody took: their device memory goes with the engine
+            self._rendered.clear()
+            self._confident.clear()
         self.engine.close()
 
     # ------------------------------------------------------------------ visualisation helpers

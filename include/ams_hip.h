@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define AMS_ABI_VERSION 5
+#define AMS_ABI_VERSION 6
 
 enum {
     AMS_OK = 0,
@@ -162,6 +162,13 @@ int ams_student_predict_frames(ams_student* s, const void* frames_dev, int32_t f
  * predict_with_metric return int32 as the reference does: the widening of 0.5 MB costs less there than copying 2 MB out of the pinned buffer). */
 int ams_student_predict_frames_u8(ams_student* s, const void* frames_dev, int32_t frames_dtype, int32_t batch, int32_t mode,
                                   const uint8_t* teacher_dev, uint8_t* labels_out_dev, int64_t* conf_mats_dev, double* losses_dev, void* stream);
+
+/* The student's certainty about the frames of the LAST forward pass (any ams_student_predict* call; the fine-tune step leaves its batch's
+ * logits there too): ams_k_upsample_confidence on the low-resolution logits that pass left on the device (AMS_REGION_LOGITS), one launch over
+ * `batch` frames.  teacher_dev uint8 [batch,H,W] or NULL; conf_u8 / conf_f32 / stats as there, each may be NULL.  Launch it on the stream of
+ * the pass and before the next one, which overwrites the logits.  batch outside 1..max_batch: AMS_E_INVALID, nothing written. */
+int ams_student_confidence(ams_student* s, int32_t batch, const uint8_t* teacher_dev, uint8_t* conf_u8, float* conf_f32, int64_t* stats,
+                           void* stream);
 
 int ams_cross_confusion(const ams_student* s, const uint8_t* labels_dev, int64_t n_pixels, int64_t* conf_mat_dev,
                         void* stream);
@@ -621,6 +628,25 @@ size_t ams_k_global_mean_scratch(int32_t B, int32_t C);
 int ams_k_upsample_argmax(const float* logits /*[B,h,w,NC]*/, int32_t B, int32_t h, int32_t w, int32_t NC,
                           const int32_t* class_idx_host, int32_t K, int32_t H, int32_t W, const uint8_t* teacher,
                           int32_t* labels_out, int64_t* conf_mat, double* loss, void* stream);
+
+/* The student's own certainty (create_student_v3's probabilities_reduced and loss_sel, utils/graph_utils.py:388-389, 410-418): the same walk
+ * over the full-resolution pixels as ams_k_upsample_argmax (same interpolation, same argmax), per pixel p = max_k softmax_k = 1 / sum_k
+ * exp(z_k - z_max).  Every output may be NULL (nothing is written there):
+ *   conf_u8  uint8 [B,H,W]   rint(p * 255)
+ *   conf_f32 float [B,H,W]   p
+ *   stats    int64 [B][ams_confidence_stats_len()], one row per frame, overwritten:
+ *            hist[NB] | hist_valid[NB] | hist_hit[NB] | bin_sum[NB] | sel_cnt[32] | sel_sum[32] | sum_all,  NB = AMS_CONFIDENCE_BINS
+ *            bin = min(NB - 1, (int)(p * NB)); hist counts every pixel and sum_all adds their rint(p * 2^20).  The other fields need `teacher`
+ *            (uint8 [B,H,W], NULL = none) and cover its valid pixels (label in the subset): hist_valid their number per bin, hist_hit those
+ *            whose argmax is the teacher's class, bin_sum their summed rint(p * 2^20); sel_cnt[k] the valid pixels whose teacher class OR
+ *            argmax is k (once when both are), sel_sum[k] their summed rint(CE * 2^20).  All integers: a frame's row does not depend on the
+ *            batch it is computed in.  A pixel whose logits hold a NaN is counted in bin 0 and adds 0 to bin_sum and sum_all; a pixel
+ *            loss that is not finite is counted in sel_cnt and adds 0 to sel_sum. */
+#define AMS_CONFIDENCE_BINS 32
+int ams_k_upsample_confidence(const float* logits /*[B,h,w,NC]*/, int32_t B, int32_t h, int32_t w, int32_t NC,
+                              const int32_t* class_idx_host, int32_t K, int32_t H, int32_t W, const uint8_t* teacher,
+                              uint8_t* conf_u8, float* conf_f32, int64_t* stats, void* stream);
+size_t ams_confidence_stats_len(void);
 
 /* K11 backward: d loss / d low-res logits (zeros for unselected classes); loss_and_count_dev: the double[2]
  * written by ams_k_upsample_argmax ([1] = number of valid pixels, the mean's denominator).
