@@ -226,12 +226,8 @@ class StudentEngine:
         """Assign every model variable present in ``variables`` (SaveHelper.restore_vars); Adam state untouched."""
         tr = self.params.cpu().numpy()
         st = self.stats.cpu().numpy()
-        for v in self.spec.trainable:
-            if v.name in variables:
-                tr[v.offset:v.offset + v.size] = np.asarray(variables[v.name], dtype=np.float32).reshape(-1)
-        for v in self.spec.stats:
-            if v.name in variables:
-                st[v.offset:v.offset + v.size] = np.asarray(variables[v.name], dtype=np.float32).reshape(-1)
+        W.fill_flat(tr, [v for v in self.spec.trainable if v.name in variables], variables)
+        W.fill_flat(st, [v for v in self.spec.stats if v.name in variables], variables)
         self.params.copy_(torch.from_numpy(tr))
         self.stats.copy_(torch.from_numpy(st))
 
@@ -294,12 +290,10 @@ class StudentEngine:
             self._reg_mask = None
             return
         flat = np.zeros(self.spec.n_trainable, dtype=np.uint8)
-        n_vars = 0
-        for v in self.spec.trainable:
-            if biases_only and 'weight' in v.name:
-                continue
-            flat[v.offset:v.offset + v.size] = 1
-            n_vars += 1
+        tvars = [v for v in self.spec.trainable if not (biases_only and 'weight' in v.name)]
+        for part in W.split_flat(flat, tvars):
+            part[...] = 1
+        n_vars = len(tvars)
         self._reg_mask = torch.from_numpy(flat).to(self.device)          # referenced by the handle: kept alive here
         hip.check(self.lib.ams_student_set_regularizer(self._h, C.c_void_p(self._reg_mask.data_ptr()), n_vars, float(coef)),
                   "ams_student_set_regularizer")
@@ -308,7 +302,7 @@ class StudentEngine:
         """feed_dict[student['teacher_labels_logits_pl']]: f32 [b, th, tw, num_classes] (host array or device tensor); returns the device tensor
         (the caller keeps it alive until the step has been enqueued on the same stream order)."""
         if teacher_logits is None:
-            assert not getattr(self, "soft_teacher", False), "soft_teacher is on: teacher_logits must be fed (teacher_labels_logits_pl)"
+            assert not self.soft_teacher, "soft_teacher is on: teacher_logits must be fed (teacher_labels_logits_pl)"
             return None
         t = teacher_logits if isinstance(teacher_logits, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(teacher_logits, dtype=np.float32))
         assert t.dim() == 4 and t.shape[0] == b and t.shape[3] == self.num_classes, "teacher logits must be [batch, th, tw, %d]" % self.num_classes

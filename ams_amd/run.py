@@ -459,6 +459,14 @@ def infer_output(ctx: Context, inf_start, inf_end, gpu_id, run_label, gt_path, e
         conf_rows.append((st.mean, st.low_fraction(0.5), st.ece))
         reliability.append(np.stack([st.hist_valid, st.hist_hit, st.bin_sum]))
 
+    def predict_with_extras(frame, gt_frame, want_views):
+        """One synchronous pass with the views and / or the confidence behind it: (predict_with_metric's 5-tuple, views or None, confidence or None)."""
+        if want_views:
+            out = semantic_network.predict_rendered(_batch1(frame), _batch1(gt_frame), views, confidence=edge_confidence)
+            return out[:5], out[5], out[6] if edge_confidence else None
+        out = semantic_network.predict_with_confidence(_batch1(frame), _batch1(gt_frame))
+        return out[:5], None, out[5]
+
     def collect(ticket):
         res = semantic_network.collect(ticket)
         confidence = None
@@ -522,14 +530,9 @@ def infer_output(ctx: Context, inf_start, inf_end, gpu_id, run_label, gt_path, e
                 in_flight.append(semantic_network.predict_with_metric_async(_batch1(frame), _batch1(gt_frame), **more_kw))
             # up to two passes of `depth` frames in flight: the one on the GPU and the one being filled
             res = collect(in_flight.popleft()) if len(in_flight) >= 2 * depth else None
-        elif device_render and pictured(i + 1):
-            if edge_confidence:
-                *res, rendered, confidence = semantic_network.predict_rendered(_batch1(frame), _batch1(gt_frame), views, confidence=True)
-            else:
-                *res, rendered = semantic_network.predict_rendered(_batch1(frame), _batch1(gt_frame), views)
-        elif edge_confidence:
-            *res, confidence = semantic_network.predict_with_confidence(_batch1(frame), _batch1(gt_frame))
-        else:
+        elif edge_confidence or (device_render and pictured(i + 1)):
+            res, rendered, confidence = predict_with_extras(frame, gt_frame, device_render and pictured(i + 1))
+        else:                                          # the reference's surface: all a CPU stand-in has
             res = semantic_network.predict_with_metric(_batch1(frame), _batch1(gt_frame))
         t_infer += time.time() - t0
         i += 1

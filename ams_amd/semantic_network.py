@@ -24,24 +24,23 @@ Deliberate differences (all listed in INTEGRATION.md):
 from __future__ import annotations
 
 import io
-import os
-import random
 import threading
 import time
-from collections import deque
-from typing import Dict, List, Optional
+from typing import Dict, List, NamedTuple, Optional
 
 import numpy as np
 import torch
 
 from . import coord_masks, hip
+from .batch_feed import HostBatchFeed
 from .confidence import Confidence, ConfidenceStats
 from . import weights as W
 from .delta import delta_layout
+from .edge_pipeline import EdgePipeline
 from .engine import StudentEngine
 from .render import VIEWS as RENDER_VIEWS, DeviceRenderer
 from .replay import DeviceReplayMemory, draw_samples
-from .utils import calculate_miou, colormap, mini_batch
+from .utils import calculate_miou, colormap
 from .weights import load_npy
 
 FROZEN_MAGIC = b"AMSF\x01"
@@ -71,6 +70,26 @@ class FrozenGraph:
         z = np.load(io.BytesIO(data[len(FROZEN_MAGIC):]))
         variables = {k.replace("|", "/"): z[k] for k in z.files if not k.startswith("__")}
         return FrozenGraph(variables, z["__class_indices"].tolist(), int(z["__height"]), int(z["__num_classes"]))
+
+
+def pass_metrics(conf_i64, loss_sum_count):
+    """What follows the labels in a result: (confusion matrix float64, IoU per class, mIoU, loss float32 or NaN) from the int64 confusion
+    matrix of a frame (or summed over a pass) and its f64 [loss sum, valid pixel count]."""
+    conf_mat_ = conf_i64.astype(np.float64)
+    iou_ = calculate_miou(conf_mat_, nan=True)
+    loss_ = np.float32(loss_sum_count[0] / loss_sum_count[1]) if loss_sum_count[1] > 0 else np.float32(np.nan)
+    return conf_mat_, iou_, np.nanmean(iou_), loss_
+
+
+class _Pass(NamedTuple):                    # one synchronous inference pass, on the host
+    labels: np.ndarray                      # int32 [B,H,W]
+    metrics: Optional[tuple]                # pass_metrics summed over the frames; None without teacher labels
+    rendered: object                        # RenderedViews (device tensors [B,H,W,3]) or None
+    confidence: Optional[Confidence]
+
+    def result(self, *extras):
+        """the tuple the public calls return: labels[, the four metrics][, extras]"""
+        return (self.labels,) + (self.metrics or ()) + extras
 
 
 class SemanticNetwork(object):
@@ -157,12 +176,6 @@ class SemanticNetwork(object):
                                         num_classes=self.TOTAL_CLASSES, device=device)
             self.engine.load_variables(frozen_graph.variables)
             self.engine.freeze()
-            self._queued = []              # (ticket, frame, label) not yet launched
-            self._pending = []             # tickets of the pass that is running on the GPU (its results are still on the device)
-            self._ready = {}               # ticket -> result, after a pass was fetched
-            self._rendered = {}            # ticket -> views painted behind its pass (predict_with_metric_async(render=...))
-            self._confident = {}           # ticket -> (confidence map, its pass's statistics rows, frame index) (..._async(confidence=True))
-            self._tickets = 0
         else:
             self.engine = StudentEngine(self.class_indices_graph, self.height, 2 * self.height,
                                         max_batch=int(max_batch or max(int(mini_batch_size), 1)), trainable=True,
@@ -182,6 +195,13 @@ class SemanticNetwork(object):
             self.curr_mask = None
             self.last_losses: List[float] = []
         self._last_train_ms = 0.0
+        self._renderer = None              # the render tables (DeviceRenderer), built and uploaded on first use
+        self._confidence_host = None       # pinned block the statistics rows of a synchronous pass leave through, on first use
+        self._held = None                  # device_masks: what the last phase left on the device (_hold_phase)
+        self._auto_mask_dev = None         # device_masks: coord_desc_auto's selection, kept for keep_mask=True
+        self._feed = None                  # training from host deques: the helper threads and their pinned ring (_host_feed)
+        # frozen with pipeline_depth >= 2: predict_with_metric_async / collect.  Every synchronous pass drains it first (one output block).
+        self._pipeline = EdgePipeline(self.engine, self._mode(), self.pipeline_depth, self._get_renderer, pass_metrics, self.class_count)
         # mem_frac (tf.ConfigProto per_process_gpu_memory_fraction, SemanticNetwork.py:73): TensorFlow refuses allocations past that share of
         # the device; the engine allocates exactly one arena, so the cap is checked once, against it
         if torch.cuda.is_available():
@@ -194,6 +214,8 @@ class SemanticNetwork(object):
     # ------------------------------------------------------------------ mask / curr_mask / train_params
     # Plain attributes on the host path.  With device_masks=True a phase leaves them on the device (``_held``: the phase's device mask and a
     # device copy of the variables at its end) and the first read brings them to the host, with the values, types and shapes of the host path.
+    # ``del`` makes one absent again (the next read materialises it); absent differs from None, so the values live in __dict__ under the
+    # properties' own names.
     def _lazy(name):
         def get(self):
             if name not in self.__dict__:
@@ -203,9 +225,12 @@ class SemanticNetwork(object):
         def put(self, value):
             self.__dict__[name] = value
             if name == "mask" and value is None:
-                self.__dict__.pop("_auto_mask_dev", None)
+                self._auto_mask_dev = None
 
-        return property(get, put)
+        def drop(self):
+            self.__dict__.pop(name, None)
+
+        return property(get, put, drop)
 
     mask = _lazy("mask")
     curr_mask = _lazy("curr_mask")
@@ -215,39 +240,33 @@ class SemanticNetwork(object):
     def _materialise(self, name):
         spec = self.engine.spec
         if name == "mask":                                    # coord_desc_auto's selection, kept for keep_mask=True
-            kept = self.__dict__.get("_auto_mask_dev")
-            if kept is not None:
-                flat = kept.cpu().numpy().astype(bool)
-                self.__dict__["mask"] = {v.name: flat[v.offset:v.offset + v.size].reshape(v.shape) for v in spec.trainable}
+            if self._auto_mask_dev is not None:
+                flat = self._auto_mask_dev.cpu().numpy().astype(bool)
+                self.mask = dict(zip((v.name for v in spec.trainable), W.split_flat(flat, spec.trainable)))
             return
-        held = self.__dict__.get("_held")
+        held = self._held
         if held is None:
             return
         if held["mask"] is not None:                          # a coord_desc_* phase: the trainable variables in arena order
-            if name == "curr_mask":
-                flat = held["mask"].cpu().numpy().astype(bool)
-                value = [flat[v.offset:v.offset + v.size].reshape(v.shape) for v in spec.trainable]
-            else:
-                flat = held["params"].cpu().numpy()
-                value = [flat[v.offset:v.offset + v.size].reshape(v.shape) for v in spec.trainable]
+            flat = held["mask"].cpu().numpy().astype(bool) if name == "curr_mask" else held["params"].cpu().numpy()
+            value = W.split_flat(flat, spec.trainable)
         else:                                                 # full_model: every variable, all-ones masks
             every = W.unpack(spec, held["params"].cpu().numpy(), held["stats"].cpu().numpy())
             value = [every[k] for k in every.keys()] if name == "train_params" else [np.ones_like(every[k], dtype=bool) for k in every.keys()]
-        self.__dict__[name] = value
+        setattr(self, name, value)
 
     def _hold_phase(self, train_strategy, mask_dev):
         """End of a device_masks phase: what curr_mask / train_params / delta_payload are made from, without a copy to the host."""
         eng = self.engine
-        held = self.__dict__.get("_held") or {"params": torch.empty_like(eng.params), "stats": None}
+        held = self._held or {"params": torch.empty_like(eng.params), "stats": None}
         held["params"].copy_(eng.params)
         if mask_dev is None:
             if held["stats"] is None:
                 held["stats"] = torch.empty_like(eng.stats)
             held["stats"].copy_(eng.stats)
         held["mask"], held["strategy"] = mask_dev, train_strategy
-        self.__dict__["_held"] = held
-        self.__dict__.pop("curr_mask", None)
-        self.__dict__.pop("train_params", None)
+        self._held = held
+        del self.curr_mask, self.train_params
 
     # ------------------------------------------------------------------ variables (SaveHelper semantics)
     def _restore_dict(self, variables: Dict[str, np.ndarray]) -> None:
@@ -268,11 +287,10 @@ class SemanticNetwork(object):
     def get_vars(self):
         out = self.engine.get_variables()
         if not self.frozen:
-            m, v = self.engine.adam_m.cpu().numpy(), self.engine.adam_v.cpu().numpy()
-            for var in self.engine.spec.trainable:
-                stem = var.name[:-2]
-                out[stem + "/Adam:0"] = m[var.offset:var.offset + var.size].reshape(var.shape).copy()
-                out[stem + "/Adam_1:0"] = v[var.offset:var.offset + var.size].reshape(var.shape).copy()
+            trainable = self.engine.spec.trainable
+            moments = (W.split_flat(self.engine.adam_m.cpu().numpy(), trainable), W.split_flat(self.engine.adam_v.cpu().numpy(), trainable))
+            for var, m, v in zip(trainable, *moments):
+                out[var.name[:-2] + "/Adam:0"], out[var.name[:-2] + "/Adam_1:0"] = m.copy(), v.copy()
             t = self.engine.adam_step
             out["beta1_power:0"] = np.float32(0.9 ** (t + 1))
             out["beta2_power:0"] = np.float32(0.999 ** (t + 1))
@@ -285,50 +303,55 @@ class SemanticNetwork(object):
     def _mode(self) -> int:
         return hip.MODE_FROZEN if self.frozen else hip.MODE_LIVE
 
-    def _drain_async(self):
-        """A synchronous call shares the engine's one output block with the asynchronous edge pipeline: a pass that is still on the GPU is
-        fetched first, so that ``collect`` later returns ITS metrics and not this call's."""
-        if self.frozen and self._pending:
-            self._fetch_pending()
+    def _run_pass(self, frames, labels_teacher, views=None, confidence=False) -> _Pass:
+        """One inference pass and what is launched behind it on the same stream: every synchronous host-returning call is this, under
+        ``process_lock``.  The engine has ONE output block, one uint8 label view and one set of low-resolution logits: the order below is fixed."""
+        eng = self.engine
+        # 1. a pass of the asynchronous pipeline that is still on the GPU leaves the output block first: ``collect`` later returns ITS metrics
+        self._pipeline.drain()
+        # 2. the pass (returns at once; the labels leave as uint8)
+        labels_dev, _conf, _loss = eng.predict_frames(frames, labels_teacher, self._mode(), u8=True)
+        frames_dev, teacher_dev = eng.last_inputs()
+        rendered = certain = None
+        # 3. one render launch: it reads the label view, the frames and the teacher labels where they are on the device, before anything
+        #    else writes the label view
+        if views is not None:
+            rendered = self._get_renderer().render(frames_dev, labels_dev, teacher_dev, views)
+        # 4. one confidence launch, before the next pass overwrites the logits; its statistics rows start towards a pinned host block (made on
+        #    first use) BEFORE the one synchronisation, so they arrive with the pass's results
+        if confidence:
+            conf_map, _f32, stats_dev = eng.confidence(teacher_dev)
+            if self._confidence_host is None:
+                self._confidence_host = torch.empty((eng.max_batch, stats_dev.shape[1]), dtype=torch.int64).pin_memory()
+            rows = self._confidence_host[:stats_dev.shape[0]]
+            rows.copy_(stats_dev, non_blocking=True)
+        # 5. one device -> host copy for labels + confusion matrices + losses (they share the output block) and one synchronisation
+        labels_student, confs, losses = eng.fetch_frames()
+        # 6. the rows are valid now
+        if confidence:
+            certain = Confidence(conf_map, [ConfidenceStats(r, self.class_count) for r in rows.numpy().copy()])
+        assert labels_student.shape == tuple(frames.shape[:-1] if hasattr(frames, 'shape') else np.shape(frames)[:-1])
+        metrics = pass_metrics(confs.sum(axis=0), losses.sum(axis=0)) if labels_teacher is not None else None
+        return _Pass(labels_student, metrics, rendered, certain)
 
     def predict_input(self, frames):
-        self.process_lock.acquire()
-        try:
-            self._drain_async()
-            labels_ = self.engine.predict_host(frames, self._mode())
-            assert labels_.shape == tuple(frames.shape[:-1] if hasattr(frames, 'shape') else np.shape(frames)[:-1])
-        finally:
-            self.process_lock.release()
-        return labels_
+        with self.process_lock:
+            return self._run_pass(frames, None).labels
 
     infer = predict_input
 
     def calc_cross_miou(self, labels):
         assert not self.frozen or self.cross_miou_compat
         assert labels.shape == (2, self.height, 2 * self.height)
-        self.process_lock.acquire()
-        try:
+        with self.process_lock:
             conf_mat_ = self.engine.cross_confusion(labels).cpu().numpy().astype(np.float64)
             iou_ = calculate_miou(conf_mat_, nan=True)
             miou_ = np.nanmean(iou_)
-        finally:
-            self.process_lock.release()
         return conf_mat_, iou_, miou_
 
     def predict_with_metric(self, frames, labels_teacher):
-        self.process_lock.acquire()
-        try:
-            self._drain_async()
-            # one device -> host copy for labels + confusion matrix + loss (they share one preallocated output block)
-            labels_student, conf_i64, ls = self.engine.predict_with_metric_host(frames, labels_teacher, self._mode())
-            conf_mat_ = conf_i64.astype(np.float64)
-            loss_ = np.float32(ls[0] / ls[1]) if ls[1] > 0 else np.float32(np.nan)
-            assert labels_student.shape == tuple(frames.shape[:-1] if hasattr(frames, 'shape') else np.shape(frames)[:-1])
-            iou_ = calculate_miou(conf_mat_, nan=True)
-            miou_ = np.nanmean(iou_)
-        finally:
-            self.process_lock.release()
-        return labels_student, conf_mat_, iou_, miou_, loss_
+        with self.process_lock:
+            return self._run_pass(frames, labels_teacher).result()
 
     def predict_rendered(self, frames, labels_teacher=None, views=RENDER_VIEWS, confidence=False):
         """One inference pass and one render launch behind it on the same stream (an addition; the reference paints on the host after the
@@ -336,159 +359,57 @@ class SemanticNetwork(object):
         Returns what ``predict_with_metric`` returns (``predict_input`` when ``labels_teacher`` is None: the labels alone), bit for bit, plus a
         ``RenderedViews`` dict: view name -> uint8 device tensor [B,H,W,3] (``.host()``: all of them in one copy).  ``confidence=True``: the
         confidence launch of ``predict_with_confidence`` behind the same pass too, its ``Confidence`` as one more element at the end."""
-        self.process_lock.acquire()
-        try:
-            self._drain_async()
-            labels_dev, _conf, _loss = self.engine.predict_frames(frames, labels_teacher, self._mode(), u8=True)
-            frames_dev, teacher_dev = self.engine.last_inputs()
-            rendered = self._get_renderer().render(frames_dev, labels_dev, teacher_dev, views)      # before anything else writes the label view
-            more = ()
-            if confidence:
-                conf_map, _f32, stats_dev = self.engine.confidence(teacher_dev)
-                stats_host = self._confidence_rows(stats_dev)
-            labels_student, confs, losses = self.engine.fetch_frames()
-            if confidence:
-                more = (Confidence(conf_map, [ConfidenceStats(r, self.class_count) for r in stats_host.numpy().copy()]),)
-            assert labels_student.shape == tuple(frames.shape[:-1] if hasattr(frames, 'shape') else np.shape(frames)[:-1])
-            if labels_teacher is None:
-                return (labels_student, rendered) + more
-            conf_mat_ = confs.sum(axis=0).astype(np.float64)
-            ls = losses.sum(axis=0)
-            loss_ = np.float32(ls[0] / ls[1]) if ls[1] > 0 else np.float32(np.nan)
-            iou_ = calculate_miou(conf_mat_, nan=True)
-            miou_ = np.nanmean(iou_)
-        finally:
-            self.process_lock.release()
-        return (labels_student, conf_mat_, iou_, miou_, loss_, rendered) + more
+        with self.process_lock:
+            p = self._run_pass(frames, labels_teacher, views if views is not None else (), confidence)      # no views: the renderer refuses
+        return p.result(p.rendered, p.confidence) if confidence else p.result(p.rendered)
 
     def predict_with_confidence(self, frames, labels_teacher=None):
         """One inference pass and one confidence launch behind it on the same stream: the student graph's ``probabilities_reduced``
         (utils/graph_utils.py:388-389), which the reference builds and no caller of it fetches.  Returns what ``predict_with_metric`` returns
         (``predict_input`` when ``labels_teacher`` is None: the labels alone), bit for bit, plus a ``Confidence``: ``.map`` the uint8 device
         tensor [B,H,W] = rint(p * 255) and ``.stats`` one ``ConfidenceStats`` per frame (calibration fields only with teacher labels)."""
-        self.process_lock.acquire()
-        try:
-            self._drain_async()
-            self.engine.predict_frames(frames, labels_teacher, self._mode(), u8=True)
-            conf_map, _f32, stats_dev = self.engine.confidence(self.engine.last_inputs()[1])      # before anything else overwrites the logits
-            stats_host = self._confidence_rows(stats_dev)          # leaves with the pass's results: fetch_frames synchronises once for both
-            labels_student, confs, losses = self.engine.fetch_frames()
-            confidence = Confidence(conf_map, [ConfidenceStats(r, self.class_count) for r in stats_host.numpy().copy()])
-            assert labels_student.shape == tuple(frames.shape[:-1] if hasattr(frames, 'shape') else np.shape(frames)[:-1])
-            if labels_teacher is None:
-                return labels_student, confidence
-            conf_mat_ = confs.sum(axis=0).astype(np.float64)
-            ls = losses.sum(axis=0)
-            loss_ = np.float32(ls[0] / ls[1]) if ls[1] > 0 else np.float32(np.nan)
-            iou_ = calculate_miou(conf_mat_, nan=True)
-            miou_ = np.nanmean(iou_)
-        finally:
-            self.process_lock.release()
-        return labels_student, conf_mat_, iou_, miou_, loss_, confidence
-
-    def _confidence_rows(self, stats_dev):
-        """the statistics rows on their way to a pinned host block (asynchronous: valid after the stream's next synchronisation)"""
-        block = self.__dict__.get("_confidence_host")
-        if block is None:
-            block = self.__dict__["_confidence_host"] = torch.empty((self.engine.max_batch, stats_dev.shape[1]), dtype=torch.int64).pin_memory()
-        view = block[:stats_dev.shape[0]]
-        view.copy_(stats_dev, non_blocking=True)
-        return view
+        with self.process_lock:
+            p = self._run_pass(frames, labels_teacher, confidence=True)
+        return p.result(p.confidence)
 
     def predict_probabilities(self, frames):
         """``student['probabilities_reduced']`` of the reference's graph: f32 ndarray [B,H,W], per pixel the largest softmax value over the
         selected classes."""
         with self.process_lock:
-            self._drain_async()
+            self._pipeline.drain()
             self.engine.predict_frames(frames, None, self._mode(), u8=True)
             return self.engine.confidence(None, f32=True)[1].cpu().numpy()
 
     def _get_renderer(self):
         """The render tables of this network, built and uploaded once."""
-        r = self.__dict__.get("_renderer")
-        if r is None:
-            r = self.__dict__["_renderer"] = DeviceRenderer(self.color_map_reduced_, colormap(), self.take_array, self.TOTAL_CLASSES,
-                                                            self.engine.device)
-        return r
+        if self._renderer is None:
+            self._renderer = DeviceRenderer(self.color_map_reduced_, colormap(), self.take_array, self.TOTAL_CLASSES, self.engine.device)
+        return self._renderer
 
-    # The edge's per-frame call, pipeline_depth frames at a time (an addition: the reference's call is synchronous).  A one-frame forward is
-    # ~45 dependent launches that leave most of the chip idle (0.49 ms); two frames in one pass take 0.59 ms, three 0.68 ms.  Submitted
-    # frames wait until pipeline_depth of them are there (or until one of them is collected), then run as ONE pass with per-frame metrics
-    # (ams_student_predict_frames).  Each frame's result is what predict_with_metric returns for it, bit for bit.
-    # ``render=views`` paints that frame's views right behind its pass, before the next pass overwrites the engine's label view (same stream);
-    # ``take_rendered(ticket)`` hands them over, ``collect`` keeps its 5-tuple.  ``confidence=True`` works the same way: one confidence launch over
-    # the pass's frames behind it, ``take_confidence(ticket)`` hands that frame's ``Confidence`` over.
+    # The edge's per-frame call, pipeline_depth frames at a time (an addition: the reference's call is synchronous): ams_amd/edge_pipeline.py.
+    # Each frame's result is what predict_with_metric returns for it, bit for bit.  ``render=views`` paints that frame's views right behind its
+    # pass, ``confidence=True`` adds the confidence launch; ``take_rendered`` / ``take_confidence`` hand them over, ``collect`` keeps its 5-tuple.
     def predict_with_metric_async(self, frames, labels_teacher, render=None, confidence=False):
         assert self.frozen and self.pipeline_depth > 1, "construct the frozen network with pipeline_depth >= 2"
         assert np.shape(frames)[0] == 1 and np.shape(labels_teacher)[0] == 1, "one frame per call"
         with self.process_lock:
-            self._tickets += 1
-            self._queued.append((self._tickets, frames, labels_teacher, tuple(render) if render else None, bool(confidence)))
-            if len(self._queued) >= self.pipeline_depth:
-                self._launch_queued()
-            return self._tickets
-
-    def _fetch_pending(self):
-        if not self._pending:
-            return
-        labs, confs, losses = self.engine.fetch_frames()          # one device -> host copy, one synchronisation for the whole pass
-        for k, t in enumerate(self._pending):
-            conf_mat_ = confs[k].astype(np.float64)
-            ls = losses[k]
-            loss_ = np.float32(ls[0] / ls[1]) if ls[1] > 0 else np.float32(np.nan)
-            iou_ = calculate_miou(conf_mat_, nan=True)
-            self._ready[t] = (labs[k:k + 1], conf_mat_, iou_, np.nanmean(iou_), loss_)
-        self._pending = []
-
-    def _launch_queued(self):
-        self._fetch_pending()             # the engine has one output block: the previous pass leaves it before the next one writes it
-        cat = (lambda xs: torch.cat(list(xs))) if hasattr(self._queued[0][1], "unsqueeze") else (lambda xs: np.concatenate([np.asarray(x) for x in xs]))
-        frames = cat(q[1] for q in self._queued)
-        labels = cat(q[2] for q in self._queued)
-        self._pending = [q[0] for q in self._queued]
-        wanted = [(k, q[0], q[3]) for k, q in enumerate(self._queued) if q[3]]
-        certain = [(k, q[0]) for k, q in enumerate(self._queued) if q[4]]
-        self._queued = []
-        labels_dev, _conf, _loss = self.engine.predict_frames(frames, labels, self._mode(), u8=True)     # returns at once: the pass runs while the caller goes on (labels leave as uint8)
-        if wanted:
-            frames_dev, teacher_dev = self.engine.last_inputs()
-            for k, ticket, views in wanted:       # enqueued behind the pass and before the next one, which overwrites the label view
-                self._rendered[ticket] = self._get_renderer().render(frames_dev[k:k + 1], labels_dev[k:k + 1], teacher_dev[k:k + 1], views)
-        if certain:                               # one launch over the whole pass, behind it and before the next one overwrites the logits
-            conf_map, _f32, stats_dev = self.engine.confidence(self.engine.last_inputs()[1])
-            rows = {"dev": stats_dev, "host": None}
-            for k, ticket in certain:
-                self._confident[ticket] = (conf_map[k:k + 1], rows, k)
+            return self._pipeline.submit(frames, labels_teacher, render, confidence)
 
     def collect(self, ticket):
         with self.process_lock:
-            if ticket not in self._ready:
-                if ticket not in self._pending:
-                    assert any(q[0] == ticket for q in self._queued), "unknown ticket"
-                    self._launch_queued()
-                self._fetch_pending()
-            return self._ready.pop(ticket)
+            return self._pipeline.collect(ticket)
 
     def take_rendered(self, ticket):
         """The views of a frame submitted with ``render=``: a ``RenderedViews`` dict of device tensors [1,H,W,3] (once per ticket; before or
         after ``collect``).  A frame that is still queued is launched first."""
         with self.process_lock:
-            if ticket not in self._rendered and any(q[0] == ticket and q[3] for q in self._queued):
-                self._launch_queued()
-            assert ticket in self._rendered, "no views were requested for this ticket (or they were taken already)"
-            return self._rendered.pop(ticket)
+            return self._pipeline.take_rendered(ticket)
 
     def take_confidence(self, ticket):
         """The ``Confidence`` of a frame submitted with ``confidence=True``: map [1,H,W] on the device, one ``ConfidenceStats`` (once per
         ticket; before or after ``collect``).  A frame that is still queued is launched first."""
         with self.process_lock:
-            if ticket not in self._confident and any(q[0] == ticket and q[4] for q in self._queued):
-                self._launch_queued()
-            assert ticket in self._confident, "no confidence was requested for this ticket (or it was taken already)"
-            conf_map, rows, k = self._confident.pop(ticket)
-            if rows["host"] is None:
-                rows["host"] = rows["dev"].cpu().numpy()          # the pass's rows, once for all its tickets
-            return Confidence(conf_map, [ConfidenceStats(rows["host"][k], self.class_count)])
+            return self._pipeline.take_confidence(ticket)
 
     # ------------------------------------------------------------------ training
     def train_with_deque(self, frame_deque, label_deque, num_of_iterations, train_strategy='full_model',
@@ -508,59 +429,34 @@ class SemanticNetwork(object):
         on_memory = isinstance(frame_deque, DeviceReplayMemory)
         if on_memory:
             assert label_deque is None and teacher_logits_deque is None, "a DeviceReplayMemory carries its labels and teacher logits itself"
-            assert (frame_deque.logits_shape is not None) == bool(getattr(self, "soft_teacher", False)), \
+            assert (frame_deque.logits_shape is not None) == self.soft_teacher, \
                 "soft_teacher=True goes with a memory constructed with logits_shape (and needs one)"
         else:
-            assert (teacher_logits_deque is not None) == bool(getattr(self, "soft_teacher", False)), \
+            assert (teacher_logits_deque is not None) == self.soft_teacher, \
                 "teacher_logits_deque goes with soft_teacher=True (and is required then)"
         if teacher_logits_deque is not None:
             assert len(teacher_logits_deque) == len(frame_deque), "one teacher-logit array per frame of the replay memory"
         if not keep_mask:
             self.mask = None
-        self.process_lock.acquire()
-        # The reference's helper threads (SemanticNetwork.py:222-231, :679-704) have no failure path: if one dies — a frame of the wrong shape
-        # trips the assert in _fill_batch — _train polls its deque forever with process_lock held.  Here every helper hands its exception
-        # over through `ctx`, every wait loop watches ctx['abort'], and the caller gets the helper's exception with the lock released.
-        ctx = self._helpers = {"abort": threading.Event(), "error": None}
-        batch_thr = None
-        try:
-            if on_memory:
-                self._train(frame_deque, num_of_iterations, train_strategy)
-            else:
-                batch_deque = deque()
-                batch_thr = threading.Thread(target=self._guarded, args=(ctx, self._fill_batch, batch_deque, frame_deque, label_deque,
-                                                                         num_of_iterations, teacher_logits_deque))
-                batch_thr.start()
-                self._train(batch_deque, num_of_iterations, train_strategy)
-        finally:
-            ctx["abort"].set()                      # after a clean phase the helpers have returned already; after an error this stops them
-            if batch_thr is not None:
-                batch_thr.join()
-            fill_thr = ctx.pop("fill_thr", None)
-            if fill_thr is not None:
-                fill_thr.join()
-            self._helpers = None
-            self._release_staging()
-            self.process_lock.release()
-        if ctx["error"] is not None:
-            raise ctx["error"]
+        with self.process_lock:
+            feed = None if on_memory else self._host_feed()
+            try:
+                if feed is not None:
+                    feed.start(num_of_iterations, frame_deque, label_deque, teacher_logits_deque)
+                self._train(frame_deque if on_memory else feed, num_of_iterations, train_strategy)
+            finally:
+                if feed is not None:
+                    feed.stop()                     # both helper threads joined, whatever happened, before the lock is released
+        if feed is not None and feed.error is not None:
+            raise feed.error                        # a helper's own exception (the reference would hang with the lock held)
 
-    @staticmethod
-    def _guarded(ctx, fn, *args):
-        """Body of a helper thread: the first exception of any helper is kept for the caller and stops the others."""
-        try:
-            fn(*args)
-        except BaseException as e:  # noqa: BLE001  (handed to the calling thread, which re-raises it)
-            if ctx["error"] is None:
-                ctx["error"] = e
-            ctx["abort"].set()
-
-    def _aborted(self):
-        h = getattr(self, "_helpers", None)
-        return h is not None and h["abort"].is_set()
-
-    class _Aborted(Exception):
-        """a wait was cut short because another helper of the same call failed"""
+    def _host_feed(self) -> HostBatchFeed:
+        """The helper threads and pinned staging ring of training from host deques (ams_amd/batch_feed.py), kept from phase to phase; made
+        on first use and again when the instance's batch geometry changed since."""
+        f = self._feed
+        if f is None or f.mini_batch_size != self.mini_batch_size or list(f.scale) != list(self.scale):
+            f = self._feed = HostBatchFeed(self.height, self.mini_batch_size, self.scale, self.engine.device)
+        return f
 
     def train_step(self, frames, labels_teacher, train_strategy='full_model', teacher_logits=None):
         """North-star alias: ONE optimisation step on an explicit batch; returns the loss (float).  With ``soft_teacher=True`` the cached teacher
@@ -578,22 +474,18 @@ class SemanticNetwork(object):
 
     def _mask_to_device(self, train_mask_: Dict[str, np.ndarray]) -> torch.Tensor:
         flat = np.empty(self.engine.spec.n_trainable, dtype=np.uint8)
-        for v in self.engine.spec.trainable:
-            flat[v.offset:v.offset + v.size] = np.asarray(train_mask_[v.name]).reshape(-1)
+        W.fill_flat(flat, self.engine.spec.trainable, train_mask_)
         return torch.from_numpy(flat).to(self.engine.device)
 
-    def _train(self, batch_deque, num_of_iterations, train_strategy):
-        signal_deque = deque()
-        ctx = getattr(self, "_helpers", None) or {"abort": threading.Event(), "error": None}
-        plan = fill_thr = None
-        if isinstance(batch_deque, DeviceReplayMemory):
-            plan = self._replay_plan(batch_deque, num_of_iterations)        # the phase's draws, before get_train_mask; no helper thread
+    def _train(self, source, num_of_iterations, train_strategy):
+        """``source``: a DeviceReplayMemory, or a started HostBatchFeed."""
+        plan = feed = None
+        if isinstance(source, DeviceReplayMemory):
+            plan = self._replay_plan(source, num_of_iterations)        # the phase's draws, before get_train_mask; no helper thread
         else:
-            fill_thr = threading.Thread(target=self._guarded, args=(ctx, self._fill_queue, batch_deque, num_of_iterations, signal_deque))
-            ctx["fill_thr"] = fill_thr                  # joined by train_with_deque's finally, whatever happens below
-            fill_thr.start()
+            feed = source
 
-        on_device = getattr(self, "device_masks", False)
+        on_device = self.device_masks
         before_dev = None
         if on_device:
             before_dev, mask_dev = self._device_train_mask(train_strategy)
@@ -603,22 +495,15 @@ class SemanticNetwork(object):
         losses = []
         t_phase = time.time()
         for it in range(num_of_iterations):
-            staged = None
-            while staged is None and plan is None:
-                try:
-                    staged = signal_deque.popleft()
-                except IndexError:
-                    if ctx["abort"].is_set():       # a helper died: its exception is raised by train_with_deque
-                        return
-                    time.sleep(self.THREAD_SLEEP_INTERVAL)
+            if feed is not None:
+                staged = feed.next_staged()
+                if staged is None:                  # a helper died: its exception is raised by train_with_deque
+                    return
             t1 = time.time()
             if plan is not None:
                 frames_dev, labels_dev, logits_dev = plan.batch(it)       # one launch on this stream into the resident batch buffer
             else:
-                frames_dev, labels_dev = self._consume_staged(staged)
-                logits_dev = staged[3] if len(staged) > 3 else None
-                if logits_dev is not None:
-                    logits_dev.record_stream(torch.cuda.current_stream(self.engine.device))
+                frames_dev, labels_dev, logits_dev = feed.consume(staged)
             if logits_dev is not None:
                 loss_dev = self.engine.train_step(frames_dev, labels_dev, self.lr, mask_dev, teacher_logits=logits_dev)
             else:
@@ -635,8 +520,8 @@ class SemanticNetwork(object):
                     before_dev = None
                     if self.verbose:
                         print("Using auto mode, Training %.3f%% of variables" % (100 * int(kept.item()) / mask_dev.numel()))
-                    self.__dict__.pop("mask", None)
-                    self.__dict__["_auto_mask_dev"] = mask_dev
+                    del self.mask
+                    self._auto_mask_dev = mask_dev
             elif train_strategy == 'coord_desc_auto':
                 if it == 0 and self.mask is None:
                     # derive the mask from the first step's |delta w|: keep the top coord_frac, roll back the rest
@@ -656,10 +541,6 @@ class SemanticNetwork(object):
                     self._restore_dict(_combine)
                     self.mask = train_mask_
                     mask_dev = self._mask_to_device(train_mask_)
-        if fill_thr is not None:
-            fill_thr.join()
-        if ctx["error"] is not None:
-            return
         stacked = torch.stack(losses).cpu().numpy() if losses else np.zeros((0, 2))
         self.last_losses = [float(s / c) if c > 0 else float("nan") for s, c in stacked]
         self._last_train_ms = (time.time() - t_phase) * 1000.0
@@ -667,7 +548,7 @@ class SemanticNetwork(object):
         if on_device:
             self._hold_phase(train_strategy, mask_dev)
             return
-        self.__dict__.pop("_held", None)
+        self._held = None
         _after_train = self._model_vars()
         if 'coord_desc_' in train_strategy:
             names = [v.name for v in self.engine.spec.trainable]
@@ -684,11 +565,10 @@ class SemanticNetwork(object):
         if train_strategy == 'full_model':
             return None, None
         if train_strategy == 'coord_desc_auto':
-            kept = self.__dict__.get("_auto_mask_dev")
-            if kept is not None:
-                return None, kept
-            if self.__dict__.get("mask") is not None:          # a mask assigned by the caller
-                return None, self._mask_to_device(self.__dict__["mask"])
+            if self._auto_mask_dev is not None:
+                return None, self._auto_mask_dev
+            if self.mask is not None:          # a mask assigned by the caller
+                return None, self._mask_to_device(self.mask)
             return self.engine.snapshot_params(), torch.ones(self.engine.spec.n_trainable, dtype=torch.uint8, device=self.engine.device)
         _before, train_mask_ = self.get_train_mask(train_strategy)
         return None, self._mask_to_device(train_mask_)
@@ -700,21 +580,9 @@ class SemanticNetwork(object):
         assert memory.logits_shape is None or (list(self.scale) == [1] and (memory.src_h, memory.src_w) == tuple(crop)), \
             "teacher logits need frames and labels at the network size and scale == [1]"
         samples = draw_samples(len(memory), (memory.src_h, memory.src_w), crop, self.scale, self.mini_batch_size, num_of_iterations,
-                               flip=getattr(self, "flip", False))
+                               flip=self.flip)
         assert memory.logits_shape is None or all(tuple(d[1:]) == (memory.src_h, memory.src_w, 0, 0, 0) for d in samples.reshape(-1, 6))
         return memory.plan(samples, crop[0], crop[1])
-
-    def _consume_staged(self, staged):
-        """Make the compute stream wait for a staged batch's copy; returns its device tensors."""
-        frames_dev, labels_dev, ready = staged[:3]
-        compute = torch.cuda.current_stream(self.engine.device)
-        compute.wait_event(ready)
-        # the buffers were allocated on the stager's copy stream: tell the caching allocator that the compute stream uses
-        # them too, or dropping the references one iteration later hands the block back to the copy stream's pool while
-        # this step's kernels (the stem weight gradient re-reads the frames in backward) are still queued
-        frames_dev.record_stream(compute)
-        labels_dev.record_stream(compute)
-        return frames_dev, labels_dev
 
     def delta_payload(self, device: bool = False):
         """The downlink model delta of reference run.py:316-336 as bytes: per variable ``np.packbits(mask.flatten())``, then
@@ -725,7 +593,7 @@ class SemanticNetwork(object):
         After a ``device_masks=True`` phase the whole payload, mask bits included, is encoded on the device from the phase's device mask and the
         engine's current variables (``ams_student_encode_delta``; call it before the model changes again, as run.py does) and comes to the
         host in one copy.  ``device=True`` returns the payload as a uint8 device tensor instead, which ``apply_delta`` accepts."""
-        held = self.__dict__.get("_held")
+        held = self._held
         if held is not None:
             with self.process_lock:
                 dev = self.engine.encode_delta(delta_layout(self.engine.spec, held["strategy"]), held["mask"])
@@ -740,12 +608,9 @@ class SemanticNetwork(object):
         on_device = len(self.curr_mask) == len(trainable) and all(m.size == v.size for m, v in zip(self.curr_mask, trainable))
         if on_device:
             flat = np.concatenate([m.reshape(-1) for m in self.curr_mask]).astype(np.uint8)
-            self.process_lock.acquire()
-            try:
+            with self.process_lock:
                 halves = self.engine.pack_masked_fp16(torch.from_numpy(flat).to(self.engine.device))
                 payload += halves.cpu().numpy().tobytes()
-            finally:
-                self.process_lock.release()
         else:
             for p_, m_ in zip(self.train_params, self.curr_mask):
                 assert p_.shape == m_.shape
@@ -763,10 +628,7 @@ class SemanticNetwork(object):
         new one: the queued ones are launched and fetched first."""
         layout = delta_layout(self.engine.spec, train_strategy)
         with self.process_lock:
-            if self.frozen:
-                if self._queued:
-                    self._launch_queued()
-                self._fetch_pending()
+            self._pipeline.flush()
             eng = self.engine
             saved = None
             if base_variables is not None:
@@ -809,147 +671,6 @@ class SemanticNetwork(object):
         train_vars_len = sum(int(np.sum(m)) for m in train_mask_.values())
         return all_vars, train_vars_len
 
-    def _fill_batch(self, batch_deque, frame_deque, label_deque, number_of_batches, teacher_logits_deque=None):
-        """Producer thread: sample mini-batches from the replay memory (utils.mini_batch contract).
-
-        Fast path (the only one run.py exercises: scale == [1], frames already at network size): draws the same
-        random numbers in the same order as ``mini_batch`` but gathers the uint8 frames directly instead of
-        materialising float64 copies (B x 12.6 MB per batch at 512x1024)."""
-        frames = list(frame_deque) if isinstance(frame_deque, deque) else frame_deque
-        labels = list(label_deque) if isinstance(label_deque, deque) else label_deque
-        crop = [self.height, self.height * 2]
-        fast = (list(self.scale) == [1] and all(f.shape[:2] == tuple(crop) for f in frames))
-        fast = fast and all(f.dtype == np.uint8 for f in frames) and all(l.dtype == np.uint8 and l.shape == tuple(crop) for l in labels)
-        soft = list(teacher_logits_deque) if teacher_logits_deque is not None else None
-        # soft targets follow the frames a batch drew: only where frames are taken as they are (no rescale / crop of the logits is defined)
-        assert soft is None or fast, "teacher_logits_deque needs uint8 frames and labels at the network size and scale == [1]"
-        for _ in range(number_of_batches):
-            if self._aborted():
-                return
-            slot = None
-            if fast:
-                picks = []
-                for _j in range(self.mini_batch_size):
-                    picks.append(np.random.choice(len(frames)))
-                    random.randint(0, 0)      # scale choice
-                    random.randint(0, 0)      # row offset  (slack is 0 when the frame already has the crop size)
-                    random.randint(0, 0)      # column offset
-                # gathered straight into a pinned staging slot: one host copy per frame, none per batch (a fresh pin_memory() per batch
-                # costs a page-lock of 12-16 MB each time)
-                try:
-                    slot = self._staging_slot()
-                except self._Aborted:
-                    return
-                image_batch, label_batch = slot[0].numpy(), slot[1].numpy()
-                for j, p in enumerate(picks):
-                    image_batch[j] = frames[p]
-                    label_batch[j] = labels[p]
-            else:
-                ib, lb = mini_batch(frames, labels, crop, self.scale, self.mini_batch_size, 1, flip=False)
-                image_batch, label_batch = ib[0], lb[0]
-            assert np.shape(label_batch) == (self.mini_batch_size, self.height, self.height * 2)
-            assert np.shape(image_batch) == (self.mini_batch_size, self.height, self.height * 2, 3)
-            batch = {'frames': image_batch, 'labels': label_batch, 'slot': slot}
-            if soft is not None:
-                batch['teacher_logits'] = np.stack([np.asarray(soft[p], dtype=np.float32) for p in picks])
-            batch_deque.append(batch)
-
-    def _staging_slot(self):
-        """Next slot of a small ring of pinned host buffers [mini_batch, H, 2H, 3] / [mini_batch, H, 2H] uint8 (created on first use).  A slot
-        is handed out again only after the stager has issued the H2D copy that reads it AND that copy has finished (its event): the sampler runs
-        at most four batches ahead of the copies."""
-        ring = getattr(self, "_staging", None)
-        shape = (self.mini_batch_size, self.height, 2 * self.height)
-        if ring is None or ring["shape"] != shape:              # first use, or the instance's batch geometry changed since
-            ring = self._staging = {"next": 0, "shape": shape, "slots": [
-                [self._pinned(shape + (3,)), self._pinned(shape), None, False] for _ in range(4)]}
-        slot = ring["slots"][ring["next"] % len(ring["slots"])]
-        ring["next"] += 1
-        while slot[3] and slot[2] is None:        # handed out earlier and still waiting in the batch deque for the stager
-            if self._aborted():                   # ... which has died: do not wait for it
-                raise self._Aborted()
-            time.sleep(self.THREAD_SLEEP_INTERVAL)
-        if slot[2] is not None:
-            slot[2].synchronize()
-            slot[2] = None
-        slot[3] = True
-        return slot
-
-    @staticmethod
-    def _pinned(shape):
-        t = torch.empty(shape, dtype=torch.uint8)
-        return t.pin_memory() if torch.cuda.is_available() else t
-
-    def _release_staging(self):
-        """After a phase (clean or failed) no slot is owed to a stager any more."""
-        ring = getattr(self, "_staging", None)
-        if ring is not None:
-            for slot in ring["slots"]:
-                if slot[2] is not None:
-                    slot[2].synchronize()
-                slot[2], slot[3] = None, False
-
-    def _fill_queue(self, batch_deque, number_of_batches, signal_deque):
-        """Stager thread (the FIFO queue of the reference graph, capacity 200): H2D on a side stream."""
-        copy_stream = self._make_copy_stream()
-        max_staged = None
-        for _ in range(number_of_batches):
-            batch = None
-            while batch is None:
-                try:
-                    batch = batch_deque.popleft()
-                except IndexError:
-                    if self._aborted():
-                        return
-                    time.sleep(self.THREAD_SLEEP_INTERVAL)
-            staged = self._stage_batch(batch, copy_stream)
-            if max_staged is None:
-                # the reference's FIFO queue holds 200 batches whatever their size (3 GB of device memory at batch 10 of 512x1024): here the
-                # staged-ahead set is bounded by BYTES — 1 GiB, at least two batches, at most the reference's 200 entries
-                nbytes = sum(int(t.numel()) * t.element_size() for t in staged[:2])
-                max_staged = max(2, min(200, (1 << 30) // max(nbytes, 1)))
-            while len(signal_deque) >= max_staged:
-                if self._aborted():
-                    return
-                time.sleep(self.THREAD_SLEEP_INTERVAL)
-            signal_deque.append(staged)
-
-    def _make_copy_stream(self):
-        return torch.cuda.Stream(device=self.engine.device)
-
-    def _stage_batch(self, batch, copy_stream):
-        """Host batch -> (frames on the device, labels on the device, event of the copies) on the copy stream."""
-        dev = self.engine.device
-        slot = batch.get('slot')
-        if slot is not None:              # already in pinned memory (_fill_batch's fast path)
-            with torch.cuda.stream(copy_stream):
-                f_dev = slot[0].to(dev, non_blocking=True)
-                l_dev = slot[1].to(dev, non_blocking=True)
-                ready = torch.cuda.Event()
-                ready.record(copy_stream)
-            slot[2] = ready
-        else:
-            fr = batch['frames']
-            fr = fr if fr.dtype == np.uint8 else fr.astype(np.float32)
-            lb = batch['labels']
-            if lb.dtype != np.uint8:
-                li = lb.astype(np.float32).astype(np.int64)
-                lb = np.where((li >= 0) & (li < 255), li, 255).astype(np.uint8)
-            with torch.cuda.stream(copy_stream):
-                f_dev = torch.from_numpy(np.ascontiguousarray(fr)).pin_memory().to(dev, non_blocking=True)
-                l_dev = torch.from_numpy(np.ascontiguousarray(lb)).pin_memory().to(dev, non_blocking=True)
-                ready = torch.cuda.Event()
-                ready.record(copy_stream)
-        if batch.get('teacher_logits') is not None:       # soft_teacher: the batch's cached teacher logits travel with it
-            with torch.cuda.stream(copy_stream):
-                t_dev = torch.from_numpy(batch['teacher_logits']).pin_memory().to(dev, non_blocking=True)
-                ready = torch.cuda.Event()
-                ready.record(copy_stream)
-            if slot is not None:
-                slot[2] = ready
-            return f_dev, l_dev, ready, t_dev
-        return f_dev, l_dev, ready
-
     # ------------------------------------------------------------------ freeze / export
     def get_frozen_graph(self):
         return FrozenGraph(self._model_vars(), self.class_indices_graph, self.height, self.TOTAL_CLASSES)
@@ -960,9 +681,7 @@ class SemanticNetwork(object):
             pb_file.write(graph_def.SerializeToString())
 
     def close_model(self):
-        if self.frozen:                   # views and confidence maps nobody took: their device memory goes with the engine
-            self._rendered.clear()
-            self._confident.clear()
+        self._pipeline.clear()             # views and confidence maps nobody took: their device memory goes with the engine
         self.engine.close()
 
     # ------------------------------------------------------------------ visualisation helpers
@@ -982,7 +701,7 @@ class SemanticNetwork(object):
     def _predict_device(self, frame):
         """Labels of one device frame as an int32 device tensor [H, W]; nothing goes through the host."""
         with self.process_lock:
-            self._drain_async()
+            self._pipeline.drain()
             return self.engine.predict(frame[None], self._mode())[0]
 
     def _render_one(self, views, frame=None, student=None, teacher=None):

@@ -57,31 +57,36 @@ def save_npy(path: str, variables: Dict[str, np.ndarray]) -> None:
     np.save(path, dict(variables))
 
 
-def pack_trainable(spec: StudentSpec, variables: Dict[str, np.ndarray]) -> np.ndarray:
-    flat = np.empty(spec.n_trainable, dtype=np.float32)
-    for v in spec.trainable:
-        a = np.asarray(variables[v.name], dtype=np.float32)
-        if a.shape != v.shape:
-            raise ValueError("%s: shape %s, expected %s" % (v.name, a.shape, v.shape))
-        flat[v.offset:v.offset + v.size] = a.reshape(-1)
+def split_flat(flat, variables):
+    """One view of the flat arena ``flat`` per variable, shaped like the variable."""
+    return [flat[v.offset:v.offset + v.size].reshape(v.shape) for v in variables]
+
+
+def fill_flat(flat, variables, by_name) -> None:
+    """Write ``by_name[v.name]`` (any shape of the variable's size, cast to the arena's dtype) into each variable's span of ``flat``."""
+    for v in variables:
+        flat[v.offset:v.offset + v.size] = np.asarray(by_name[v.name]).reshape(-1)
+
+
+def _pack(n: int, group, variables: Dict[str, np.ndarray]) -> np.ndarray:
+    for v in group:
+        if np.shape(variables[v.name]) != v.shape:
+            raise ValueError("%s: shape %s, expected %s" % (v.name, np.shape(variables[v.name]), v.shape))
+    flat = np.empty(n, dtype=np.float32)
+    fill_flat(flat, group, variables)
     return flat
+
+
+def pack_trainable(spec: StudentSpec, variables: Dict[str, np.ndarray]) -> np.ndarray:
+    return _pack(spec.n_trainable, spec.trainable, variables)
 
 
 def pack_stats(spec: StudentSpec, variables: Dict[str, np.ndarray]) -> np.ndarray:
-    flat = np.empty(spec.n_stats, dtype=np.float32)
-    for v in spec.stats:
-        a = np.asarray(variables[v.name], dtype=np.float32)
-        if a.shape != v.shape:
-            raise ValueError("%s: shape %s, expected %s" % (v.name, a.shape, v.shape))
-        flat[v.offset:v.offset + v.size] = a.reshape(-1)
-    return flat
+    return _pack(spec.n_stats, spec.stats, variables)
 
 
 def unpack(spec: StudentSpec, trainable_flat: np.ndarray, stats_flat: np.ndarray) -> Dict[str, np.ndarray]:
     """Inverse of pack_*: dict in GraphDef variable order (the order ``get_vars`` reports)."""
-    out: Dict[str, np.ndarray] = {}
-    for name in spec.all_variable_names():
-        v = spec.by_name[name]
-        src = trainable_flat if v.trainable else stats_flat
-        out[name] = np.array(src[v.offset:v.offset + v.size], dtype=np.float32).reshape(v.shape)
-    return out
+    parts = dict(zip((v.name for v in spec.trainable), split_flat(trainable_flat, spec.trainable)))
+    parts.update(zip((v.name for v in spec.stats), split_flat(stats_flat, spec.stats)))
+    return {name: np.array(parts[name], dtype=np.float32) for name in spec.all_variable_names()}

@@ -227,6 +227,32 @@ def test_predict_with_confidence_equals_the_plain_calls_and_the_kernel(lib, edge
     assert len(edge.predict_rendered(frames, labels, views=("cross_mask",))) == 6          # not asked for: the call as it was
 
 
+@pytest.mark.parametrize("n", [1, 3])
+def test_label_free_forms_of_the_pass(edge, clip, n):
+    """Without teacher labels predict_rendered and predict_with_confidence hand back predict_input's labels, no metrics, and what does not
+    depend on the labels exactly as the call with labels gives it; of the statistics only the label-free fields are populated."""
+    frames, labels = clip[0][:n], clip[1][:n]
+    views = ("colour_student", "overlay_student")
+    plain = edge.predict_input(frames)
+    full = edge.predict_rendered(frames, labels, views, confidence=True)
+    assert len(full) == 7
+    rendered = edge.predict_rendered(frames, None, views, confidence=True)
+    certain = edge.predict_with_confidence(frames, None)
+    assert len(rendered) == 3 and len(certain) == 2
+    for got in (rendered, certain):
+        assert np.array_equal(got[0], plain) and got[0].dtype == plain.dtype == np.int32
+        conf = got[-1]
+        assert torch.equal(conf.map, full[6].map) and len(conf.stats) == n
+        for s, t in zip(conf.stats, full[6].stats):
+            assert np.array_equal(s.hist, t.hist) and s.sum_all == t.sum_all and s.n_pixels == H * 2 * H and s.mean == t.mean
+            assert not s.has_teacher and t.has_teacher
+            assert not s.hist_valid.any() and not s.hist_hit.any() and not s.bin_sum.any() and not s.sel_cnt.any() and not s.sel_sum.any()
+    assert list(rendered[1]) == list(views)
+    for v in views:
+        assert rendered[1][v].is_cuda and torch.equal(rendered[1][v], full[5][v])
+    assert len(edge.predict_rendered(frames, None, views)) == 2
+
+
 def test_confidence_refuses_a_batch_out_of_range(lib, edge):
     n = Cf.STATS_LEN
     stats = torch.full((4, n), -1, dtype=torch.int64, device=DEV)

@@ -162,7 +162,9 @@ class _Net(SemanticNetwork):
         self.process_lock = threading.Lock()
         self.height, self.mini_batch_size, self.scale, self.lr = H, MB, scale, 1e-3
         self.frozen, self.mask, self.verbose, self.coord_frac = False, None, False, 0.1
+        self.device_masks = self.soft_teacher = self.flip = False
         self.engine = _Engine()
+        self._held = None
         self.train_params = self.curr_mask = None
         self.last_losses = []
 

@@ -1,6 +1,6 @@
-"""Host side of `SemanticNetwork.train_with_deque` without a GPU: the sampler thread, the stager thread and the training loop of the
-reference (SemanticNetwork.py:215-300, :679-704) with the device work replaced by stand-ins.  What is under test is the hand-over
-machinery: more iterations than staging slots, and — the reference's flaw a drop-in must not inherit — a helper thread that dies must
+"""Host side of `SemanticNetwork.train_with_deque` without a GPU: the sampler thread and the stager thread (ams_amd/batch_feed.py) and the
+training loop of the reference (SemanticNetwork.py:215-300, :679-704) with the device work replaced by stand-ins.  What is under test is the
+hand-over machinery: more iterations than staging slots, and — the reference's flaw a drop-in must not inherit — a helper thread that dies must
 surface as its exception from `train_with_deque`, promptly, with `process_lock` released and every thread joined."""
 import threading
 import time
@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+from ams_amd.batch_feed import HostBatchFeed
 from ams_amd.semantic_network import SemanticNetwork
 
 H, MB = 8, 2
@@ -36,21 +37,10 @@ class _Engine:
         return torch.tensor([float(self.steps), 1.0], dtype=torch.float64)
 
 
-class _Net(SemanticNetwork):
-    """The real train_with_deque / _train / _fill_batch / _fill_queue / _staging_slot over stand-ins for the three device touch points."""
-
-    def __init__(self):               # the constructor builds a StudentEngine (GPU only): set the attributes the training path reads
-        self.process_lock = threading.Lock()
-        self.height, self.mini_batch_size, self.scale, self.lr = H, MB, [1], 1e-3
-        self.frozen, self.mask, self.verbose, self.coord_frac = False, None, False, 0.1
-        self.engine = _Engine()
-        self.train_params = self.curr_mask = None
-        self.last_losses = []
-        self.stage_fail_at = None
-        self.staged = 0
-
-    def _model_vars(self):
-        return {}
+class _Feed(HostBatchFeed):
+    """The real sampler thread, stager thread, staging ring and hand-over, over stand-ins for the three device touch points."""
+    stage_fail_at = None
+    staged = 0
 
     def _make_copy_stream(self):
         return None
@@ -71,8 +61,26 @@ class _Net(SemanticNetwork):
             slot[2] = _Done()
         return f, l, None
 
-    def _consume_staged(self, staged):
-        return staged[0], staged[1]
+    def consume(self, staged):
+        return staged[0], staged[1], None
+
+
+class _Net(SemanticNetwork):
+    """The real train_with_deque / _train over the stand-in engine and feed."""
+
+    def __init__(self):               # the constructor builds a StudentEngine (GPU only): set what the training path reads
+        self.process_lock = threading.Lock()
+        self.height, self.mini_batch_size, self.scale, self.lr = H, MB, [1], 1e-3
+        self.frozen, self.verbose, self.coord_frac = False, False, 0.1
+        self.device_masks = self.soft_teacher = False
+        self.engine = _Engine()
+        self._held = None
+        self.mask = self.train_params = self.curr_mask = None
+        self.last_losses = []
+        self._feed = _Feed(H, MB, self.scale, "cpu")
+
+    def _model_vars(self):
+        return {}
 
 
 def _memory(n=5, bad=None):
@@ -126,7 +134,7 @@ def test_wrong_shaped_frame_raises_instead_of_hanging():
 
 def test_stager_failure_surfaces():
     net = _Net()
-    net.stage_fail_at = 3
+    net._feed.stage_fail_at = 3
     frames, labels = _memory()
     before = threading.active_count()
     t0 = time.time()
