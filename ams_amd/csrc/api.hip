@@ -229,6 +229,15 @@ int ams_student_confidence(ams_student* s, int32_t batch, const uint8_t* teacher
                                       conf_u8, conf_f32, stats, (hipStream_t)stream);
 }
 
+int ams_student_soft_metric(ams_student* s, int32_t batch, const uint8_t* teacher_dev, const float* teacher_logits_dev, int32_t th, int32_t tw,
+                            int64_t* stats, float* p_f32, float* ce_f32, void* stream) {
+    AMS_REQUIRE(s, "soft_metric: null student");
+    AMS_REQUIRE(batch >= 1 && batch <= s->cfg.max_batch, "soft_metric: batch %d outside 1..%d", batch, s->cfg.max_batch);
+    const ams_student_config& c = s->cfg;
+    return launch_upsample_soft_metric(s->logits, 32, batch, s->h, s->w, c.class_indices, c.n_selected, c.height, c.width, teacher_dev, c.num_classes,
+                                       teacher_logits_dev, th, tw, stats, p_f32, ce_f32, (hipStream_t)stream);
+}
+
 int ams_cross_confusion(const ams_student* s, const uint8_t* labels_dev, int64_t n_pixels, int64_t* conf_mat_dev, void* stream) {
     AMS_REQUIRE(s && labels_dev && conf_mat_dev && n_pixels > 0, "cross_confusion: bad argument");
     int32_t lut[256];
@@ -773,6 +782,14 @@ int ams_k_upsample_confidence(const float* logits, int32_t B, int32_t h, int32_t
     return launch_upsample_confidence(logits, NC, B, h, w, class_idx_host, K, H, W, teacher, NC, conf_u8, conf_f32, stats, (hipStream_t)stream);
 }
 size_t ams_confidence_stats_len(void) { return (size_t)confidence_stats_len(); }
+
+int ams_k_upsample_soft_metric(const float* logits, int32_t B, int32_t h, int32_t w, int32_t NC, const int32_t* class_idx_host, int32_t K,
+                               int32_t H, int32_t W, const uint8_t* teacher, const float* teacher_logits, int32_t th, int32_t tw, int64_t* stats,
+                               float* p_f32, float* ce_f32, void* stream) {
+    return launch_upsample_soft_metric(logits, NC, B, h, w, class_idx_host, K, H, W, teacher, NC, teacher_logits, th, tw, stats, p_f32, ce_f32,
+                                       (hipStream_t)stream);
+}
+size_t ams_soft_metric_stats_len(int32_t K) { return K >= 1 && K <= 32 ? (size_t)soft_metric_stats_len(K) : 0; }
 
 int ams_k_ce_grad(const float* logits, int32_t B, int32_t h, int32_t w, int32_t NC, const int32_t* class_idx_host, int32_t K, int32_t H,
                   int32_t W, const uint8_t* teacher, const double* loss_and_count_dev, float* dlogits, void* stream) {

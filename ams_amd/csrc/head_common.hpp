@@ -1,4 +1,4 @@
-// Geometry and interpolation arithmetic shared by the output-head kernels (k_head.hip, k_confidence.hip): every kernel that walks the
+// Geometry and interpolation arithmetic shared by the output-head kernels (k_head.hip, k_confidence.hip, k_soft_metric.hip): every kernel that walks the
 // full-resolution pixels forms a pixel's K interpolated logits with these functions, in this order, so they all see the same bits.
 #pragma once
 #include "kernels.hpp"
@@ -46,6 +46,24 @@ static inline HeadGeom head_geom(int ld, int B, int h, int w, int K, int H, int 
     g.sy = H > 1 ? (float)(h - 1) / (float)(H - 1) : 0.f;
     g.sx = W > 1 ? (float)(w - 1) / (float)(W - 1) : 0.f;
     return g;
+}
+
+// Soft-teacher targets (create_student_v3 with soft_teacher=True, utils/graph_utils.py:359, 375-376, 403-404): teacher logits
+// [B][th][tw][ld] f32 fed through teacher_labels_logits_pl; the target of a pixel is softmax(gather(teacher_logits, class_weights)).  th x tw is
+// either the label size (the reference's feed: the loss needs the shape of filtered_logits) or any smaller grid, which is then interpolated
+// to H x W exactly as the student's own logits are (align corners) — at th == H, tw == W that interpolation is the identity, bit for bit.
+struct SoftTeacher {
+    const float* t;
+    int th, tw, ld;
+    float sy, sx;
+};
+
+static inline SoftTeacher soft_teacher_geom(const float* t, int th, int tw, int ld, int H, int W) {
+    SoftTeacher s;
+    s.t = t; s.th = th; s.tw = tw; s.ld = ld;
+    s.sy = H > 1 ? (float)(th - 1) / (float)(H - 1) : 0.f;          // as head_geom does for the student's own logits
+    s.sx = W > 1 ? (float)(tw - 1) / (float)(W - 1) : 0.f;
+    return s;
 }
 
 // the grid of the kernels that walk down columns: (column strips of 256, row bands, frames).  32 bands per column strip and image, fewer

@@ -8,16 +8,6 @@
 
 namespace ams {
 
-// Soft-teacher targets (create_student_v3 with soft_teacher=True, utils/graph_utils.py:359, 375-376, 403-404): teacher logits
-// [B][th][tw][ld] f32 fed through teacher_labels_logits_pl; the target of a pixel is softmax(gather(teacher_logits, class_weights)).  th x tw is
-// either the label size (the reference's feed: the loss needs the shape of filtered_logits) or any smaller grid, which is then interpolated
-// to H x W exactly as the student's own logits are (align corners) — at th == H, tw == W that interpolation is the identity, bit for bit.
-struct SoftTeacher {
-    const float* t;
-    int th, tw, ld;
-    float sy, sx;
-};
-
 // KMAX > 0: K <= KMAX and the K horizontally interpolated values of the two source rows live in registers while the thread walks
 // DOWN its column through a band of consecutive output rows — they change only when the source row does (every ~16 output rows at
 // 512 from 33), so an output pixel costs K vertical lerps + the argmax instead of 4K loads and 3K lerps.  Same arithmetic in the same
@@ -505,9 +495,7 @@ int launch_ce_loss_grad(const float* logits, int ld, int B, int h, int w, const 
     memset(&sft, 0, sizeof(sft));
     if (soft_logits) {
         AMS_REQUIRE(soft_h >= 1 && soft_w >= 1 && soft_h <= H && soft_w <= W, "ce_loss_grad: teacher logits of %d x %d for labels of %d x %d", soft_h, soft_w, H, W);
-        sft.t = soft_logits; sft.th = soft_h; sft.tw = soft_w; sft.ld = NC;
-        sft.sy = H > 1 ? (float)(soft_h - 1) / (float)(H - 1) : 0.f;          // as head_geom does for the student's own logits
-        sft.sx = W > 1 ? (float)(soft_w - 1) / (float)(W - 1) : 0.f;
+        sft = soft_teacher_geom(soft_logits, soft_h, soft_w, NC, H, W);
     }
     note_kernel(soft_logits ? "ce_loss_grad_kernel<soft>" : "ce_loss_grad_kernel");
     if (soft_logits) {

@@ -396,6 +396,13 @@ int confidence_stats_len();
 int launch_upsample_confidence(const float* logits, int ld, int B, int h, int w, const int32_t* cls, int K, int H, int W, const uint8_t* teacher,
                                int NC, uint8_t* conf_u8, float* conf_f32, int64_t* stats, hipStream_t st);
 
+// ---- k_soft_metric.hip : the soft-teacher loss and the probabilistic confusion matrices (prob_confmat, prob_confmat_star), the same walk ----
+// teacher uint8 [B][H][W] or null (every pixel valid), teacher_logits f32 [B][th][tw][NC] (th <= H, tw <= W); stats [B][soft_metric_stats_len(K)],
+// p_f32 [B][H][W][K], ce_f32 [B][H][W] (layout: include/ams_hip.h); each output may be null
+int soft_metric_stats_len(int K);
+int launch_upsample_soft_metric(const float* logits, int ld, int B, int h, int w, const int32_t* cls, int K, int H, int W, const uint8_t* teacher,
+                                int NC, const float* teacher_logits, int th, int tw, int64_t* stats, float* p_f32, float* ce_f32, hipStream_t st);
+
 // ---- k_replay.hip : the replay memory on the device: a mini-batch in one launch, cached teacher logits, the phi-score pairs ----
 // samples_host / pairs_host: the host copies of the device tables, checked before anything is launched
 int launch_replay_gather(const uint8_t* frame_slots, int64_t frame_stride, const uint8_t* label_slots, int64_t label_stride, int capacity, int Hs,

@@ -574,6 +574,30 @@ class StudentEngine:
                                                   C.c_void_p(stats.data_ptr()), self._stream()), "ams_student_confidence")
         return conf_u8, conf_f32, stats
 
+    def soft_metric(self, batch: Optional[int], teacher, teacher_logits, want_maps: bool = False):
+        """The soft-teacher loss and the probabilistic confusion matrices of the frames of the LAST pass (k_soft_metric.hip; one launch on the
+        current stream, nothing is synchronised): (int64 statistics [B, soft_metric.stats_len(K)], f32 p [B,H,W,K] or None, f32 pixel loss
+        [B,H,W] or None) as fresh device tensors.  ``teacher``: uint8 ids [B,H,W] (host array or device tensor) or None = every pixel counts;
+        ``teacher_logits``: f32 [B,th,tw,num_classes] with th <= H, tw <= W (host array or device tensor).  ``batch``: frames of that pass
+        (None: those of the last ``predict_frames``).  Call it before the next pass, which overwrites the low-resolution logits it reads."""
+        b = int(batch if batch is not None else self._frames_b)
+        assert 0 < b <= self.max_batch, "soft_metric: no pass to read (batch %d outside 1..%d)" % (b, self.max_batch)
+        lab = self._labels_to_device(teacher, b) if teacher is not None else None
+        t = teacher_logits if isinstance(teacher_logits, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(teacher_logits, dtype=np.float32))
+        assert t.dim() == 4 and t.shape[0] == b and t.shape[3] == self.num_classes, \
+            "teacher logits must be [%d, th, tw, %d], got %s" % (b, self.num_classes, tuple(t.shape))
+        assert 1 <= t.shape[1] <= self.height and 1 <= t.shape[2] <= self.width
+        t = t.to(self.device, dtype=torch.float32, non_blocking=True).contiguous()
+        stats = torch.empty((b, int(self.lib.ams_soft_metric_stats_len(self.K))), dtype=torch.int64, device=self.device)
+        p = torch.empty((b, self.height, self.width, self.K), dtype=torch.float32, device=self.device) if want_maps else None
+        ce = torch.empty((b, self.height, self.width), dtype=torch.float32, device=self.device) if want_maps else None
+        hip.check(self.lib.ams_student_soft_metric(self._h, b, C.c_void_p(lab.data_ptr()) if lab is not None else None, C.c_void_p(t.data_ptr()),
+                                                   int(t.shape[1]), int(t.shape[2]), C.c_void_p(stats.data_ptr()),
+                                                   C.c_void_p(p.data_ptr()) if want_maps else None, C.c_void_p(ce.data_ptr()) if want_maps else None,
+                                                   self._stream()), "ams_student_soft_metric")
+        self._soft_keepalive = (lab, t)          # alive until the next call replaces them (the launch is stream-ordered behind their copies)
+        return stats, p, ce
+
     def cross_confusion(self, labels_pair) -> torch.Tensor:
         a = np.asarray(labels_pair)
         assert a.shape[0] == 2

@@ -20,6 +20,8 @@ Deliberate differences (all listed in INTEGRATION.md):
   * ``predict_with_confidence`` / ``predict_probabilities`` / ``predict_with_metric_async(..., confidence=True)`` + ``take_confidence`` expose
     the student graph's ``probabilities_reduced`` (the per-pixel softmax maximum) and its statistics, computed right behind the inference pass
     (k_confidence.hip, ams_amd/confidence.py).
+  * ``predict_with_soft_metric`` / ``predict_soft_probabilities`` / ``evaluate_memory`` evaluate the soft-teacher objective and the reference's
+    ``prob_confmat`` / ``prob_confmat_star`` against given teacher logits without an optimisation step (k_soft_metric.hip, ams_amd/soft_metric.py).
 """
 from __future__ import annotations
 
@@ -39,7 +41,8 @@ from .delta import delta_layout
 from .edge_pipeline import EdgePipeline
 from .engine import StudentEngine
 from .render import VIEWS as RENDER_VIEWS, DeviceRenderer
-from .replay import DeviceReplayMemory, draw_samples
+from .replay import SAMPLE_FIELDS, DeviceReplayMemory, draw_samples
+from .soft_metric import SoftMetric
 from .utils import calculate_miou, colormap
 from .weights import load_npy
 
@@ -86,6 +89,7 @@ class _Pass(NamedTuple):                    # one synchronous inference pass, on
     metrics: Optional[tuple]                # pass_metrics summed over the frames; None without teacher labels
     rendered: object                        # RenderedViews (device tensors [B,H,W,3]) or None
     confidence: Optional[Confidence]
+    soft: Optional[SoftMetric] = None       # over the frames of the pass
 
     def result(self, *extras):
         """the tuple the public calls return: labels[, the four metrics][, extras]"""
@@ -197,6 +201,7 @@ class SemanticNetwork(object):
         self._last_train_ms = 0.0
         self._renderer = None              # the render tables (DeviceRenderer), built and uploaded on first use
         self._confidence_host = None       # pinned block the statistics rows of a synchronous pass leave through, on first use
+        self._soft_host = None             # the same for the rows of the soft-teacher metric
         self._held = None                  # device_masks: what the last phase left on the device (_hold_phase)
         self._auto_mask_dev = None         # device_masks: coord_desc_auto's selection, kept for keep_mask=True
         self._feed = None                  # training from host deques: the helper threads and their pinned ring (_host_feed)
@@ -303,7 +308,7 @@ class SemanticNetwork(object):
     def _mode(self) -> int:
         return hip.MODE_FROZEN if self.frozen else hip.MODE_LIVE
 
-    def _run_pass(self, frames, labels_teacher, views=None, confidence=False) -> _Pass:
+    def _run_pass(self, frames, labels_teacher, views=None, confidence=False, soft_logits=None) -> _Pass:
         """One inference pass and what is launched behind it on the same stream: every synchronous host-returning call is this, under
         ``process_lock``.  The engine has ONE output block, one uint8 label view and one set of low-resolution logits: the order below is fixed."""
         eng = self.engine
@@ -325,14 +330,22 @@ class SemanticNetwork(object):
                 self._confidence_host = torch.empty((eng.max_batch, stats_dev.shape[1]), dtype=torch.int64).pin_memory()
             rows = self._confidence_host[:stats_dev.shape[0]]
             rows.copy_(stats_dev, non_blocking=True)
+        #    ... and, with teacher logits, one soft-metric launch under the same rule (it reads the same logits and writes only its own rows)
+        if soft_logits is not None:
+            soft_dev = eng.soft_metric(None, teacher_dev, soft_logits)[0]
+            if self._soft_host is None:
+                self._soft_host = torch.empty((eng.max_batch, soft_dev.shape[1]), dtype=torch.int64).pin_memory()
+            soft_rows = self._soft_host[:soft_dev.shape[0]]
+            soft_rows.copy_(soft_dev, non_blocking=True)
         # 5. one device -> host copy for labels + confusion matrices + losses (they share the output block) and one synchronisation
         labels_student, confs, losses = eng.fetch_frames()
         # 6. the rows are valid now
         if confidence:
             certain = Confidence(conf_map, [ConfidenceStats(r, self.class_count) for r in rows.numpy().copy()])
+        soft = SoftMetric.sum(soft_rows.numpy().copy()) if soft_logits is not None else None
         assert labels_student.shape == tuple(frames.shape[:-1] if hasattr(frames, 'shape') else np.shape(frames)[:-1])
         metrics = pass_metrics(confs.sum(axis=0), losses.sum(axis=0)) if labels_teacher is not None else None
-        return _Pass(labels_student, metrics, rendered, certain)
+        return _Pass(labels_student, metrics, rendered, certain, soft)
 
     def predict_input(self, frames):
         with self.process_lock:
@@ -379,6 +392,51 @@ class SemanticNetwork(object):
             self._pipeline.drain()
             self.engine.predict_frames(frames, None, self._mode(), u8=True)
             return self.engine.confidence(None, f32=True)[1].cpu().numpy()
+
+    def predict_with_soft_metric(self, frames, labels_teacher, teacher_logits):
+        """One inference pass and one soft-metric launch behind it on the same stream: what a ``soft_teacher=True`` graph of the reference
+        reports as ``student['loss']`` (utils/graph_utils.py:375-376, 403-408) and its ``prob_confmat`` / ``prob_confmat_star``
+        (:265-317), evaluated without an optimisation step.  ``teacher_logits``: f32 [B, th, tw, TOTAL_CLASSES] with th <= H, tw <= 2H (host
+        array or device tensor); ``soft_teacher`` need not be set.  Returns what ``predict_with_metric`` returns, bit for bit, plus one
+        ``SoftMetric`` over the frames of the call (``.row``: their summed integer row)."""
+        assert teacher_logits.shape[0] == len(frames) and teacher_logits.shape[-1] == self.TOTAL_CLASSES, \
+            "teacher_logits must be [%d, th, tw, %d], got %s" % (len(frames), self.TOTAL_CLASSES, tuple(teacher_logits.shape))
+        with self.process_lock:
+            p = self._run_pass(frames, labels_teacher, soft_logits=teacher_logits)
+        return p.result(p.soft)
+
+    def predict_soft_probabilities(self, frames, teacher_logits):
+        """The per-pixel values behind ``predict_with_soft_metric``: (f32 ndarray [B,H,W,K] = the teacher's distribution over the selected
+        classes, ``filtered_teacher_labels_probs``; f32 ndarray [B,H,W] = the pixel's soft cross-entropy against the student)."""
+        assert teacher_logits.shape[0] == len(frames) and teacher_logits.shape[-1] == self.TOTAL_CLASSES
+        with self.process_lock:
+            self._pipeline.drain()
+            self.engine.predict_frames(frames, None, self._mode(), u8=True)
+            _rows, p, ce = self.engine.soft_metric(None, None, teacher_logits, want_maps=True)
+            return p.cpu().numpy(), ce.cpu().numpy()
+
+    def evaluate_memory(self, memory, slots=None):
+        """The soft-teacher loss and both confusion matrices over a ``DeviceReplayMemory`` built with ``logits_shape``, without stepping: the
+        call to make before a model is published.  The frames are taken as stored (no rescale, crop or flip: the memory's frames have the
+        network's size), ``max_batch`` at a time, gathered on the device.  ``slots``: logical indices (0 = the oldest), None = all.  Returns
+        (``SoftMetric`` summed over the slots, hard confusion matrix float64 [K,K] summed over them); one synchronisation per pass."""
+        assert isinstance(memory, DeviceReplayMemory), "evaluate_memory walks a DeviceReplayMemory"
+        if memory.logits_shape is None:
+            raise ValueError("evaluate_memory needs the teacher logits: construct the DeviceReplayMemory with logits_shape")
+        eng = self.engine
+        assert (memory.src_h, memory.src_w) == (eng.height, eng.width), "the memory's frames must be [%d, %d]" % (eng.height, eng.width)
+        slots = np.arange(len(memory), dtype=np.int64) if slots is None else np.asarray(slots, dtype=np.int64).reshape(-1)
+        assert slots.size > 0, "no slot to evaluate"
+        table = np.zeros((slots.size, SAMPLE_FIELDS), dtype=np.int32)
+        table[:, 0], table[:, 1], table[:, 2] = slots, memory.src_h, memory.src_w          # (slot, th, tw, top, left, flip): the copy case
+        rows, conf = [], np.zeros((self.class_count, self.class_count), dtype=np.int64)
+        with self.process_lock:
+            for first in range(0, slots.size, eng.max_batch):
+                frames, labels, logits = memory.plan(table[None, first:first + eng.max_batch], eng.height, eng.width).batch(0)
+                p = self._run_pass(frames, labels, soft_logits=logits)
+                rows.append(p.soft.row)
+                conf += p.metrics[0].astype(np.int64)
+        return SoftMetric.sum(rows), conf.astype(np.float64)
 
     def _get_renderer(self):
         """The render tables of this network, built and uploaded once."""

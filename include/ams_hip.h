@@ -170,6 +170,14 @@ int ams_student_predict_frames_u8(ams_student* s, const void* frames_dev, int32_
 int ams_student_confidence(ams_student* s, int32_t batch, const uint8_t* teacher_dev, uint8_t* conf_u8, float* conf_f32, int64_t* stats,
                            void* stream);
 
+/* The soft-teacher loss and the probabilistic confusion matrices of the frames of the LAST forward pass: ams_k_upsample_soft_metric on the
+ * low-resolution logits that pass left on the device (AMS_REGION_LOGITS, read in place), one launch over `batch` frames.  teacher_dev uint8
+ * [batch,H,W] or NULL; teacher_logits_dev f32 [batch,th,tw,num_classes]; stats / p_f32 / ce_f32 as there, each may be NULL.  Launch it on the
+ * stream of the pass and before the next one, which overwrites the logits.  The batch and the teacher grid are arguments: the call does not read
+ * the feed armed by ams_student_feed_teacher_logits.  batch outside 1..max_batch: AMS_E_INVALID, nothing written. */
+int ams_student_soft_metric(ams_student* s, int32_t batch, const uint8_t* teacher_dev, const float* teacher_logits_dev, int32_t th, int32_t tw,
+                            int64_t* stats, float* p_f32, float* ce_f32, void* stream);
+
 int ams_cross_confusion(const ams_student* s, const uint8_t* labels_dev, int64_t n_pixels, int64_t* conf_mat_dev,
                         void* stream);
 
@@ -647,6 +655,27 @@ int ams_k_upsample_confidence(const float* logits /*[B,h,w,NC]*/, int32_t B, int
                               const int32_t* class_idx_host, int32_t K, int32_t H, int32_t W, const uint8_t* teacher,
                               uint8_t* conf_u8, float* conf_f32, int64_t* stats, void* stream);
 size_t ams_confidence_stats_len(void);
+
+/* Evaluation of the soft-teacher objective (create_student_v3 with soft_teacher=True; prob_confmat / prob_confmat_star, utils/graph_utils.py:265-317,
+ * and the soft loss, :375-376, 397, 403-408): the same walk over the full-resolution pixels as ams_k_upsample_argmax (same interpolation, same
+ * argmax).  teacher_logits f32 [B,th,tw,NC] with th <= H, tw <= W: at the label size they are read as they are, a smaller grid is interpolated
+ * as in ams_k_ce_loss_grad_soft.  Per pixel z = the K gathered student logits, t = the K gathered teacher logits, p = softmax(t),
+ * ce = sum_k p_k (logsumexp(z) - z_k), in f32.  teacher uint8 [B,H,W]: a pixel is valid when its id is in the subset; NULL: every pixel is
+ * valid (prob_confmat's unmasked form).  Every output may be NULL (nothing is written there):
+ *   p_f32  float [B,H,W,K]  p          ce_f32  float [B,H,W]  ce          (every pixel, valid or not)
+ *   stats  int64 [B][ams_soft_metric_stats_len(K)] = [B][2 + 2 K K], one row per frame, overwritten:
+ *          valid_cnt | ce_sum | M_stu[K*K] | M_star[K*K]
+ *          ce_sum = sum over the valid pixels of rint(ce * 2^20); M_stu[c*K + i] = sum over the valid pixels whose argmax is i of
+ *          rint(p_c * 2^20); M_star[c*K + i] the same over those whose reduced teacher label is i (zeros when teacher == NULL): rows are the
+ *          probability class, columns the label.  All integers: a frame's row does not depend on the batch it is computed in.  A valid pixel
+ *          with a NaN in either logit vector, or whose ce is not finite, is counted in valid_cnt and adds 0 everywhere else.
+ * AMS_E_INVALID, nothing written: B < 1, K outside 1..32, a teacher grid larger than H x W, more than 2047 rows per band of the launch grid
+ * (H > 65504: a thread's 32-bit column sums). */
+int ams_k_upsample_soft_metric(const float* logits /*[B,h,w,NC]*/, int32_t B, int32_t h, int32_t w, int32_t NC,
+                               const int32_t* class_idx_host, int32_t K, int32_t H, int32_t W, const uint8_t* teacher,
+                               const float* teacher_logits /*[B,th,tw,NC]*/, int32_t th, int32_t tw, int64_t* stats, float* p_f32,
+                               float* ce_f32, void* stream);
+size_t ams_soft_metric_stats_len(int32_t K);    /* 2 + 2 K K; 0 for K outside 1..32 */
 
 /* K11 backward: d loss / d low-res logits (zeros for unselected classes); loss_and_count_dev: the double[2]
  * written by ams_k_upsample_argmax ([1] = number of valid pixels, the mean's denominator).
