@@ -97,8 +97,10 @@ class HostBatchFeed:
         fast = (list(self.scale) == [1] and all(f.shape[:2] == tuple(crop) for f in frames))
         fast = fast and all(f.dtype == np.uint8 for f in frames) and all(l.dtype == np.uint8 and l.shape == tuple(crop) for l in labels)
         soft = list(teacher_logits_deque) if teacher_logits_deque is not None else None
-        # soft targets follow the frames a batch drew: only where frames are taken as they are (no rescale / crop of the logits is defined)
-        assert soft is None or fast, "teacher_logits_deque needs uint8 frames and labels at the network size and scale == [1]"
+        # soft targets follow the frames a batch drew: on this path only where frames are taken as they are.  Rescaled, cropped and flipped
+        # soft batches are a capability of the device memory (replay.DeviceReplayMemory with logits cached at the frame size)
+        assert soft is None or fast, ("teacher_logits_deque needs uint8 frames and labels at the network size and scale == [1]; a "
+                                      "DeviceReplayMemory with logits_shape at the frame size trains on rescaled, cropped and flipped soft batches")
         for _ in range(number_of_batches):
             if self._abort.is_set():
                 return

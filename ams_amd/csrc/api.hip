@@ -270,6 +270,13 @@ int ams_replay_gather_f32(const float* slots_dev, int64_t slot_stride, int32_t c
                                      (hipStream_t)stream);
 }
 
+int ams_replay_gather_logits(const float* slots_dev, int64_t slot_stride, int32_t capacity, int32_t src_h, int32_t src_w, int32_t channels,
+                             const ams_replay_sample* samples_dev, const ams_replay_sample* samples_host, int32_t batch, int32_t H, int32_t W,
+                             float* out_dev, void* stream) {
+    return launch_replay_gather_logits(slots_dev, slot_stride, capacity, src_h, src_w, channels, samples_dev, samples_host, batch, H, W, out_dev,
+                                       (hipStream_t)stream);
+}
+
 size_t ams_render_table_bytes(void) { return AMS_RENDER_TABLE_BYTES; }
 
 int ams_render_views(const uint8_t* frames_dev, const void* student_dev, int32_t student_dtype, const uint8_t* teacher_dev, int32_t batch, int32_t H,

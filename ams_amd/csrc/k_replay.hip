@@ -10,6 +10,14 @@
 //                                 The copy case, what a scale list of [1] over frames at the network size hits on every step, is byte
 //                                 traffic: 16 bytes per lane where the row pitches, the crop origin and the bases allow it.
 //   replay_gather_rows_kernel     whole f32 slots (the cached teacher logits of the drawn frames) by the same table
+//   replay_gather_logits_kernel   f32 [Hs, Ws, C] slots (teacher logits cached at the frame size) through the same descriptors: the crop of the
+//                                 logits rescaled to (th, tw), mirrored when flip, at the label size [B, H, W, C].  The rule is this
+//                                 project's (include/ams_hip.h: the reference never resamples logits): cv2.resize's float INTER_LINEAR
+//                                 geometry, taps in double, the blend in f32 with every operation rounded once.  A block owns a segment of
+//                                 an output row: its x-taps go to LDS once per pixel, then the segment's seg * C floats are walked flat, so
+//                                 that stores are contiguous and the four tap loads of neighbouring lanes fall in the same lines.  Equal
+//                                 sizes copy (nothing of a neighbouring pixel enters), 16 bytes per lane where the pitches, the origin and
+//                                 the bases allow it and the sample is not mirrored.
 //   cross_confusion_pairs_kernel  the K x K phi-score confusion matrices of n pairs of label slots in one launch (blockIdx.z = the pair)
 //
 // Every descriptor is checked on the host before the launch (api.hip); the kernels check it again against the sizes they are given and
@@ -102,6 +110,96 @@ __global__ __launch_bounds__(256) void replay_gather_rows_kernel(const float* __
     }
 }
 
+constexpr int kLogitsSeg = 128;                  // pixels of an output row per block (19 classes: 2432 floats, 9.5 per thread)
+
+struct LogitsGeom {
+    int capacity, Hs, Ws, C, H, W;
+    int64_t slot_stride;                         // f32 elements from one slot to the next
+    int vec;                                     // pitches and bases allow 16-byte accesses
+};
+
+// one axis of the logits rule: the source position of output index d in double, the weight of the second tap in f32; past either border
+// the nearest sample alone
+__device__ __forceinline__ void linear_tap(int d, int n_in, int n_out, int& s0, int& s1, float& w) {
+    const double f = ((double)d + 0.5) * ((double)n_in / (double)n_out) - 0.5;
+    const double fl = floor(f);
+    int s = (int)fl;
+    w = (float)(f - fl);
+    if (s < 0) { s = 0; w = 0.f; }
+    if (s >= n_in - 1) { s = n_in - 1; w = 0.f; }
+    s0 = s;
+    s1 = s + 1 < n_in - 1 ? s + 1 : n_in - 1;
+}
+
+__global__ __launch_bounds__(256) void replay_gather_logits_kernel(const float* __restrict__ slots, const ams_replay_sample* __restrict__ samples,
+                                                                   LogitsGeom g, float* __restrict__ out) {
+    __shared__ int s_x0[kLogitsSeg], s_x1[kLogitsSeg];          // element offsets of a pixel's two taps inside a source row
+    __shared__ float s_wx[kLogitsSeg];
+    const int b = blockIdx.z, oy = blockIdx.y, x_first = blockIdx.x * kLogitsSeg, t = threadIdx.x;
+    const ams_replay_sample d = samples[b];
+    if (!(d.slot >= 0 && d.slot < g.capacity && d.th > 0 && d.tw > 0 && d.top >= 0 && d.left >= 0 && d.top <= d.th - g.H && d.left <= d.tw - g.W)) return;
+    const int seg = g.W - x_first < kLogitsSeg ? g.W - x_first : kLogitsSeg;
+    const int n = seg * g.C;
+    const int64_t pitch = (int64_t)g.Ws * g.C;
+    const float* src = slots + (int64_t)d.slot * g.slot_stride;
+    float* dst = out + (((int64_t)b * g.H + oy) * g.W + x_first) * g.C;
+    const int cy = d.top + oy;                                   // the row of the rescaled logits
+    const bool same = d.th == g.Hs && d.tw == g.Ws;              // (every branch on d is uniform over the block)
+
+    if (same && !d.flip) {
+        const float* row = src + cy * pitch + (int64_t)(d.left + x_first) * g.C;
+        if (g.vec && (((int64_t)d.left * g.C) & 3) == 0) {
+            for (int i = t; i < (n >> 2); i += 256) st4(dst + 4 * i, ld4(row + 4 * i));
+        } else {
+            for (int i = t; i < n; i += 256) dst[i] = row[i];
+        }
+        return;
+    }
+
+    if (t < seg) {
+        const int x = x_first + t, cx = d.left + (d.flip ? g.W - 1 - x : x);
+        if (same) {
+            s_x0[t] = cx * g.C;
+        } else {
+            int x0, x1;
+            float wx;
+            linear_tap(cx, g.Ws, d.tw, x0, x1, wx);
+            s_x0[t] = x0 * g.C;
+            s_x1[t] = x1 * g.C;
+            s_wx[t] = wx;
+        }
+    }
+    __syncthreads();
+
+    // flat over the segment's floats: element i is channel c of pixel p; i advances by the block size without a division
+    int p = t / g.C, c = t - p * g.C;
+    const int dp = 256 / g.C, dc = 256 - dp * g.C;
+    if (same) {                                                  // the mirrored copy
+        const float* row = src + cy * pitch;
+        for (int i = t; i < n; i += 256) {
+            dst[i] = row[s_x0[p] + c];
+            p += dp; c += dc;
+            if (c >= g.C) { c -= g.C; ++p; }
+        }
+        return;
+    }
+    int y0, y1;
+    float wy;
+    linear_tap(cy, g.Hs, d.th, y0, y1, wy);
+    const float* row0 = src + y0 * pitch;
+    const float* row1 = src + y1 * pitch;
+    const float my = 1.f - wy;
+    for (int i = t; i < n; i += 256) {
+        const int a0 = s_x0[p] + c, a1 = s_x1[p] + c;
+        const float wx = s_wx[p], mx = 1.f - wx;
+        const float r0 = row0[a0] * mx + row0[a1] * wx;
+        const float r1 = row1[a0] * mx + row1[a1] * wx;
+        dst[i] = r0 * my + r1 * wy;
+        p += dp; c += dc;
+        if (c >= g.C) { c -= g.C; ++p; }
+    }
+}
+
 __global__ __launch_bounds__(256) void cross_confusion_pairs_kernel(const uint8_t* __restrict__ label_slots, int64_t label_stride, int capacity,
                                                                     const int32_t* __restrict__ pairs, int64_t n, ClassTable ct, int K,
                                                                     unsigned long long* __restrict__ conf) {
@@ -160,6 +258,31 @@ int launch_replay_gather_rows(const float* slots, int64_t slot_stride, int capac
     gx = gx < 1 ? 1 : gx > 1024 ? 1024 : gx;
     note_kernel("replay_gather_rows_kernel");
     hipLaunchKernelGGL(replay_gather_rows_kernel, dim3((int)gx, 1, B), dim3(256), 0, st, slots, slot_stride, capacity, samples_dev, n, vec, out);
+    AMS_CHECK_LAUNCH();
+    return AMS_OK;
+}
+
+int launch_replay_gather_logits(const float* slots, int64_t slot_stride, int capacity, int Hs, int Ws, int C, const ams_replay_sample* samples_dev,
+                                const ams_replay_sample* samples_host, int B, int H, int W, float* out, hipStream_t st) {
+    AMS_REQUIRE(slots && samples_dev && samples_host && out, "replay_gather_logits: null pointer");
+    AMS_REQUIRE(capacity > 0 && Hs > 0 && Ws > 0 && C > 0 && H > 0 && W > 0 && B > 0 && B <= 65535 && H <= 65535 && (int64_t)Ws * C <= INT32_MAX &&
+                    (int64_t)W * C <= INT32_MAX,
+                "replay_gather_logits: bad geometry %dx%dx%d -> %d x %dx%d, %d slots", Hs, Ws, C, B, H, W, capacity);
+    AMS_REQUIRE(slot_stride >= (int64_t)Hs * Ws * C, "replay_gather_logits: slot stride %lld below a %dx%dx%d slot", (long long)slot_stride, Hs, Ws, C);
+    for (int b = 0; b < B; ++b) {
+        const ams_replay_sample& d = samples_host[b];
+        AMS_REQUIRE(d.slot >= 0 && d.slot < capacity, "replay_gather_logits: sample %d draws slot %d of %d", b, d.slot, capacity);
+        AMS_REQUIRE(d.th > 0 && d.tw > 0 && d.th - H >= 0 && d.tw - W >= 0, "replay_gather_logits: sample %d: a %dx%d crop of a %dx%d image (negative slack)",
+                    b, H, W, d.th, d.tw);
+        AMS_REQUIRE(d.top >= 0 && d.left >= 0 && d.top <= d.th - H && d.left <= d.tw - W, "replay_gather_logits: sample %d: crop origin (%d, %d) outside %dx%d",
+                    b, d.top, d.left, d.th, d.tw);
+    }
+    LogitsGeom g;
+    g.capacity = capacity; g.Hs = Hs; g.Ws = Ws; g.C = C; g.H = H; g.W = W;
+    g.slot_stride = slot_stride;
+    g.vec = ((int64_t)Ws * C) % 4 == 0 && ((int64_t)W * C) % 4 == 0 && slot_stride % 4 == 0 && aligned16(slots) && aligned16(out);
+    note_kernel("replay_gather_logits_kernel");
+    hipLaunchKernelGGL(replay_gather_logits_kernel, dim3(cdiv(W, kLogitsSeg), H, B), dim3(256), 0, st, slots, samples_dev, g, out);
     AMS_CHECK_LAUNCH();
     return AMS_OK;
 }

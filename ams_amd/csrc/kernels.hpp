@@ -410,6 +410,8 @@ int launch_replay_gather(const uint8_t* frame_slots, int64_t frame_stride, const
                          uint8_t* frames_out, uint8_t* labels_out, hipStream_t st);
 int launch_replay_gather_rows(const float* slots, int64_t slot_stride, int capacity, int th, int tw, int C, const ams_replay_sample* samples_dev,
                               const ams_replay_sample* samples_host, int B, float* out, hipStream_t st);
+int launch_replay_gather_logits(const float* slots, int64_t slot_stride, int capacity, int Hs, int Ws, int C, const ams_replay_sample* samples_dev,
+                                const ams_replay_sample* samples_host, int B, int H, int W, float* out, hipStream_t st);
 int launch_cross_confusion_pairs(const uint8_t* label_slots, int64_t label_stride, int capacity, int64_t n, const int32_t* pairs_dev,
                                  const int32_t* pairs_host, int n_pairs, const int32_t* lut /*[256] -> subset idx or -1*/, int K, int64_t* conf,
                                  hipStream_t st);

@@ -9,7 +9,9 @@ mini-batch sampler that reads it there (reference utils/utils.py:129-185, ``mini
 The random numbers are the host generators', drawn in ``mini_batch``'s order (``draw_samples``): which frames a seeded run trains on does not
 depend on where the memory lives.  What the draws select is built by one launch per mini-batch (``ams_replay_gather``, k_replay.hip), bit for
 bit what ``mini_batch`` returns for them: the crop of the rescaled frame (cv2.resize's 8-bit INTER_LINEAR; INTER_NEAREST for the label),
-mirrored when flipped.  One source geometry per memory (the frames of one video have one size); the host deques stay the answer for mixed
+mirrored when flipped.  Teacher logits cached at the frame size follow the frame through the same descriptors (``ams_replay_gather_logits``:
+this project's rule, include/ams_hip.h; the reference never resamples logits); logits cached on a smaller grid follow whole frames only.
+One source geometry per memory (the frames of one video have one size); the host deques stay the answer for mixed
 sizes.  No CPU fallback: the launches need the HIP library and a GPU; the bookkeeping (``Ring``, ``draw_samples``, the byte budget) does not.
 """
 from __future__ import annotations
@@ -26,6 +28,8 @@ from .utils import calculate_miou
 
 SAMPLE_FIELDS = 6            # ams_replay_sample: slot, th, tw, top, left, flip (int32 each)
 SLOT_ALIGN = 256             # slots start at multiples of this many bytes: every 16-byte access of the copy case is aligned
+LOW_RES_LOGITS = ("a low-resolution teacher-logit cache (%dx%d logits for %dx%d frames) follows whole frames only: scale == [1], frames at the "
+                  "network size, no flip; cache the logits at the frame size to rescale, crop or flip them with the frames")
 
 
 def draw_samples(n_mem: int, src_hw: Sequence[int], crop: Sequence[int], scale: Sequence[float], batch: int, iters: int,
@@ -121,13 +125,18 @@ class ReplayPlan:
         self.memory, self.table_host, self.H, self.W = memory, table_host, H, W
         self.iters, self.batch_size = int(table_host.shape[0]), int(table_host.shape[1])
         self.table_dev = memory._upload(table_host)
-        self.frames, self.labels, self.logits = memory._batch_buffers(self.batch_size, H, W)
+        # whole frames: every draw takes a frame of the crop's size as it is.  Only then may the logits live on another grid than the frame's
+        # (they are copied slot by slot, the path and the bits of a scale == [1] phase); otherwise they are resampled with the frame
+        self.whole_frames = (memory.src_h, memory.src_w) == (H, W) and bool((table_host[..., 1:] == (H, W, 0, 0, 0)).all())
+        assert memory.logits_shape is None or self.whole_frames or memory.logits_at_source, \
+            LOW_RES_LOGITS % (memory.logits_shape[:2] + (memory.src_h, memory.src_w))
+        self.frames, self.labels, self.logits = memory._batch_buffers(self.batch_size, H, W, self.whole_frames)
 
     def batch(self, it: int):
         m = self.memory
         m._gather(self.table_host[it], self.table_dev[it], self.H, self.W, self.frames, self.labels)
         if self.logits is not None:
-            m._gather_logits(self.table_host[it], self.table_dev[it], self.logits)
+            m._gather_logits(self.table_host[it], self.table_dev[it], self.logits, None if self.whole_frames else (self.H, self.W))
         return self.frames, self.labels, self.logits
 
 
@@ -135,7 +144,8 @@ class DeviceReplayMemory:
     def __init__(self, capacity: int, src_h: int, src_w: int, device, logits_shape: Optional[Sequence[int]] = None,
                  max_bytes: Optional[int] = None):
         """``capacity`` slots of uint8 [src_h, src_w, 3] frames and uint8 [src_h, src_w] labels, with ``logits_shape`` = (th, tw, classes) also
-        f32 teacher logits per slot (soft_teacher).  The bytes wanted are computed up front (``nbytes``; at 512x1024: 2 MB per slot, 42 MB with
+        f32 teacher logits per slot (soft_teacher; (src_h, src_w, classes) lets them follow rescale, crop and flip, a smaller grid follows
+        whole frames only).  The bytes wanted are computed up front (``nbytes``; at 512x1024: 2 MB per slot, 42 MB with
         full-size logits) and ``MemoryError`` is raised above ``max_bytes`` before anything is allocated."""
         self.ring = Ring(capacity)
         self.capacity, self.src_h, self.src_w = int(capacity), int(src_h), int(src_w)
@@ -154,6 +164,11 @@ class DeviceReplayMemory:
         self._labels = torch.empty(self.capacity * self.label_stride, dtype=torch.uint8, device=self.device)
         self._logits = torch.empty(self.capacity * self.logits_stride, dtype=torch.float32, device=self.device) if self.logits_shape else None
         self._buffers = None
+
+    @property
+    def logits_at_source(self) -> bool:
+        """The teacher logits are cached at the frames' size: they can follow a frame through rescale, crop and flip."""
+        return self.logits_shape is not None and self.logits_shape[:2] == (self.src_h, self.src_w)
 
     # ------------------------------------------------------------------ deque(maxlen=capacity) surface
     def __len__(self) -> int:
@@ -202,11 +217,15 @@ class DeviceReplayMemory:
         table[..., 0] = self.ring.physical(table[..., 0].astype(np.int64))
         return ReplayPlan(self, table, int(H), int(W))
 
-    def _batch_buffers(self, batch: int, H: int, W: int):
-        """The resident mini-batch buffer: allocated once per batch geometry."""
-        key = (batch, H, W)
+    def _batch_buffers(self, batch: int, H: int, W: int, whole_frames: bool = True):
+        """The resident mini-batch buffer: allocated once per batch geometry.  The logits of whole frames keep their cached grid; resampled
+        with the frames they have the label size."""
+        logits_shape = None
+        if self.logits_shape:
+            logits_shape = (batch,) + (self.logits_shape if whole_frames else (H, W, self.logits_shape[2]))
+        key = (batch, H, W, logits_shape)
         if self._buffers is None or self._buffers[0] != key:
-            logits = torch.empty((batch,) + self.logits_shape, dtype=torch.float32, device=self.device) if self.logits_shape else None
+            logits = torch.empty(logits_shape, dtype=torch.float32, device=self.device) if logits_shape else None
             self._buffers = (key, torch.empty((batch, H, W, 3), dtype=torch.uint8, device=self.device),
                              torch.empty((batch, H, W), dtype=torch.uint8, device=self.device), logits)
         return self._buffers[1:]
@@ -227,10 +246,18 @@ class DeviceReplayMemory:
                                               samples_host.ctypes.data_as(C.c_void_p), batch, H, W, C.c_void_p(frames_out.data_ptr()),
                                               C.c_void_p(labels_out.data_ptr()), self._stream()), "ams_replay_gather")
 
-    def _gather_logits(self, samples_host: np.ndarray, samples_dev: torch.Tensor, out: torch.Tensor) -> None:
+    def _gather_logits(self, samples_host: np.ndarray, samples_dev: torch.Tensor, out: torch.Tensor, crop=None) -> None:
+        """``crop`` None: whole slots on their cached grid.  ``crop`` = (H, W): source-size logits rescaled, cropped and mirrored with the frame."""
         th, tw, ch = self.logits_shape
         batch = int(samples_host.shape[0])
         assert samples_host.dtype == np.int32 and samples_host.flags.c_contiguous and samples_dev.is_contiguous()
+        if crop is not None:
+            assert self.logits_at_source and out.numel() == batch * crop[0] * crop[1] * ch
+            hip.check(hip.lib().ams_replay_gather_logits(C.c_void_p(self._logits.data_ptr()), self.logits_stride, self.capacity, self.src_h, self.src_w,
+                                                         ch, C.c_void_p(samples_dev.data_ptr()), samples_host.ctypes.data_as(C.c_void_p), batch,
+                                                         crop[0], crop[1], C.c_void_p(out.data_ptr()), self._stream()), "ams_replay_gather_logits")
+            return
+        assert out.numel() == batch * th * tw * ch
         hip.check(hip.lib().ams_replay_gather_f32(C.c_void_p(self._logits.data_ptr()), self.logits_stride, self.capacity, th, tw, ch,
                                                   C.c_void_p(samples_dev.data_ptr()), samples_host.ctypes.data_as(C.c_void_p), batch,
                                                   C.c_void_p(out.data_ptr()), self._stream()), "ams_replay_gather_f32")
@@ -241,6 +268,12 @@ class DeviceReplayMemory:
         p = self.plan(np.asarray(samples)[None], H, W)
         frames, labels, _ = p.batch(0)
         return frames.clone(), labels.clone()
+
+    def gather_logits(self, samples: np.ndarray, H: int, W: int) -> torch.Tensor:
+        """The teacher logits of that mini-batch: a fresh f32 device tensor, [batch, H, W, classes] for logits cached at the frame size
+        (rescaled, cropped and mirrored with the frames), the cached grid for whole frames."""
+        assert self.logits_shape is not None, "the memory was constructed without logits_shape"
+        return self.plan(np.asarray(samples)[None], H, W).batch(0)[2].clone()
 
     # ------------------------------------------------------------------ ASR's phi-score
     def cross_miou_pairs(self, network, first: int = 0):

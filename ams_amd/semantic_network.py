@@ -13,7 +13,8 @@ Deliberate differences (all listed in INTEGRATION.md):
   * per-iteration loss printing is off unless ``verbose=True`` (each print forces a device sync).
   * ``device_masks=True`` keeps the server side of a model update on the device (coordinate selection, masks, the delta's bytes); same results.
   * ``train_with_deque`` also takes an ``ams_amd.replay.DeviceReplayMemory`` in place of the two deques: the replay memory and its sampler on
-    the device, no helper thread; ``flip=True`` (the reference passes False) is reachable on that path.
+    the device, no helper thread; ``flip=True`` (the reference passes False) is reachable on that path, and so are ``soft_teacher`` batches
+    with ``scale != [1]``, crops and flips: teacher logits cached at the frame size are resampled with their frames (ams_amd/replay.py).
   * ``colorize`` / ``colorize_teacher`` / ``cross_ignore`` also take torch device tensors and then paint on the device (k_render.hip) and return
     device tensors; ``predict_rendered`` and ``predict_with_metric_async(..., render=)`` / ``take_rendered`` paint right behind the inference pass.
     On the device a label out of range gives defined output where the host helpers raise IndexError (ams_amd/render.py).
@@ -41,7 +42,7 @@ from .delta import delta_layout
 from .edge_pipeline import EdgePipeline
 from .engine import StudentEngine
 from .render import VIEWS as RENDER_VIEWS, DeviceRenderer
-from .replay import SAMPLE_FIELDS, DeviceReplayMemory, draw_samples
+from .replay import LOW_RES_LOGITS, SAMPLE_FIELDS, DeviceReplayMemory, draw_samples
 from .soft_metric import SoftMetric
 from .utils import calculate_miou, colormap
 from .weights import load_npy
@@ -477,8 +478,9 @@ class SemanticNetwork(object):
         ``frame_deque``; a mini-batch takes the logits of the frames it drew.
 
         ``frame_deque`` may be an ``ams_amd.replay.DeviceReplayMemory`` (``label_deque`` and ``teacher_logits_deque`` are then None; with
-        ``soft_teacher=True`` the logits come from the memory).  That path starts no helper thread and uses no pinned staging: the calling
-        thread draws the phase's descriptors (``replay.draw_samples``, all iterations), uploads them once, and per iteration launches the gather
+        ``soft_teacher=True`` the logits come from the memory: cached at the frame size they are rescaled, cropped and flipped with the frames,
+        cached on a smaller grid they follow whole frames only, as on the host path).  That path starts no helper thread and uses no pinned
+        staging: the calling thread draws the phase's descriptors (``replay.draw_samples``, all iterations), uploads them once, and per iteration launches the gather
         on the engine's stream into one resident batch buffer before the same ``engine.train_step``; everything after the step is shared with
         the host path.  Order of the random draws: the sample descriptors of the whole phase FIRST, then ``get_train_mask``.  On the host path
         that order is a race between the sampler thread and ``get_train_mask`` (in the reference too), so the two paths are bit-identical,
@@ -634,12 +636,13 @@ class SemanticNetwork(object):
     def _replay_plan(self, memory, num_of_iterations):
         """A phase on a DeviceReplayMemory: mini_batch's draws for every iteration, on the calling thread, uploaded once."""
         crop = [self.height, self.height * 2]
-        # soft targets follow the frames a batch drew: only where frames are taken as they are (no rescale / crop of the logits is defined)
-        assert memory.logits_shape is None or (list(self.scale) == [1] and (memory.src_h, memory.src_w) == tuple(crop)), \
-            "teacher logits need frames and labels at the network size and scale == [1]"
+        # soft targets follow the frames a batch drew: logits cached at the frame size through rescale, crop and flip (ams_replay_gather_logits),
+        # logits cached on a smaller grid only where frames are taken as they are (composing the two resamplings is not defined)
+        whole_frames = list(self.scale) == [1] and (memory.src_h, memory.src_w) == tuple(crop) and not self.flip
+        assert memory.logits_shape is None or whole_frames or memory.logits_at_source, \
+            LOW_RES_LOGITS % (memory.logits_shape[:2] + (memory.src_h, memory.src_w))
         samples = draw_samples(len(memory), (memory.src_h, memory.src_w), crop, self.scale, self.mini_batch_size, num_of_iterations,
                                flip=self.flip)
-        assert memory.logits_shape is None or all(tuple(d[1:]) == (memory.src_h, memory.src_w, 0, 0, 0) for d in samples.reshape(-1, 6))
         return memory.plan(samples, crop[0], crop[1])
 
     def delta_payload(self, device: bool = False):

@@ -468,10 +468,36 @@ int ams_replay_gather(const uint8_t* frame_slots_dev, int64_t frame_slot_stride,
 
 /* The cached teacher logits of the frames a batch drew (replaces the np.stack + pin_memory + upload of the soft-teacher batch; the reference
  * feeds teacher_labels_logits_pl per batch, utils/graph_utils.py:359): slot p is f32 [th, tw, channels] at slots_dev + p * slot_stride
- * (stride in elements), out_dev f32 [batch, th, tw, channels].  Whole slots only: a descriptor with a crop origin or a flip is refused (no
- * rescale or crop of teacher logits is defined).  One launch (replay_gather_rows_kernel); no allocation, no synchronisation. */
+ * (stride in elements), out_dev f32 [batch, th, tw, channels].  Whole slots only: a descriptor with a crop origin or a flip is refused
+ * (logits cached on a grid smaller than the frame follow whole frames only; ams_replay_gather_logits rescales, crops and mirrors logits
+ * cached at the frame size).  One launch (replay_gather_rows_kernel); no allocation, no synchronisation. */
 int ams_replay_gather_f32(const float* slots_dev, int64_t slot_stride, int32_t capacity, int32_t th, int32_t tw, int32_t channels,
                           const ams_replay_sample* samples_dev, const ams_replay_sample* samples_host, int32_t batch, float* out_dev, void* stream);
+
+/* The teacher logits of a rescaled, cropped and mirrored batch: what the descriptors of ams_replay_gather do to a frame, done to the logits
+ * cached for it AT THE FRAME SIZE.  Slot p is f32 [src_h, src_w, channels] at slots_dev + p * slot_stride (stride in elements); out_dev is
+ * f32 [batch, H, W, channels], the label size, which ams_student_feed_teacher_logits(th = H, tw = W) reads as it is.
+ *
+ * The rule is this project's own (the reference's mini_batch never sees logits): the geometry of cv2.resize's float INTER_LINEAR, so that
+ * the logits are resampled where their frame is.  Output (y, x) of a descriptor (slot, th, tw, top, left, flip) samples the rescaled
+ * logits at cy = top + y, cx = left + (flip ? W - 1 - x : x).  Per axis (x shown), in double: f = (cx + 0.5) * ((double)src_w / (double)tw)
+ * - 0.5, s = floor(f), w = (float)(f - s); s < 0 gives s = 0, w = 0; s >= src_w - 1 gives s = src_w - 1, w = 0; the second tap is
+ * min(s + 1, src_w - 1).  Per channel, in f32, every operation rounded once (no fused multiply-add):
+ *
+ *     r0  = t[sy ][sx] * (1 - wx) + t[sy ][sx1] * wx
+ *     r1  = t[sy1][sx] * (1 - wx) + t[sy1][sx1] * wx
+ *     out = r0 * (1 - wy) + r1 * wy
+ *
+ * th == src_h && tw == src_w (per sample) is a plain copy of the crop window, mirrored when flip: an inf or NaN of a neighbouring pixel
+ * does not enter.  An exact 2x down-scale lands on w = 0.5, the 2 x 2 mean.  Logits cached on a smaller grid than the frame are not served
+ * (composing the align-corners upsample with this resize is a 16-tap filter): they follow whole frames through ams_replay_gather_f32.
+ *
+ * The descriptors are checked as by ams_replay_gather, on the host before the launch (AMS_E_INVALID, nothing launched) and again in the
+ * kernel.  16-byte aligned bases, slot_stride, src_w * channels and W * channels multiples of 4 let the unmirrored copy case with
+ * left * channels a multiple of 4 move 16 bytes per lane.  One launch (replay_gather_logits_kernel); no allocation, no synchronisation. */
+int ams_replay_gather_logits(const float* slots_dev, int64_t slot_stride, int32_t capacity, int32_t src_h, int32_t src_w, int32_t channels,
+                             const ams_replay_sample* samples_dev, const ams_replay_sample* samples_host, int32_t batch, int32_t H, int32_t W,
+                             float* out_dev, void* stream);
 
 /* The phi-score confusion matrices of n_pairs pairs of label slots at once (replaces the loop of run.py:287-291 over calc_cross_miou,
  * SemanticNetwork.py:124-139: one upload and one synchronising read per pair): pair i is (pairs[2i], pairs[2i + 1]) = (before, after)

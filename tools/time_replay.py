@@ -7,13 +7,15 @@ Host clock around ``train_with_deque`` (which ends with the read-back of the los
   a  hard labels, scale [1]                       (what run.py runs)
   b  soft_teacher with teacher logits at the label size
   c  scale [1, 1.25, 1.5]                         (the host path falls to utils.mini_batch)
+  d  soft_teacher, logits at the frame size, scale [1, 1.25, 1.5], flip   (device path only: the host path refuses the combination)
 
 Both paths start every phase from the same seeds, so they train on the same draws.  The baseline of every ratio is the host path timed in
-the same run.  Beside them: HIP-event times of the gather launch alone (copy case, bilinear case; stream otherwise idle), and the ASR event
+the same run.  Case d has no host path to compare against and no threshold: its phase time is recorded next to HIP-event times of the logits
+gather alone (ams_replay_gather_logits, one launch per mini-batch).  Beside them: HIP-event times of the gather launch alone (copy case, bilinear case; stream otherwise idle), and the ASR event
 with 10 label pairs as the loop over calc_cross_miou against one cross_miou_pairs call (host clock).  Writes one JSON (--out) and prints it.
 Cases b and c are slow on the host path (seconds per phase): --reps_b / --reps_c set their own counts, recorded in the JSON.
 
-    python tools/time_replay.py [--cases a,b,c,gather,asr] [--reps 50] [--warmup 5] [--out out/time_replay.json]
+    python tools/time_replay.py [--cases a,b,c,d,gather,asr] [--reps 50] [--warmup 5] [--out out/time_replay.json]
 """
 import argparse
 import json
@@ -86,6 +88,41 @@ def time_gather(mem, H, scale, batch, reps, warmup):
     return stats(us)
 
 
+def time_device_phases(net, mem, iters, reps, warmup):
+    """the device path alone; per-phase wall times in ms"""
+    dev = net.engine.device
+    ms = []
+    for r in range(warmup + reps):
+        seed(100 + r)
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        net.train_with_deque(mem, None, iters, "full_model")
+        torch.cuda.synchronize(dev)
+        if r >= warmup:
+            ms.append((time.perf_counter() - t0) * 1e3)
+    return stats(ms)
+
+
+def time_logits_gather(mem, H, scale, flip, batch, reps, warmup):
+    """HIP events around the logits gather of a mini-batch alone (the frames' gather is not in the window)"""
+    dev = mem.device
+    st = torch.cuda.current_stream(dev)
+    seed(7)
+    plan = mem.plan(draw_samples(len(mem), (mem.src_h, mem.src_w), [H, 2 * H], scale, batch, warmup + reps, flip=flip), H, 2 * H)
+    assert not plan.whole_frames
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    us = []
+    for r in range(warmup + reps):
+        torch.cuda.synchronize(dev)
+        e0.record(st)
+        mem._gather_logits(plan.table_host[r], plan.table_dev[r], plan.logits, (H, 2 * H))
+        e1.record(st)
+        torch.cuda.synchronize(dev)
+        if r >= warmup:
+            us.append(e0.elapsed_time(e1) * 1e3)
+    return stats(us)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--height", type=int, default=512)
@@ -96,7 +133,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--reps_b", type=int, default=None)
     ap.add_argument("--reps_c", type=int, default=None)
-    ap.add_argument("--cases", default="a,b,c,gather,asr")
+    ap.add_argument("--reps_d", type=int, default=None)
+    ap.add_argument("--cases", default="a,b,c,d,gather,asr")
     ap.add_argument("--out", default="out/time_replay.json")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "time_replay needs the GPU"
@@ -142,7 +180,7 @@ def main():
         result["asr_pairs"] = pairs
         result["asr_loop_ms"], result["asr_one_call_ms"] = stats(loop_ms), stats(call_ms)
         result["asr_loop_over_one_call"] = result["asr_loop_ms"]["median"] / result["asr_one_call_ms"]["median"]
-    if "b" in cases:
+    if "b" in cases or "d" in cases:
         rng = np.random.default_rng(5)
         tl = [rng.standard_normal((H, 2 * H, 19)).astype(np.float32) for _ in range(a.slots)]
         soft_mem = DeviceReplayMemory(a.slots, H, 2 * H, dev, logits_shape=(H, 2 * H, 19))
@@ -150,10 +188,21 @@ def main():
             soft_mem.append(f, l, t)
         net.soft_teacher = True
         net.engine.set_soft_teacher(True)
+    if "b" in cases:
         result["b_soft_teacher_full_size"] = time_phases(net, (host[0], host[1], deque(tl)), soft_mem, a.iters, a.reps_b or a.reps, a.warmup)
         result["b_soft_teacher_full_size"]["memory_bytes"] = soft_mem.nbytes
+    if "d" in cases:
+        net.scale, net.flip = [1, 1.25, 1.5], True
+        reps_d = a.reps_d or a.reps
+        phase = time_device_phases(net, soft_mem, a.iters, reps_d, a.warmup)
+        result["d_soft_teacher_augmented"] = {
+            "scale": net.scale, "flip": True, "device_ms": phase, "step_ms": phase["median"] / a.iters,
+            "logits_gather_us": time_logits_gather(soft_mem, H, net.scale, True, a.batch, reps_d, a.warmup),
+            "logits_bytes_written": a.batch * H * 2 * H * 19 * 4, "memory_bytes": soft_mem.nbytes}
+        net.scale, net.flip = [1], False
     result["note"] = ("*_ms: host clock around train_with_deque, stream drained before and after, host path and device path alternating with equal "
-                      "seeds; gather_*_us: HIP events around the one launch, stream otherwise idle; asr_*: host clock, results compared")
+                      "seeds; gather_*_us: HIP events around the one launch, stream otherwise idle; asr_*: host clock, results compared; "
+                      "d_*: device path only, logits_gather_us = HIP events around ams_replay_gather_logits alone")
     net.close_model()
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
