@@ -128,6 +128,8 @@ class HostBatchFeed:
             assert np.shape(image_batch) == (self.mini_batch_size, self.height, self.height * 2, 3)
             batch = {'frames': image_batch, 'labels': label_batch, 'slot': slot}
             if soft is not None:
+                # [th, tw, classes] arrays, or [th, tw, K] ones (the network's classes alone): stacked and uploaded as they are, the engine
+                # tells the layout by the last dimension
                 batch['teacher_logits'] = np.stack([np.asarray(soft[p], dtype=np.float32) for p in picks])
             self._batches.append(batch)
 

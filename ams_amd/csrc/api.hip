@@ -229,13 +229,19 @@ int ams_student_confidence(ams_student* s, int32_t batch, const uint8_t* teacher
                                       conf_u8, conf_f32, stats, (hipStream_t)stream);
 }
 
-int ams_student_soft_metric(ams_student* s, int32_t batch, const uint8_t* teacher_dev, const float* teacher_logits_dev, int32_t th, int32_t tw,
-                            int64_t* stats, float* p_f32, float* ce_f32, void* stream) {
+int ams_student_soft_metric_layout(ams_student* s, int32_t batch, const uint8_t* teacher_dev, const float* teacher_logits_dev, int32_t th, int32_t tw,
+                                   int64_t* stats, float* p_f32, float* ce_f32, void* stream, int32_t layout) {
     AMS_REQUIRE(s, "soft_metric: null student");
     AMS_REQUIRE(batch >= 1 && batch <= s->cfg.max_batch, "soft_metric: batch %d outside 1..%d", batch, s->cfg.max_batch);
+    AMS_REQUIRE(layout == AMS_TLOGITS_FULL || layout == AMS_TLOGITS_SELECTED, "soft_metric: unknown teacher-logit layout %d", layout);
     const ams_student_config& c = s->cfg;
     return launch_upsample_soft_metric(s->logits, 32, batch, s->h, s->w, c.class_indices, c.n_selected, c.height, c.width, teacher_dev, c.num_classes,
-                                       teacher_logits_dev, th, tw, stats, p_f32, ce_f32, (hipStream_t)stream);
+                                       teacher_logits_dev, th, tw, stats, p_f32, ce_f32, (hipStream_t)stream, layout);
+}
+
+int ams_student_soft_metric(ams_student* s, int32_t batch, const uint8_t* teacher_dev, const float* teacher_logits_dev, int32_t th, int32_t tw,
+                            int64_t* stats, float* p_f32, float* ce_f32, void* stream) {
+    return ams_student_soft_metric_layout(s, batch, teacher_dev, teacher_logits_dev, th, tw, stats, p_f32, ce_f32, stream, AMS_TLOGITS_FULL);
 }
 
 int ams_cross_confusion(const ams_student* s, const uint8_t* labels_dev, int64_t n_pixels, int64_t* conf_mat_dev, void* stream) {
@@ -277,6 +283,17 @@ int ams_replay_gather_logits(const float* slots_dev, int64_t slot_stride, int32_
                                        (hipStream_t)stream);
 }
 
+int ams_replay_pack_logits(const float* logits_dev, int32_t th, int32_t tw, int32_t num_classes, const int32_t* class_idx_host, int32_t K,
+                           int32_t layout, float* slot_dev, void* stream) {
+    AMS_REQUIRE(layout == AMS_TLOGITS_FULL || layout == AMS_TLOGITS_SELECTED, "replay_pack_logits: unknown teacher-logit layout %d", layout);
+    if (layout == AMS_TLOGITS_FULL) {                              // a full slot is the input itself
+        AMS_REQUIRE(logits_dev && slot_dev && th > 0 && tw > 0 && num_classes > 0, "replay_pack_logits: bad argument (%d x %d x %d)", th, tw, num_classes);
+        AMS_CHECK_HIP(hipMemcpyAsync(slot_dev, logits_dev, sizeof(float) * (size_t)th * tw * num_classes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        return AMS_OK;
+    }
+    return launch_replay_pack_logits(logits_dev, th, tw, num_classes, class_idx_host, K, slot_dev, (hipStream_t)stream);
+}
+
 size_t ams_render_table_bytes(void) { return AMS_RENDER_TABLE_BYTES; }
 
 int ams_render_views(const uint8_t* frames_dev, const void* student_dev, int32_t student_dtype, const uint8_t* teacher_dev, int32_t batch, int32_t H,
@@ -308,13 +325,18 @@ int ams_student_f16_fallback_layers(const ams_student* s, int32_t* n_layers) {
     return AMS_OK;
 }
 
-int ams_student_feed_teacher_logits(ams_student* s, const float* teacher_logits_dev, int32_t th, int32_t tw) {
+int ams_student_feed_teacher_logits_layout(ams_student* s, const float* teacher_logits_dev, int32_t th, int32_t tw, int32_t layout) {
     AMS_REQUIRE(s, "feed_teacher_logits: null student");
-    if (!teacher_logits_dev) { s->teacher_logits = nullptr; s->teacher_th = s->teacher_tw = 0; return AMS_OK; }
+    AMS_REQUIRE(layout == AMS_TLOGITS_FULL || layout == AMS_TLOGITS_SELECTED, "feed_teacher_logits: unknown teacher-logit layout %d", layout);
+    if (!teacher_logits_dev) { s->teacher_logits = nullptr; s->teacher_th = s->teacher_tw = 0; s->teacher_layout = AMS_TLOGITS_FULL; return AMS_OK; }
     AMS_REQUIRE(th >= 1 && tw >= 1 && th <= s->cfg.height && tw <= s->cfg.width, "feed_teacher_logits: %d x %d teacher logits for %d x %d labels", th, tw,
                 s->cfg.height, s->cfg.width);
-    s->teacher_logits = teacher_logits_dev; s->teacher_th = th; s->teacher_tw = tw;
+    s->teacher_logits = teacher_logits_dev; s->teacher_th = th; s->teacher_tw = tw; s->teacher_layout = layout;
     return AMS_OK;
+}
+
+int ams_student_feed_teacher_logits(ams_student* s, const float* teacher_logits_dev, int32_t th, int32_t tw) {
+    return ams_student_feed_teacher_logits_layout(s, teacher_logits_dev, th, tw, AMS_TLOGITS_FULL);
 }
 
 int ams_student_set_regularizer(ams_student* s, const uint8_t* reg_mask_dev, int32_t n_vars, float coef) {
@@ -790,11 +812,20 @@ int ams_k_upsample_confidence(const float* logits, int32_t B, int32_t h, int32_t
 }
 size_t ams_confidence_stats_len(void) { return (size_t)confidence_stats_len(); }
 
+int ams_k_upsample_soft_metric_layout(const float* logits, int32_t B, int32_t h, int32_t w, int32_t ld, int32_t NC, const int32_t* class_idx_host,
+                                      int32_t K, int32_t H, int32_t W, const uint8_t* teacher, const float* teacher_logits, int32_t th, int32_t tw,
+                                      int32_t layout, int64_t* stats, float* p_f32, float* ce_f32, void* stream) {
+    AMS_REQUIRE(class_idx_host, "soft_metric: null class table");
+    AMS_REQUIRE(layout == AMS_TLOGITS_FULL || layout == AMS_TLOGITS_SELECTED, "soft_metric: unknown teacher-logit layout %d", layout);
+    return launch_upsample_soft_metric(logits, ld, B, h, w, class_idx_host, K, H, W, teacher, NC, teacher_logits, th, tw, stats, p_f32, ce_f32,
+                                       (hipStream_t)stream, layout);
+}
+
 int ams_k_upsample_soft_metric(const float* logits, int32_t B, int32_t h, int32_t w, int32_t NC, const int32_t* class_idx_host, int32_t K,
                                int32_t H, int32_t W, const uint8_t* teacher, const float* teacher_logits, int32_t th, int32_t tw, int64_t* stats,
                                float* p_f32, float* ce_f32, void* stream) {
     return launch_upsample_soft_metric(logits, NC, B, h, w, class_idx_host, K, H, W, teacher, NC, teacher_logits, th, tw, stats, p_f32, ce_f32,
-                                       (hipStream_t)stream);
+                                       (hipStream_t)stream, AMS_TLOGITS_FULL);
 }
 size_t ams_soft_metric_stats_len(int32_t K) { return K >= 1 && K <= 32 ? (size_t)soft_metric_stats_len(K) : 0; }
 
@@ -819,13 +850,24 @@ int ams_k_ce_loss_grad(const float* logits, int32_t B, int32_t h, int32_t w, int
 int ams_k_ce_loss_grad_soft(const float* logits, int32_t B, int32_t h, int32_t w, int32_t NC, const int32_t* class_idx_host, int32_t K, int32_t H,
                             int32_t W, const uint8_t* teacher, const float* teacher_logits, int32_t th, int32_t tw, double* loss_dev, float* dlogits,
                             float* scratch, size_t scratch_floats, void* stream) {
+    return ams_k_ce_loss_grad_soft_layout(logits, B, h, w, NC, NC, class_idx_host, K, H, W, teacher, teacher_logits, th, tw, AMS_TLOGITS_FULL, loss_dev,
+                                          dlogits, scratch, scratch_floats, stream);
+}
+
+int ams_k_ce_loss_grad_soft_layout(const float* logits, int32_t B, int32_t h, int32_t w, int32_t ld, int32_t NC, const int32_t* class_idx_host,
+                                   int32_t K, int32_t H, int32_t W, const uint8_t* teacher, const float* teacher_logits, int32_t th, int32_t tw, int32_t layout,
+                                   double* loss_dev, float* dlogits, float* scratch, size_t scratch_floats, void* stream) {
     AMS_REQUIRE(teacher_logits, "ce_loss_grad_soft: null teacher logits");
+    AMS_REQUIRE(class_idx_host, "ce_loss_grad_soft: null class table");
+    AMS_REQUIRE(K >= 1 && K <= 32, "ce_loss_grad_soft: K=%d out of range (1..32)", K);
+    AMS_REQUIRE(layout == AMS_TLOGITS_FULL || layout == AMS_TLOGITS_SELECTED, "ce_loss_grad_soft: unknown teacher-logit layout %d", layout);
+    AMS_REQUIRE(ld >= NC && ld <= 256, "ce_loss_grad_soft: row stride %d must hold %d classes", ld, NC);
     AMS_REQUIRE(ce_loss_grad_supported(w, W), "ce_loss_grad: %d output columns on %d source columns is outside the one-pass kernel", W, w);
     AMS_REQUIRE(scratch && scratch_floats >= ce_loss_grad_scratch(B, h, w, K), "ce_loss_grad: scratch too small (need %zu floats)",
                 ce_loss_grad_scratch(B, h, w, K));
     hipStream_t st = (hipStream_t)stream;
-    RUN(launch_ce_loss_grad(logits, NC, B, h, w, class_idx_host, K, H, W, teacher, NC, loss_dev, scratch, st, teacher_logits, th, tw));
-    return launch_ce_combine(B, h, w, class_idx_host, K, NC, loss_dev, scratch, dlogits, NC, st);
+    RUN(launch_ce_loss_grad(logits, ld, B, h, w, class_idx_host, K, H, W, teacher, NC, loss_dev, scratch, st, teacher_logits, th, tw, layout));
+    return launch_ce_combine(B, h, w, class_idx_host, K, NC, loss_dev, scratch, dlogits, ld, st);
 }
 
 size_t ams_k_pointwise_wgrad_scratch(int64_t M, int32_t K, int32_t N) { return pointwise_wgrad_scratch(M, K, N); }

@@ -52,17 +52,27 @@ static inline HeadGeom head_geom(int ld, int B, int h, int w, int K, int H, int 
 // [B][th][tw][ld] f32 fed through teacher_labels_logits_pl; the target of a pixel is softmax(gather(teacher_logits, class_weights)).  th x tw is
 // either the label size (the reference's feed: the loss needs the shape of filtered_logits) or any smaller grid, which is then interpolated
 // to H x W exactly as the student's own logits are (align corners) — at th == H, tw == W that interpolation is the identity, bit for bit.
+//
+// Two layouts of a teacher pixel (AMS_TLOGITS_*): FULL, ld = NC floats of which channel ct.idx[k] is class k's; SELECTED, ld = K floats, channel k
+// holding what the full layout holds at ct.idx[k] (what a replay memory built with logits_select caches).  tidx[k] is class k's channel
+// in whichever layout is fed: the kernels are the same instantiations for both, so the same values meet the same instructions.
 struct SoftTeacher {
     const float* t;
     int th, tw, ld;
     float sy, sx;
+    int tidx[kMaxK];
 };
 
-static inline SoftTeacher soft_teacher_geom(const float* t, int th, int tw, int ld, int H, int W) {
+static inline bool tlogits_layout_ok(int layout) { return layout == AMS_TLOGITS_FULL || layout == AMS_TLOGITS_SELECTED; }
+
+// ct: the filled class table of the K selected classes (fill_class_table)
+static inline SoftTeacher soft_teacher_geom(const float* t, int th, int tw, int layout, const ClassTable& ct, int K, int NC, int H, int W) {
     SoftTeacher s;
-    s.t = t; s.th = th; s.tw = tw; s.ld = ld;
+    const bool selected = layout == AMS_TLOGITS_SELECTED;
+    s.t = t; s.th = th; s.tw = tw; s.ld = selected ? K : NC;
     s.sy = H > 1 ? (float)(th - 1) / (float)(H - 1) : 0.f;          // as head_geom does for the student's own logits
     s.sx = W > 1 ? (float)(tw - 1) / (float)(W - 1) : 0.f;
+    for (int k = 0; k < kMaxK; ++k) s.tidx[k] = k < K ? (selected ? k : ct.idx[k]) : 0;
     return s;
 }
 

@@ -348,14 +348,14 @@ __global__ __launch_bounds__(192) void ce_loss_grad_kernel(const float* __restri
                 float pmax = -3.0e38f;
                 if (qty == 0.f && qtx == 0.f) {           // on a grid point (always, when the teacher logits come at the label size)
 #pragma unroll
-                    for (int k = 0; k < KMAX; ++k) { pt[k] = qtl[ct.idx[k < g.K ? k : 0]]; if (k < g.K) pmax = fmaxf(pmax, pt[k]); }
+                    for (int k = 0; k < KMAX; ++k) { pt[k] = qtl[sft.tidx[k < g.K ? k : 0]]; if (k < g.K) pmax = fmaxf(pmax, pt[k]); }
                 } else {
                     const float* qtr = qbase + ((int64_t)qy0 * sft.tw + qx1) * sft.ld;
                     const float* qbl = qbase + ((int64_t)qy1 * sft.tw + qx0) * sft.ld;
                     const float* qbr = qbase + ((int64_t)qy1 * sft.tw + qx1) * sft.ld;
 #pragma unroll
                     for (int k = 0; k < KMAX; ++k) {
-                        const int c = ct.idx[k < g.K ? k : 0];
+                        const int c = sft.tidx[k < g.K ? k : 0];
                         pt[k] = bilerp(qtl[c], qtr[c], qbl[c], qbr[c], qtx, qty);
                         if (k < g.K) pmax = fmaxf(pmax, pt[k]);
                     }
@@ -476,7 +476,7 @@ __global__ __launch_bounds__(256) void ce_loss_sum_kernel(const double* __restri
 
 // pass 1: loss[0] += CE sum, loss[1] += valid pixels (loss zeroed here), unnormalised gradient planes into scratch
 int launch_ce_loss_grad(const float* logits, int ld, int B, int h, int w, const int32_t* cls, int K, int H, int W, const uint8_t* teacher,
-                        int NC, double* loss, float* scratch, hipStream_t st, const float* soft_logits, int soft_h, int soft_w) {
+                        int NC, double* loss, float* scratch, hipStream_t st, const float* soft_logits, int soft_h, int soft_w, int soft_layout) {
     ClassTable ct;
     int rc = fill_class_table(cls, K, NC, &ct);
     if (rc) return rc;
@@ -495,7 +495,8 @@ int launch_ce_loss_grad(const float* logits, int ld, int B, int h, int w, const 
     memset(&sft, 0, sizeof(sft));
     if (soft_logits) {
         AMS_REQUIRE(soft_h >= 1 && soft_w >= 1 && soft_h <= H && soft_w <= W, "ce_loss_grad: teacher logits of %d x %d for labels of %d x %d", soft_h, soft_w, H, W);
-        sft = soft_teacher_geom(soft_logits, soft_h, soft_w, NC, H, W);
+        AMS_REQUIRE(tlogits_layout_ok(soft_layout), "ce_loss_grad: unknown teacher-logit layout %d", soft_layout);
+        sft = soft_teacher_geom(soft_logits, soft_h, soft_w, soft_layout, ct, K, NC, H, W);
     }
     note_kernel(soft_logits ? "ce_loss_grad_kernel<soft>" : "ce_loss_grad_kernel");
     if (soft_logits) {

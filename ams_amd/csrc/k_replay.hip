@@ -17,7 +17,14 @@
 //                                 an output row: its x-taps go to LDS once per pixel, then the segment's seg * C floats are walked flat, so
 //                                 that stores are contiguous and the four tap loads of neighbouring lanes fall in the same lines.  Equal
 //                                 sizes copy (nothing of a neighbouring pixel enters), 16 bytes per lane where the pitches, the origin and
-//                                 the bases allow it and the sample is not mirrored.
+//                                 the bases allow it and the sample is not mirrored; with channels a multiple of 4 (a slot that holds the K
+//                                 selected channels, K = 4 or 8) every pixel starts on 16 bytes and the mirrored copy moves 16 bytes per
+//                                 lane too.
+//   replay_pack_logits_kernel     f32 [th, tw, NC] teacher logits -> a slot in the selected layout f32 [th, tw, K], channel k = input channel
+//                                 idx[k]: what append does to logits that are already on the device.  A block owns a run of pixels of one
+//                                 row: the run's run * NC input floats go through LDS with contiguous loads, the run * K output floats
+//                                 leave contiguously.  16-byte loads and 16-byte stores where the bases and the row pitches allow them,
+//                                 each chosen by the launcher for the whole launch.  Copies only: every bit pattern survives.
 //   cross_confusion_pairs_kernel  the K x K phi-score confusion matrices of n pairs of label slots in one launch (blockIdx.z = the pair)
 //
 // Every descriptor is checked on the host before the launch (api.hip); the kernels check it again against the sizes they are given and
@@ -176,6 +183,14 @@ __global__ __launch_bounds__(256) void replay_gather_logits_kernel(const float* 
     const int dp = 256 / g.C, dc = 256 - dp * g.C;
     if (same) {                                                  // the mirrored copy
         const float* row = src + cy * pitch;
+        if (g.vec && (g.C & 3) == 0) {                           // every pixel starts on 16 bytes: whole quads of one pixel
+            const int q = g.C >> 2;
+            for (int i = t; i < (n >> 2); i += 256) {
+                const int pp = i / q;
+                st4(dst + 4 * i, ld4(row + s_x0[pp] + 4 * (i - pp * q)));
+            }
+            return;
+        }
         for (int i = t; i < n; i += 256) {
             dst[i] = row[s_x0[p] + c];
             p += dp; c += dc;
@@ -197,6 +212,55 @@ __global__ __launch_bounds__(256) void replay_gather_logits_kernel(const float* 
         dst[i] = r0 * my + r1 * wy;
         p += dp; c += dc;
         if (c >= g.C) { c -= g.C; ++p; }
+    }
+}
+
+constexpr int kPackFloats = 4096;               // input floats of a run in LDS (16 KB)
+constexpr int kPackRun = 128;                   // pixels per block at most; fewer when NC > 32
+
+struct PackGeom {
+    int th, tw, NC, K, run;                      // run: pixels per block, a multiple of 4 (a run's floats start on 16 bytes when the row does)
+    int vec_in, vec_out;
+    int idx[kMaxK];
+};
+
+__global__ __launch_bounds__(256) void replay_pack_logits_kernel(const float* __restrict__ in, PackGeom g, float* __restrict__ out) {
+    __shared__ __attribute__((aligned(16))) float s_in[kPackFloats];
+    __shared__ int s_idx[kMaxK];
+    const int y = blockIdx.y, x_first = blockIdx.x * g.run, t = threadIdx.x;
+    if (y >= g.th || x_first >= g.tw) return;                   // (uniform over the block)
+    const int seg = g.tw - x_first < g.run ? g.tw - x_first : g.run;
+    const int n_in = seg * g.NC, n_out = seg * g.K;
+    const float* src = in + ((int64_t)y * g.tw + x_first) * g.NC;
+    float* dst = out + ((int64_t)y * g.tw + x_first) * g.K;
+#pragma unroll
+    for (int k = 0; k < kMaxK; ++k)
+        if (t == k) s_idx[k] = g.idx[k];                         // (constant k: the table stays in scalar registers)
+    if (g.vec_in) {
+        for (int i = t; i < (n_in >> 2); i += 256) *reinterpret_cast<float4*>(s_in + 4 * i) = ld4(src + 4 * i);
+    } else {
+        for (int i = t; i < n_in; i += 256) s_in[i] = src[i];
+    }
+    __syncthreads();
+    if (g.vec_out) {
+        for (int i = t; i < (n_out >> 2); i += 256) {
+            int p = 4 * i / g.K, k = 4 * i - p * g.K;
+            float v[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                v[e] = s_in[p * g.NC + s_idx[k]];
+                if (++k == g.K) { k = 0; ++p; }
+            }
+            st4(dst + 4 * i, make_float4(v[0], v[1], v[2], v[3]));
+        }
+    } else {
+        int p = t / g.K, k = t - p * g.K;
+        const int dp = 256 / g.K, dk = 256 - dp * g.K;
+        for (int i = t; i < n_out; i += 256) {
+            dst[i] = s_in[p * g.NC + s_idx[k]];
+            p += dp; k += dk;
+            if (k >= g.K) { k -= g.K; ++p; }
+        }
     }
 }
 
@@ -283,6 +347,27 @@ int launch_replay_gather_logits(const float* slots, int64_t slot_stride, int cap
     g.vec = ((int64_t)Ws * C) % 4 == 0 && ((int64_t)W * C) % 4 == 0 && slot_stride % 4 == 0 && aligned16(slots) && aligned16(out);
     note_kernel("replay_gather_logits_kernel");
     hipLaunchKernelGGL(replay_gather_logits_kernel, dim3(cdiv(W, kLogitsSeg), H, B), dim3(256), 0, st, slots, samples_dev, g, out);
+    AMS_CHECK_LAUNCH();
+    return AMS_OK;
+}
+
+int launch_replay_pack_logits(const float* in, int th, int tw, int NC, const int32_t* idx_host, int K, float* out, hipStream_t st) {
+    AMS_REQUIRE(in && out && idx_host, "replay_pack_logits: null pointer");
+    AMS_REQUIRE(th > 0 && tw > 0 && th <= 65535 && NC > 0 && NC <= 256 && (int64_t)tw * NC <= INT32_MAX, "replay_pack_logits: bad geometry %dx%dx%d", th, tw, NC);
+    AMS_REQUIRE(K >= 1 && K <= kMaxK, "replay_pack_logits: K=%d out of range (1..%d)", K, kMaxK);
+    PackGeom g;
+    for (int k = 0; k < kMaxK; ++k) g.idx[k] = 0;
+    for (int k = 0; k < K; ++k) {
+        AMS_REQUIRE(idx_host[k] >= 0 && idx_host[k] < NC, "replay_pack_logits: channel %d of %d", idx_host[k], NC);
+        g.idx[k] = idx_host[k];
+    }
+    g.th = th; g.tw = tw; g.NC = NC; g.K = K;
+    g.run = kPackFloats / NC < kPackRun ? (kPackFloats / NC) & ~3 : kPackRun;
+    // a run is a multiple of 4 pixels: with a row pitch that is a multiple of 4 floats every run of every row starts and ends on 16 bytes
+    g.vec_in = aligned16(in) && ((int64_t)tw * NC) % 4 == 0;
+    g.vec_out = aligned16(out) && ((int64_t)tw * K) % 4 == 0;
+    note_kernel("replay_pack_logits_kernel");
+    hipLaunchKernelGGL(replay_pack_logits_kernel, dim3(cdiv(tw, g.run), th), dim3(256), 0, st, in, g, out);
     AMS_CHECK_LAUNCH();
     return AMS_OK;
 }

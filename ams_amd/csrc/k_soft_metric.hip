@@ -104,7 +104,7 @@ __global__ __launch_bounds__(256) void upsample_soft_metric_kernel(const float* 
             return bilerp(ptl[c], ptr[c], pbl[c], pbr[c], tx, ty);
         };
         auto teach = [&](int k) -> float {
-            const int c = ct.idx[k];
+            const int c = sft.tidx[k];
             return on_grid ? qtl[c] : bilerp(qtl[c], qtr[c], qbl[c], qbr[c], qtx, qty);
         };
         // pass 1: the argmax (first maximum wins, tf.argmax) and both streaming log-sum-exps, as the loss path of upsample_argmax_kernel:
@@ -184,17 +184,18 @@ __global__ __launch_bounds__(256) void upsample_soft_metric_kernel(const float* 
 
 // cls: HOST pointer to the K selected class ids.  Every output pointer may be null: nothing is written there.  A refused call writes nothing.
 int launch_upsample_soft_metric(const float* logits, int ld, int B, int h, int w, const int32_t* cls, int K, int H, int W, const uint8_t* teacher,
-                                int NC, const float* teacher_logits, int th, int tw, int64_t* stats, float* p_f32, float* ce_f32, hipStream_t st) {
+                                int NC, const float* teacher_logits, int th, int tw, int64_t* stats, float* p_f32, float* ce_f32, hipStream_t st, int layout) {
     ClassTable ct;
     int rc = fill_class_table(cls, K, NC, &ct);
     if (rc) return rc;
     AMS_REQUIRE(logits && teacher_logits && B > 0 && h > 0 && w > 0 && H > 0 && W > 0, "soft_metric: B=%d, %d x %d -> %d x %d", B, h, w, H, W);
     AMS_REQUIRE(ld >= NC, "soft_metric: row stride %d below %d classes", ld, NC);
+    AMS_REQUIRE(tlogits_layout_ok(layout), "soft_metric: unknown teacher-logit layout %d", layout);
     AMS_REQUIRE(th >= 1 && tw >= 1 && th <= H && tw <= W, "soft_metric: teacher logits of %d x %d for labels of %d x %d", th, tw, H, W);
     const HeadGeom g = head_geom(ld, B, h, w, K, H, W, NC);
     const dim3 grid = head_band_grid(B, H, W);
     AMS_REQUIRE(cdiv(H, (int)grid.y) <= kSoftMaxBandRows, "soft_metric: %d rows per band overflow a thread's column sums", cdiv(H, (int)grid.y));
-    const SoftTeacher sft = soft_teacher_geom(teacher_logits, th, tw, NC, H, W);
+    const SoftTeacher sft = soft_teacher_geom(teacher_logits, th, tw, layout, ct, K, NC, H, W);
     if (stats) AMS_CHECK_HIP(hipMemsetAsync(stats, 0, sizeof(int64_t) * soft_metric_stats_len(K) * B, st));
     note_kernel("upsample_soft_metric_kernel");
     if (K <= 8)

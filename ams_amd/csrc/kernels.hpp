@@ -374,8 +374,10 @@ int launch_ce_grad(const float* logits, int ld, int B, int h, int w, const int32
 bool ce_loss_grad_supported(int w, int W);
 size_t ce_loss_grad_scratch(int B, int h, int w, int K);
 // soft_logits != nullptr: soft-teacher targets, teacher logits [B][soft_h][soft_w][NC] f32 (utils/graph_utils.py:375-376, 403-404; k_head.hip SoftTeacher)
+// soft_layout: AMS_TLOGITS_FULL, or AMS_TLOGITS_SELECTED = [B][soft_h][soft_w][K], channel k holding class cls[k]'s logit (head_common.hpp)
 int launch_ce_loss_grad(const float* logits, int ld, int B, int h, int w, const int32_t* cls, int K, int H, int W, const uint8_t* teacher,
-                        int NC, double* loss, float* scratch, hipStream_t st, const float* soft_logits = nullptr, int soft_h = 0, int soft_w = 0);
+                        int NC, double* loss, float* scratch, hipStream_t st, const float* soft_logits = nullptr, int soft_h = 0, int soft_w = 0,
+                        int soft_layout = AMS_TLOGITS_FULL);
 // empty_val: every selected class's gradient when NO pixel of the (global) batch is valid: 0, or NaN = the reference's 0 / 0
 // (utils/graph_utils.py:408: loss = sum(w ce) / sum(w))
 int launch_ce_combine(int B, int h, int w, const int32_t* cls, int K, int NC, const double* loss_and_count, const float* scratch,
@@ -401,7 +403,8 @@ int launch_upsample_confidence(const float* logits, int ld, int B, int h, int w,
 // p_f32 [B][H][W][K], ce_f32 [B][H][W] (layout: include/ams_hip.h); each output may be null
 int soft_metric_stats_len(int K);
 int launch_upsample_soft_metric(const float* logits, int ld, int B, int h, int w, const int32_t* cls, int K, int H, int W, const uint8_t* teacher,
-                                int NC, const float* teacher_logits, int th, int tw, int64_t* stats, float* p_f32, float* ce_f32, hipStream_t st);
+                                int NC, const float* teacher_logits, int th, int tw, int64_t* stats, float* p_f32, float* ce_f32, hipStream_t st,
+                                int layout = AMS_TLOGITS_FULL /* AMS_TLOGITS_SELECTED: teacher_logits [B][th][tw][K] */);
 
 // ---- k_replay.hip : the replay memory on the device: a mini-batch in one launch, cached teacher logits, the phi-score pairs ----
 // samples_host / pairs_host: the host copies of the device tables, checked before anything is launched
@@ -412,6 +415,8 @@ int launch_replay_gather_rows(const float* slots, int64_t slot_stride, int capac
                               const ams_replay_sample* samples_host, int B, float* out, hipStream_t st);
 int launch_replay_gather_logits(const float* slots, int64_t slot_stride, int capacity, int Hs, int Ws, int C, const ams_replay_sample* samples_dev,
                                 const ams_replay_sample* samples_host, int B, int H, int W, float* out, hipStream_t st);
+// in f32 [th][tw][NC] -> out f32 [th][tw][K], out channel k = in channel idx_host[k] (the selected layout of a replay slot); idx_host: HOST pointer
+int launch_replay_pack_logits(const float* in, int th, int tw, int NC, const int32_t* idx_host, int K, float* out, hipStream_t st);
 int launch_cross_confusion_pairs(const uint8_t* label_slots, int64_t label_stride, int capacity, int64_t n, const int32_t* pairs_dev,
                                  const int32_t* pairs_host, int n_pairs, const int32_t* lut /*[256] -> subset idx or -1*/, int K, int64_t* conf,
                                  hipStream_t st);

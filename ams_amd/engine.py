@@ -298,18 +298,32 @@ class StudentEngine:
         hip.check(self.lib.ams_student_set_regularizer(self._h, C.c_void_p(self._reg_mask.data_ptr()), n_vars, float(coef)),
                   "ams_student_set_regularizer")
 
-    def _feed_teacher_logits(self, teacher_logits, b: int):
-        """feed_dict[student['teacher_labels_logits_pl']]: f32 [b, th, tw, num_classes] (host array or device tensor); returns the device tensor
-        (the caller keeps it alive until the step has been enqueued on the same stream order)."""
+    def teacher_logits_layout(self, channels: int, layout: Optional[str] = None) -> int:
+        """AMS_TLOGITS_* of teacher logits whose last dimension is ``channels``.  ``layout`` None: ``num_classes`` channels are the full
+        layout, ``K`` channels (K != num_classes) the selected one — the student's classes, in the order of its class index list."""
+        channels = int(channels)
+        if layout is None:
+            assert channels in (self.num_classes, self.K), \
+                "teacher logits must be [batch, th, tw, %d] (full) or [batch, th, tw, %d] (the selected classes), got %d channels" % (self.num_classes, self.K, channels)
+            layout = "full" if channels == self.num_classes else "selected"
+        assert layout in hip.TLOGITS_LAYOUTS, "layout is 'full' or 'selected', got %r" % (layout,)
+        want = self.num_classes if layout == "full" else self.K
+        assert channels == want, "teacher logits in the %s layout must be [batch, th, tw, %d], got %d channels" % (layout, want, channels)
+        return hip.TLOGITS_LAYOUTS[layout]
+
+    def _feed_teacher_logits(self, teacher_logits, b: int, layout: Optional[str] = None):
+        """feed_dict[student['teacher_labels_logits_pl']]: f32 [b, th, tw, num_classes], or [b, th, tw, K] in the selected layout (host array
+        or device tensor); returns the device tensor (the caller keeps it alive until the step has been enqueued on the same stream order)."""
         if teacher_logits is None:
             assert not self.soft_teacher, "soft_teacher is on: teacher_logits must be fed (teacher_labels_logits_pl)"
             return None
         t = teacher_logits if isinstance(teacher_logits, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(teacher_logits, dtype=np.float32))
-        assert t.dim() == 4 and t.shape[0] == b and t.shape[3] == self.num_classes, "teacher logits must be [batch, th, tw, %d]" % self.num_classes
+        assert t.dim() == 4 and t.shape[0] == b, "teacher logits must be [batch, th, tw, %d]" % self.num_classes
+        code = self.teacher_logits_layout(t.shape[3], layout)
         assert t.shape[1] <= self.height and t.shape[2] <= self.width
         t = t.to(self.device, dtype=torch.float32, non_blocking=True).contiguous()
-        hip.check(self.lib.ams_student_feed_teacher_logits(self._h, C.c_void_p(t.data_ptr()), int(t.shape[1]), int(t.shape[2])),
-                  "ams_student_feed_teacher_logits")
+        hip.check(self.lib.ams_student_feed_teacher_logits_layout(self._h, C.c_void_p(t.data_ptr()), int(t.shape[1]), int(t.shape[2]), code),
+                  "ams_student_feed_teacher_logits_layout")
         return t
 
     def set_nan_grads(self, on: bool) -> None:
@@ -574,27 +588,29 @@ class StudentEngine:
                                                   C.c_void_p(stats.data_ptr()), self._stream()), "ams_student_confidence")
         return conf_u8, conf_f32, stats
 
-    def soft_metric(self, batch: Optional[int], teacher, teacher_logits, want_maps: bool = False):
+    def soft_metric(self, batch: Optional[int], teacher, teacher_logits, want_maps: bool = False, layout: Optional[str] = None):
         """The soft-teacher loss and the probabilistic confusion matrices of the frames of the LAST pass (k_soft_metric.hip; one launch on the
         current stream, nothing is synchronised): (int64 statistics [B, soft_metric.stats_len(K)], f32 p [B,H,W,K] or None, f32 pixel loss
         [B,H,W] or None) as fresh device tensors.  ``teacher``: uint8 ids [B,H,W] (host array or device tensor) or None = every pixel counts;
-        ``teacher_logits``: f32 [B,th,tw,num_classes] with th <= H, tw <= W (host array or device tensor).  ``batch``: frames of that pass
+        ``teacher_logits``: f32 [B,th,tw,num_classes] with th <= H, tw <= W (host array or device tensor), or [B,th,tw,K] in the selected
+        layout (``layout``: 'full', 'selected', or None = by the last dimension, ``teacher_logits_layout``).  ``batch``: frames of that pass
         (None: those of the last ``predict_frames``).  Call it before the next pass, which overwrites the low-resolution logits it reads."""
         b = int(batch if batch is not None else self._frames_b)
         assert 0 < b <= self.max_batch, "soft_metric: no pass to read (batch %d outside 1..%d)" % (b, self.max_batch)
         lab = self._labels_to_device(teacher, b) if teacher is not None else None
         t = teacher_logits if isinstance(teacher_logits, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(teacher_logits, dtype=np.float32))
-        assert t.dim() == 4 and t.shape[0] == b and t.shape[3] == self.num_classes, \
-            "teacher logits must be [%d, th, tw, %d], got %s" % (b, self.num_classes, tuple(t.shape))
+        assert t.dim() == 4 and t.shape[0] == b, "teacher logits must be [%d, th, tw, %d], got %s" % (b, self.num_classes, tuple(t.shape))
+        code = self.teacher_logits_layout(t.shape[3], layout)
         assert 1 <= t.shape[1] <= self.height and 1 <= t.shape[2] <= self.width
         t = t.to(self.device, dtype=torch.float32, non_blocking=True).contiguous()
         stats = torch.empty((b, int(self.lib.ams_soft_metric_stats_len(self.K))), dtype=torch.int64, device=self.device)
         p = torch.empty((b, self.height, self.width, self.K), dtype=torch.float32, device=self.device) if want_maps else None
         ce = torch.empty((b, self.height, self.width), dtype=torch.float32, device=self.device) if want_maps else None
-        hip.check(self.lib.ams_student_soft_metric(self._h, b, C.c_void_p(lab.data_ptr()) if lab is not None else None, C.c_void_p(t.data_ptr()),
-                                                   int(t.shape[1]), int(t.shape[2]), C.c_void_p(stats.data_ptr()),
-                                                   C.c_void_p(p.data_ptr()) if want_maps else None, C.c_void_p(ce.data_ptr()) if want_maps else None,
-                                                   self._stream()), "ams_student_soft_metric")
+        hip.check(self.lib.ams_student_soft_metric_layout(self._h, b, C.c_void_p(lab.data_ptr()) if lab is not None else None, C.c_void_p(t.data_ptr()),
+                                                          int(t.shape[1]), int(t.shape[2]), C.c_void_p(stats.data_ptr()),
+                                                          C.c_void_p(p.data_ptr()) if want_maps else None,
+                                                          C.c_void_p(ce.data_ptr()) if want_maps else None, self._stream(), code),
+                  "ams_student_soft_metric_layout")
         self._soft_keepalive = (lab, t)          # alive until the next call replaces them (the launch is stream-ordered behind their copies)
         return stats, p, ce
 
@@ -609,7 +625,8 @@ class StudentEngine:
         return conf.view(self.K, self.K)
 
     def train_step(self, frames, labels_teacher, lr: float, mask: Optional[torch.Tensor] = None,
-                   allreduce=None, global_batch: Optional[int] = None, comm=None, teacher_logits=None) -> torch.Tensor:
+                   allreduce=None, global_batch: Optional[int] = None, comm=None, teacher_logits=None,
+                   teacher_logits_layout: Optional[str] = None) -> torch.Tensor:
         """One Adam iteration; returns the device tensor f64[2] = (CE sum over valid pixels, valid pixel count).
 
         Data-parallel step, ``global_batch`` = frames over all ranks: ``comm`` = an ``ams_amd.dist.RcclComm``
@@ -618,7 +635,7 @@ class StudentEngine:
         assert self.trainable, "Can't train frozen graph!!!"
         t, dt, b = self._frames_to_device(frames)
         lab = self._labels_to_device(labels_teacher, b)
-        self._teacher_logits_dev = self._feed_teacher_logits(teacher_logits, b)          # soft_teacher only; alive until the next step replaces it
+        self._teacher_logits_dev = self._feed_teacher_logits(teacher_logits, b, teacher_logits_layout)          # soft_teacher only; alive until the next step replaces it
         loss = torch.empty(2, dtype=torch.float64, device=self.device)
         mptr = C.c_void_p(mask.data_ptr()) if mask is not None else C.c_void_p(0)
         if mask is not None:

@@ -39,6 +39,8 @@ OPT_DUAL_PARTS = 13
 OPT_NAN_GRADS = 18
 OPT_TRAIN_FWD_F16 = 24
 OPT_SOFT_TEACHER = 25
+TLOGITS_FULL, TLOGITS_SELECTED = 0, 1          # AMS_TLOGITS_*: teacher logits [..., num_classes] / [..., K] (the student's classes, in order)
+TLOGITS_LAYOUTS = {"full": TLOGITS_FULL, "selected": TLOGITS_SELECTED}
 OPT_OVERLAP_WGRAD = 19
 OPT_OVERLAP_HEAD = 20
 OPT_STREAM_MIN_ROWS = 21
@@ -107,6 +109,8 @@ SIGNATURES = {
     "ams_student_soft_metric": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ams_cross_confusion": (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
     "ams_cross_confusion_pairs": (C.c_int, [_vp, _vp, _i64, _i32, _i64, _vp, _vp, _i32, _vp, _vp]),
+    "ams_student_soft_metric_layout": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32]),
+    "ams_replay_pack_logits": (C.c_int, [_vp, _i32, _i32, _i32, C.POINTER(_i32), _i32, _i32, _vp, _vp]),
     "ams_replay_gather": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "ams_replay_gather_f32": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp]),
     "ams_replay_gather_logits": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp]),
@@ -124,6 +128,7 @@ SIGNATURES = {
     "ams_student_train_step_rccl": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _vp]),
     "ams_student_set_option": (C.c_int, [_vp, _i32, _i32]),
     "ams_student_feed_teacher_logits": (C.c_int, [_vp, _vp, _i32, _i32]),
+    "ams_student_feed_teacher_logits_layout": (C.c_int, [_vp, _vp, _i32, _i32, _i32]),
     "ams_student_f16_fallback_layers": (C.c_int, [_vp, C.POINTER(_i32)]),
     "ams_student_set_regularizer": (C.c_int, [_vp, _vp, _i32, _f32]),
     "ams_student_profile": (C.c_int, [_vp, _i32]),
@@ -160,11 +165,13 @@ SIGNATURES = {
     "ams_k_upsample_confidence": (C.c_int, [_vp, _i32, _i32, _i32, _i32, C.POINTER(_i32), _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "ams_confidence_stats_len": (_sz, []),
     "ams_k_upsample_soft_metric": (C.c_int, [_vp, _i32, _i32, _i32, _i32, C.POINTER(_i32), _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "ams_k_upsample_soft_metric_layout": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i32), _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ams_soft_metric_stats_len": (_sz, [_i32]),
     "ams_k_ce_grad": (C.c_int, [_vp, _i32, _i32, _i32, _i32, C.POINTER(_i32), _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ams_k_ce_loss_grad": (C.c_int, [_vp, _i32, _i32, _i32, _i32, C.POINTER(_i32), _i32, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ams_k_ce_loss_grad_scratch": (_sz, [_i32, _i32, _i32, _i32]),
     "ams_k_ce_loss_grad_soft": (C.c_int, [_vp, _i32, _i32, _i32, _i32, C.POINTER(_i32), _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "ams_k_ce_loss_grad_soft_layout": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i32), _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
     "ams_debug_launch_table_needs_attr": (C.c_int, [_i32, C.c_uint64, _sz]),
     "ams_debug_reload_knobs": (C.c_int, []),
     "ams_debug_phase_cycles": (C.c_int, [C.c_int32, C.POINTER(C.c_uint64), C.c_int32]),

@@ -12,7 +12,9 @@ bit what ``mini_batch`` returns for them: the crop of the rescaled frame (cv2.re
 mirrored when flipped.  Teacher logits cached at the frame size follow the frame through the same descriptors (``ams_replay_gather_logits``:
 this project's rule, include/ams_hip.h; the reference never resamples logits); logits cached on a smaller grid follow whole frames only.
 One source geometry per memory (the frames of one video have one size); the host deques stay the answer for mixed
-sizes.  No CPU fallback: the launches need the HIP library and a GPU; the bookkeeping (``Ring``, ``draw_samples``, the byte budget) does not.
+sizes.  ``logits_select=class_idx`` caches only the student's K channels of every frame's logits (the selected layout, AMS_TLOGITS_SELECTED:
+the loss gathers exactly those, so nothing is lost and every result keeps its bits; K / classes of the memory, the upload and the gather
+traffic).  No CPU fallback: the launches need the HIP library and a GPU; the bookkeeping (``Ring``, ``draw_samples``, the byte budget) does not.
 """
 from __future__ import annotations
 
@@ -142,11 +144,13 @@ class ReplayPlan:
 
 class DeviceReplayMemory:
     def __init__(self, capacity: int, src_h: int, src_w: int, device, logits_shape: Optional[Sequence[int]] = None,
-                 max_bytes: Optional[int] = None):
+                 max_bytes: Optional[int] = None, logits_select: Optional[Sequence[int]] = None):
         """``capacity`` slots of uint8 [src_h, src_w, 3] frames and uint8 [src_h, src_w] labels, with ``logits_shape`` = (th, tw, classes) also
         f32 teacher logits per slot (soft_teacher; (src_h, src_w, classes) lets them follow rescale, crop and flip, a smaller grid follows
-        whole frames only).  The bytes wanted are computed up front (``nbytes``; at 512x1024: 2 MB per slot, 42 MB with
-        full-size logits) and ``MemoryError`` is raised above ``max_bytes`` before anything is allocated."""
+        whole frames only).  ``logits_select`` = the student's class index list: a slot keeps those K channels alone, in that order
+        (``logits_cached_shape`` = (th, tw, K), ``logits_layout`` = "selected"); ``logits_shape`` stays what ``append`` is fed.  The bytes
+        wanted are computed up front (``nbytes``; at 512x1024: 2 MB per slot, 42 MB with full-size logits of 19 classes, 14.6 MB with six
+        selected) and ``MemoryError`` is raised above ``max_bytes`` before anything is allocated."""
         self.ring = Ring(capacity)
         self.capacity, self.src_h, self.src_w = int(capacity), int(src_h), int(src_w)
         assert self.src_h > 0 and self.src_w > 0
@@ -155,7 +159,19 @@ class DeviceReplayMemory:
         assert self.logits_shape is None or len(self.logits_shape) == 3, "logits_shape is (th, tw, classes)"
         self.frame_stride = _round_up(self.src_h * self.src_w * 3, SLOT_ALIGN)          # bytes
         self.label_stride = _round_up(self.src_h * self.src_w, SLOT_ALIGN)
-        self.logits_stride = _round_up(4 * int(np.prod(self.logits_shape)), SLOT_ALIGN) // 4 if self.logits_shape else 0     # f32 elements
+        self.logits_select = tuple(int(c) for c in logits_select) if logits_select is not None else None
+        if self.logits_select is not None:
+            assert self.logits_shape is not None, "logits_select goes with logits_shape"
+            assert 1 <= len(self.logits_select) <= 32, "logits_select names 1..32 classes, got %d" % len(self.logits_select)
+            assert all(0 <= c < self.logits_shape[2] for c in self.logits_select), \
+                "logits_select %s names a class outside 0..%d" % (list(self.logits_select), self.logits_shape[2] - 1)
+            assert self.logits_shape[2] <= 256, "at most 256 classes"
+        self.logits_layout = "selected" if self.logits_select is not None else "full"
+        # what a slot holds: every class, or the selected ones
+        self.logits_cached_shape = None
+        if self.logits_shape is not None:
+            self.logits_cached_shape = self.logits_shape[:2] + (len(self.logits_select) if self.logits_select is not None else self.logits_shape[2],)
+        self.logits_stride = _round_up(4 * int(np.prod(self.logits_cached_shape)), SLOT_ALIGN) // 4 if self.logits_shape else 0     # f32 elements
         self.nbytes = self.capacity * (self.frame_stride + self.label_stride + 4 * self.logits_stride)
         if max_bytes is not None and self.nbytes > int(max_bytes):
             raise MemoryError("a replay memory of %d slots of %dx%d needs %d bytes, above max_bytes = %d"
@@ -182,16 +198,21 @@ class DeviceReplayMemory:
         l = self._labels[p * self.label_stride:p * self.label_stride + self.src_h * self.src_w].view(self.src_h, self.src_w)
         if self._logits is None:
             return f, l
-        n = int(np.prod(self.logits_shape))
-        return f, l, self._logits[p * self.logits_stride:p * self.logits_stride + n].view(self.logits_shape)
+        n = int(np.prod(self.logits_cached_shape))
+        return f, l, self._logits[p * self.logits_stride:p * self.logits_stride + n].view(self.logits_cached_shape)
 
     def __getitem__(self, i: int):
-        """Device views (frame, label[, logits]) of logical element ``i`` (0 = the oldest); valid until the slot is evicted."""
+        """Device views (frame, label[, logits]) of logical element ``i`` (0 = the oldest); valid until the slot is evicted.  The logits have
+        ``logits_cached_shape``."""
         return self._slot_views(self.ring.physical(i))
 
     def append(self, frame, label, logits=None) -> None:
         """Host arrays or device tensors; a device tensor (e.g. ``FrameIngest``'s) is stored by a device copy on the current stream.  Past the
-        capacity the oldest element is evicted.  Labels go through the uint8 rule of ``StudentEngine._labels_to_device``."""
+        capacity the oldest element is evicted.  Labels go through the uint8 rule of ``StudentEngine._labels_to_device``.
+
+        A memory with ``logits_select`` takes full logits (``logits_shape``) or logits already reduced (``logits_cached_shape``): full logits
+        on the device go through ``ams_replay_pack_logits`` on the current stream, a full host array is reduced on the host (``np.take``)
+        so that only the K channels are uploaded, reduced logits are stored as they are."""
         f = frame if isinstance(frame, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(frame))
         assert f.dtype == torch.uint8, "the replay memory holds uint8 frames, got %s" % f.dtype
         assert tuple(f.shape) == (self.src_h, self.src_w, 3), "one source geometry per memory: [%d, %d, 3], got %s" % (self.src_h, self.src_w, tuple(f.shape))
@@ -200,14 +221,39 @@ class DeviceReplayMemory:
         assert (logits is not None) == (self._logits is not None), "teacher logits go with a memory constructed with logits_shape (and are required then)"
         t = None
         if logits is not None:
-            t = logits if isinstance(logits, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(logits, dtype=np.float32))
-            assert tuple(t.shape) == self.logits_shape, "teacher logits must be %s, got %s" % (self.logits_shape, tuple(t.shape))
+            t = self._logits_for_slot(logits)
         views = self._slot_views(self.ring.push())
         # device -> device copies are stream-ordered; a host array is copied before this returns (the caller may reuse it at once)
         views[0].copy_(f, non_blocking=f.is_cuda)
         views[1].copy_(l, non_blocking=l.is_cuda)
-        if t is not None:
+        if isinstance(t, tuple):          # full logits on the device for a selected slot
+            self._pack_logits(t[0], views[2])
+        elif t is not None:
             views[2].copy_(t.to(torch.float32), non_blocking=t.is_cuda)
+
+    def _logits_for_slot(self, logits):
+        """What ``append`` stores: a tensor of ``logits_cached_shape`` to copy, or ``(full device tensor,)`` for the pack kernel."""
+        shape = tuple(logits.shape)
+        if self.logits_select is None:
+            assert shape == self.logits_shape, "teacher logits must be %s, got %s" % (self.logits_shape, shape)
+        else:
+            assert shape in (self.logits_shape, self.logits_cached_shape), \
+                "teacher logits must be %s or, already reduced to the selected classes, %s, got %s" % (self.logits_shape, self.logits_cached_shape, shape)
+        reduce = self.logits_select is not None and shape == self.logits_shape          # (K == classes: the two shapes coincide and mean full)
+        if isinstance(logits, torch.Tensor):
+            if reduce and logits.is_cuda:
+                return (logits.to(torch.float32).contiguous(),)
+            return logits[..., list(self.logits_select)] if reduce else logits
+        a = np.asarray(logits, dtype=np.float32)
+        if reduce:
+            a = np.take(a, self.logits_select, axis=-1)          # only the K channels cross to the device
+        return torch.from_numpy(np.ascontiguousarray(a))
+
+    def _pack_logits(self, full: torch.Tensor, slot_view: torch.Tensor) -> None:
+        th, tw, nc = self.logits_shape
+        idx = (C.c_int32 * len(self.logits_select))(*self.logits_select)
+        hip.check(hip.lib().ams_replay_pack_logits(C.c_void_p(full.data_ptr()), th, tw, nc, idx, len(self.logits_select), hip.TLOGITS_SELECTED,
+                                                   C.c_void_p(slot_view.data_ptr()), self._stream()), "ams_replay_pack_logits")
 
     # ------------------------------------------------------------------ sampling
     def plan(self, samples: np.ndarray, H: int, W: int) -> ReplayPlan:
@@ -222,7 +268,7 @@ class DeviceReplayMemory:
         with the frames they have the label size."""
         logits_shape = None
         if self.logits_shape:
-            logits_shape = (batch,) + (self.logits_shape if whole_frames else (H, W, self.logits_shape[2]))
+            logits_shape = (batch,) + (self.logits_cached_shape if whole_frames else (H, W, self.logits_cached_shape[2]))
         key = (batch, H, W, logits_shape)
         if self._buffers is None or self._buffers[0] != key:
             logits = torch.empty(logits_shape, dtype=torch.float32, device=self.device) if logits_shape else None
@@ -248,7 +294,7 @@ class DeviceReplayMemory:
 
     def _gather_logits(self, samples_host: np.ndarray, samples_dev: torch.Tensor, out: torch.Tensor, crop=None) -> None:
         """``crop`` None: whole slots on their cached grid.  ``crop`` = (H, W): source-size logits rescaled, cropped and mirrored with the frame."""
-        th, tw, ch = self.logits_shape
+        th, tw, ch = self.logits_cached_shape
         batch = int(samples_host.shape[0])
         assert samples_host.dtype == np.int32 and samples_host.flags.c_contiguous and samples_dev.is_contiguous()
         if crop is not None:
@@ -270,8 +316,8 @@ class DeviceReplayMemory:
         return frames.clone(), labels.clone()
 
     def gather_logits(self, samples: np.ndarray, H: int, W: int) -> torch.Tensor:
-        """The teacher logits of that mini-batch: a fresh f32 device tensor, [batch, H, W, classes] for logits cached at the frame size
-        (rescaled, cropped and mirrored with the frames), the cached grid for whole frames."""
+        """The teacher logits of that mini-batch: a fresh f32 device tensor, [batch, H, W, channels] for logits cached at the frame size
+        (rescaled, cropped and mirrored with the frames), the cached grid for whole frames; channels = ``logits_cached_shape[2]``."""
         assert self.logits_shape is not None, "the memory was constructed without logits_shape"
         return self.plan(np.asarray(samples)[None], H, W).batch(0)[2].clone()
 

@@ -309,7 +309,7 @@ class SemanticNetwork(object):
     def _mode(self) -> int:
         return hip.MODE_FROZEN if self.frozen else hip.MODE_LIVE
 
-    def _run_pass(self, frames, labels_teacher, views=None, confidence=False, soft_logits=None) -> _Pass:
+    def _run_pass(self, frames, labels_teacher, views=None, confidence=False, soft_logits=None, soft_layout=None) -> _Pass:
         """One inference pass and what is launched behind it on the same stream: every synchronous host-returning call is this, under
         ``process_lock``.  The engine has ONE output block, one uint8 label view and one set of low-resolution logits: the order below is fixed."""
         eng = self.engine
@@ -333,7 +333,7 @@ class SemanticNetwork(object):
             rows.copy_(stats_dev, non_blocking=True)
         #    ... and, with teacher logits, one soft-metric launch under the same rule (it reads the same logits and writes only its own rows)
         if soft_logits is not None:
-            soft_dev = eng.soft_metric(None, teacher_dev, soft_logits)[0]
+            soft_dev = eng.soft_metric(None, teacher_dev, soft_logits, layout=soft_layout)[0]
             if self._soft_host is None:
                 self._soft_host = torch.empty((eng.max_batch, soft_dev.shape[1]), dtype=torch.int64).pin_memory()
             soft_rows = self._soft_host[:soft_dev.shape[0]]
@@ -398,22 +398,41 @@ class SemanticNetwork(object):
         """One inference pass and one soft-metric launch behind it on the same stream: what a ``soft_teacher=True`` graph of the reference
         reports as ``student['loss']`` (utils/graph_utils.py:375-376, 403-408) and its ``prob_confmat`` / ``prob_confmat_star``
         (:265-317), evaluated without an optimisation step.  ``teacher_logits``: f32 [B, th, tw, TOTAL_CLASSES] with th <= H, tw <= 2H (host
-        array or device tensor); ``soft_teacher`` need not be set.  Returns what ``predict_with_metric`` returns, bit for bit, plus one
+        array or device tensor), or [B, th, tw, K] = the network's own classes alone, in the order of its class index list (the selected
+        layout; the same bits); ``soft_teacher`` need not be set.  Returns what ``predict_with_metric`` returns, bit for bit, plus one
         ``SoftMetric`` over the frames of the call (``.row``: their summed integer row)."""
-        assert teacher_logits.shape[0] == len(frames) and teacher_logits.shape[-1] == self.TOTAL_CLASSES, \
-            "teacher_logits must be [%d, th, tw, %d], got %s" % (len(frames), self.TOTAL_CLASSES, tuple(teacher_logits.shape))
+        layout = self._logits_layout(teacher_logits, len(frames))
         with self.process_lock:
-            p = self._run_pass(frames, labels_teacher, soft_logits=teacher_logits)
+            p = self._run_pass(frames, labels_teacher, soft_logits=teacher_logits, soft_layout=layout)
         return p.result(p.soft)
+
+    def _logits_layout(self, teacher_logits, batch: int) -> str:
+        """The layout of explicit teacher logits, by their last dimension: TOTAL_CLASSES channels are the full layout, K != TOTAL_CLASSES
+        channels the selected one."""
+        shape = tuple(teacher_logits.shape)
+        assert len(shape) == 4 and shape[0] == batch and shape[-1] in (self.TOTAL_CLASSES, self.class_count), \
+            "teacher_logits must be [%d, th, tw, %d] or, reduced to the network's classes, [%d, th, tw, %d], got %s" \
+            % (batch, self.TOTAL_CLASSES, batch, self.class_count, shape)
+        return "full" if shape[-1] == self.TOTAL_CLASSES else "selected"
+
+    def _memory_layout(self, memory) -> str:
+        """The layout of a DeviceReplayMemory's cached logits; a memory that selected other channels than this network's is refused (the
+        kernels would take channel k for class k of THIS network)."""
+        if memory.logits_select is not None:
+            own = [int(c) for c in self.class_indices_graph]
+            assert list(memory.logits_select) == own, \
+                "the replay memory caches the teacher-logit channels logits_select = %s, this network's class index list is %s" \
+                % (list(memory.logits_select), own)
+        return memory.logits_layout
 
     def predict_soft_probabilities(self, frames, teacher_logits):
         """The per-pixel values behind ``predict_with_soft_metric``: (f32 ndarray [B,H,W,K] = the teacher's distribution over the selected
         classes, ``filtered_teacher_labels_probs``; f32 ndarray [B,H,W] = the pixel's soft cross-entropy against the student)."""
-        assert teacher_logits.shape[0] == len(frames) and teacher_logits.shape[-1] == self.TOTAL_CLASSES
+        layout = self._logits_layout(teacher_logits, len(frames))
         with self.process_lock:
             self._pipeline.drain()
             self.engine.predict_frames(frames, None, self._mode(), u8=True)
-            _rows, p, ce = self.engine.soft_metric(None, None, teacher_logits, want_maps=True)
+            _rows, p, ce = self.engine.soft_metric(None, None, teacher_logits, want_maps=True, layout=layout)
             return p.cpu().numpy(), ce.cpu().numpy()
 
     def evaluate_memory(self, memory, slots=None):
@@ -425,6 +444,7 @@ class SemanticNetwork(object):
         if memory.logits_shape is None:
             raise ValueError("evaluate_memory needs the teacher logits: construct the DeviceReplayMemory with logits_shape")
         eng = self.engine
+        layout = self._memory_layout(memory)
         assert (memory.src_h, memory.src_w) == (eng.height, eng.width), "the memory's frames must be [%d, %d]" % (eng.height, eng.width)
         slots = np.arange(len(memory), dtype=np.int64) if slots is None else np.asarray(slots, dtype=np.int64).reshape(-1)
         assert slots.size > 0, "no slot to evaluate"
@@ -434,7 +454,7 @@ class SemanticNetwork(object):
         with self.process_lock:
             for first in range(0, slots.size, eng.max_batch):
                 frames, labels, logits = memory.plan(table[None, first:first + eng.max_batch], eng.height, eng.width).batch(0)
-                p = self._run_pass(frames, labels, soft_logits=logits)
+                p = self._run_pass(frames, labels, soft_logits=logits, soft_layout=layout)
                 rows.append(p.soft.row)
                 conf += p.metrics[0].astype(np.int64)
         return SoftMetric.sum(rows), conf.astype(np.float64)
@@ -475,7 +495,8 @@ class SemanticNetwork(object):
                          keep_mask=False, teacher_logits_deque=None):
         """``teacher_logits_deque`` (soft_teacher=True only; the reference's _train never feeds teacher_labels_logits_pl, so its soft graph cannot
         run through this method at all): the cached teacher logits of the replay memory, one f32 [th, tw, TOTAL_CLASSES] array per frame of
-        ``frame_deque``; a mini-batch takes the logits of the frames it drew.
+        ``frame_deque`` (or [th, tw, K]: the network's classes alone, in the order of its class index list, uploaded as they are); a
+        mini-batch takes the logits of the frames it drew.
 
         ``frame_deque`` may be an ``ams_amd.replay.DeviceReplayMemory`` (``label_deque`` and ``teacher_logits_deque`` are then None; with
         ``soft_teacher=True`` the logits come from the memory: cached at the frame size they are rescaled, cropped and flipped with the frames,
@@ -521,15 +542,18 @@ class SemanticNetwork(object):
     def train_step(self, frames, labels_teacher, train_strategy='full_model', teacher_logits=None):
         """North-star alias: ONE optimisation step on an explicit batch; returns the loss (float).  With ``soft_teacher=True`` the cached teacher
         logits of the batch are fed as ``teacher_logits`` f32 [B, th, tw, TOTAL_CLASSES] — what a caller of the reference puts into
-        ``feed_dict[student['teacher_labels_logits_pl']]`` (th x tw = the label size, or a smaller cached grid: include/ams_hip.h)."""
+        ``feed_dict[student['teacher_labels_logits_pl']]`` (th x tw = the label size, or a smaller cached grid: include/ams_hip.h) — or as
+        [B, th, tw, K], the network's classes alone (the selected layout: the same loss and update, bit for bit)."""
         assert not self.frozen, "Can't train frozen graph!!!"
         assert (teacher_logits is not None) == self.soft_teacher, "teacher_logits go with soft_teacher=True (and are required then)"
+        layout = self._logits_layout(teacher_logits, len(frames)) if teacher_logits is not None else None
         with self.process_lock:
             mask_dev = None
             if 'coord_desc_' in train_strategy:
                 _before, train_mask_ = self.get_train_mask(train_strategy)
                 mask_dev = self._mask_to_device(train_mask_)
-            ls = self.engine.train_step(frames, labels_teacher, self.lr, mask_dev, teacher_logits=teacher_logits).cpu().numpy()
+            ls = self.engine.train_step(frames, labels_teacher, self.lr, mask_dev, teacher_logits=teacher_logits,
+                                        teacher_logits_layout=layout).cpu().numpy()
         return float(ls[0] / ls[1]) if ls[1] > 0 else float("nan")
 
     def _mask_to_device(self, train_mask_: Dict[str, np.ndarray]) -> torch.Tensor:
@@ -539,8 +563,9 @@ class SemanticNetwork(object):
 
     def _train(self, source, num_of_iterations, train_strategy):
         """``source``: a DeviceReplayMemory, or a started HostBatchFeed."""
-        plan = feed = None
+        plan = feed = logits_layout = None                          # (no layout named: the engine tells it by the last dimension)
         if isinstance(source, DeviceReplayMemory):
+            logits_layout = self._memory_layout(source)
             plan = self._replay_plan(source, num_of_iterations)        # the phase's draws, before get_train_mask; no helper thread
         else:
             feed = source
@@ -564,7 +589,10 @@ class SemanticNetwork(object):
                 frames_dev, labels_dev, logits_dev = plan.batch(it)       # one launch on this stream into the resident batch buffer
             else:
                 frames_dev, labels_dev, logits_dev = feed.consume(staged)
-            if logits_dev is not None:
+            if logits_dev is not None and logits_layout == "selected":
+                loss_dev = self.engine.train_step(frames_dev, labels_dev, self.lr, mask_dev, teacher_logits=logits_dev,
+                                                  teacher_logits_layout=logits_layout)
+            elif logits_dev is not None:
                 loss_dev = self.engine.train_step(frames_dev, labels_dev, self.lr, mask_dev, teacher_logits=logits_dev)
             else:
                 loss_dev = self.engine.train_step(frames_dev, labels_dev, self.lr, mask_dev)

@@ -177,6 +177,10 @@ int ams_student_confidence(ams_student* s, int32_t batch, const uint8_t* teacher
  * the feed armed by ams_student_feed_teacher_logits.  batch outside 1..max_batch: AMS_E_INVALID, nothing written. */
 int ams_student_soft_metric(ams_student* s, int32_t batch, const uint8_t* teacher_dev, const float* teacher_logits_dev, int32_t th, int32_t tw,
                             int64_t* stats, float* p_f32, float* ce_f32, void* stream);
+/* The same for teacher logits in either layout (AMS_TLOGITS_*, below; utils/graph_utils.py:359, 375-376): AMS_TLOGITS_SELECTED reads
+ * teacher_logits_dev as f32 [batch,th,tw,n_selected].  A layout other than the two: AMS_E_INVALID, nothing launched, nothing written. */
+int ams_student_soft_metric_layout(ams_student* s, int32_t batch, const uint8_t* teacher_dev, const float* teacher_logits_dev, int32_t th, int32_t tw,
+                                   int64_t* stats, float* p_f32, float* ce_f32, void* stream, int32_t layout);
 
 int ams_cross_confusion(const ams_student* s, const uint8_t* labels_dev, int64_t n_pixels, int64_t* conf_mat_dev,
                         void* stream);
@@ -212,6 +216,17 @@ int ams_student_f16_fallback_layers(const ams_student* s, int32_t* n_layers);
  * NULL switches the term off); n_vars = len(tvars).  The gradient term (coef / n_vars) v is added after the cross-rank gradient sum of a
  * data-parallel step, the loss term to loss_dev[0] scaled by the valid-pixel count, so that loss_dev[0] / loss_dev[1] is the fetched loss. */
 int ams_student_feed_teacher_logits(ams_student* s, const float* teacher_logits_dev, int32_t th, int32_t tw);
+
+/* Layouts of teacher logits (the feed of teacher_labels_logits_pl, utils/graph_utils.py:359; the loss reads gather(teacher logits,
+ * class_weights) alone, :375-376).  AMS_TLOGITS_FULL: f32 [..., num_classes], what the reference feeds.  AMS_TLOGITS_SELECTED: f32 [..., K],
+ * channel k holding what the full layout holds at class_indices[k] — the gather done once, when a frame enters the replay memory
+ * (ams_replay_pack_logits), instead of per pixel and step.  Every kernel that reads teacher logits runs the same instantiation on either
+ * layout, so the results are equal bit for bit.  The entries without _layout take AMS_TLOGITS_FULL. */
+enum { AMS_TLOGITS_FULL = 0, AMS_TLOGITS_SELECTED = 1 };
+
+/* ams_student_feed_teacher_logits with the layout named (utils/graph_utils.py:359, 375-376): AMS_TLOGITS_SELECTED feeds f32 [batch, th, tw,
+ * n_selected] in the order of the student's class_indices.  A layout other than the two: AMS_E_INVALID, the armed feed stays as it was. */
+int ams_student_feed_teacher_logits_layout(ams_student* s, const float* teacher_logits_dev, int32_t th, int32_t tw, int32_t layout);
 int ams_student_set_regularizer(ams_student* s, const uint8_t* reg_mask_dev, int32_t n_vars, float coef);
 
 /* ---- data-parallel split of the same step (one process per GPU) -------------------------
@@ -494,10 +509,22 @@ int ams_replay_gather_f32(const float* slots_dev, int64_t slot_stride, int32_t c
  *
  * The descriptors are checked as by ams_replay_gather, on the host before the launch (AMS_E_INVALID, nothing launched) and again in the
  * kernel.  16-byte aligned bases, slot_stride, src_w * channels and W * channels multiples of 4 let the unmirrored copy case with
- * left * channels a multiple of 4 move 16 bytes per lane.  One launch (replay_gather_logits_kernel); no allocation, no synchronisation. */
+ * left * channels a multiple of 4 move 16 bytes per lane; with channels a multiple of 4 (slots in the selected layout, K = 4, 8, ...) that
+ * holds for every left, and the mirrored copy moves 16 bytes per lane too.  One launch (replay_gather_logits_kernel); no allocation, no synchronisation. */
 int ams_replay_gather_logits(const float* slots_dev, int64_t slot_stride, int32_t capacity, int32_t src_h, int32_t src_w, int32_t channels,
                              const ams_replay_sample* samples_dev, const ams_replay_sample* samples_host, int32_t batch, int32_t H, int32_t W,
                              float* out_dev, void* stream);
+
+/* A frame's teacher logits into a replay slot (the append of logits that are already on the device; the reference keeps what it feeds to
+ * teacher_labels_logits_pl on the host, utils/graph_utils.py:359, and its loss reads the class_weights channels alone, :375-376):
+ * logits_dev f32 [th, tw, num_classes] -> slot_dev.  AMS_TLOGITS_SELECTED writes f32 [th, tw, K], channel k = input channel
+ * class_idx_host[k] (a HOST array, checked here, passed by value): copies, every bit pattern survives.  AMS_TLOGITS_FULL copies the input
+ * as it is (class_idx_host and K are not read).  One launch (replay_pack_logits_kernel: a block stages a run of pixels of one row in LDS;
+ * 16-byte loads when logits_dev is 16-byte aligned and tw * num_classes a multiple of 4, 16-byte stores when slot_dev is and tw * K is).
+ * AMS_E_INVALID, nothing launched, nothing written: a layout other than the two, a NULL pointer, K outside 1..32, an index outside
+ * 0..num_classes - 1, num_classes > 256, th > 65535. */
+int ams_replay_pack_logits(const float* logits_dev, int32_t th, int32_t tw, int32_t num_classes, const int32_t* class_idx_host, int32_t K,
+                           int32_t layout, float* slot_dev, void* stream);
 
 /* The phi-score confusion matrices of n_pairs pairs of label slots at once (replaces the loop of run.py:287-291 over calc_cross_miou,
  * SemanticNetwork.py:124-139: one upload and one synchronising read per pair): pair i is (pairs[2i], pairs[2i + 1]) = (before, after)
@@ -701,6 +728,13 @@ int ams_k_upsample_soft_metric(const float* logits /*[B,h,w,NC]*/, int32_t B, in
                                const int32_t* class_idx_host, int32_t K, int32_t H, int32_t W, const uint8_t* teacher,
                                const float* teacher_logits /*[B,th,tw,NC]*/, int32_t th, int32_t tw, int64_t* stats, float* p_f32,
                                float* ce_f32, void* stream);
+/* The same for teacher logits in either layout (AMS_TLOGITS_*; utils/graph_utils.py:359, 375-376): AMS_TLOGITS_SELECTED reads teacher_logits as
+ * f32 [B,th,tw,K], channel k = class class_idx_host[k].  ld >= NC: the row stride of `logits` (the engine's logits block has 32).  Also
+ * AMS_E_INVALID, nothing launched, nothing written: a layout other than the two, class_idx_host == NULL. */
+int ams_k_upsample_soft_metric_layout(const float* logits /*[B,h,w,ld]*/, int32_t B, int32_t h, int32_t w, int32_t ld, int32_t NC,
+                                      const int32_t* class_idx_host, int32_t K, int32_t H, int32_t W, const uint8_t* teacher,
+                                      const float* teacher_logits, int32_t th, int32_t tw, int32_t layout, int64_t* stats, float* p_f32,
+                                      float* ce_f32, void* stream);
 size_t ams_soft_metric_stats_len(int32_t K);    /* 2 + 2 K K; 0 for K outside 1..32 */
 
 /* K11 backward: d loss / d low-res logits (zeros for unselected classes); loss_and_count_dev: the double[2]
@@ -723,6 +757,13 @@ size_t ams_k_ce_loss_grad_scratch(int32_t B, int32_t h, int32_t w, int32_t K);
 int ams_k_ce_loss_grad_soft(const float* logits, int32_t B, int32_t h, int32_t w, int32_t NC, const int32_t* class_idx_host,
                             int32_t K, int32_t H, int32_t W, const uint8_t* teacher, const float* teacher_logits, int32_t th, int32_t tw,
                             double* loss_dev, float* dlogits, float* scratch, size_t scratch_floats, void* stream);
+/* The same for teacher logits in either layout (AMS_TLOGITS_*; utils/graph_utils.py:359, 375-376): AMS_TLOGITS_SELECTED reads teacher_logits as
+ * f32 [B, th, tw, K], channel k = class class_idx_host[k].  ld (NC <= ld <= 256): the row stride of `logits` and of `dlogits`, whose pad
+ * columns get 0 (the engine's logits block has 32).  AMS_E_INVALID, nothing launched, nothing written: a layout other than the two,
+ * class_idx_host == NULL, K outside 1..32. */
+int ams_k_ce_loss_grad_soft_layout(const float* logits, int32_t B, int32_t h, int32_t w, int32_t ld, int32_t NC, const int32_t* class_idx_host,
+                                   int32_t K, int32_t H, int32_t W, const uint8_t* teacher, const float* teacher_logits, int32_t th, int32_t tw,
+                                   int32_t layout, double* loss_dev, float* dlogits, float* scratch, size_t scratch_floats, void* stream);
 
 /* K13: weight gradient of a 1x1 conv: dw[K,N] = x[M,K]^T @ dy[M,N]. scratch: >= ams_k_pointwise_wgrad_scratch floats */
 int ams_k_pointwise_wgrad(const float* x, const float* dy, int64_t M, int32_t K, int32_t N, float* dw,

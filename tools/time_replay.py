@@ -8,14 +8,18 @@ Host clock around ``train_with_deque`` (which ends with the read-back of the los
   b  soft_teacher with teacher logits at the label size
   c  scale [1, 1.25, 1.5]                         (the host path falls to utils.mini_batch)
   d  soft_teacher, logits at the frame size, scale [1, 1.25, 1.5], flip   (device path only: the host path refuses the combination)
+  e  case d on a memory that caches every class against one that caches the six selected (logits_select), alternating
 
 Both paths start every phase from the same seeds, so they train on the same draws.  The baseline of every ratio is the host path timed in
 the same run.  Case d has no host path to compare against and no threshold: its phase time is recorded next to HIP-event times of the logits
 gather alone (ams_replay_gather_logits, one launch per mini-batch).  Beside them: HIP-event times of the gather launch alone (copy case, bilinear case; stream otherwise idle), and the ASR event
-with 10 label pairs as the loop over calc_cross_miou against one cross_miou_pairs call (host clock).  Writes one JSON (--out) and prints it.
+with 10 label pairs as the loop over calc_cross_miou against one cross_miou_pairs call (host clock).  Case e compares the two logit layouts of
+the same build in the same run, never a number of an earlier run: the phase (host clock), the logits gather alone (HIP events, equal
+descriptors) and one ``append`` of a frame whose logits are a device tensor (HIP events: the copy against the pack kernel) or a NumPy
+array (host clock, synchronised: 19 against 6 channels uploaded).  Writes one JSON (--out) and prints it.
 Cases b and c are slow on the host path (seconds per phase): --reps_b / --reps_c set their own counts, recorded in the JSON.
 
-    python tools/time_replay.py [--cases a,b,c,d,gather,asr] [--reps 50] [--warmup 5] [--out out/time_replay.json]
+    python tools/time_replay.py [--cases a,b,c,d,e,gather,asr] [--reps 50] [--warmup 5] [--out out/time_replay.json]
 """
 import argparse
 import json
@@ -123,6 +127,64 @@ def time_logits_gather(mem, H, scale, flip, batch, reps, warmup):
     return stats(us)
 
 
+def time_layouts(net, mems, H, scale, flip, batch, iters, reps, warmup):
+    """case e: ``mems`` = {"full": memory, "selected": memory} with equal contents; the layouts alternate within every repetition"""
+    dev = net.engine.device
+    st = torch.cuda.current_stream(dev)
+    phase_ms = {k: [] for k in mems}
+    for r in range(warmup + reps):
+        for k, mem in mems.items():
+            seed(100 + r)
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            net.train_with_deque(mem, None, iters, "full_model")
+            torch.cuda.synchronize(dev)
+            if r >= warmup:
+                phase_ms[k].append((time.perf_counter() - t0) * 1e3)
+    seed(7)
+    samples = draw_samples(len(mems["full"]), (H, 2 * H), [H, 2 * H], scale, batch, warmup + reps, flip=flip)
+    plans = {k: mem.plan(samples, H, 2 * H) for k, mem in mems.items()}
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    gather_us = {k: [] for k in mems}
+    for r in range(warmup + reps):
+        for k, mem in mems.items():
+            plan = plans[k]
+            torch.cuda.synchronize(dev)
+            e0.record(st)
+            mem._gather_logits(plan.table_host[r], plan.table_dev[r], plan.logits, (H, 2 * H))
+            e1.record(st)
+            torch.cuda.synchronize(dev)
+            if r >= warmup:
+                gather_us[k].append(e0.elapsed_time(e1) * 1e3)
+    # one append: the frame and the label are device tensors in both forms, so that the window holds the logits' way in
+    f_dev, l_dev, t_dev = (x.clone() for x in mems["full"][0])
+    t_host = t_dev.cpu().numpy()
+    append_dev_us, append_np_ms = {k: [] for k in mems}, {k: [] for k in mems}
+    for r in range(warmup + reps):
+        for k, mem in mems.items():
+            torch.cuda.synchronize(dev)
+            e0.record(st)
+            mem.append(f_dev, l_dev, t_dev)
+            e1.record(st)
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            mem.append(f_dev, l_dev, t_host)
+            torch.cuda.synchronize(dev)
+            if r >= warmup:
+                append_dev_us[k].append(e0.elapsed_time(e1) * 1e3)
+                append_np_ms[k].append((time.perf_counter() - t0) * 1e3)
+    out = {}
+    for k, mem in mems.items():
+        ch = mem.logits_cached_shape[2]
+        out[k] = {"channels": ch, "memory_bytes": mem.nbytes, "slot_bytes": mem.nbytes // mem.capacity,
+                  "logits_bytes_written": batch * H * 2 * H * ch * 4, "device_ms": stats(phase_ms[k]),
+                  "step_ms": float(np.median(phase_ms[k])) / iters, "logits_gather_us": stats(gather_us[k]),
+                  "append_device_tensor_us": stats(append_dev_us[k]), "append_numpy_ms": stats(append_np_ms[k])}
+    for q in ("device_ms", "logits_gather_us", "append_device_tensor_us", "append_numpy_ms"):
+        out["full_over_selected_" + q] = out["full"][q]["median"] / out["selected"][q]["median"]
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--height", type=int, default=512)
@@ -134,7 +196,8 @@ def main():
     ap.add_argument("--reps_b", type=int, default=None)
     ap.add_argument("--reps_c", type=int, default=None)
     ap.add_argument("--reps_d", type=int, default=None)
-    ap.add_argument("--cases", default="a,b,c,d,gather,asr")
+    ap.add_argument("--reps_e", type=int, default=None)
+    ap.add_argument("--cases", default="a,b,c,d,e,gather,asr")
     ap.add_argument("--out", default="out/time_replay.json")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "time_replay needs the GPU"
@@ -180,7 +243,7 @@ def main():
         result["asr_pairs"] = pairs
         result["asr_loop_ms"], result["asr_one_call_ms"] = stats(loop_ms), stats(call_ms)
         result["asr_loop_over_one_call"] = result["asr_loop_ms"]["median"] / result["asr_one_call_ms"]["median"]
-    if "b" in cases or "d" in cases:
+    if "b" in cases or "d" in cases or "e" in cases:
         rng = np.random.default_rng(5)
         tl = [rng.standard_normal((H, 2 * H, 19)).astype(np.float32) for _ in range(a.slots)]
         soft_mem = DeviceReplayMemory(a.slots, H, 2 * H, dev, logits_shape=(H, 2 * H, 19))
@@ -200,9 +263,19 @@ def main():
             "logits_gather_us": time_logits_gather(soft_mem, H, net.scale, True, a.batch, reps_d, a.warmup),
             "logits_bytes_written": a.batch * H * 2 * H * 19 * 4, "memory_bytes": soft_mem.nbytes}
         net.scale, net.flip = [1], False
+    if "e" in cases:
+        sel_mem = DeviceReplayMemory(a.slots, H, 2 * H, dev, logits_shape=(H, 2 * H, 19), logits_select=CI)
+        for f, l, t in zip(frames, labels, tl):
+            sel_mem.append(f, l, t)
+        net.scale, net.flip = [1, 1.25, 1.5], True
+        result["e_logit_layouts"] = time_layouts(net, {"full": soft_mem, "selected": sel_mem}, H, net.scale, True, a.batch, a.iters,
+                                                 a.reps_e or a.reps, a.warmup)
+        result["e_logit_layouts"].update({"scale": net.scale, "flip": True, "class_idx": CI})
+        net.scale, net.flip = [1], False
     result["note"] = ("*_ms: host clock around train_with_deque, stream drained before and after, host path and device path alternating with equal "
                       "seeds; gather_*_us: HIP events around the one launch, stream otherwise idle; asr_*: host clock, results compared; "
-                      "d_*: device path only, logits_gather_us = HIP events around ams_replay_gather_logits alone")
+                      "d_*: device path only, logits_gather_us = HIP events around ams_replay_gather_logits alone; e_*: the full and the "
+                      "selected layout alternating with equal seeds and descriptors, append_* = one append of a frame with its logits")
     net.close_model()
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
