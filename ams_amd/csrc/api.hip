@@ -283,6 +283,13 @@ int ams_replay_gather_logits(const float* slots_dev, int64_t slot_stride, int32_
                                        (hipStream_t)stream);
 }
 
+int ams_replay_gather_logits_lowres(const float* slots_dev, int64_t slot_stride, int32_t capacity, int32_t lh, int32_t lw, int32_t channels, int32_t src_h,
+                                    int32_t src_w, const ams_replay_sample* samples_dev, const ams_replay_sample* samples_host, int32_t batch, int32_t H,
+                                    int32_t W, float* out_dev, void* stream) {
+    return launch_replay_gather_logits_lowres(slots_dev, slot_stride, capacity, lh, lw, channels, src_h, src_w, samples_dev, samples_host, batch, H, W,
+                                              out_dev, (hipStream_t)stream);
+}
+
 int ams_replay_pack_logits(const float* logits_dev, int32_t th, int32_t tw, int32_t num_classes, const int32_t* class_idx_host, int32_t K,
                            int32_t layout, float* slot_dev, void* stream) {
     AMS_REQUIRE(layout == AMS_TLOGITS_FULL || layout == AMS_TLOGITS_SELECTED, "replay_pack_logits: unknown teacher-logit layout %d", layout);

@@ -20,6 +20,17 @@
 //                                 the bases allow it and the sample is not mirrored; with channels a multiple of 4 (a slot that holds the K
 //                                 selected channels, K = 4 or 8) every pixel starts on 16 bytes and the mirrored copy moves 16 bytes per
 //                                 lane too.
+//   replay_gather_logits_lowres_kernel
+//                                 f32 [lh, lw, C] slots (teacher logits cached on a grid no larger than the frame) through the same
+//                                 descriptors: the slot behaves, bit for bit, as a frame-size slot that holds its own align-corners
+//                                 upsample U (the soft loss kernel's: src_tap / bilerp of head_common.hpp, a grid point the cached sample
+//                                 itself), and replay_gather_logits_kernel's rule is applied to U, which is never stored.  Same block
+//                                 shape: the y-side (the rule's two rows of U, and for each the two cached rows and ty) is uniform per
+//                                 block, the x-side (per tap of the rule two element offsets into a cached row and tx, plus wx) goes to
+//                                 LDS once per pixel, then the segment's seg * C floats are walked flat.  Where both rows of U fall
+//                                 between the same two cached rows (15 of 16 output rows for a 33 x 65 cache of 512 x 1024 frames) the
+//                                 x-interpolated pair is formed once and serves both: 8 loads per float instead of 16, the same operations
+//                                 on the same values.  The loads hit L1 / L2 (a 33 x 65 x 19 slot is 163 KB): HBM sees the stores alone, the time is the tap loads'.
 //   replay_pack_logits_kernel     f32 [th, tw, NC] teacher logits -> a slot in the selected layout f32 [th, tw, K], channel k = input channel
 //                                 idx[k]: what append does to logits that are already on the device.  A block owns a run of pixels of one
 //                                 row: the run's run * NC input floats go through LDS with contiguous loads, the run * K output floats
@@ -33,6 +44,7 @@
 #include "kernels.hpp"
 #include "resize_taps.hpp"
 #include "cross_conf.hpp"
+#include "head_common.hpp"
 
 namespace ams {
 
@@ -215,6 +227,124 @@ __global__ __launch_bounds__(256) void replay_gather_logits_kernel(const float* 
     }
 }
 
+struct LowresGeom {
+    int capacity, lh, lw, C, Hs, Ws, H, W;       // slots f32 [lh, lw, C], frames Hs x Ws, crop H x W
+    int64_t slot_stride;                         // f32 elements from one slot to the next
+    float sy, sx;                                // (lh-1)/(Hs-1), (lw-1)/(Ws-1) as f32: soft_teacher_geom's scales for a teacher grid read at Hs x Ws
+};
+
+// U at one point from the four cached samples around it: the soft loss kernel's two branches (k_head.hip), the cached sample itself on a grid point
+__device__ __forceinline__ float upsampled(float tl, float tr, float bl, float br, float tx, float ty) {
+    const float v = bilerp(tl, tr, bl, br, tx, ty);
+    return (tx == 0.f && ty == 0.f) ? tl : v;
+}
+
+__global__ __launch_bounds__(256) void replay_gather_logits_lowres_kernel(const float* __restrict__ slots, const ams_replay_sample* __restrict__ samples,
+                                                                          LowresGeom g, float* __restrict__ out) {
+    // per pixel and tap of the frame-size rule (one tap in the copy case): element offsets of U's two cached columns inside a cached row, tx
+    __shared__ int s_lo[2][kLogitsSeg], s_hi[2][kLogitsSeg];
+    __shared__ float s_tx[2][kLogitsSeg], s_wx[kLogitsSeg];
+    const int b = blockIdx.z, oy = blockIdx.y, x_first = blockIdx.x * kLogitsSeg, t = threadIdx.x;
+    const ams_replay_sample d = samples[b];
+    if (!(d.slot >= 0 && d.slot < g.capacity && d.th > 0 && d.tw > 0 && d.top >= 0 && d.left >= 0 && d.top <= d.th - g.H && d.left <= d.tw - g.W)) return;
+    if (!(g.lh >= 1 && g.lh <= g.Hs && g.lw >= 1 && g.lw <= g.Ws && g.slot_stride >= (int64_t)g.lh * g.lw * g.C)) return;
+    const int seg = g.W - x_first < kLogitsSeg ? g.W - x_first : kLogitsSeg;
+    const int n = seg * g.C;
+    const int64_t pitch = (int64_t)g.lw * g.C;
+    const float* src = slots + (int64_t)d.slot * g.slot_stride;
+    float* dst = out + (((int64_t)b * g.H + oy) * g.W + x_first) * g.C;
+    const int cy = d.top + oy;                                   // the row of the rescaled logits
+    const bool same = d.th == g.Hs && d.tw == g.Ws;              // (every branch on d is uniform over the block)
+
+    // src_tap of a position p <= n_src - 1 of U stays inside the cached axis: p * scale <= (n_in - 1) * (1 + 2^-23) < n_in, so lo <= n_in - 1
+    if (t < seg) {
+        const int x = x_first + t, cx = d.left + (d.flip ? g.W - 1 - x : x);
+        int lo, hi;
+        float tx;
+        if (same) {
+            src_tap(cx, g.sx, g.lw, lo, hi, tx);
+            s_lo[0][t] = lo * g.C; s_hi[0][t] = hi * g.C; s_tx[0][t] = tx;
+        } else {
+            int x0, x1;
+            float wx;
+            linear_tap(cx, g.Ws, d.tw, x0, x1, wx);
+            src_tap(x0, g.sx, g.lw, lo, hi, tx);
+            s_lo[0][t] = lo * g.C; s_hi[0][t] = hi * g.C; s_tx[0][t] = tx;
+            src_tap(x1, g.sx, g.lw, lo, hi, tx);
+            s_lo[1][t] = lo * g.C; s_hi[1][t] = hi * g.C; s_tx[1][t] = tx;
+            s_wx[t] = wx;
+        }
+    }
+    __syncthreads();
+
+    // flat over the segment's floats: element i is channel c of pixel p; i advances by the block size without a division
+    int p = t / g.C, c = t - p * g.C;
+    const int dp = 256 / g.C, dc = 256 - dp * g.C;
+    if (same) {                                                  // U's window itself, mirrored when flip
+        int l0, h0;
+        float ty;
+        src_tap(cy, g.sy, g.lh, l0, h0, ty);
+        const float* top = src + l0 * pitch;
+        const float* bot = src + h0 * pitch;
+        for (int i = t; i < n; i += 256) {
+            const int a = s_lo[0][p] + c, e = s_hi[0][p] + c;
+            dst[i] = upsampled(top[a], top[e], bot[a], bot[e], s_tx[0][p], ty);
+            p += dp; c += dc;
+            if (c >= g.C) { c -= g.C; ++p; }
+        }
+        return;
+    }
+    int y0, y1, l0, h0, l1, h1;
+    float wy, ty0, ty1;
+    linear_tap(cy, g.Hs, d.th, y0, y1, wy);
+    src_tap(y0, g.sy, g.lh, l0, h0, ty0);
+    src_tap(y1, g.sy, g.lh, l1, h1, ty1);
+    const float my = __fsub_rn(1.f, wy);
+    const float* top0 = src + l0 * pitch;
+    const float* bot0 = src + h0 * pitch;
+    if (l0 == l1 && h0 == h1) {                                  // both rows of U between the same two cached rows: one x-interpolated pair
+        for (int i = t; i < n; i += 256) {
+            float ua[2], ub[2];
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const int a = s_lo[k][p] + c, e = s_hi[k][p] + c;
+                const float tx = s_tx[k][p], tl = top0[a], bl = bot0[a];
+                const float tp = __fadd_rn(tl, __fmul_rn(__fsub_rn(top0[e], tl), tx));          // bilerp's top and bot
+                const float bt = __fadd_rn(bl, __fmul_rn(__fsub_rn(bot0[e], bl), tx));
+                const float df = __fsub_rn(bt, tp);
+                const float va = __fadd_rn(tp, __fmul_rn(df, ty0)), vb = __fadd_rn(tp, __fmul_rn(df, ty1));
+                ua[k] = (tx == 0.f && ty0 == 0.f) ? tl : va;
+                ub[k] = (tx == 0.f && ty1 == 0.f) ? tl : vb;
+            }
+            const float wx = s_wx[p], mx = __fsub_rn(1.f, wx);
+            const float r0 = __fadd_rn(__fmul_rn(ua[0], mx), __fmul_rn(ua[1], wx));
+            const float r1 = __fadd_rn(__fmul_rn(ub[0], mx), __fmul_rn(ub[1], wx));
+            dst[i] = __fadd_rn(__fmul_rn(r0, my), __fmul_rn(r1, wy));
+            p += dp; c += dc;
+            if (c >= g.C) { c -= g.C; ++p; }
+        }
+        return;
+    }
+    const float* top1 = src + l1 * pitch;
+    const float* bot1 = src + h1 * pitch;
+    for (int i = t; i < n; i += 256) {
+        float ua[2], ub[2];
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int a = s_lo[k][p] + c, e = s_hi[k][p] + c;
+            const float tx = s_tx[k][p];
+            ua[k] = upsampled(top0[a], top0[e], bot0[a], bot0[e], tx, ty0);
+            ub[k] = upsampled(top1[a], top1[e], bot1[a], bot1[e], tx, ty1);
+        }
+        const float wx = s_wx[p], mx = __fsub_rn(1.f, wx);
+        const float r0 = __fadd_rn(__fmul_rn(ua[0], mx), __fmul_rn(ua[1], wx));
+        const float r1 = __fadd_rn(__fmul_rn(ub[0], mx), __fmul_rn(ub[1], wx));
+        dst[i] = __fadd_rn(__fmul_rn(r0, my), __fmul_rn(r1, wy));
+        p += dp; c += dc;
+        if (c >= g.C) { c -= g.C; ++p; }
+    }
+}
+
 constexpr int kPackFloats = 4096;               // input floats of a run in LDS (16 KB)
 constexpr int kPackRun = 128;                   // pixels per block at most; fewer when NC > 32
 
@@ -347,6 +477,35 @@ int launch_replay_gather_logits(const float* slots, int64_t slot_stride, int cap
     g.vec = ((int64_t)Ws * C) % 4 == 0 && ((int64_t)W * C) % 4 == 0 && slot_stride % 4 == 0 && aligned16(slots) && aligned16(out);
     note_kernel("replay_gather_logits_kernel");
     hipLaunchKernelGGL(replay_gather_logits_kernel, dim3(cdiv(W, kLogitsSeg), H, B), dim3(256), 0, st, slots, samples_dev, g, out);
+    AMS_CHECK_LAUNCH();
+    return AMS_OK;
+}
+
+int launch_replay_gather_logits_lowres(const float* slots, int64_t slot_stride, int capacity, int lh, int lw, int C, int Hs, int Ws,
+                                       const ams_replay_sample* samples_dev, const ams_replay_sample* samples_host, int B, int H, int W, float* out,
+                                       hipStream_t st) {
+    AMS_REQUIRE(slots && samples_dev && samples_host && out, "replay_gather_logits_lowres: null pointer");
+    AMS_REQUIRE(capacity > 0 && Hs > 0 && Ws > 0 && C > 0 && H > 0 && W > 0 && B > 0 && B <= 65535 && H <= 65535 && (int64_t)Ws * C <= INT32_MAX &&
+                    (int64_t)W * C <= INT32_MAX,
+                "replay_gather_logits_lowres: bad geometry %dx%dx%d -> %d x %dx%d, %d slots", Hs, Ws, C, B, H, W, capacity);
+    AMS_REQUIRE(lh >= 1 && lh <= Hs && lw >= 1 && lw <= Ws, "replay_gather_logits_lowres: a %dx%d cache for %dx%d frames (1 <= lh <= src_h, 1 <= lw <= src_w)", lh,
+                lw, Hs, Ws);
+    AMS_REQUIRE(slot_stride >= (int64_t)lh * lw * C, "replay_gather_logits_lowres: slot stride %lld below a %dx%dx%d slot", (long long)slot_stride, lh, lw, C);
+    for (int b = 0; b < B; ++b) {
+        const ams_replay_sample& d = samples_host[b];
+        AMS_REQUIRE(d.slot >= 0 && d.slot < capacity, "replay_gather_logits_lowres: sample %d draws slot %d of %d", b, d.slot, capacity);
+        AMS_REQUIRE(d.th > 0 && d.tw > 0 && d.th - H >= 0 && d.tw - W >= 0,
+                    "replay_gather_logits_lowres: sample %d: a %dx%d crop of a %dx%d image (negative slack)", b, H, W, d.th, d.tw);
+        AMS_REQUIRE(d.top >= 0 && d.left >= 0 && d.top <= d.th - H && d.left <= d.tw - W,
+                    "replay_gather_logits_lowres: sample %d: crop origin (%d, %d) outside %dx%d", b, d.top, d.left, d.th, d.tw);
+    }
+    LowresGeom g;
+    g.capacity = capacity; g.lh = lh; g.lw = lw; g.C = C; g.Hs = Hs; g.Ws = Ws; g.H = H; g.W = W;
+    g.slot_stride = slot_stride;
+    g.sy = Hs > 1 ? (float)(lh - 1) / (float)(Hs - 1) : 0.f;          // as soft_teacher_geom does for a teacher grid under Hs x Ws labels
+    g.sx = Ws > 1 ? (float)(lw - 1) / (float)(Ws - 1) : 0.f;
+    note_kernel("replay_gather_logits_lowres_kernel");
+    hipLaunchKernelGGL(replay_gather_logits_lowres_kernel, dim3(cdiv(W, kLogitsSeg), H, B), dim3(256), 0, st, slots, samples_dev, g, out);
     AMS_CHECK_LAUNCH();
     return AMS_OK;
 }

@@ -415,6 +415,10 @@ int launch_replay_gather_rows(const float* slots, int64_t slot_stride, int capac
                               const ams_replay_sample* samples_host, int B, float* out, hipStream_t st);
 int launch_replay_gather_logits(const float* slots, int64_t slot_stride, int capacity, int Hs, int Ws, int C, const ams_replay_sample* samples_dev,
                                 const ams_replay_sample* samples_host, int B, int H, int W, float* out, hipStream_t st);
+// slots f32 [lh][lw][C] with lh <= Hs, lw <= Ws: launch_replay_gather_logits' rule applied to the slot's align-corners upsample to Hs x Ws
+int launch_replay_gather_logits_lowres(const float* slots, int64_t slot_stride, int capacity, int lh, int lw, int C, int Hs, int Ws,
+                                       const ams_replay_sample* samples_dev, const ams_replay_sample* samples_host, int B, int H, int W, float* out,
+                                       hipStream_t st);
 // in f32 [th][tw][NC] -> out f32 [th][tw][K], out channel k = in channel idx_host[k] (the selected layout of a replay slot); idx_host: HOST pointer
 int launch_replay_pack_logits(const float* in, int th, int tw, int NC, const int32_t* idx_host, int K, float* out, hipStream_t st);
 int launch_cross_confusion_pairs(const uint8_t* label_slots, int64_t label_stride, int capacity, int64_t n, const int32_t* pairs_dev,

@@ -10,7 +10,9 @@ The random numbers are the host generators', drawn in ``mini_batch``'s order (``
 depend on where the memory lives.  What the draws select is built by one launch per mini-batch (``ams_replay_gather``, k_replay.hip), bit for
 bit what ``mini_batch`` returns for them: the crop of the rescaled frame (cv2.resize's 8-bit INTER_LINEAR; INTER_NEAREST for the label),
 mirrored when flipped.  Teacher logits cached at the frame size follow the frame through the same descriptors (``ams_replay_gather_logits``:
-this project's rule, include/ams_hip.h; the reference never resamples logits); logits cached on a smaller grid follow whole frames only.
+this project's rule, include/ams_hip.h; the reference never resamples logits); logits cached on a smaller grid follow whole frames only,
+unless the memory is constructed with ``logits_upsample=True``: then a slot behaves, bit for bit, as a frame-size slot holding its own
+align-corners upsample (the soft loss kernel's), evaluated inside the gather (``ams_replay_gather_logits_lowres``) and never stored.
 One source geometry per memory (the frames of one video have one size); the host deques stay the answer for mixed
 sizes.  ``logits_select=class_idx`` caches only the student's K channels of every frame's logits (the selected layout, AMS_TLOGITS_SELECTED:
 the loss gathers exactly those, so nothing is lost and every result keeps its bits; K / classes of the memory, the upload and the gather
@@ -31,7 +33,10 @@ from .utils import calculate_miou
 SAMPLE_FIELDS = 6            # ams_replay_sample: slot, th, tw, top, left, flip (int32 each)
 SLOT_ALIGN = 256             # slots start at multiples of this many bytes: every 16-byte access of the copy case is aligned
 LOW_RES_LOGITS = ("a low-resolution teacher-logit cache (%dx%d logits for %dx%d frames) follows whole frames only: scale == [1], frames at the "
-                  "network size, no flip; cache the logits at the frame size to rescale, crop or flip them with the frames")
+                  "network size, no flip; cache the logits at the frame size to rescale, crop or flip them with the frames, or construct the "
+                  "memory with logits_upsample=True (the cached grid then stands for its align-corners upsample to the frame size)")
+LARGE_LOGITS = ("logits_upsample=True needs a teacher-logit grid no larger than the frame on either axis: %dx%d logits for %dx%d frames would be "
+                "down-sampled, and only the align-corners upsample (the soft loss kernel's) is defined")
 
 
 def draw_samples(n_mem: int, src_hw: Sequence[int], crop: Sequence[int], scale: Sequence[float], batch: int, iters: int,
@@ -128,9 +133,10 @@ class ReplayPlan:
         self.iters, self.batch_size = int(table_host.shape[0]), int(table_host.shape[1])
         self.table_dev = memory._upload(table_host)
         # whole frames: every draw takes a frame of the crop's size as it is.  Only then may the logits live on another grid than the frame's
-        # (they are copied slot by slot, the path and the bits of a scale == [1] phase); otherwise they are resampled with the frame
+        # (they are copied slot by slot, the path and the bits of a scale == [1] phase); otherwise they are resampled with the frame (a smaller
+        # grid only on a memory with logits_upsample)
         self.whole_frames = (memory.src_h, memory.src_w) == (H, W) and bool((table_host[..., 1:] == (H, W, 0, 0, 0)).all())
-        assert memory.logits_shape is None or self.whole_frames or memory.logits_at_source, \
+        assert memory.logits_shape is None or self.whole_frames or memory.logits_follow_frames, \
             LOW_RES_LOGITS % (memory.logits_shape[:2] + (memory.src_h, memory.src_w))
         self.frames, self.labels, self.logits = memory._batch_buffers(self.batch_size, H, W, self.whole_frames)
 
@@ -144,10 +150,11 @@ class ReplayPlan:
 
 class DeviceReplayMemory:
     def __init__(self, capacity: int, src_h: int, src_w: int, device, logits_shape: Optional[Sequence[int]] = None,
-                 max_bytes: Optional[int] = None, logits_select: Optional[Sequence[int]] = None):
+                 max_bytes: Optional[int] = None, logits_select: Optional[Sequence[int]] = None, logits_upsample: bool = False):
         """``capacity`` slots of uint8 [src_h, src_w, 3] frames and uint8 [src_h, src_w] labels, with ``logits_shape`` = (th, tw, classes) also
         f32 teacher logits per slot (soft_teacher; (src_h, src_w, classes) lets them follow rescale, crop and flip, a smaller grid follows
-        whole frames only).  ``logits_select`` = the student's class index list: a slot keeps those K channels alone, in that order
+        whole frames only, or with ``logits_upsample=True`` every descriptor too: the grid, no larger than the frame on either axis, then stands
+        for its align-corners upsample to the frame size, formed inside the gather).  ``logits_select`` = the student's class index list: a slot keeps those K channels alone, in that order
         (``logits_cached_shape`` = (th, tw, K), ``logits_layout`` = "selected"); ``logits_shape`` stays what ``append`` is fed.  The bytes
         wanted are computed up front (``nbytes``; at 512x1024: 2 MB per slot, 42 MB with full-size logits of 19 classes, 14.6 MB with six
         selected) and ``MemoryError`` is raised above ``max_bytes`` before anything is allocated."""
@@ -157,6 +164,11 @@ class DeviceReplayMemory:
         self.device = torch.device(device)
         self.logits_shape = tuple(int(d) for d in logits_shape) if logits_shape is not None else None
         assert self.logits_shape is None or len(self.logits_shape) == 3, "logits_shape is (th, tw, classes)"
+        self.logits_upsample = bool(logits_upsample)
+        if self.logits_upsample:
+            assert self.logits_shape is not None, "logits_upsample goes with logits_shape"
+            assert 1 <= self.logits_shape[0] <= self.src_h and 1 <= self.logits_shape[1] <= self.src_w, \
+                LARGE_LOGITS % (self.logits_shape[:2] + (self.src_h, self.src_w))
         self.frame_stride = _round_up(self.src_h * self.src_w * 3, SLOT_ALIGN)          # bytes
         self.label_stride = _round_up(self.src_h * self.src_w, SLOT_ALIGN)
         self.logits_select = tuple(int(c) for c in logits_select) if logits_select is not None else None
@@ -185,6 +197,12 @@ class DeviceReplayMemory:
     def logits_at_source(self) -> bool:
         """The teacher logits are cached at the frames' size: they can follow a frame through rescale, crop and flip."""
         return self.logits_shape is not None and self.logits_shape[:2] == (self.src_h, self.src_w)
+
+    @property
+    def logits_follow_frames(self) -> bool:
+        """The teacher logits can follow a frame through rescale, crop and flip: cached at the frames' size, or on a smaller grid that stands
+        for its upsample (``logits_upsample``)."""
+        return self.logits_at_source or (self.logits_shape is not None and self.logits_upsample)
 
     # ------------------------------------------------------------------ deque(maxlen=capacity) surface
     def __len__(self) -> int:
@@ -293,12 +311,20 @@ class DeviceReplayMemory:
                                               C.c_void_p(labels_out.data_ptr()), self._stream()), "ams_replay_gather")
 
     def _gather_logits(self, samples_host: np.ndarray, samples_dev: torch.Tensor, out: torch.Tensor, crop=None) -> None:
-        """``crop`` None: whole slots on their cached grid.  ``crop`` = (H, W): source-size logits rescaled, cropped and mirrored with the frame."""
+        """``crop`` None: whole slots on their cached grid.  ``crop`` = (H, W): source-size logits rescaled, cropped and mirrored with the frame;
+        on a ``logits_upsample`` memory with a smaller grid, the grid's align-corners upsample to the source size takes their place."""
         th, tw, ch = self.logits_cached_shape
         batch = int(samples_host.shape[0])
         assert samples_host.dtype == np.int32 and samples_host.flags.c_contiguous and samples_dev.is_contiguous()
+        if crop is not None and not self.logits_at_source:
+            assert self.logits_upsample and out.numel() == batch * crop[0] * crop[1] * ch
+            hip.check(hip.lib().ams_replay_gather_logits_lowres(C.c_void_p(self._logits.data_ptr()), self.logits_stride, self.capacity, th, tw, ch,
+                                                                self.src_h, self.src_w, C.c_void_p(samples_dev.data_ptr()),
+                                                                samples_host.ctypes.data_as(C.c_void_p), batch, crop[0], crop[1],
+                                                                C.c_void_p(out.data_ptr()), self._stream()), "ams_replay_gather_logits_lowres")
+            return
         if crop is not None:
-            assert self.logits_at_source and out.numel() == batch * crop[0] * crop[1] * ch
+            assert out.numel() == batch * crop[0] * crop[1] * ch
             hip.check(hip.lib().ams_replay_gather_logits(C.c_void_p(self._logits.data_ptr()), self.logits_stride, self.capacity, self.src_h, self.src_w,
                                                          ch, C.c_void_p(samples_dev.data_ptr()), samples_host.ctypes.data_as(C.c_void_p), batch,
                                                          crop[0], crop[1], C.c_void_p(out.data_ptr()), self._stream()), "ams_replay_gather_logits")
@@ -316,8 +342,9 @@ class DeviceReplayMemory:
         return frames.clone(), labels.clone()
 
     def gather_logits(self, samples: np.ndarray, H: int, W: int) -> torch.Tensor:
-        """The teacher logits of that mini-batch: a fresh f32 device tensor, [batch, H, W, channels] for logits cached at the frame size
-        (rescaled, cropped and mirrored with the frames), the cached grid for whole frames; channels = ``logits_cached_shape[2]``."""
+        """The teacher logits of that mini-batch: a fresh f32 device tensor, [batch, H, W, channels] for logits cached at the frame size or,
+        with ``logits_upsample``, on a smaller grid (rescaled, cropped and mirrored with the frames), the cached grid for whole frames;
+        channels = ``logits_cached_shape[2]``."""
         assert self.logits_shape is not None, "the memory was constructed without logits_shape"
         return self.plan(np.asarray(samples)[None], H, W).batch(0)[2].clone()
 

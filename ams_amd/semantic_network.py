@@ -665,9 +665,10 @@ class SemanticNetwork(object):
         """A phase on a DeviceReplayMemory: mini_batch's draws for every iteration, on the calling thread, uploaded once."""
         crop = [self.height, self.height * 2]
         # soft targets follow the frames a batch drew: logits cached at the frame size through rescale, crop and flip (ams_replay_gather_logits),
-        # logits cached on a smaller grid only where frames are taken as they are (composing the two resamplings is not defined)
+        # logits cached on a smaller grid only where frames are taken as they are, unless the memory was built with logits_upsample: its grid
+        # then stands for its align-corners upsample to the frame size (ams_replay_gather_logits_lowres)
         whole_frames = list(self.scale) == [1] and (memory.src_h, memory.src_w) == tuple(crop) and not self.flip
-        assert memory.logits_shape is None or whole_frames or memory.logits_at_source, \
+        assert memory.logits_shape is None or whole_frames or memory.logits_follow_frames, \
             LOW_RES_LOGITS % (memory.logits_shape[:2] + (memory.src_h, memory.src_w))
         samples = draw_samples(len(memory), (memory.src_h, memory.src_w), crop, self.scale, self.mini_batch_size, num_of_iterations,
                                flip=self.flip)

@@ -484,8 +484,8 @@ int ams_replay_gather(const uint8_t* frame_slots_dev, int64_t frame_slot_stride,
 /* The cached teacher logits of the frames a batch drew (replaces the np.stack + pin_memory + upload of the soft-teacher batch; the reference
  * feeds teacher_labels_logits_pl per batch, utils/graph_utils.py:359): slot p is f32 [th, tw, channels] at slots_dev + p * slot_stride
  * (stride in elements), out_dev f32 [batch, th, tw, channels].  Whole slots only: a descriptor with a crop origin or a flip is refused
- * (logits cached on a grid smaller than the frame follow whole frames only; ams_replay_gather_logits rescales, crops and mirrors logits
- * cached at the frame size).  One launch (replay_gather_rows_kernel); no allocation, no synchronisation. */
+ * (ams_replay_gather_logits rescales, crops and mirrors logits cached at the frame size, ams_replay_gather_logits_lowres logits cached on
+ * a smaller grid).  One launch (replay_gather_rows_kernel); no allocation, no synchronisation. */
 int ams_replay_gather_f32(const float* slots_dev, int64_t slot_stride, int32_t capacity, int32_t th, int32_t tw, int32_t channels,
                           const ams_replay_sample* samples_dev, const ams_replay_sample* samples_host, int32_t batch, float* out_dev, void* stream);
 
@@ -504,8 +504,8 @@ int ams_replay_gather_f32(const float* slots_dev, int64_t slot_stride, int32_t c
  *     out = r0 * (1 - wy) + r1 * wy
  *
  * th == src_h && tw == src_w (per sample) is a plain copy of the crop window, mirrored when flip: an inf or NaN of a neighbouring pixel
- * does not enter.  An exact 2x down-scale lands on w = 0.5, the 2 x 2 mean.  Logits cached on a smaller grid than the frame are not served
- * (composing the align-corners upsample with this resize is a 16-tap filter): they follow whole frames through ams_replay_gather_f32.
+ * does not enter.  An exact 2x down-scale lands on w = 0.5, the 2 x 2 mean.  Logits cached on a smaller grid than the frame are served by
+ * ams_replay_gather_logits_lowres (this rule applied to their align-corners upsample); whole frames go through ams_replay_gather_f32.
  *
  * The descriptors are checked as by ams_replay_gather, on the host before the launch (AMS_E_INVALID, nothing launched) and again in the
  * kernel.  16-byte aligned bases, slot_stride, src_w * channels and W * channels multiples of 4 let the unmirrored copy case with
@@ -514,6 +514,38 @@ int ams_replay_gather_f32(const float* slots_dev, int64_t slot_stride, int32_t c
 int ams_replay_gather_logits(const float* slots_dev, int64_t slot_stride, int32_t capacity, int32_t src_h, int32_t src_w, int32_t channels,
                              const ams_replay_sample* samples_dev, const ams_replay_sample* samples_host, int32_t batch, int32_t H, int32_t W,
                              float* out_dev, void* stream);
+
+/* The same for teacher logits cached on a grid NO LARGER THAN THE FRAME (e.g. 33 x 65 for 512 x 1024 frames: what a teacher of output stride
+ * 16 produces; 163 KB per slot at 19 classes instead of 40 MB).  Slot p is f32 [lh, lw, channels] at slots_dev + p * slot_stride, 1 <= lh <=
+ * src_h, 1 <= lw <= src_w; channels is every class or the K selected ones; out_dev is f32 [batch, H, W, channels] as above.
+ *
+ * The rule: a low-resolution slot behaves, bit for bit, as a frame-size slot that holds its own align-corners upsample.  Two stages, both
+ * already defined, evaluated in one kernel (the frame-size tensor U is never stored):
+ *
+ *   Stage U, the virtual logits f32 [src_h, src_w, channels], by the arithmetic of the soft loss kernel (what ams_student_feed_teacher_logits
+ *   does to a teacher grid smaller than the labels): sy = src_h > 1 ? (float)(lh - 1) / (float)(src_h - 1) : 0, sx likewise, in f32.  Per axis
+ *   (y shown), in f32: src = (float)Y * sy, lo = floor(src), hi = min(lo + 1, lh - 1), ty = src - floor(src).  On a grid point, ty == 0 &&
+ *   tx == 0, U(Y, X, c) is the cached sample t[lo_y][lo_x][c] itself (the sign of a zero survives).  Otherwise, every operation rounded once:
+ *
+ *       top = tl + (tr - tl) * tx,  bot = bl + (br - bl) * tx,  U(Y, X, c) = top + (bot - top) * ty
+ *
+ *   with tl = t[lo_y][lo_x][c], tr = t[lo_y][hi_x][c], bl = t[hi_y][lo_x][c], br = t[hi_y][hi_x][c].
+ *
+ *   Stage G, the rule of ams_replay_gather_logits applied to U: cy = top + y, cx = left + (flip ? W - 1 - x : x); th == src_h && tw == src_w
+ *   copies U's window; otherwise the taps in double per axis with their two clamps, r0 = U[sy][sx] * (1 - wx) + U[sy][sx1] * wx, r1 likewise
+ *   on row sy1, out = r0 * (1 - wy) + r1 * wy in f32.
+ *
+ * lh == src_h && lw == src_w makes every point a grid point: the result is ams_replay_gather_logits' (that entry's copy case moves 16 bytes
+ * per lane; prefer it there).  A whole-frame batch needs no gather at this size at all: ams_replay_gather_f32 copies the cached grids and the
+ * loss kernel's own upsample gives the bits of U.  The contract is for finite logits: a non-finite cached value spreads to the pixels between
+ * it and its neighbours through the interpolation, as it does in the loss kernel, and no bit pattern is promised for those.
+ *
+ * Checked on the host before the launch (AMS_E_INVALID, nothing launched, nothing written) and again in the kernel: the descriptors as by
+ * ams_replay_gather_logits, 1 <= lh <= src_h, 1 <= lw <= src_w, slot_stride >= lh * lw * channels, no NULL pointer.  One launch
+ * (replay_gather_logits_lowres_kernel); no allocation, no synchronisation. */
+int ams_replay_gather_logits_lowres(const float* slots_dev, int64_t slot_stride, int32_t capacity, int32_t lh, int32_t lw, int32_t channels,
+                                    int32_t src_h, int32_t src_w, const ams_replay_sample* samples_dev, const ams_replay_sample* samples_host,
+                                    int32_t batch, int32_t H, int32_t W, float* out_dev, void* stream);
 
 /* A frame's teacher logits into a replay slot (the append of logits that are already on the device; the reference keeps what it feeds to
  * teacher_labels_logits_pl on the host, utils/graph_utils.py:359, and its loss reads the class_weights channels alone, :375-376):

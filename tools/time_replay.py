@@ -9,6 +9,7 @@ Host clock around ``train_with_deque`` (which ends with the read-back of the los
   c  scale [1, 1.25, 1.5]                         (the host path falls to utils.mini_batch)
   d  soft_teacher, logits at the frame size, scale [1, 1.25, 1.5], flip   (device path only: the host path refuses the combination)
   e  case d on a memory that caches every class against one that caches the six selected (logits_select), alternating
+  f  case d on a memory with logits at the frame size against one with a 33 x 65 cache and logits_upsample, alternating
 
 Both paths start every phase from the same seeds, so they train on the same draws.  The baseline of every ratio is the host path timed in
 the same run.  Case d has no host path to compare against and no threshold: its phase time is recorded next to HIP-event times of the logits
@@ -16,10 +17,12 @@ gather alone (ams_replay_gather_logits, one launch per mini-batch).  Beside them
 with 10 label pairs as the loop over calc_cross_miou against one cross_miou_pairs call (host clock).  Case e compares the two logit layouts of
 the same build in the same run, never a number of an earlier run: the phase (host clock), the logits gather alone (HIP events, equal
 descriptors) and one ``append`` of a frame whose logits are a device tensor (HIP events: the copy against the pack kernel) or a NumPy
-array (host clock, synchronised: 19 against 6 channels uploaded).  Writes one JSON (--out) and prints it.
+array (host clock, synchronised: 19 against 6 channels uploaded).  Case f likewise compares two memories of the same build in the same run:
+the frame-size cache (ams_replay_gather_logits) against the low-resolution one (ams_replay_gather_logits_lowres), equal seeds and descriptors,
+the phase on the host clock, the logits gather alone in HIP events, ``nbytes`` of both.  Writes one JSON (--out) and prints it.
 Cases b and c are slow on the host path (seconds per phase): --reps_b / --reps_c set their own counts, recorded in the JSON.
 
-    python tools/time_replay.py [--cases a,b,c,d,e,gather,asr] [--reps 50] [--warmup 5] [--out out/time_replay.json]
+    python tools/time_replay.py [--cases a,b,c,d,e,f,gather,asr] [--reps 50] [--warmup 5] [--out out/time_replay.json]
 """
 import argparse
 import json
@@ -185,6 +188,48 @@ def time_layouts(net, mems, H, scale, flip, batch, iters, reps, warmup):
     return out
 
 
+def time_lowres(net, mems, H, scale, flip, batch, iters, reps, warmup):
+    """case f: ``mems`` = {"full_size": memory, "lowres": memory}, frames and labels equal, the small cache standing for its upsample; the two
+    alternate within every repetition, first the phases, then the logits gather alone"""
+    dev = net.engine.device
+    st = torch.cuda.current_stream(dev)
+    phase_ms = {k: [] for k in mems}
+    for r in range(warmup + reps):
+        for k, mem in mems.items():
+            seed(100 + r)
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            net.train_with_deque(mem, None, iters, "full_model")
+            torch.cuda.synchronize(dev)
+            if r >= warmup:
+                phase_ms[k].append((time.perf_counter() - t0) * 1e3)
+    seed(7)
+    samples = draw_samples(len(mems["full_size"]), (H, 2 * H), [H, 2 * H], scale, batch, warmup + reps, flip=flip)
+    plans = {k: mem.plan(samples, H, 2 * H) for k, mem in mems.items()}
+    assert not any(p.whole_frames for p in plans.values())
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    gather_us = {k: [] for k in mems}
+    for r in range(warmup + reps):
+        for k, mem in mems.items():
+            plan = plans[k]
+            torch.cuda.synchronize(dev)
+            e0.record(st)
+            mem._gather_logits(plan.table_host[r], plan.table_dev[r], plan.logits, (H, 2 * H))
+            e1.record(st)
+            torch.cuda.synchronize(dev)
+            if r >= warmup:
+                gather_us[k].append(e0.elapsed_time(e1) * 1e3)
+    out = {}
+    for k, mem in mems.items():
+        out[k] = {"logits_cached_shape": list(mem.logits_cached_shape), "memory_bytes": mem.nbytes, "slot_bytes": mem.nbytes // mem.capacity,
+                  "logits_bytes_written": batch * H * 2 * H * mem.logits_cached_shape[2] * 4, "device_ms": stats(phase_ms[k]),
+                  "step_ms": float(np.median(phase_ms[k])) / iters, "logits_gather_us": stats(gather_us[k])}
+    for q in ("device_ms", "logits_gather_us"):
+        out["lowres_over_full_size_" + q] = out["lowres"][q]["median"] / out["full_size"][q]["median"]
+    out["full_size_over_lowres_memory_bytes"] = out["full_size"]["memory_bytes"] / out["lowres"]["memory_bytes"]
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--height", type=int, default=512)
@@ -197,7 +242,9 @@ def main():
     ap.add_argument("--reps_c", type=int, default=None)
     ap.add_argument("--reps_d", type=int, default=None)
     ap.add_argument("--reps_e", type=int, default=None)
-    ap.add_argument("--cases", default="a,b,c,d,e,gather,asr")
+    ap.add_argument("--reps_f", type=int, default=None)
+    ap.add_argument("--lowres", default="33,65", help="case f: the cached grid of the low-resolution memory")
+    ap.add_argument("--cases", default="a,b,c,d,e,f,gather,asr")
     ap.add_argument("--out", default="out/time_replay.json")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "time_replay needs the GPU"
@@ -243,7 +290,7 @@ def main():
         result["asr_pairs"] = pairs
         result["asr_loop_ms"], result["asr_one_call_ms"] = stats(loop_ms), stats(call_ms)
         result["asr_loop_over_one_call"] = result["asr_loop_ms"]["median"] / result["asr_one_call_ms"]["median"]
-    if "b" in cases or "d" in cases or "e" in cases:
+    if "b" in cases or "d" in cases or "e" in cases or "f" in cases:
         rng = np.random.default_rng(5)
         tl = [rng.standard_normal((H, 2 * H, 19)).astype(np.float32) for _ in range(a.slots)]
         soft_mem = DeviceReplayMemory(a.slots, H, 2 * H, dev, logits_shape=(H, 2 * H, 19))
@@ -272,10 +319,22 @@ def main():
                                                  a.reps_e or a.reps, a.warmup)
         result["e_logit_layouts"].update({"scale": net.scale, "flip": True, "class_idx": CI})
         net.scale, net.flip = [1], False
+    if "f" in cases:
+        lh, lw = (int(v) for v in a.lowres.split(","))
+        low_mem = DeviceReplayMemory(a.slots, H, 2 * H, dev, logits_shape=(lh, lw, 19), logits_upsample=True)
+        for f, l in zip(frames, labels):
+            low_mem.append(f, l, rng.standard_normal((lh, lw, 19)).astype(np.float32))
+        net.scale, net.flip = [1, 1.25, 1.5], True
+        result["f_lowres_logits"] = time_lowres(net, {"full_size": soft_mem, "lowres": low_mem}, H, net.scale, True, a.batch, a.iters,
+                                                a.reps_f or a.reps, a.warmup)
+        result["f_lowres_logits"].update({"scale": net.scale, "flip": True, "reps": a.reps_f or a.reps})
+        net.scale, net.flip = [1], False
     result["note"] = ("*_ms: host clock around train_with_deque, stream drained before and after, host path and device path alternating with equal "
                       "seeds; gather_*_us: HIP events around the one launch, stream otherwise idle; asr_*: host clock, results compared; "
                       "d_*: device path only, logits_gather_us = HIP events around ams_replay_gather_logits alone; e_*: the full and the "
-                      "selected layout alternating with equal seeds and descriptors, append_* = one append of a frame with its logits")
+                      "selected layout alternating with equal seeds and descriptors, append_* = one append of a frame with its logits; f_*: a memory "
+                      "with logits at the frame size and one with a low-resolution cache (logits_upsample) alternating with equal seeds and "
+                      "descriptors, logits_gather_us = HIP events around ams_replay_gather_logits / ams_replay_gather_logits_lowres alone")
     net.close_model()
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
