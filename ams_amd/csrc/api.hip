@@ -301,6 +301,11 @@ int ams_replay_pack_logits(const float* logits_dev, int32_t th, int32_t tw, int3
     return launch_replay_pack_logits(logits_dev, th, tw, num_classes, class_idx_host, K, slot_dev, (hipStream_t)stream);
 }
 
+int ams_teacher_labels_from_logits(const float* logits_dev, int64_t slot_stride, int32_t n, int32_t lh, int32_t lw, int32_t num_classes, int32_t Hs,
+                                   int32_t Ws, uint8_t* labels_out_dev, int64_t out_stride, void* stream) {
+    return launch_teacher_labels_from_logits(logits_dev, slot_stride, n, lh, lw, num_classes, Hs, Ws, labels_out_dev, out_stride, (hipStream_t)stream);
+}
+
 size_t ams_render_table_bytes(void) { return AMS_RENDER_TABLE_BYTES; }
 
 int ams_render_views(const uint8_t* frames_dev, const void* student_dev, int32_t student_dtype, const uint8_t* teacher_dev, int32_t batch, int32_t H,

@@ -36,6 +36,9 @@
 //                                 row: the run's run * NC input floats go through LDS with contiguous loads, the run * K output floats
 //                                 leave contiguously.  16-byte loads and 16-byte stores where the bases and the row pitches allow them,
 //                                 each chosen by the launcher for the whole launch.  Copies only: every bit pattern survives.
+//   teacher_labels_kernel         f32 [lh, lw, NC] teacher logits -> the uint8 [Hs, Ws] label map a slot stores beside them: the argmax over
+//                                 every class (the first maximum, tf.argmax's) of the same upsample U, what the reference's teacher calls
+//                                 its predictions (utils/graph_utils.py:143-152).  append(frame, None, logits) fills the label slot with it.
 //   cross_confusion_pairs_kernel  the K x K phi-score confusion matrices of n pairs of label slots in one launch (blockIdx.z = the pair)
 //
 // Every descriptor is checked on the host before the launch (api.hip); the kernels check it again against the sizes they are given and
@@ -394,6 +397,89 @@ __global__ __launch_bounds__(256) void replay_pack_logits_kernel(const float* __
     }
 }
 
+constexpr int kLabelSeg = 128;                  // pixels of an output row per block at most, one per lane
+constexpr int kLabelLdsBytes = 32 * 1024;       // staged cached samples per block at most (the launcher narrows the segment until they fit)
+
+struct LabelGeom {
+    int n, lh, lw, NC, Hs, Ws;                   // items f32 [lh, lw, NC], labels Hs x Ws
+    int seg;                                     // pixels of a row per block: 4 .. kLabelSeg, a power of two
+    int lds_floats;                              // dynamic LDS the launch was given
+    int vec;                                     // every segment of every row of every item starts on 4 bytes: packed stores
+    int64_t slot_stride, out_stride;             // f32 elements / bytes from one item to the next
+    float sy, sx;                                // (lh-1)/(Hs-1), (lw-1)/(Ws-1) as f32: soft_teacher_geom's scales
+};
+
+// label(Y, X) = argmax_c U(Y, X, c), U = the align-corners upsample of replay_gather_logits_lowres_kernel (Stage U).  A block owns a segment
+// of one output row: the y-side (two cached rows, ty) is the same for the whole block, and the segment's pixels fall between the cached
+// columns lo(first pixel) .. hi(last pixel) (src_tap is monotone in the position).  Those columns of the two rows, every class, go to LDS
+// with contiguous loads (a 128-pixel segment of a 1024-wide row over a 65-wide cache: 10 columns x 2 rows x 19 floats); then each lane
+// scans the classes of its own pixel out of LDS.  A pixel's stride in LDS is NC | 1 floats: odd, so that lanes on neighbouring cached
+// columns (all of them where the cache has the frame's size) fall on different banks.
+__global__ __launch_bounds__(kLabelSeg) void teacher_labels_kernel(const float* __restrict__ logits, LabelGeom g, uint8_t* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) float s_stage[];
+    const int b = blockIdx.z, Y = blockIdx.y, x_first = blockIdx.x * g.seg, t = threadIdx.x;
+    // the launcher's checks again (uniform over the block)
+    if (!(g.n >= 1 && b < g.n && g.lh >= 1 && g.lh <= g.Hs && g.lw >= 1 && g.lw <= g.Ws && g.NC >= 1 && g.NC <= 255 &&
+          g.slot_stride >= (int64_t)g.lh * g.lw * g.NC && g.out_stride >= (int64_t)g.Hs * g.Ws))
+        return;
+    if (!(g.seg >= 1 && g.seg <= kLabelSeg) || Y >= g.Hs || x_first >= g.Ws) return;
+    const int seg = g.Ws - x_first < g.seg ? g.Ws - x_first : g.seg;
+    const int ld = g.NC | 1;
+
+    int l0, h0, c_lo, c_hi, lo_last, unused;
+    float ty, tx_unused;
+    src_tap(Y, g.sy, g.lh, l0, h0, ty);
+    src_tap(x_first, g.sx, g.lw, c_lo, unused, tx_unused);
+    src_tap(x_first + seg - 1, g.sx, g.lw, lo_last, c_hi, tx_unused);
+    const int ncols = c_hi - c_lo + 1;
+    const int rows = h0 == l0 ? 1 : 2;
+    // (src_tap keeps lo <= n_in - 1 for positions of U, see replay_gather_logits_lowres_kernel; a geometry that broke that, or a launch with
+    // less LDS than the segment needs, writes nothing)
+    if (l0 < 0 || l0 >= g.lh || c_lo < 0 || lo_last > c_hi || ncols < 1 || (int64_t)rows * ncols * ld > g.lds_floats) return;
+
+    const float* src = logits + (int64_t)b * g.slot_stride;
+    const int64_t pitch = (int64_t)g.lw * g.NC;
+    const int n_row = ncols * g.NC;
+    for (int r = 0; r < rows; ++r) {
+        const float* row = src + (r ? h0 : l0) * pitch + (int64_t)c_lo * g.NC;
+        float* dst = s_stage + r * ncols * ld;
+        // flat over the row piece's floats: element i is class c of cached column p; i advances by the block size without a division
+        int p = t / g.NC, c = t - p * g.NC;
+        const int dp = kLabelSeg / g.NC, dc = kLabelSeg - dp * g.NC;
+        for (int i = t; i < n_row; i += kLabelSeg) {
+            dst[p * ld + c] = row[i];
+            p += dp; c += dc;
+            if (c >= g.NC) { c -= g.NC; ++p; }
+        }
+    }
+    __syncthreads();
+
+    // lanes past the segment scan its last pixel and store nothing: every lane of a wave reaches the shuffles below
+    const int x = x_first + (t < seg ? t : seg - 1);
+    int lo, hi;
+    float tx;
+    src_tap(x, g.sx, g.lw, lo, hi, tx);
+    const float* top = s_stage + (lo - c_lo) * ld;
+    const float* bot = top + (rows - 1) * ncols * ld;
+    const int e = (hi - lo) * ld;
+    // tf.argmax: the first maximum.  A strict > from class 0 keeps the lowest index of equal values (-0.0 == +0.0)
+    float best = upsampled(top[0], top[e], bot[0], bot[e], tx, ty);
+    int label = 0;
+    for (int c = 1; c < g.NC; ++c) {
+        const float v = upsampled(top[c], top[e + c], bot[c], bot[e + c], tx, ty);
+        if (v > best) { best = v; label = c; }
+    }
+
+    uint8_t* dst = out + (int64_t)b * g.out_stride + (int64_t)Y * g.Ws + x_first;
+    if (g.vec) {                                                 // (then Ws and seg are multiples of 4: so is every segment's length)
+        // four pixels of four neighbouring lanes leave as one word
+        const uint32_t l1 = (uint32_t)__shfl_down(label, 1), l2 = (uint32_t)__shfl_down(label, 2), l3 = (uint32_t)__shfl_down(label, 3);
+        if ((t & 3) == 0 && t + 3 < seg) *reinterpret_cast<uint32_t*>(dst + t) = (uint32_t)label | (l1 << 8) | (l2 << 16) | (l3 << 24);
+        return;
+    }
+    if (t < seg) dst[t] = (uint8_t)label;
+}
+
 __global__ __launch_bounds__(256) void cross_confusion_pairs_kernel(const uint8_t* __restrict__ label_slots, int64_t label_stride, int capacity,
                                                                     const int32_t* __restrict__ pairs, int64_t n, ClassTable ct, int K,
                                                                     unsigned long long* __restrict__ conf) {
@@ -527,6 +613,57 @@ int launch_replay_pack_logits(const float* in, int th, int tw, int NC, const int
     g.vec_out = aligned16(out) && ((int64_t)tw * K) % 4 == 0;
     note_kernel("replay_pack_logits_kernel");
     hipLaunchKernelGGL(replay_pack_logits_kernel, dim3(cdiv(tw, g.run), th), dim3(256), 0, st, in, g, out);
+    AMS_CHECK_LAUNCH();
+    return AMS_OK;
+}
+
+// src_tap's lo / hi on the host (one f32 product, as __fmul_rn gives it)
+static inline void src_tap_host(int dst, float scale, int n_in, int& lo, int& hi) {
+    const float src = (float)dst * scale;
+    lo = (int)floorf(src);
+    hi = lo + 1 < n_in ? lo + 1 : n_in - 1;
+}
+
+// the most cached columns a segment of seg pixels of a Ws-wide row touches
+static int label_segment_columns(int Ws, int lw, float sx, int seg) {
+    int most = 1;
+    for (int x_first = 0; x_first < Ws; x_first += seg) {
+        const int x_last = x_first + seg < Ws ? x_first + seg - 1 : Ws - 1;
+        int lo, hi, unused;
+        src_tap_host(x_first, sx, lw, lo, unused);
+        src_tap_host(x_last, sx, lw, unused, hi);
+        if (hi - lo + 1 > most) most = hi - lo + 1;
+    }
+    return most;
+}
+
+int launch_teacher_labels_from_logits(const float* logits, int64_t slot_stride, int n, int lh, int lw, int NC, int Hs, int Ws, uint8_t* out,
+                                      int64_t out_stride, hipStream_t st) {
+    AMS_REQUIRE(logits && out, "teacher_labels_from_logits: null pointer");
+    AMS_REQUIRE(n >= 1 && n <= 65535, "teacher_labels_from_logits: n=%d out of range (1..65535)", n);
+    AMS_REQUIRE(Hs >= 1 && Ws >= 1 && Hs <= 65535, "teacher_labels_from_logits: bad label size %dx%d", Hs, Ws);
+    AMS_REQUIRE(lh >= 1 && lh <= Hs && lw >= 1 && lw <= Ws, "teacher_labels_from_logits: %dx%d logits for %dx%d labels (1 <= lh <= Hs, 1 <= lw <= Ws)", lh, lw, Hs,
+                Ws);
+    AMS_REQUIRE(NC >= 1 && NC <= 255, "teacher_labels_from_logits: num_classes=%d out of range (1..255: id 255 stays \"unlabelled\")", NC);
+    AMS_REQUIRE(slot_stride >= (int64_t)lh * lw * NC, "teacher_labels_from_logits: slot stride %lld below a %dx%dx%d item", (long long)slot_stride, lh, lw, NC);
+    AMS_REQUIRE(out_stride >= (int64_t)Hs * Ws, "teacher_labels_from_logits: output stride %lld below a %dx%d label map", (long long)out_stride, Hs, Ws);
+    LabelGeom g;
+    g.n = n; g.lh = lh; g.lw = lw; g.NC = NC; g.Hs = Hs; g.Ws = Ws;
+    g.slot_stride = slot_stride; g.out_stride = out_stride;
+    g.sy = Hs > 1 ? (float)(lh - 1) / (float)(Hs - 1) : 0.f;          // as soft_teacher_geom does for a teacher grid under Hs x Ws labels
+    g.sx = Ws > 1 ? (float)(lw - 1) / (float)(Ws - 1) : 0.f;
+    // the widest segment whose cached columns (two rows of them, every class) fit: 128 pixels unless the classes are many and the grid dense
+    const int ld = NC | 1;
+    int seg = kLabelSeg, cols = label_segment_columns(Ws, lw, g.sx, seg);
+    while (seg > 4 && (int64_t)2 * cols * ld * (int64_t)sizeof(float) > kLabelLdsBytes) {
+        seg >>= 1;
+        cols = label_segment_columns(Ws, lw, g.sx, seg);
+    }
+    g.seg = seg;
+    g.lds_floats = 2 * cols * ld;                                      // (seg = 4, NC = 255: 5 columns, 10 KB)
+    g.vec = Ws % 4 == 0 && out_stride % 4 == 0 && ((uintptr_t)out & 3) == 0;
+    note_kernel("teacher_labels_kernel");
+    hipLaunchKernelGGL(teacher_labels_kernel, dim3(cdiv(Ws, seg), Hs, n), dim3(kLabelSeg), sizeof(float) * g.lds_floats, st, logits, g, out);
     AMS_CHECK_LAUNCH();
     return AMS_OK;
 }

@@ -421,6 +421,10 @@ int launch_replay_gather_logits_lowres(const float* slots, int64_t slot_stride, 
                                        hipStream_t st);
 // in f32 [th][tw][NC] -> out f32 [th][tw][K], out channel k = in channel idx_host[k] (the selected layout of a replay slot); idx_host: HOST pointer
 int launch_replay_pack_logits(const float* in, int th, int tw, int NC, const int32_t* idx_host, int K, float* out, hipStream_t st);
+// logits f32 [n][lh][lw][NC] (item stride in elements) -> out uint8 [n][Hs][Ws] (item stride in bytes): the argmax over every class, first
+// maximum, of the items' align-corners upsample to Hs x Ws
+int launch_teacher_labels_from_logits(const float* logits, int64_t slot_stride, int n, int lh, int lw, int NC, int Hs, int Ws, uint8_t* out,
+                                      int64_t out_stride, hipStream_t st);
 int launch_cross_confusion_pairs(const uint8_t* label_slots, int64_t label_stride, int capacity, int64_t n, const int32_t* pairs_dev,
                                  const int32_t* pairs_host, int n_pairs, const int32_t* lut /*[256] -> subset idx or -1*/, int K, int64_t* conf,
                                  hipStream_t st);

@@ -16,7 +16,10 @@ align-corners upsample (the soft loss kernel's), evaluated inside the gather (``
 One source geometry per memory (the frames of one video have one size); the host deques stay the answer for mixed
 sizes.  ``logits_select=class_idx`` caches only the student's K channels of every frame's logits (the selected layout, AMS_TLOGITS_SELECTED:
 the loss gathers exactly those, so nothing is lost and every result keeps its bits; K / classes of the memory, the upload and the gather
-traffic).  No CPU fallback: the launches need the HIP library and a GPU; the bookkeeping (``Ring``, ``draw_samples``, the byte budget) does not.
+traffic).  A memory that caches logits needs no labels from the caller: ``append(frame, None, logits)`` derives the slot's hard labels from
+the full logits on the device (``ams_teacher_labels_from_logits``: the argmax of their align-corners upsample, the teacher's own
+``predictions``), so a 512x1024 sample uploads its 33x65x19 grid (163 KB) and no 512 KB label map.  No CPU fallback: the launches need the
+HIP library and a GPU; the bookkeeping (``Ring``, ``draw_samples``, the byte budget) does not.
 """
 from __future__ import annotations
 
@@ -230,10 +233,25 @@ class DeviceReplayMemory:
 
         A memory with ``logits_select`` takes full logits (``logits_shape``) or logits already reduced (``logits_cached_shape``): full logits
         on the device go through ``ams_replay_pack_logits`` on the current stream, a full host array is reduced on the host (``np.take``)
-        so that only the K channels are uploaded, reduced logits are stored as they are."""
+        so that only the K channels are uploaded, reduced logits are stored as they are.
+
+        ``label=None`` (a memory with ``logits_shape`` only): the label slot is derived from the logits on the device, on the current stream
+        (``ams_teacher_labels_from_logits``: the argmax over every class of the logits' align-corners upsample to the frame size, what the
+        teacher itself calls its predictions).  The logits must be full (``logits_shape``): host logits are uploaded once at every class, the
+        labels are derived from them, and only then are they reduced for a selected slot."""
         f = frame if isinstance(frame, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(frame))
         assert f.dtype == torch.uint8, "the replay memory holds uint8 frames, got %s" % f.dtype
         assert tuple(f.shape) == (self.src_h, self.src_w, 3), "one source geometry per memory: [%d, %d, 3], got %s" % (self.src_h, self.src_w, tuple(f.shape))
+        if label is None:
+            full = self._full_logits_on_device(logits)
+            views = self._slot_views(self.ring.push())
+            views[0].copy_(f, non_blocking=f.is_cuda)
+            self._derive_labels(full, views[1])
+            if self.logits_select is not None:
+                self._pack_logits(full, views[2])
+            else:
+                views[2].copy_(full, non_blocking=True)
+            return
         l = labels_to_u8(label)
         assert tuple(l.shape) == (self.src_h, self.src_w), "labels must be [%d, %d], got %s" % (self.src_h, self.src_w, tuple(l.shape))
         assert (logits is not None) == (self._logits is not None), "teacher logits go with a memory constructed with logits_shape (and are required then)"
@@ -272,6 +290,36 @@ class DeviceReplayMemory:
         idx = (C.c_int32 * len(self.logits_select))(*self.logits_select)
         hip.check(hip.lib().ams_replay_pack_logits(C.c_void_p(full.data_ptr()), th, tw, nc, idx, len(self.logits_select), hip.TLOGITS_SELECTED,
                                                    C.c_void_p(slot_view.data_ptr()), self._stream()), "ams_replay_pack_logits")
+
+    # ------------------------------------------------------------------ hard labels from the teacher logits
+    def _full_logits_on_device(self, logits) -> torch.Tensor:
+        """The full logits of one frame as a contiguous f32 device tensor: a device tensor in place, a host array uploaded once."""
+        assert self._logits is not None and logits is not None, \
+            "label=None derives the labels from the teacher logits: it needs a memory constructed with logits_shape, and the logits"
+        shape = tuple(logits.shape)
+        if shape != self.logits_shape and shape == self.logits_cached_shape:
+            raise ValueError("label=None needs the full teacher logits %s: the argmax over all classes is not defined for logits already "
+                             "reduced to the selected classes %s (a class outside the selection may hold the maximum)"
+                             % (self.logits_shape, shape))
+        assert shape == self.logits_shape, "teacher logits must be %s, got %s" % (self.logits_shape, shape)
+        assert self.logits_shape[2] <= 255, "labels are derived for at most 255 classes (id 255 stays \"unlabelled\")"
+        assert self.logits_shape[0] <= self.src_h and self.logits_shape[1] <= self.src_w, LARGE_LOGITS.replace("logits_upsample=True", "label=None") \
+            % (self.logits_shape[:2] + (self.src_h, self.src_w))
+        if isinstance(logits, torch.Tensor):
+            return logits.to(device=self.device, dtype=torch.float32).contiguous()
+        return torch.from_numpy(np.ascontiguousarray(logits, dtype=np.float32)).to(self.device)
+
+    def _derive_labels(self, full: torch.Tensor, out: torch.Tensor) -> None:
+        lh, lw, nc = self.logits_shape
+        hip.check(hip.lib().ams_teacher_labels_from_logits(C.c_void_p(full.data_ptr()), lh * lw * nc, 1, lh, lw, nc, self.src_h, self.src_w,
+                                                           C.c_void_p(out.data_ptr()), self.src_h * self.src_w, self._stream()),
+                  "ams_teacher_labels_from_logits")
+
+    def labels_from_logits(self, logits) -> torch.Tensor:
+        """The label map ``append(frame, None, logits)`` would store, as a fresh uint8 [src_h, src_w] device tensor; nothing is stored."""
+        out = torch.empty((self.src_h, self.src_w), dtype=torch.uint8, device=self.device)
+        self._derive_labels(self._full_logits_on_device(logits), out)
+        return out
 
     # ------------------------------------------------------------------ sampling
     def plan(self, samples: np.ndarray, H: int, W: int) -> ReplayPlan:

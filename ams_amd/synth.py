@@ -39,19 +39,51 @@ class SyntheticVideo:
                 else int(outside[int(rng.integers(0, len(outside)))])))
         self._ignore_ids = outside + [255]
 
+    def _background_label(self, t: int) -> np.ndarray:
+        lbl = np.full((self.h, self.w), self.classes[0], dtype=np.uint8)
+        lbl[self._yy < 0.35 + 0.05 * np.sin(4 * self._xx + 0.01 * t)] = self.classes[min(3, len(self.classes) - 1)]
+        return lbl
+
+    def _shape_masks(self, t: int):
+        """(shape, bool [H,2H] of the pixels it covers at time index t), in painting order."""
+        for s in self.shapes:
+            cx = (s["cx"] + s["vx"] * t) % 1.0
+            cy = (s["cy"] + s["vy"] * t) % 1.0
+            dx, dy = (self._xx - cx) / s["rx"], (self._yy - cy) / s["ry"]
+            yield s, ((np.abs(dx) < 1) & (np.abs(dy) < 1) if s["kind"] == 0 else (dx * dx + dy * dy < 1))
+
+    def clean_label(self, t: int) -> np.ndarray:
+        """uint8 [H,2H]: the teacher label of ``frame(t)`` before the ignore pixels are sprinkled on it (the scene itself)."""
+        lbl = self._background_label(t)
+        for s, m in self._shape_masks(t):
+            lbl[m] = s["cls"]
+        return lbl
+
+    def teacher_logits(self, t: int, lh: int, lw: int, margin: float = 8.0) -> np.ndarray:
+        """f32 [lh, lw, num_classes]: what a teacher of that output grid would cache for ``frame(t)``.  The clean label map is sampled at the
+        align-corners grid positions (cached sample (i, j) sits on pixel (i (H-1)/(lh-1), j (2H-1)/(lw-1)), rounded); a sample holds
+        ``margin * onehot(label) + noise`` with |noise| <= 0.99 margin / 4 < margin / 4, so its argmax is the label whatever the noise.  An
+        unlabelled sample (255) takes the lowest class id outside the student's subset (class 0 if there is none): the loss masks it either
+        way.  Deterministic, and drawn from a generator of its own ((seed, t) and a tag): ``frame(t)`` does not depend on calls to this."""
+        assert 1 <= lh <= self.h and 1 <= lw <= self.w
+        ys = np.rint(np.linspace(0, self.h - 1, lh)).astype(np.int64)
+        xs = np.rint(np.linspace(0, self.w - 1, lw)).astype(np.int64)
+        cls = self.clean_label(t)[ys][:, xs].astype(np.int64)
+        outside = [c for c in range(self.num_classes) if c not in self.classes]
+        cls[cls >= self.num_classes] = outside[0] if outside else 0
+        rng = np.random.default_rng((self._rng_seed, t, 0x7EAC4E2))
+        logits = (rng.uniform(-1.0, 1.0, size=(lh, lw, self.num_classes)) * (0.99 * margin / 4)).astype(np.float32)
+        np.put_along_axis(logits, cls[..., None], np.take_along_axis(logits, cls[..., None], 2) + np.float32(margin), axis=2)
+        return logits
+
     def frame(self, t: int) -> Tuple[np.ndarray, np.ndarray]:
         """(frame uint8 RGB [H,2H,3], teacher label uint8 [H,2H]) at time index t."""
         img = np.empty((self.h, self.w, 3), dtype=np.float32)
         for c in range(3):
             img[..., c] = 110 + 60 * np.sin(2 * np.pi * self._bg_freq[c, 0] * self._xx + self._bg_phase[c, 0] + 0.02 * t) \
                 * np.cos(2 * np.pi * self._bg_freq[c, 1] * self._yy + self._bg_phase[c, 1])
-        lbl = np.full((self.h, self.w), self.classes[0], dtype=np.uint8)
-        lbl[self._yy < 0.35 + 0.05 * np.sin(4 * self._xx + 0.01 * t)] = self.classes[min(3, len(self.classes) - 1)]
-        for s in self.shapes:
-            cx = (s["cx"] + s["vx"] * t) % 1.0
-            cy = (s["cy"] + s["vy"] * t) % 1.0
-            dx, dy = (self._xx - cx) / s["rx"], (self._yy - cy) / s["ry"]
-            m = (np.abs(dx) < 1) & (np.abs(dy) < 1) if s["kind"] == 0 else (dx * dx + dy * dy < 1)
+        lbl = self._background_label(t)
+        for s, m in self._shape_masks(t):
             img[m] = s["color"]
             lbl[m] = s["cls"]
         rng = np.random.default_rng(self._rng_seed * 100003 + t)

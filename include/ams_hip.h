@@ -558,6 +558,27 @@ int ams_replay_gather_logits_lowres(const float* slots_dev, int64_t slot_stride,
 int ams_replay_pack_logits(const float* logits_dev, int32_t th, int32_t tw, int32_t num_classes, const int32_t* class_idx_host, int32_t K,
                            int32_t layout, float* slot_dev, void* stream);
 
+/* The hard teacher labels of cached teacher logits (what a replay slot stores beside the logits; the reference's teacher derives its
+ * `predictions` the same way, argmax of its bilinearly upsampled logits, utils/graph_utils.py:143-152, and extract_labels.py writes them to
+ * gt_*.png): item i is f32 [lh, lw, num_classes] at logits_dev + i * slot_stride (stride in elements), the FULL layout, 1 <= lh <= Hs,
+ * 1 <= lw <= Ws; labels_out_dev + i * out_stride (stride in bytes) receives uint8 [Hs, Ws] of class ids 0 .. num_classes - 1:
+ *
+ *     label(Y, X) = argmax_c U(Y, X, c)
+ *
+ * U is Stage U of ams_replay_gather_logits_lowres above, bit for bit (sy = Hs > 1 ? (float)(lh - 1) / (float)(Hs - 1) : 0, the f32 taps, the
+ * cached sample itself on a grid point, every f32 operation rounded once), over all num_classes channels; lh == Hs && lw == Ws makes every
+ * position a grid point.  The argmax is tf.argmax's: the first maximum wins (a strict > scan from class 0), so a tie takes the lowest index,
+ * and -0.0 and +0.0 tie.  The contract is for finite logits, as for Stage U: no label is promised at a pixel whose interpolation a NaN or an
+ * infinity enters.  Bytes past Hs * Ws of an item's out_stride are not written.
+ *
+ * Checked on the host before the launch (AMS_E_INVALID, nothing launched, nothing written) and again in the kernel: no NULL pointer,
+ * 1 <= n <= 65535, Hs <= 65535, 1 <= lh <= Hs, 1 <= lw <= Ws, 1 <= num_classes <= 255 (id 255 stays "unlabelled"), slot_stride >= lh * lw *
+ * num_classes, out_stride >= Hs * Ws.  One launch (teacher_labels_kernel: a block stages the cached columns under a segment of an output row
+ * in LDS, each lane scans the classes of one pixel; labels_out_dev and out_stride multiples of 4 with Ws a multiple of 4 make the stores
+ * 4 bytes wide); no allocation, no synchronisation. */
+int ams_teacher_labels_from_logits(const float* logits_dev, int64_t slot_stride, int32_t n, int32_t lh, int32_t lw, int32_t num_classes, int32_t Hs,
+                                   int32_t Ws, uint8_t* labels_out_dev, int64_t out_stride, void* stream);
+
 /* The phi-score confusion matrices of n_pairs pairs of label slots at once (replaces the loop of run.py:287-291 over calc_cross_miou,
  * SemanticNetwork.py:124-139: one upload and one synchronising read per pair): pair i is (pairs[2i], pairs[2i + 1]) = (before, after)
  * physical slots, conf_mats_dev int64 [n_pairs][K][K] overwritten with the integers ams_cross_confusion gives pair by pair.  pairs_host

@@ -10,6 +10,8 @@ Host clock around ``train_with_deque`` (which ends with the read-back of the los
   d  soft_teacher, logits at the frame size, scale [1, 1.25, 1.5], flip   (device path only: the host path refuses the combination)
   e  case d on a memory that caches every class against one that caches the six selected (logits_select), alternating
   f  case d on a memory with logits at the frame size against one with a 33 x 65 cache and logits_upsample, alternating
+  g  one append of a frame with a 33 x 65 x 19 grid: the label derived on the device (append(frame, None, logits)) against the label map
+     uploaded from the host (512 KB), alternating
 
 Both paths start every phase from the same seeds, so they train on the same draws.  The baseline of every ratio is the host path timed in
 the same run.  Case d has no host path to compare against and no threshold: its phase time is recorded next to HIP-event times of the logits
@@ -19,10 +21,14 @@ the same build in the same run, never a number of an earlier run: the phase (hos
 descriptors) and one ``append`` of a frame whose logits are a device tensor (HIP events: the copy against the pack kernel) or a NumPy
 array (host clock, synchronised: 19 against 6 channels uploaded).  Case f likewise compares two memories of the same build in the same run:
 the frame-size cache (ams_replay_gather_logits) against the low-resolution one (ams_replay_gather_logits_lowres), equal seeds and descriptors,
-the phase on the host clock, the logits gather alone in HIP events, ``nbytes`` of both.  Writes one JSON (--out) and prints it.
+the phase on the host clock, the logits gather alone in HIP events, ``nbytes`` of both.  Case g times one ``append`` of host arrays into a
+memory as run.py --soft_teacher builds it (33 x 65 cache, logits_upsample, the six selected channels): HIP events around the append alone,
+the form with a host label map (what the parent of this case offers: 512 KB of labels and 6 channels of logits uploaded) against label=None
+(19 channels uploaded, ams_teacher_labels_from_logits, the pack kernel), alternating; beside it the label kernel alone on device logits.
+Writes one JSON (--out) and prints it.
 Cases b and c are slow on the host path (seconds per phase): --reps_b / --reps_c set their own counts, recorded in the JSON.
 
-    python tools/time_replay.py [--cases a,b,c,d,e,f,gather,asr] [--reps 50] [--warmup 5] [--out out/time_replay.json]
+    python tools/time_replay.py [--cases a,b,c,d,e,f,g,gather,asr] [--reps 50] [--warmup 5] [--out out/time_replay.json]
 """
 import argparse
 import json
@@ -230,6 +236,38 @@ def time_lowres(net, mems, H, scale, flip, batch, iters, reps, warmup):
     return out
 
 
+def time_append_labels(mem, frame, label, logits, reps, warmup):
+    """case g: ``mem`` caches ``logits``' grid; host arrays in both forms.  HIP events around one append (the stream is idle before, the
+    window ends when the slot is complete), the two forms alternating; then the label kernel alone on logits that are on the device."""
+    dev = mem.device
+    st = torch.cuda.current_stream(dev)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    us = {"label_uploaded": [], "label_derived": [], "label_kernel_alone": []}
+    for r in range(warmup + reps):
+        for k in ("label_uploaded", "label_derived"):
+            torch.cuda.synchronize(dev)
+            e0.record(st)
+            mem.append(frame, label if k == "label_uploaded" else None, logits)
+            e1.record(st)
+            torch.cuda.synchronize(dev)
+            if r >= warmup:
+                us[k].append(e0.elapsed_time(e1) * 1e3)
+    logits_dev = torch.from_numpy(logits).to(dev)
+    for r in range(warmup + reps):
+        torch.cuda.synchronize(dev)
+        e0.record(st)
+        mem.labels_from_logits(logits_dev)
+        e1.record(st)
+        torch.cuda.synchronize(dev)
+        if r >= warmup:
+            us["label_kernel_alone"].append(e0.elapsed_time(e1) * 1e3)
+    out = {k + "_us": stats(v) for k, v in us.items()}
+    out["derived_over_uploaded"] = out["label_derived_us"]["median"] / out["label_uploaded_us"]["median"]
+    k = mem.logits_cached_shape[2]
+    out["bytes_uploaded"] = {"label_uploaded": frame.nbytes + label.nbytes + logits.nbytes // logits.shape[2] * k, "label_derived": frame.nbytes + logits.nbytes}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--height", type=int, default=512)
@@ -243,8 +281,9 @@ def main():
     ap.add_argument("--reps_d", type=int, default=None)
     ap.add_argument("--reps_e", type=int, default=None)
     ap.add_argument("--reps_f", type=int, default=None)
-    ap.add_argument("--lowres", default="33,65", help="case f: the cached grid of the low-resolution memory")
-    ap.add_argument("--cases", default="a,b,c,d,e,f,gather,asr")
+    ap.add_argument("--reps_g", type=int, default=None)
+    ap.add_argument("--lowres", default="33,65", help="cases f and g: the cached grid of the low-resolution memory")
+    ap.add_argument("--cases", default="a,b,c,d,e,f,g,gather,asr")
     ap.add_argument("--out", default="out/time_replay.json")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "time_replay needs the GPU"
@@ -329,12 +368,21 @@ def main():
                                                 a.reps_f or a.reps, a.warmup)
         result["f_lowres_logits"].update({"scale": net.scale, "flip": True, "reps": a.reps_f or a.reps})
         net.scale, net.flip = [1], False
+    if "g" in cases:
+        lh, lw = (int(v) for v in a.lowres.split(","))
+        video = synth.SyntheticVideo(H, a.slots, CI, seed=3)
+        grid_mem = DeviceReplayMemory(a.slots, H, 2 * H, dev, logits_shape=(lh, lw, 19), logits_upsample=True, logits_select=CI)
+        result["g_append_labels_from_logits"] = time_append_labels(grid_mem, frames[0], labels[0], video.teacher_logits(0, lh, lw), a.reps_g or a.reps,
+                                                                   a.warmup)
+        result["g_append_labels_from_logits"].update({"logits_shape": [lh, lw, 19], "class_idx": CI, "reps": a.reps_g or a.reps})
     result["note"] = ("*_ms: host clock around train_with_deque, stream drained before and after, host path and device path alternating with equal "
                       "seeds; gather_*_us: HIP events around the one launch, stream otherwise idle; asr_*: host clock, results compared; "
                       "d_*: device path only, logits_gather_us = HIP events around ams_replay_gather_logits alone; e_*: the full and the "
                       "selected layout alternating with equal seeds and descriptors, append_* = one append of a frame with its logits; f_*: a memory "
                       "with logits at the frame size and one with a low-resolution cache (logits_upsample) alternating with equal seeds and "
-                      "descriptors, logits_gather_us = HIP events around ams_replay_gather_logits / ams_replay_gather_logits_lowres alone")
+                      "descriptors, logits_gather_us = HIP events around ams_replay_gather_logits / ams_replay_gather_logits_lowres alone; g_*: HIP events "
+                      "around one append of host arrays (frame, 33 x 65 x 19 logits) with the label map uploaded or derived on the device, "
+                      "alternating, and around ams_teacher_labels_from_logits alone")
     net.close_model()
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
