@@ -40,11 +40,14 @@ static inline int fill_class_table(const int32_t* cls_host, int K, int NC, Class
     return AMS_OK;
 }
 
+// the scale of an align-corners resize of n_in samples to n_out, as f32 (TF: CalculateResizeScale with align_corners)
+static inline float align_corners_scale(int n_in, int n_out) { return n_out > 1 ? (float)(n_in - 1) / (float)(n_out - 1) : 0.f; }
+
 static inline HeadGeom head_geom(int ld, int B, int h, int w, int K, int H, int W, int NC) {
     HeadGeom g;
     g.B = B; g.h = h; g.w = w; g.ld = ld; g.K = K; g.H = H; g.W = W; g.NC = NC; g.per_frame = 0; g.labels_u8 = 0;
-    g.sy = H > 1 ? (float)(h - 1) / (float)(H - 1) : 0.f;
-    g.sx = W > 1 ? (float)(w - 1) / (float)(W - 1) : 0.f;
+    g.sy = align_corners_scale(h, H);
+    g.sx = align_corners_scale(w, W);
     return g;
 }
 
@@ -70,8 +73,8 @@ static inline SoftTeacher soft_teacher_geom(const float* t, int th, int tw, int 
     SoftTeacher s;
     const bool selected = layout == AMS_TLOGITS_SELECTED;
     s.t = t; s.th = th; s.tw = tw; s.ld = selected ? K : NC;
-    s.sy = H > 1 ? (float)(th - 1) / (float)(H - 1) : 0.f;          // as head_geom does for the student's own logits
-    s.sx = W > 1 ? (float)(tw - 1) / (float)(W - 1) : 0.f;
+    s.sy = align_corners_scale(th, H);                              // as head_geom does for the student's own logits
+    s.sx = align_corners_scale(tw, W);
     for (int k = 0; k < kMaxK; ++k) s.tidx[k] = k < K ? (selected ? k : ct.idx[k]) : 0;
     return s;
 }

@@ -13,36 +13,40 @@
 //   replay_gather_logits_kernel   f32 [Hs, Ws, C] slots (teacher logits cached at the frame size) through the same descriptors: the crop of the
 //                                 logits rescaled to (th, tw), mirrored when flip, at the label size [B, H, W, C].  The rule is this
 //                                 project's (include/ams_hip.h: the reference never resamples logits): cv2.resize's float INTER_LINEAR
-//                                 geometry, taps in double, the blend in f32 with every operation rounded once.  A block owns a segment of
-//                                 an output row: its x-taps go to LDS once per pixel, then the segment's seg * C floats are walked flat, so
-//                                 that stores are contiguous and the four tap loads of neighbouring lanes fall in the same lines.  Equal
-//                                 sizes copy (nothing of a neighbouring pixel enters), 16 bytes per lane where the pitches, the origin and
-//                                 the bases allow it and the sample is not mirrored; with channels a multiple of 4 (a slot that holds the K
-//                                 selected channels, K = 4 or 8) every pixel starts on 16 bytes and the mirrored copy moves 16 bytes per
-//                                 lane too.
+//                                 geometry, taps in double (linear_tap), the blend in f32 with every operation rounded once (logits_blend).
+//                                 A block owns a segment of an output row: its x-taps go to LDS once per pixel, then the segment's seg * C
+//                                 floats are walked flat (FlatWalk), so that stores are contiguous and the four tap loads of neighbouring
+//                                 lanes fall in the same lines.  Equal sizes copy (nothing of a neighbouring pixel enters), 16 bytes per
+//                                 lane where the pitches, the origin and the bases allow it and the sample is not mirrored; with channels a
+//                                 multiple of 4 (a slot that holds the K selected channels, K = 4 or 8) every pixel starts on 16 bytes and
+//                                 the mirrored copy moves 16 bytes per lane too.
 //   replay_gather_logits_lowres_kernel
 //                                 f32 [lh, lw, C] slots (teacher logits cached on a grid no larger than the frame) through the same
 //                                 descriptors: the slot behaves, bit for bit, as a frame-size slot that holds its own align-corners
 //                                 upsample U (the soft loss kernel's: src_tap / bilerp of head_common.hpp, a grid point the cached sample
-//                                 itself), and replay_gather_logits_kernel's rule is applied to U, which is never stored.  Same block
-//                                 shape: the y-side (the rule's two rows of U, and for each the two cached rows and ty) is uniform per
-//                                 block, the x-side (per tap of the rule two element offsets into a cached row and tx, plus wx) goes to
-//                                 LDS once per pixel, then the segment's seg * C floats are walked flat.  Where both rows of U fall
-//                                 between the same two cached rows (15 of 16 output rows for a 33 x 65 cache of 512 x 1024 frames) the
-//                                 x-interpolated pair is formed once and serves both: 8 loads per float instead of 16, the same operations
-//                                 on the same values.  The loads hit L1 / L2 (a 33 x 65 x 19 slot is 163 KB): HBM sees the stores alone, the time is the tap loads'.
+//                                 itself), and replay_gather_logits_kernel's rule (the same linear_tap and logits_blend) is applied to U,
+//                                 which is never stored.  Same block shape and walk: the y-side (the rule's two rows of U, and for each the
+//                                 two cached rows and ty) is uniform per block, the x-side (per tap of the rule two element offsets into a
+//                                 cached row and tx, plus wx) goes to LDS once per pixel.  Where both rows of U fall between the same two
+//                                 cached rows (15 of 16 output rows for a 33 x 65 cache of 512 x 1024 frames) the x-interpolated pair is
+//                                 formed once and serves both: 8 loads per float instead of 16, the same operations on the same values.
+//                                 The loads hit L1 / L2 (a 33 x 65 x 19 slot is 163 KB): HBM sees the stores alone, the time is the tap loads'.
 //   replay_pack_logits_kernel     f32 [th, tw, NC] teacher logits -> a slot in the selected layout f32 [th, tw, K], channel k = input channel
 //                                 idx[k]: what append does to logits that are already on the device.  A block owns a run of pixels of one
 //                                 row: the run's run * NC input floats go through LDS with contiguous loads, the run * K output floats
-//                                 leave contiguously.  16-byte loads and 16-byte stores where the bases and the row pitches allow them,
-//                                 each chosen by the launcher for the whole launch.  Copies only: every bit pattern survives.
+//                                 leave contiguously (FlatWalk over them).  16-byte loads and 16-byte stores where the bases and the row
+//                                 pitches allow them, each chosen by the launcher for the whole launch.  Copies only: every bit pattern
+//                                 survives.
 //   teacher_labels_kernel         f32 [lh, lw, NC] teacher logits -> the uint8 [Hs, Ws] label map a slot stores beside them: the argmax over
 //                                 every class (the first maximum, tf.argmax's) of the same upsample U, what the reference's teacher calls
 //                                 its predictions (utils/graph_utils.py:143-152).  append(frame, None, logits) fills the label slot with it.
 //   cross_confusion_pairs_kernel  the K x K phi-score confusion matrices of n pairs of label slots in one launch (blockIdx.z = the pair)
 //
-// Every descriptor is checked on the host before the launch (api.hip); the kernels check it again against the sizes they are given and
-// skip a sample that fails, so that a table that changed between the two cannot reach outside the slots.
+// Shared by the kernels, each written once: the descriptor check (replay_sample_ok on the device, check_replay_samples on the host), the
+// division-free flat walk over a block's floats (FlatWalk), one axis of the logits rule and its blend (linear_tap, logits_blend), U at one
+// point (upsampled).  Every descriptor is checked on the host before the launch (check_replay_samples); the kernels check it again against
+// the sizes they are given (replay_sample_ok) and skip a sample that fails, so that a table that changed between the two cannot reach
+// outside the slots.
 #include "common.hpp"
 #include "kernels.hpp"
 #include "resize_taps.hpp"
@@ -52,21 +56,34 @@
 namespace ams {
 
 struct ReplayGeom {
-    int capacity, Hs, Ws, H, W, B;
+    int capacity, Hs, Ws, H, W;
     int64_t frame_stride, label_stride;          // bytes from one slot to the next
     int vec;                                     // pitches and bases allow 16-byte accesses
 };
 
-__device__ __forceinline__ bool replay_sample_ok(const ams_replay_sample& d, const ReplayGeom& g) {
-    return d.slot >= 0 && d.slot < g.capacity && d.th > 0 && d.tw > 0 && d.top >= 0 && d.left >= 0 && d.top <= d.th - g.H && d.left <= d.tw - g.W;
+// the descriptor check: the slot exists and the H x W crop lies inside the th x tw image
+__device__ __forceinline__ bool replay_sample_ok(const ams_replay_sample& d, int capacity, int H, int W) {
+    return d.slot >= 0 && d.slot < capacity && d.th > 0 && d.tw > 0 && d.top >= 0 && d.left >= 0 && d.top <= d.th - H && d.left <= d.tw - W;
 }
+
+// The flat walk: a block of `block` threads walks n * C floats, thread t taking the elements i = t, t + block, ...; element i is channel c of
+// pixel p.  One division when the walk starts, none inside the loop: next() follows i += block.
+// (c < C and dc = block % C < C, with dp = 0 and dc = block where C > block: c + dc < 2 C, so one conditional subtraction suffices)
+struct FlatWalk {
+    int p, c, dp, dc, C;
+    __device__ __forceinline__ FlatWalk(int t, int C_, int block) : p(t / C_), c(t - p * C_), dp(block / C_), dc(block - dp * C_), C(C_) {}
+    __device__ __forceinline__ void next() {
+        p += dp; c += dc;
+        if (c >= C) { c -= C; ++p; }
+    }
+};
 
 __global__ __launch_bounds__(256) void replay_gather_kernel(const uint8_t* __restrict__ frame_slots, const uint8_t* __restrict__ label_slots,
                                                             const ams_replay_sample* __restrict__ samples, ReplayGeom g,
                                                             uint8_t* __restrict__ frames_out, uint8_t* __restrict__ labels_out) {
     const int b = blockIdx.z, oy = blockIdx.y;
     const ams_replay_sample d = samples[b];
-    if (!replay_sample_ok(d, g)) return;
+    if (!replay_sample_ok(d, g.capacity, g.H, g.W)) return;
     const uint8_t* fsrc = frame_slots + (int64_t)d.slot * g.frame_stride;
     const uint8_t* lsrc = label_slots + (int64_t)d.slot * g.label_stride;
     uint8_t* fdst = frames_out + ((int64_t)b * g.H + oy) * g.W * 3;
@@ -153,13 +170,21 @@ __device__ __forceinline__ void linear_tap(int d, int n_in, int n_out, int& s0, 
     s1 = s + 1 < n_in - 1 ? s + 1 : n_in - 1;
 }
 
+// the blend of the logits rule: u[row][column] of the four taps, the weights of the second column and the second row; every operation rounded once
+__device__ __forceinline__ float logits_blend(float u00, float u01, float u10, float u11, float wx, float wy) {
+    const float mx = __fsub_rn(1.f, wx), my = __fsub_rn(1.f, wy);
+    const float r0 = __fadd_rn(__fmul_rn(u00, mx), __fmul_rn(u01, wx));
+    const float r1 = __fadd_rn(__fmul_rn(u10, mx), __fmul_rn(u11, wx));
+    return __fadd_rn(__fmul_rn(r0, my), __fmul_rn(r1, wy));
+}
+
 __global__ __launch_bounds__(256) void replay_gather_logits_kernel(const float* __restrict__ slots, const ams_replay_sample* __restrict__ samples,
                                                                    LogitsGeom g, float* __restrict__ out) {
     __shared__ int s_x0[kLogitsSeg], s_x1[kLogitsSeg];          // element offsets of a pixel's two taps inside a source row
     __shared__ float s_wx[kLogitsSeg];
     const int b = blockIdx.z, oy = blockIdx.y, x_first = blockIdx.x * kLogitsSeg, t = threadIdx.x;
     const ams_replay_sample d = samples[b];
-    if (!(d.slot >= 0 && d.slot < g.capacity && d.th > 0 && d.tw > 0 && d.top >= 0 && d.left >= 0 && d.top <= d.th - g.H && d.left <= d.tw - g.W)) return;
+    if (!replay_sample_ok(d, g.capacity, g.H, g.W)) return;
     const int seg = g.W - x_first < kLogitsSeg ? g.W - x_first : kLogitsSeg;
     const int n = seg * g.C;
     const int64_t pitch = (int64_t)g.Ws * g.C;
@@ -193,9 +218,7 @@ __global__ __launch_bounds__(256) void replay_gather_logits_kernel(const float* 
     }
     __syncthreads();
 
-    // flat over the segment's floats: element i is channel c of pixel p; i advances by the block size without a division
-    int p = t / g.C, c = t - p * g.C;
-    const int dp = 256 / g.C, dc = 256 - dp * g.C;
+    FlatWalk w(t, g.C, 256);                                     // over the segment's floats
     if (same) {                                                  // the mirrored copy
         const float* row = src + cy * pitch;
         if (g.vec && (g.C & 3) == 0) {                           // every pixel starts on 16 bytes: whole quads of one pixel
@@ -206,11 +229,7 @@ __global__ __launch_bounds__(256) void replay_gather_logits_kernel(const float* 
             }
             return;
         }
-        for (int i = t; i < n; i += 256) {
-            dst[i] = row[s_x0[p] + c];
-            p += dp; c += dc;
-            if (c >= g.C) { c -= g.C; ++p; }
-        }
+        for (int i = t; i < n; i += 256, w.next()) dst[i] = row[s_x0[w.p] + w.c];
         return;
     }
     int y0, y1;
@@ -218,15 +237,9 @@ __global__ __launch_bounds__(256) void replay_gather_logits_kernel(const float* 
     linear_tap(cy, g.Hs, d.th, y0, y1, wy);
     const float* row0 = src + y0 * pitch;
     const float* row1 = src + y1 * pitch;
-    const float my = 1.f - wy;
-    for (int i = t; i < n; i += 256) {
-        const int a0 = s_x0[p] + c, a1 = s_x1[p] + c;
-        const float wx = s_wx[p], mx = 1.f - wx;
-        const float r0 = row0[a0] * mx + row0[a1] * wx;
-        const float r1 = row1[a0] * mx + row1[a1] * wx;
-        dst[i] = r0 * my + r1 * wy;
-        p += dp; c += dc;
-        if (c >= g.C) { c -= g.C; ++p; }
+    for (int i = t; i < n; i += 256, w.next()) {
+        const int a0 = s_x0[w.p] + w.c, a1 = s_x1[w.p] + w.c;
+        dst[i] = logits_blend(row0[a0], row0[a1], row1[a0], row1[a1], s_wx[w.p], wy);
     }
 }
 
@@ -249,7 +262,7 @@ __global__ __launch_bounds__(256) void replay_gather_logits_lowres_kernel(const 
     __shared__ float s_tx[2][kLogitsSeg], s_wx[kLogitsSeg];
     const int b = blockIdx.z, oy = blockIdx.y, x_first = blockIdx.x * kLogitsSeg, t = threadIdx.x;
     const ams_replay_sample d = samples[b];
-    if (!(d.slot >= 0 && d.slot < g.capacity && d.th > 0 && d.tw > 0 && d.top >= 0 && d.left >= 0 && d.top <= d.th - g.H && d.left <= d.tw - g.W)) return;
+    if (!replay_sample_ok(d, g.capacity, g.H, g.W)) return;
     if (!(g.lh >= 1 && g.lh <= g.Hs && g.lw >= 1 && g.lw <= g.Ws && g.slot_stride >= (int64_t)g.lh * g.lw * g.C)) return;
     const int seg = g.W - x_first < kLogitsSeg ? g.W - x_first : kLogitsSeg;
     const int n = seg * g.C;
@@ -280,20 +293,16 @@ __global__ __launch_bounds__(256) void replay_gather_logits_lowres_kernel(const 
     }
     __syncthreads();
 
-    // flat over the segment's floats: element i is channel c of pixel p; i advances by the block size without a division
-    int p = t / g.C, c = t - p * g.C;
-    const int dp = 256 / g.C, dc = 256 - dp * g.C;
+    FlatWalk w(t, g.C, 256);                                     // over the segment's floats
     if (same) {                                                  // U's window itself, mirrored when flip
         int l0, h0;
         float ty;
         src_tap(cy, g.sy, g.lh, l0, h0, ty);
         const float* top = src + l0 * pitch;
         const float* bot = src + h0 * pitch;
-        for (int i = t; i < n; i += 256) {
-            const int a = s_lo[0][p] + c, e = s_hi[0][p] + c;
-            dst[i] = upsampled(top[a], top[e], bot[a], bot[e], s_tx[0][p], ty);
-            p += dp; c += dc;
-            if (c >= g.C) { c -= g.C; ++p; }
+        for (int i = t; i < n; i += 256, w.next()) {
+            const int a = s_lo[0][w.p] + w.c, e = s_hi[0][w.p] + w.c;
+            dst[i] = upsampled(top[a], top[e], bot[a], bot[e], s_tx[0][w.p], ty);
         }
         return;
     }
@@ -302,50 +311,37 @@ __global__ __launch_bounds__(256) void replay_gather_logits_lowres_kernel(const 
     linear_tap(cy, g.Hs, d.th, y0, y1, wy);
     src_tap(y0, g.sy, g.lh, l0, h0, ty0);
     src_tap(y1, g.sy, g.lh, l1, h1, ty1);
-    const float my = __fsub_rn(1.f, wy);
     const float* top0 = src + l0 * pitch;
     const float* bot0 = src + h0 * pitch;
-    if (l0 == l1 && h0 == h1) {                                  // both rows of U between the same two cached rows: one x-interpolated pair
-        for (int i = t; i < n; i += 256) {
+    const float* top1 = src + l1 * pitch;
+    const float* bot1 = src + h1 * pitch;
+    // the rescale loop: ua / ub = the two rows of U at the rule's two x-taps.  shared: both rows of U lie between the same two cached rows
+    // (top1 == top0, bot1 == bot0), so bilerp's x-interpolated pair is formed once and serves both
+    auto rescale = [&](auto shared) {
+        for (int i = t; i < n; i += 256, w.next()) {
             float ua[2], ub[2];
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
-                const int a = s_lo[k][p] + c, e = s_hi[k][p] + c;
-                const float tx = s_tx[k][p], tl = top0[a], bl = bot0[a];
-                const float tp = __fadd_rn(tl, __fmul_rn(__fsub_rn(top0[e], tl), tx));          // bilerp's top and bot
-                const float bt = __fadd_rn(bl, __fmul_rn(__fsub_rn(bot0[e], bl), tx));
-                const float df = __fsub_rn(bt, tp);
-                const float va = __fadd_rn(tp, __fmul_rn(df, ty0)), vb = __fadd_rn(tp, __fmul_rn(df, ty1));
-                ua[k] = (tx == 0.f && ty0 == 0.f) ? tl : va;
-                ub[k] = (tx == 0.f && ty1 == 0.f) ? tl : vb;
+                const int a = s_lo[k][w.p] + w.c, e = s_hi[k][w.p] + w.c;
+                const float tx = s_tx[k][w.p];
+                if constexpr (decltype(shared)::value) {
+                    const float tl = top0[a], bl = bot0[a];
+                    const float tp = __fadd_rn(tl, __fmul_rn(__fsub_rn(top0[e], tl), tx));          // bilerp's top and bot
+                    const float bt = __fadd_rn(bl, __fmul_rn(__fsub_rn(bot0[e], bl), tx));
+                    const float df = __fsub_rn(bt, tp);
+                    const float va = __fadd_rn(tp, __fmul_rn(df, ty0)), vb = __fadd_rn(tp, __fmul_rn(df, ty1));
+                    ua[k] = (tx == 0.f && ty0 == 0.f) ? tl : va;
+                    ub[k] = (tx == 0.f && ty1 == 0.f) ? tl : vb;
+                } else {
+                    ua[k] = upsampled(top0[a], top0[e], bot0[a], bot0[e], tx, ty0);
+                    ub[k] = upsampled(top1[a], top1[e], bot1[a], bot1[e], tx, ty1);
+                }
             }
-            const float wx = s_wx[p], mx = __fsub_rn(1.f, wx);
-            const float r0 = __fadd_rn(__fmul_rn(ua[0], mx), __fmul_rn(ua[1], wx));
-            const float r1 = __fadd_rn(__fmul_rn(ub[0], mx), __fmul_rn(ub[1], wx));
-            dst[i] = __fadd_rn(__fmul_rn(r0, my), __fmul_rn(r1, wy));
-            p += dp; c += dc;
-            if (c >= g.C) { c -= g.C; ++p; }
+            dst[i] = logits_blend(ua[0], ua[1], ub[0], ub[1], s_wx[w.p], wy);
         }
-        return;
-    }
-    const float* top1 = src + l1 * pitch;
-    const float* bot1 = src + h1 * pitch;
-    for (int i = t; i < n; i += 256) {
-        float ua[2], ub[2];
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const int a = s_lo[k][p] + c, e = s_hi[k][p] + c;
-            const float tx = s_tx[k][p];
-            ua[k] = upsampled(top0[a], top0[e], bot0[a], bot0[e], tx, ty0);
-            ub[k] = upsampled(top1[a], top1[e], bot1[a], bot1[e], tx, ty1);
-        }
-        const float wx = s_wx[p], mx = __fsub_rn(1.f, wx);
-        const float r0 = __fadd_rn(__fmul_rn(ua[0], mx), __fmul_rn(ua[1], wx));
-        const float r1 = __fadd_rn(__fmul_rn(ub[0], mx), __fmul_rn(ub[1], wx));
-        dst[i] = __fadd_rn(__fmul_rn(r0, my), __fmul_rn(r1, wy));
-        p += dp; c += dc;
-        if (c >= g.C) { c -= g.C; ++p; }
-    }
+    };
+    if (l0 == l1 && h0 == h1) rescale(std::true_type());         // (uniform over the block)
+    else rescale(std::false_type());
 }
 
 constexpr int kPackFloats = 4096;               // input floats of a run in LDS (16 KB)
@@ -387,13 +383,8 @@ __global__ __launch_bounds__(256) void replay_pack_logits_kernel(const float* __
             st4(dst + 4 * i, make_float4(v[0], v[1], v[2], v[3]));
         }
     } else {
-        int p = t / g.K, k = t - p * g.K;
-        const int dp = 256 / g.K, dk = 256 - dp * g.K;
-        for (int i = t; i < n_out; i += 256) {
-            dst[i] = s_in[p * g.NC + s_idx[k]];
-            p += dp; k += dk;
-            if (k >= g.K) { k -= g.K; ++p; }
-        }
+        FlatWalk w(t, g.K, 256);                                 // over the run's output floats
+        for (int i = t; i < n_out; i += 256, w.next()) dst[i] = s_in[w.p * g.NC + s_idx[w.c]];
     }
 }
 
@@ -443,14 +434,8 @@ __global__ __launch_bounds__(kLabelSeg) void teacher_labels_kernel(const float* 
     for (int r = 0; r < rows; ++r) {
         const float* row = src + (r ? h0 : l0) * pitch + (int64_t)c_lo * g.NC;
         float* dst = s_stage + r * ncols * ld;
-        // flat over the row piece's floats: element i is class c of cached column p; i advances by the block size without a division
-        int p = t / g.NC, c = t - p * g.NC;
-        const int dp = kLabelSeg / g.NC, dc = kLabelSeg - dp * g.NC;
-        for (int i = t; i < n_row; i += kLabelSeg) {
-            dst[p * ld + c] = row[i];
-            p += dp; c += dc;
-            if (c >= g.NC) { c -= g.NC; ++p; }
-        }
+        FlatWalk w(t, g.NC, kLabelSeg);                          // over the row piece's floats: class c of cached column p
+        for (int i = t; i < n_row; i += kLabelSeg, w.next()) dst[w.p * ld + w.c] = row[i];
     }
     __syncthreads();
 
@@ -492,7 +477,25 @@ __global__ __launch_bounds__(256) void cross_confusion_pairs_kernel(const uint8_
 
 static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
-// samples_host: the table the caller uploaded to samples_dev, checked here before anything is launched
+// The descriptor check on the host, over samples_host: the table the caller uploaded to samples_dev, checked before anything is launched.
+// entry names the C entry in the messages.
+static int check_replay_slot(const char* entry, int b, const ams_replay_sample& d, int capacity) {
+    AMS_REQUIRE(d.slot >= 0 && d.slot < capacity, "%s: sample %d draws slot %d of %d", entry, b, d.slot, capacity);
+    return AMS_OK;
+}
+
+static int check_replay_samples(const char* entry, const ams_replay_sample* samples_host, int B, int capacity, int H, int W) {
+    for (int b = 0; b < B; ++b) {
+        const ams_replay_sample& d = samples_host[b];
+        RUN_RC(check_replay_slot(entry, b, d, capacity));
+        AMS_REQUIRE(d.th > 0 && d.tw > 0 && d.th - H >= 0 && d.tw - W >= 0, "%s: sample %d: a %dx%d crop of a %dx%d image (negative slack)", entry, b, H, W,
+                    d.th, d.tw);
+        AMS_REQUIRE(d.top >= 0 && d.left >= 0 && d.top <= d.th - H && d.left <= d.tw - W, "%s: sample %d: crop origin (%d, %d) outside %dx%d", entry, b,
+                    d.top, d.left, d.th, d.tw);
+    }
+    return AMS_OK;
+}
+
 int launch_replay_gather(const uint8_t* frame_slots, int64_t frame_stride, const uint8_t* label_slots, int64_t label_stride, int capacity, int Hs,
                          int Ws, const ams_replay_sample* samples_dev, const ams_replay_sample* samples_host, int B, int H, int W,
                          uint8_t* frames_out, uint8_t* labels_out, hipStream_t st) {
@@ -501,16 +504,9 @@ int launch_replay_gather(const uint8_t* frame_slots, int64_t frame_stride, const
                 Hs, Ws, B, H, W, capacity);
     AMS_REQUIRE(frame_stride >= (int64_t)Hs * Ws * 3 && label_stride >= (int64_t)Hs * Ws, "replay_gather: slot strides %lld / %lld below a %dx%d frame",
                 (long long)frame_stride, (long long)label_stride, Hs, Ws);
-    for (int b = 0; b < B; ++b) {
-        const ams_replay_sample& d = samples_host[b];
-        AMS_REQUIRE(d.slot >= 0 && d.slot < capacity, "replay_gather: sample %d draws slot %d of %d", b, d.slot, capacity);
-        AMS_REQUIRE(d.th > 0 && d.tw > 0 && d.th - H >= 0 && d.tw - W >= 0, "replay_gather: sample %d: a %dx%d crop of a %dx%d image (negative slack)", b, H, W,
-                    d.th, d.tw);
-        AMS_REQUIRE(d.top >= 0 && d.left >= 0 && d.top <= d.th - H && d.left <= d.tw - W, "replay_gather: sample %d: crop origin (%d, %d) outside %dx%d", b,
-                    d.top, d.left, d.th, d.tw);
-    }
+    RUN_RC(check_replay_samples("replay_gather", samples_host, B, capacity, H, W));
     ReplayGeom g;
-    g.capacity = capacity; g.Hs = Hs; g.Ws = Ws; g.H = H; g.W = W; g.B = B;
+    g.capacity = capacity; g.Hs = Hs; g.Ws = Ws; g.H = H; g.W = W;
     g.frame_stride = frame_stride; g.label_stride = label_stride;
     g.vec = W % 16 == 0 && Ws % 16 == 0 && frame_stride % 16 == 0 && label_stride % 16 == 0 && aligned16(frame_slots) && aligned16(label_slots) &&
             aligned16(frames_out) && aligned16(labels_out);
@@ -529,7 +525,7 @@ int launch_replay_gather_rows(const float* slots, int64_t slot_stride, int capac
     AMS_REQUIRE(slot_stride >= n, "replay_gather_f32: slot stride %lld below %lld elements", (long long)slot_stride, (long long)n);
     for (int b = 0; b < B; ++b) {
         const ams_replay_sample& d = samples_host[b];
-        AMS_REQUIRE(d.slot >= 0 && d.slot < capacity, "replay_gather_f32: sample %d draws slot %d of %d", b, d.slot, capacity);
+        RUN_RC(check_replay_slot("replay_gather_f32", b, d, capacity));
         // soft targets follow frames that are taken as they are: no rescale / crop / flip of teacher logits is defined
         AMS_REQUIRE(d.top == 0 && d.left == 0 && d.flip == 0, "replay_gather_f32: sample %d is cropped or flipped (%d, %d, %d)", b, d.top, d.left, d.flip);
     }
@@ -549,14 +545,7 @@ int launch_replay_gather_logits(const float* slots, int64_t slot_stride, int cap
                     (int64_t)W * C <= INT32_MAX,
                 "replay_gather_logits: bad geometry %dx%dx%d -> %d x %dx%d, %d slots", Hs, Ws, C, B, H, W, capacity);
     AMS_REQUIRE(slot_stride >= (int64_t)Hs * Ws * C, "replay_gather_logits: slot stride %lld below a %dx%dx%d slot", (long long)slot_stride, Hs, Ws, C);
-    for (int b = 0; b < B; ++b) {
-        const ams_replay_sample& d = samples_host[b];
-        AMS_REQUIRE(d.slot >= 0 && d.slot < capacity, "replay_gather_logits: sample %d draws slot %d of %d", b, d.slot, capacity);
-        AMS_REQUIRE(d.th > 0 && d.tw > 0 && d.th - H >= 0 && d.tw - W >= 0, "replay_gather_logits: sample %d: a %dx%d crop of a %dx%d image (negative slack)",
-                    b, H, W, d.th, d.tw);
-        AMS_REQUIRE(d.top >= 0 && d.left >= 0 && d.top <= d.th - H && d.left <= d.tw - W, "replay_gather_logits: sample %d: crop origin (%d, %d) outside %dx%d",
-                    b, d.top, d.left, d.th, d.tw);
-    }
+    RUN_RC(check_replay_samples("replay_gather_logits", samples_host, B, capacity, H, W));
     LogitsGeom g;
     g.capacity = capacity; g.Hs = Hs; g.Ws = Ws; g.C = C; g.H = H; g.W = W;
     g.slot_stride = slot_stride;
@@ -577,19 +566,12 @@ int launch_replay_gather_logits_lowres(const float* slots, int64_t slot_stride, 
     AMS_REQUIRE(lh >= 1 && lh <= Hs && lw >= 1 && lw <= Ws, "replay_gather_logits_lowres: a %dx%d cache for %dx%d frames (1 <= lh <= src_h, 1 <= lw <= src_w)", lh,
                 lw, Hs, Ws);
     AMS_REQUIRE(slot_stride >= (int64_t)lh * lw * C, "replay_gather_logits_lowres: slot stride %lld below a %dx%dx%d slot", (long long)slot_stride, lh, lw, C);
-    for (int b = 0; b < B; ++b) {
-        const ams_replay_sample& d = samples_host[b];
-        AMS_REQUIRE(d.slot >= 0 && d.slot < capacity, "replay_gather_logits_lowres: sample %d draws slot %d of %d", b, d.slot, capacity);
-        AMS_REQUIRE(d.th > 0 && d.tw > 0 && d.th - H >= 0 && d.tw - W >= 0,
-                    "replay_gather_logits_lowres: sample %d: a %dx%d crop of a %dx%d image (negative slack)", b, H, W, d.th, d.tw);
-        AMS_REQUIRE(d.top >= 0 && d.left >= 0 && d.top <= d.th - H && d.left <= d.tw - W,
-                    "replay_gather_logits_lowres: sample %d: crop origin (%d, %d) outside %dx%d", b, d.top, d.left, d.th, d.tw);
-    }
+    RUN_RC(check_replay_samples("replay_gather_logits_lowres", samples_host, B, capacity, H, W));
     LowresGeom g;
     g.capacity = capacity; g.lh = lh; g.lw = lw; g.C = C; g.Hs = Hs; g.Ws = Ws; g.H = H; g.W = W;
     g.slot_stride = slot_stride;
-    g.sy = Hs > 1 ? (float)(lh - 1) / (float)(Hs - 1) : 0.f;          // as soft_teacher_geom does for a teacher grid under Hs x Ws labels
-    g.sx = Ws > 1 ? (float)(lw - 1) / (float)(Ws - 1) : 0.f;
+    g.sy = align_corners_scale(lh, Hs);                               // as soft_teacher_geom does for a teacher grid under Hs x Ws labels
+    g.sx = align_corners_scale(lw, Ws);
     note_kernel("replay_gather_logits_lowres_kernel");
     hipLaunchKernelGGL(replay_gather_logits_lowres_kernel, dim3(cdiv(W, kLogitsSeg), H, B), dim3(256), 0, st, slots, samples_dev, g, out);
     AMS_CHECK_LAUNCH();
@@ -650,8 +632,8 @@ int launch_teacher_labels_from_logits(const float* logits, int64_t slot_stride, 
     LabelGeom g;
     g.n = n; g.lh = lh; g.lw = lw; g.NC = NC; g.Hs = Hs; g.Ws = Ws;
     g.slot_stride = slot_stride; g.out_stride = out_stride;
-    g.sy = Hs > 1 ? (float)(lh - 1) / (float)(Hs - 1) : 0.f;          // as soft_teacher_geom does for a teacher grid under Hs x Ws labels
-    g.sx = Ws > 1 ? (float)(lw - 1) / (float)(Ws - 1) : 0.f;
+    g.sy = align_corners_scale(lh, Hs);                               // as soft_teacher_geom does for a teacher grid under Hs x Ws labels
+    g.sx = align_corners_scale(lw, Ws);
     // the widest segment whose cached columns (two rows of them, every class) fit: 128 pixels unless the classes are many and the grid dense
     const int ld = NC | 1;
     int seg = kLabelSeg, cols = label_segment_columns(Ws, lw, g.sx, seg);

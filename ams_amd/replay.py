@@ -364,23 +364,19 @@ class DeviceReplayMemory:
         th, tw, ch = self.logits_cached_shape
         batch = int(samples_host.shape[0])
         assert samples_host.dtype == np.int32 and samples_host.flags.c_contiguous and samples_dev.is_contiguous()
-        if crop is not None and not self.logits_at_source:
-            assert self.logits_upsample and out.numel() == batch * crop[0] * crop[1] * ch
-            hip.check(hip.lib().ams_replay_gather_logits_lowres(C.c_void_p(self._logits.data_ptr()), self.logits_stride, self.capacity, th, tw, ch,
-                                                                self.src_h, self.src_w, C.c_void_p(samples_dev.data_ptr()),
-                                                                samples_host.ctypes.data_as(C.c_void_p), batch, crop[0], crop[1],
-                                                                C.c_void_p(out.data_ptr()), self._stream()), "ams_replay_gather_logits_lowres")
-            return
-        if crop is not None:
-            assert out.numel() == batch * crop[0] * crop[1] * ch
-            hip.check(hip.lib().ams_replay_gather_logits(C.c_void_p(self._logits.data_ptr()), self.logits_stride, self.capacity, self.src_h, self.src_w,
-                                                         ch, C.c_void_p(samples_dev.data_ptr()), samples_host.ctypes.data_as(C.c_void_p), batch,
-                                                         crop[0], crop[1], C.c_void_p(out.data_ptr()), self._stream()), "ams_replay_gather_logits")
-            return
-        assert out.numel() == batch * th * tw * ch
-        hip.check(hip.lib().ams_replay_gather_f32(C.c_void_p(self._logits.data_ptr()), self.logits_stride, self.capacity, th, tw, ch,
-                                                  C.c_void_p(samples_dev.data_ptr()), samples_host.ctypes.data_as(C.c_void_p), batch,
-                                                  C.c_void_p(out.data_ptr()), self._stream()), "ams_replay_gather_f32")
+        oh, ow = (th, tw) if crop is None else crop
+        assert out.numel() == batch * oh * ow * ch
+        slots = (C.c_void_p(self._logits.data_ptr()), self.logits_stride, self.capacity)
+        samples = (C.c_void_p(samples_dev.data_ptr()), samples_host.ctypes.data_as(C.c_void_p), batch)
+        tail = (C.c_void_p(out.data_ptr()), self._stream())
+        if crop is None:
+            name, args = "ams_replay_gather_f32", slots + (th, tw, ch) + samples + tail
+        elif self.logits_at_source:
+            name, args = "ams_replay_gather_logits", slots + (self.src_h, self.src_w, ch) + samples + (oh, ow) + tail
+        else:
+            assert self.logits_upsample
+            name, args = "ams_replay_gather_logits_lowres", slots + (th, tw, ch, self.src_h, self.src_w) + samples + (oh, ow) + tail
+        hip.check(getattr(hip.lib(), name)(*args), name)
 
     def gather(self, samples: np.ndarray, H: int, W: int):
         """One mini-batch for ``[batch, 6]`` descriptors with logical slots: fresh device tensors (frames uint8 [batch,H,W,3], labels uint8

@@ -1,7 +1,8 @@
 """NumPy restatement of ``ams_teacher_labels_from_logits`` (include/ams_hip.h): label(Y, X) = argmax_c U(Y, X, c), where U is the
 align-corners upsample of the cached teacher logits by the soft loss kernel's arithmetic, float32 operations one at a time (f32 scale, f32
 product, f32 weights, bilerp's operation order, the cached sample itself on a grid point), and the argmax is tf.argmax's (the first maximum).
-Shared by the CPU and the GPU tests of the derived labels; nothing here touches a device."""
+``src_taps`` / ``upsample`` are the only restatement of Stage U: the CPU and the GPU tests of the derived labels and the GPU tests of the
+low-resolution logits gather share them; nothing here touches a device."""
 import numpy as np
 
 

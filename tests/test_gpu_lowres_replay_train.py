@@ -1,6 +1,6 @@
 """Soft-teacher fine-tuning from a replay memory whose teacher logits are cached on a small grid (``logits_upsample=True``): a phase on it
 equals, loss for loss and bit for bit in every variable, the same phase on a full-size memory whose slots hold the NumPy restatement of the
-grid's align-corners upsample (U, tests/test_gpu_replay_logits_lowres.py), with the same seeds.
+grid's align-corners upsample (U, tests/teacher_labels_ref.py), with the same seeds.
 
 The whole-frames phase pins the definition: there the small grid goes through the whole-slot entry and the loss kernel's own upsample, so
 equality says that the restated U is the loss kernel's interpolation.  The augmented phase (two scales, flips) is the feature."""
@@ -12,7 +12,7 @@ import pytest
 from ams_amd import exp_configs, spec as S, weights as Wt
 from ams_amd.replay import DeviceReplayMemory, draw_samples
 from ams_amd.semantic_network import SemanticNetwork
-from test_gpu_replay_logits_lowres import upsample
+from teacher_labels_ref import upsample
 
 pytestmark = pytest.mark.gpu
 

@@ -1,7 +1,7 @@
 """Teacher logits cached on a grid smaller than the frame through the replay memory's descriptors (ams_replay_gather_logits_lowres,
 k_replay.hip).  The rule (include/ams_hip.h): a low-resolution slot behaves, bit for bit, as a frame-size slot that holds its own
-align-corners upsample.  Stage U, the upsample by the soft loss kernel's arithmetic, is restated here in NumPy — f32 scale, f32 product, f32
-weights, bilerp's operation order, the cached sample itself on a grid point; Stage G is the restatement of tests/test_gpu_replay_logits.py.
+align-corners upsample.  Stage U, the upsample by the soft loss kernel's arithmetic, is restated in NumPy in tests/teacher_labels_ref.py — f32
+scale, f32 product, f32 weights, bilerp's operation order, the cached sample itself on a grid point; Stage G is the restatement of tests/test_gpu_replay_logits.py.
 The expected value is ``resample_batch(U(slots), desc, H, W)`` and the kernel must give its bits.
 
 The three rescaling cases are that file's, each with its own source size (an exact 2x down-scale to a 16 x 32 crop does not exist for 24 x 40
@@ -14,6 +14,7 @@ import torch
 
 from ams_amd import hip
 from ams_amd.replay import DeviceReplayMemory
+from teacher_labels_ref import src_taps, upsample
 from test_gpu_replay_logits import CROP, RESCALE, SRC, _bits, _logits, resample_batch
 
 pytestmark = pytest.mark.gpu
@@ -23,35 +24,6 @@ E_INVALID = -1                    # AMS_E_INVALID (include/ams_hip.h)
 GRIDS = [(5, 9), (3, 5), (1, 1), (24, 9), (5, 40)]
 CHANNELS = [19, 21, 1, 8]
 CI6 = [0, 1, 2, 10, 11, 13]
-
-
-# ---------------------------------------------------------------------------------------------------------
-# Stage U, restated
-# ---------------------------------------------------------------------------------------------------------
-def src_taps(n_out, n_in):
-    """src_tap of head_common.hpp for every position of an axis of n_out points over n_in cached ones: lo, hi, weight (f32)"""
-    scale = np.float32(n_in - 1) / np.float32(n_out - 1) if n_out > 1 else np.float32(0)
-    assert scale.dtype == np.float32
-    src = np.arange(n_out, dtype=np.float32) * scale
-    fl = np.floor(src)
-    t = src - fl
-    assert src.dtype == np.float32 and t.dtype == np.float32
-    lo = fl.astype(np.int64)
-    return lo, np.minimum(lo + 1, n_in - 1), t
-
-
-def upsample(t, src_h, src_w):
-    """The virtual frame-size logits of one slot: ``t`` f32 [lh, lw, C] -> f32 [src_h, src_w, C]."""
-    t = np.asarray(t, dtype=np.float32)
-    ylo, yhi, ty = src_taps(src_h, t.shape[0])
-    xlo, xhi, tx = src_taps(src_w, t.shape[1])
-    tl, tr, bl, br = t[ylo][:, xlo], t[ylo][:, xhi], t[yhi][:, xlo], t[yhi][:, xhi]
-    tx, ty = tx[None, :, None], ty[:, None, None]
-    top = tl + (tr - tl) * tx
-    bot = bl + (br - bl) * tx
-    v = top + (bot - top) * ty
-    assert v.dtype == np.float32
-    return np.where((ty == 0) & (tx == 0), tl, v)                  # a grid point is the cached sample itself
 
 
 def assert_interpolates(grid, src):

@@ -101,46 +101,11 @@ def time_gather(mem, H, scale, batch, reps, warmup):
     return stats(us)
 
 
-def time_device_phases(net, mem, iters, reps, warmup):
-    """the device path alone; per-phase wall times in ms"""
+def alternating_phases(net, mems, iters, reps, warmup):
+    """``mems`` = {name: memory}: within every repetition one device-path phase from each in turn, equal seeds; per-phase wall times in ms
+    by name"""
     dev = net.engine.device
-    ms = []
-    for r in range(warmup + reps):
-        seed(100 + r)
-        torch.cuda.synchronize(dev)
-        t0 = time.perf_counter()
-        net.train_with_deque(mem, None, iters, "full_model")
-        torch.cuda.synchronize(dev)
-        if r >= warmup:
-            ms.append((time.perf_counter() - t0) * 1e3)
-    return stats(ms)
-
-
-def time_logits_gather(mem, H, scale, flip, batch, reps, warmup):
-    """HIP events around the logits gather of a mini-batch alone (the frames' gather is not in the window)"""
-    dev = mem.device
-    st = torch.cuda.current_stream(dev)
-    seed(7)
-    plan = mem.plan(draw_samples(len(mem), (mem.src_h, mem.src_w), [H, 2 * H], scale, batch, warmup + reps, flip=flip), H, 2 * H)
-    assert not plan.whole_frames
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    us = []
-    for r in range(warmup + reps):
-        torch.cuda.synchronize(dev)
-        e0.record(st)
-        mem._gather_logits(plan.table_host[r], plan.table_dev[r], plan.logits, (H, 2 * H))
-        e1.record(st)
-        torch.cuda.synchronize(dev)
-        if r >= warmup:
-            us.append(e0.elapsed_time(e1) * 1e3)
-    return stats(us)
-
-
-def time_layouts(net, mems, H, scale, flip, batch, iters, reps, warmup):
-    """case e: ``mems`` = {"full": memory, "selected": memory} with equal contents; the layouts alternate within every repetition"""
-    dev = net.engine.device
-    st = torch.cuda.current_stream(dev)
-    phase_ms = {k: [] for k in mems}
+    ms = {k: [] for k in mems}
     for r in range(warmup + reps):
         for k, mem in mems.items():
             seed(100 + r)
@@ -149,12 +114,22 @@ def time_layouts(net, mems, H, scale, flip, batch, iters, reps, warmup):
             net.train_with_deque(mem, None, iters, "full_model")
             torch.cuda.synchronize(dev)
             if r >= warmup:
-                phase_ms[k].append((time.perf_counter() - t0) * 1e3)
+                ms[k].append((time.perf_counter() - t0) * 1e3)
+    return ms
+
+
+def alternating_logits_gathers(mems, H, scale, flip, batch, reps, warmup):
+    """``mems`` = {name: memory} of equal frame size: HIP events around the logits gather of a mini-batch alone (the frames' gather is not in
+    the window), equal descriptors, the memories in turn within every repetition; times in us by name"""
+    first = next(iter(mems.values()))
+    dev = first.device
+    st = torch.cuda.current_stream(dev)
     seed(7)
-    samples = draw_samples(len(mems["full"]), (H, 2 * H), [H, 2 * H], scale, batch, warmup + reps, flip=flip)
+    samples = draw_samples(len(first), (first.src_h, first.src_w), [H, 2 * H], scale, batch, warmup + reps, flip=flip)
     plans = {k: mem.plan(samples, H, 2 * H) for k, mem in mems.items()}
+    assert not any(p.whole_frames for p in plans.values())
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    gather_us = {k: [] for k in mems}
+    us = {k: [] for k in mems}
     for r in range(warmup + reps):
         for k, mem in mems.items():
             plan = plans[k]
@@ -164,7 +139,28 @@ def time_layouts(net, mems, H, scale, flip, batch, iters, reps, warmup):
             e1.record(st)
             torch.cuda.synchronize(dev)
             if r >= warmup:
-                gather_us[k].append(e0.elapsed_time(e1) * 1e3)
+                us[k].append(e0.elapsed_time(e1) * 1e3)
+    return us
+
+
+def time_device_phases(net, mem, iters, reps, warmup):
+    """the device path alone; per-phase wall times in ms"""
+    return stats(alternating_phases(net, {"device": mem}, iters, reps, warmup)["device"])
+
+
+def time_logits_gather(mem, H, scale, flip, batch, reps, warmup):
+    """HIP events around the logits gather of a mini-batch alone, one memory"""
+    return stats(alternating_logits_gathers({"device": mem}, H, scale, flip, batch, reps, warmup)["device"])
+
+
+def time_layouts(net, mems, H, scale, flip, batch, iters, reps, warmup):
+    """case e: ``mems`` = {"full": memory, "selected": memory} with equal contents; the layouts alternate within every repetition, first the
+    phases, then the logits gather alone, then one append"""
+    dev = net.engine.device
+    st = torch.cuda.current_stream(dev)
+    phase_ms = alternating_phases(net, mems, iters, reps, warmup)
+    gather_us = alternating_logits_gathers(mems, H, scale, flip, batch, reps, warmup)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     # one append: the frame and the label are device tensors in both forms, so that the window holds the logits' way in
     f_dev, l_dev, t_dev = (x.clone() for x in mems["full"][0])
     t_host = t_dev.cpu().numpy()
@@ -197,34 +193,8 @@ def time_layouts(net, mems, H, scale, flip, batch, iters, reps, warmup):
 def time_lowres(net, mems, H, scale, flip, batch, iters, reps, warmup):
     """case f: ``mems`` = {"full_size": memory, "lowres": memory}, frames and labels equal, the small cache standing for its upsample; the two
     alternate within every repetition, first the phases, then the logits gather alone"""
-    dev = net.engine.device
-    st = torch.cuda.current_stream(dev)
-    phase_ms = {k: [] for k in mems}
-    for r in range(warmup + reps):
-        for k, mem in mems.items():
-            seed(100 + r)
-            torch.cuda.synchronize(dev)
-            t0 = time.perf_counter()
-            net.train_with_deque(mem, None, iters, "full_model")
-            torch.cuda.synchronize(dev)
-            if r >= warmup:
-                phase_ms[k].append((time.perf_counter() - t0) * 1e3)
-    seed(7)
-    samples = draw_samples(len(mems["full_size"]), (H, 2 * H), [H, 2 * H], scale, batch, warmup + reps, flip=flip)
-    plans = {k: mem.plan(samples, H, 2 * H) for k, mem in mems.items()}
-    assert not any(p.whole_frames for p in plans.values())
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    gather_us = {k: [] for k in mems}
-    for r in range(warmup + reps):
-        for k, mem in mems.items():
-            plan = plans[k]
-            torch.cuda.synchronize(dev)
-            e0.record(st)
-            mem._gather_logits(plan.table_host[r], plan.table_dev[r], plan.logits, (H, 2 * H))
-            e1.record(st)
-            torch.cuda.synchronize(dev)
-            if r >= warmup:
-                gather_us[k].append(e0.elapsed_time(e1) * 1e3)
+    phase_ms = alternating_phases(net, mems, iters, reps, warmup)
+    gather_us = alternating_logits_gathers(mems, H, scale, flip, batch, reps, warmup)
     out = {}
     for k, mem in mems.items():
         out[k] = {"logits_cached_shape": list(mem.logits_cached_shape), "memory_bytes": mem.nbytes, "slot_bytes": mem.nbytes // mem.capacity,
