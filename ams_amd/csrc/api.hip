@@ -457,6 +457,10 @@ int ams_student_set_option(ams_student* s, int32_t option, int32_t value) {
         s->overlap_head = value != 0;
         return AMS_OK;
     }
+    if (option == AMS_OPT_FUSE_HEAD) {
+        s->fuse_head = value < 0 ? 0 : value & 3;
+        return AMS_OK;
+    }
     if (option == AMS_OPT_STREAM_MIN_ROWS) {
         AMS_REQUIRE(value >= 0, "set_option: AMS_OPT_STREAM_MIN_ROWS must be >= 0");
         s->stream_min_rows = value;

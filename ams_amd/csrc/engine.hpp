@@ -148,6 +148,9 @@ struct ams_student {
     int overlap_head = 0;            // frozen inference: image-pooling branch on the side stream beside the aspp0 GEMM (AMS_OVERLAP_HEAD).
                                      // Off: measured 3.63 vs 3.61 ms at 32 frames and 1.90 k vs 2.01 k frames/s at one — the fork / join events
                                      // cost more than the three small launches they hide
+    int fuse_head = 3;               // frozen inference (AMS_OPT_FUSE_HEAD), bit 0: aspp0 -> concat_projection -> logits as one chained kernel where all
+                                     // three run the fp16 product (k_head_chain.hip); bit 1: the project GEMMs in front of a streamed block without a
+                                     // residual skip the f32 copy of their result (PwArgs::y_skip_f32); 0 = the plan before both
     int overlap_wgrad = 1;
     int wgrad_fork_every = 1;        // weight gradients per hand-over to the side stream (AMS_OPT_WGRAD_FORK_EVERY)
     int train_fwd_f16 = 0;           // fine-tune step under AMS_MATMUL_SPLIT_F16: 1 = the FORWARD 1x1 products on two fp16 parts (AMS_OPT_TRAIN_FWD_F16).
@@ -240,7 +243,9 @@ static inline PwArgs pw_args(const float* x, int64_t M, int K, int ldx, const fl
 // algorithmic bytes (f32 storage): every operand read once, every result written once
 static inline double pw_bytes(const PwArgs& a) {
     // (+ the part planes of the result a project GEMM leaves for the streaming kernel of the next block: 2 bytes per value and part)
-    return 4.0 * ((double)a.M * (a.K + a.N + (a.res ? a.N : 0)) + (double)a.Kw * a.N) + (a.ysplit ? 2.0 * a.ysplit_np * (double)a.M * a.N : 0.0);
+    // (... which are its only form where PwArgs::y_skip_f32 drops the f32 store)
+    return 4.0 * ((double)a.M * (a.K + (a.ysplit && a.y_skip_f32 ? 0 : a.N) + (a.res ? a.N : 0)) + (double)a.Kw * a.N) +
+           (a.ysplit ? 2.0 * a.ysplit_np * (double)a.M * a.N : 0.0);
 }
 static inline double dw_bytes(const LayerRt& l, int B) { return 4.0 * ((double)B * (l.px_in + l.px_out) * l.d.cin + 9.0 * l.d.cin); }
 

@@ -79,7 +79,8 @@ static FrozenView view_slice(const ams_student* s, const void* frames, int dtype
 // bf16 / fp16 parts of a block input in FrozenView::xsplit, as the project GEMM in front of a streamed block leaves them
 struct PartsFmt { int np = 0, fmt = 0; };      // np 0: none; PwArgs::ysplit_np / ysplit_fmt
 // where a pass stands: the next layer, its input (in act[cur_i]) and what else exists of that input
-struct Cursor { int i; const float* cur; int cur_i; PartsFmt parts; };
+// cur_f32: act[cur_i] really holds that input as f32 (false: the project GEMM before wrote the part planes only, BlockPlan::out_parts_only)
+struct Cursor { int i; const float* cur; int cur_i; PartsFmt parts; bool cur_f32 = true; };
 
 static int other(const FrozenView& v, int avoid0, int avoid1) {
     for (int k = 0; k < 4; ++k) if (k != avoid0 && k != avoid1 && k != v.reserved) return k;
@@ -103,6 +104,7 @@ struct BlockPlan {
     bool d_h2i = false;                        // the depthwise result reaches the project GEMM as fp16 pairs (PwArgs::x_fmt 1)
     PwForm project_form = PW_F32;
     PartsFmt out;                              // what the project GEMM leaves in xsplit for the next block
+    bool out_parts_only = false;               // ... and nothing else: the next block reads the planes and adds no residual (PwArgs::y_skip_f32)
 };
 
 // arguments of the backbone's 1x1 layer `layer` over B frames; `res`: the block input, where the layer adds it.  The planner asks with
@@ -223,6 +225,14 @@ static BlockPlan plan_block(const ams_student* s, const FrozenView& v, int i, Pa
     if (stream_ok(s, B, ij + 1) && v.xsplit && (size_t)a.M * a.N <= v.xsplit_plane && p.project_form != PW_F32 && pointwise_split_writes_parts(a) &&
         !(s->emulate_bf16_storage && lj.px_out == (int64_t)s->h * s->w))       // (the parts would be those of the unrounded result)
         p.out = stream_parts(s, ij + 1);
+    // The f32 copy of that result is read again only as the next block's residual or by a streaming kernel that was not given parts.  The
+    // next block (expand ij + 1, depthwise, project ij + 3) streams on the planes (stream_ok above, and in.np admits every width); without a
+    // residual there nothing reads the f32 form: 4 M N bytes the fp16 GEMM's vector epilogue does not store
+    // (not across the boundary between the early section and a sub-batched late one: the late passes start without parts)
+    if ((s->fuse_head & 2) && p.out.np && p.project_form == PW_F16 && !s->emulate_bf16_storage && !(s->late_subbatch > 0 && B > s->late_subbatch) && ij + 3 <= nb && role(ij + 3) == AMS_ROLE_PROJECT &&
+        !s->L[ij + 3].d.residual_from && !(s->fuse_block && block_fused_supported(s->L[ij + 1].d.cin, s->L[ij + 1].d.cout, s->L[ij + 3].d.cout,
+                                                                                  s->L[ij + 2].d.stride, s->L[ij + 2].d.rate, false)))
+        p.out_parts_only = true;
     return p;
 }
 
@@ -285,11 +295,12 @@ static int run_project(ams_student* s, const FrozenView& v, Cursor& c, const Blo
     const int o = other(v, c.cur_i, d_i);
     PwArgs a = layer_args(s, ij, v.B, d, v.act[o], c.cur);
     a.x_fmt = p.d_h2i ? 1 : 0;
-    if (p.out.np) { a.ysplit = v.xsplit; a.ysplit_plane = a.M * a.N; a.ysplit_np = p.out.np; a.ysplit_fmt = p.out.fmt; }
+    AMS_REQUIRE(!a.res || c.cur_f32, "engine: layer %d adds a block input that was left as part planes only", ij);
+    if (p.out.np) { a.ysplit = v.xsplit; a.ysplit_plane = a.M * a.N; a.ysplit_np = p.out.np; a.ysplit_fmt = p.out.fmt; a.y_skip_f32 = p.out_parts_only ? 1 : 0; }
     RUN(frozen_pointwise(s, ij, a, p.project_form, st));
     if (s->emulate_bf16_storage && l.px_out == (int64_t)s->h * s->w)
         RUN(launch_round_bf16(v.act[o], (int64_t)v.B * l.px_out * l.d.cout, st));            // block input as bf16 storage would hold it
-    c.cur = v.act[o]; c.cur_i = o; c.i = ij + 1; c.parts = p.out;
+    c.cur = v.act[o]; c.cur_i = o; c.i = ij + 1; c.parts = p.out; c.cur_f32 = !p.out_parts_only;
     return AMS_OK;
 }
 
@@ -326,6 +337,9 @@ static int run_block_expand_dw(ams_student* s, const FrozenView& v, Cursor& c, c
     const double bytes = 4.0 * ((double)B * (le.px_in * le.d.cin + ld.px_out * ld.d.cout) + (double)le.d.cin * le.d.cout + 9.0 * ld.d.cin);
     const uint16_t* x_parts = p.in.np ? v.xsplit : nullptr;
     const int64_t xplane = (int64_t)B * le.px_in * le.d.cin;
+    // a block input left as part planes only (BlockPlan::out_parts_only): c.cur names its buffer, but only the planes may be read
+    AMS_REQUIRE(c.cur_f32 || (x_parts && (p.form == BLOCK_WREG || (p.form == BLOCK_STREAM && le.d.cin > 32))),
+                "engine: block at layer %d reads an f32 input that was left as part planes only", i);
     if (p.form == BLOCK_TILED)
         RUNK(i + 1, bytes, launch_expand_dw(c.cur, B, le.Hin, le.Win, le.d.cin, P + le.d.w_off, le.fscale, le.fshift, le.d.act, le.d.cout,
                                             P + ld.d.w_off, ld.d.stride, ld.d.rate, ld.fscale, ld.fshift, ld.d.act, v.act[o], st));
@@ -377,6 +391,7 @@ static int run_block_layers(ams_student* s, const FrozenView& v, Cursor& c, cons
 static int run_blocks(ams_student* s, const FrozenView& v, Cursor& c, int i_stop, hipStream_t st) {
     while (c.i <= s->n_backbone && c.i < i_stop) {
         const BlockPlan p = plan_block(s, v, c.i, c.parts);
+        AMS_REQUIRE(c.cur_f32 || p.form == BLOCK_STREAM || p.form == BLOCK_WREG, "engine: block at layer %d reads an f32 input that was left as part planes only", c.i);
         switch (p.form) {
             case BLOCK_WHOLE: RUN(run_block_whole(s, v, c, p, st)); break;
             case BLOCK_TILED: case BLOCK_STREAM: case BLOCK_WREG: RUN(run_block_expand_dw(s, v, c, p, st)); break;
@@ -391,6 +406,7 @@ static int run_head(ams_student* s, const FrozenView& v, const Cursor& c, hipStr
     const float* P = s->fparams;
     const LayerRt& lp = s->L[s->iPool]; const LayerRt& la = s->L[s->iAspp]; const LayerRt& lc = s->L[s->iProj]; const LayerRt& ll = s->L[s->iLogits];
     const int B = v.B;
+    AMS_REQUIRE(c.cur_f32, "engine: the head reads an f32 input that was left as part planes only");
     const int64_t HW = (int64_t)s->h * s->w, M = (int64_t)B * HW;
     // The image-pooling branch (global mean -> 1x1 + BN + ReLU -> its share of concat_projection as a per-image bias) is three
     // latency-bound launches on a handful of rows (58 us at 32 frames, 22 us at one).  With overlap_head it runs on the side stream
@@ -418,15 +434,32 @@ static int run_head(ams_student* s, const FrozenView& v, const Cursor& c, hipStr
     const int o1 = other(v, c.cur_i, -1), o2 = other(v, c.cur_i, o1);
     PwArgs a = pw_args(c.cur, M, la.d.cin, la.d.cin, P + la.d.w_off, la.d.cout, v.act[o1], la.d.cout);
     a.scale = la.fscale; a.shift = la.fshift; a.act = la.d.act;
-    RUN(frozen_pointwise(s, s->iAspp, a, pointwise_form(s, s->iAspp, a, false), st));
-    if (fork) AMS_CHECK_HIP(hipStreamWaitEvent(st, s->ev_head, 0));
     PwArgs b = pw_args(v.act[o1], M, la.d.cout, la.d.cout, P + lc.d.w_off + (int64_t)lp.d.cout * lc.d.cout, lc.d.cout,
                        v.act[o2], lc.d.cout);
     b.img_bias = v.img_bias; b.rows_per_img = HW; b.scale = lc.fscale; b.shift = lc.fshift; b.act = lc.d.act;
-    RUN(frozen_pointwise(s, s->iProj, b, pointwise_form(s, s->iProj, b, false), st));
     PwArgs d = pw_args(v.act[o2], M, lc.d.cout, lc.d.cout, P + ll.d.w_off, ll.d.cout, v.logits, 32);
     d.shift = P + ll.d.gamma_off;      // biases
-    RUN(frozen_pointwise(s, s->iLogits, d, pointwise_form(s, s->iLogits, d, false), st));
+    const PwForm fa = pointwise_form(s, s->iAspp, a, false), fb = pointwise_form(s, s->iProj, b, false), fd = pointwise_form(s, s->iLogits, d, false);
+    // The three GEMMs as one chained kernel (k_head_chain.hip): only where each of them would run the two-fp16-part product — a layer the
+    // freeze moved off it (whf == nullptr), another matmul mode or too few rows for the split forms keep the three launches, whose bits
+    // the chain reproduces
+    // (a sub-batched late section, AMS_OPT_LATE_SUBBATCH, keeps them too: the option is off by default and its passes are told apart by their GEMMs)
+    if ((s->fuse_head & 1) && !s->emulate_bf16_storage && !(s->late_subbatch > 0) && fa == PW_F16 && fb == PW_F16 && fd == PW_F16 && la.Kp == la.d.cin && lc.Kp == la.d.cout &&
+        ll.Kp == lc.d.cout && head_chain_supported(la.d.cin, la.d.cout, la.d.cout, lc.d.cout, lc.d.cout, ll.d.cout)) {
+        if (fork) AMS_CHECK_HIP(hipStreamWaitEvent(st, s->ev_head, 0));
+        // bytes: the operand, the three panels (two fp16 parts), the vectors and the 32-column logits
+        const double bytes = 4.0 * M * (la.d.cin + 32) + 4.0 * ((double)la.Kp * la.d.cout + (double)lc.Kp * lc.d.cout + (double)ll.Kp * ll.d.cout) +
+                             4.0 * (2.0 * la.d.cout + 2.0 * lc.d.cout + ll.d.cout + (double)B * lc.d.cout);
+        s->prof_flops_x6 = 2.0 * M * ((double)la.d.cin * la.d.cout + (double)la.d.cout * lc.d.cout + (double)lc.d.cout * ll.d.cout);
+        RUNK(s->iLogits, bytes, launch_head_chain(c.cur, M, la.d.cin, la.whf, (int64_t)la.d.cout * la.Kp, la.fscale, la.fshift, la.d.act,
+                                                  lc.whf, (int64_t)lc.d.cout * lc.Kp, lc.fscale, lc.fshift, lc.d.act, v.img_bias, HW,
+                                                  ll.whf, (int64_t)ll.d.cout * ll.Kp, d.shift, d.act, ll.d.cout, v.logits, st));
+        return AMS_OK;
+    }
+    RUN(frozen_pointwise(s, s->iAspp, a, fa, st));
+    if (fork) AMS_CHECK_HIP(hipStreamWaitEvent(st, s->ev_head, 0));
+    RUN(frozen_pointwise(s, s->iProj, b, fb, st));
+    RUN(frozen_pointwise(s, s->iLogits, d, fd, st));
     return AMS_OK;
 }
 
@@ -450,6 +483,7 @@ static int forward_frozen(ams_student* s, const FrozenView& v, int dtype, hipStr
     for (int b0 = 0; b0 < v.B; b0 += s->late_subbatch) {
         const int bp = v.B - b0 < s->late_subbatch ? v.B - b0 : s->late_subbatch;
         const FrozenView lv = view_late(s, v, b0, bp, c.cur_i);
+        AMS_REQUIRE(c.cur_f32, "engine: the late section's input was left as part planes only");
         Cursor lc = {i_late, c.cur + (int64_t)b0 * late_in_frame, c.cur_i, PartsFmt()};
         RUN(run_blocks(s, lv, lc, s->n_backbone + 1, st));
         RUN(run_head(s, lv, lc, st));

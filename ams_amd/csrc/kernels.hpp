@@ -72,6 +72,7 @@ struct PwArgs {
     int64_t ysplit_plane;
     int ysplit_np;
     int ysplit_fmt;        // 0: bf16 parts; 1: two fp16 parts (hi | lo 2^11; ysplit_np = 2), the operand format of the fp16 streaming kernels
+    int y_skip_f32;        // with ysplit, vector epilogues: the part planes are the ONLY form of the result — y is not written (nothing may read it)
     // operand storage (launch_pointwise_split_f16 only): 0 = f32; 1 = "H2I", fp16 (hi | lo 2^11) pairs interleaved per 8 channels — 16 bytes
     // of hi, 16 bytes of lo — at the same 4 K bytes per row as f32 (requires ldx == K)
     int x_fmt;
@@ -128,6 +129,12 @@ bool pointwise_f16_applies(const PwArgs& a);
 int launch_pointwise_split_f16(const PwArgs& a, const uint16_t* whi, int64_t plane, int Kp, hipStream_t st);
 int launch_pack_h2i(const float* x, int64_t M, int C, float* out, hipStream_t st);      // f32 [M][C] -> H2I (PwArgs::x_fmt 1)
 bool pointwise_split_writes_parts(const PwArgs& a);      // the split kernels will honour a.ysplit (vector epilogue)
+// the frozen head's three GEMMs (aspp0 -> concat_projection + per-image bias -> logits) as one kernel on the same fp16 panels, bit-identical to
+// the three launch_pointwise_split_f16 calls it replaces (k_head_chain.hip); y [M][32], NC <= 32 columns written
+bool head_chain_supported(int KA, int NA, int KB, int NB, int KC, int NC);
+int launch_head_chain(const float* x, int64_t M, int KA, const uint16_t* wA, int64_t planeA, const float* scA, const float* shA, int actA,
+                      const uint16_t* wB, int64_t planeB, const float* scB, const float* shB, int actB, const float* img_bias, int64_t rows_per_img,
+                      const uint16_t* wC, int64_t planeC, const float* biasC, int actC, int NC, float* y, hipStream_t st);
 
 // dw[K,N] = x[M,K]^T @ dy[M,N];  scratch holds the per-split partial products.
 struct WgArgs {

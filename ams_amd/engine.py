@@ -28,6 +28,7 @@ _ENV_OPTIONS = {
     "AMS_OVERLAP_WGRAD": hip.OPT_OVERLAP_WGRAD, "AMS_FUSE_DGRAD_BN": hip.OPT_FUSE_DGRAD_BN, "AMS_FUSE_GEMM_RED": hip.OPT_FUSE_GEMM_RED,
     "AMS_TRAIN_RECOMPUTE": hip.OPT_TRAIN_RECOMPUTE, "AMS_NAN_GRADS": hip.OPT_NAN_GRADS, "AMS_FUSE_OPERAND_BN": hip.OPT_FUSE_OPERAND_BN,
     "AMS_WGRAD_FORK_EVERY": hip.OPT_WGRAD_FORK_EVERY, "AMS_TRAIN_FWD_F16": hip.OPT_TRAIN_FWD_F16,
+    "AMS_FUSE_HEAD": hip.OPT_FUSE_HEAD,
 }
 
 
@@ -364,6 +365,12 @@ class StudentEngine:
     def set_fuse_block(self, on: bool) -> None:
         """Frozen inference: every early block with Cin <= 32 as ONE kernel (expand + depthwise + project [+ input]; default on)."""
         hip.check(self.lib.ams_student_set_option(self._h, hip.OPT_FUSE_BLOCK, int(bool(on))), "ams_student_set_option")
+
+    def set_fuse_head(self, on) -> None:
+        """Frozen inference, two bits: 1 = aspp0 -> concat_projection -> logits as one chained kernel where all three layers run the fp16
+        product; 2 = no f32 store of a project result that only the next block's part planes carry on.  True = both (3, the default),
+        False = the three GEMMs and every store.  Bit-identical for every value."""
+        hip.check(self.lib.ams_student_set_option(self._h, hip.OPT_FUSE_HEAD, 3 if on is True else int(on)), "ams_student_set_option")
 
     def set_fuse_expand_dw(self, on: int) -> None:
         """Frozen inference, expand + depthwise of a block as one kernel: 0 never, 1 (default) the blocks where it is

@@ -39,6 +39,7 @@ OPT_DUAL_PARTS = 13
 OPT_NAN_GRADS = 18
 OPT_TRAIN_FWD_F16 = 24
 OPT_SOFT_TEACHER = 25
+OPT_FUSE_HEAD = 26
 TLOGITS_FULL, TLOGITS_SELECTED = 0, 1          # AMS_TLOGITS_*: teacher logits [..., num_classes] / [..., K] (the student's classes, in order)
 TLOGITS_LAYOUTS = {"full": TLOGITS_FULL, "selected": TLOGITS_SELECTED}
 OPT_OVERLAP_WGRAD = 19

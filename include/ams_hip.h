@@ -274,7 +274,11 @@ int ams_student_train_step_rccl(ams_student* s, const void* frames_dev, int32_t 
  *   AMS_MATMUL_SPLIT_F16     frozen inference with two fp16 parts / 3 MFMAs, f32-level (see the enum below)
  *   AMS_MATMUL_SPLIT_BF16    frozen inference with two parts / 3 MFMAs: +5 % frames/s, ~1e-5 per layer, 2e-4 .. 5e-4 on
  *                            the logits (inside the 1e-3 tolerance, not at f32 level); the fine-tune step stays three-part. */
-enum { AMS_OPT_SOFT_TEACHER = 25 /* fine-tune step: 1 = soft-teacher loss (ams_student_feed_teacher_logits); 0 (default) hard labels */,
+enum { AMS_OPT_FUSE_HEAD = 26 /* frozen inference, two bits (default 3).  Bit 0: the head's three GEMMs (aspp0, concat_projection, logits) as ONE chained
+                                kernel where all three run the two-fp16-part product (k_head_chain.hip: the 256-wide f32 tensors between them are never
+                                written; not under AMS_OPT_LATE_SUBBATCH).  Bit 1: the project GEMMs whose f32 result nothing reads (the next block streams
+                                on the part planes and adds no residual) store the planes only.  0 = three launches, every store.  Same bits for every value */,
+       AMS_OPT_SOFT_TEACHER = 25 /* fine-tune step: 1 = soft-teacher loss (ams_student_feed_teacher_logits); 0 (default) hard labels */,
        AMS_OPT_TRAIN_FWD_F16 = 24 /* fine-tune step under AMS_MATMUL_SPLIT_F16: 1 = the FORWARD 1x1 products of the split layers run on two fp16
                                       parts (3 MFMAs; the per-step weight split leaves fp16 planes beside the bf16 ones), the input-gradient and weight-
                                       gradient products stay on three bf16 parts (gradients span a range fp16 cannot hold); 0 (default) = three bf16
