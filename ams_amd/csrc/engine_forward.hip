@@ -568,10 +568,16 @@ static int bn_from_partials(ams_student* s, LayerRt& l, const BnEma& e, const fl
 
 // pre_rows > 0: the kernel that wrote l.z already left the statistics' partial rows [pre_rows][2][C] in s->scratch
 static int bn_train(ams_student* s, LayerRt& l, int64_t M_local, double n_global, bool update_ema, const SyncCtx* sc,
-                    const float* res, hipStream_t st, int pre_rows = 0, bool act_pass = true) {
+                    const float* res, hipStream_t st, int pre_rows = 0, bool act_pass = true, bool f64_sums = false) {
     const BnEma e = bn_ema(s, l, update_ema);
     if (pre_rows > 0) {
         RUN(bn_from_partials(s, l, e, s->scratch, pre_rows, 2 * (int64_t)l.d.cout, n_global, sc, st));
+    } else if (f64_sums) {
+        // a layer of a few rows: the sums in f64 throughout (k_elementwise.hip colstats_f64_kernel), the same launches with and without ranks
+        RUN(launch_colstats_f64(l.z, M_local, l.d.cout, e.center, l.fsums, st));
+        RUN(sync_doubles(sc, l.fsums, 2 * (size_t)l.d.cout, st));
+        RUN(launch_bn_finalize(l.fsums, n_global, l.d.cout, e.center, s->params + l.d.gamma_off, s->params + l.d.beta_off, l.d.bn_eps, e.omd,
+                               e.mm, e.mv, l.scale, l.shift, l.mean, l.rstd, st));
     } else if (!sc || !sc->cb) {
         // no cross-rank sum between the statistics and their use: the reduction's second stage finishes the BN arithmetic
         RUNK(0, 4.0 * M_local * l.d.cout,
@@ -697,7 +703,7 @@ int forward_live(ams_student* s, const void* frames, int dtype, int B, int globa
     {
         PwArgs a = pw_args(s->pooled, B, lp.d.cin, lp.d.cin, P + lp.d.w_off, lp.d.cout, lp.z, lp.d.cout);
         RUNK(0, pw_bytes(a), live_pointwise(s, a, st));
-        RUN(bn_train(s, lp, B, (double)global_B, update_ema, sc, nullptr, st));     // statistics over the batch only
+        RUN(bn_train(s, lp, B, (double)global_B, update_ema, sc, nullptr, st, 0, true, /*f64_sums=*/true));     // statistics over the batch only
         PwArgs b = pw_args(lp.a, B, lp.d.cout, lp.d.cout, P + lc.d.w_off, lc.d.cout, s->img_bias, lc.d.cout);
         RUNK(0, pw_bytes(b), live_pointwise(s, b, st));
     }

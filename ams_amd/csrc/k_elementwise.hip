@@ -208,6 +208,32 @@ int launch_colstats(const float* z, int64_t M, int C, const float* center, doubl
     return run_col_reduce<2, OpStats, double>(op, M, 1, C, C, 1.0, scratch, sums, st);
 }
 
+// The same sums with every difference, square and addition in f64, one thread per channel: for a layer of a few rows (the image-pooling
+// branch: one row per frame).  Frames of one clip pool to nearly the same vector, so the batch variance is far smaller than the squared
+// distance of the batch mean from the centre, and (z - center)^2 rounded to f32 loses the variance: measured 1.2e-4 on the branch's
+// activation at two frames (tests/test_gpu_layer_links.py)
+__global__ __launch_bounds__(128) void colstats_f64_kernel(const float* __restrict__ z, int64_t M, int C, const float* __restrict__ center,
+                                                           double* __restrict__ sums) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    const double ctr = center ? (double)center[c] : 0.0;
+    double s0 = 0.0, s1 = 0.0;
+    for (int64_t r = 0; r < M; ++r) {
+        const double d = (double)z[r * C + c] - ctr;
+        s0 += d;
+        s1 += d * d;
+    }
+    sums[c] = s0;
+    sums[C + c] = s1;
+}
+
+int launch_colstats_f64(const float* z, int64_t M, int C, const float* center, double* sums, hipStream_t st) {
+    note_kernel("colstats_f64_kernel");
+    hipLaunchKernelGGL(colstats_f64_kernel, dim3(cdiv(C, 128)), dim3(128), 0, st, z, M, C, center, sums);
+    AMS_CHECK_LAUNCH();
+    return AMS_OK;
+}
+
 template <class Op, class Fin>
 static int run_col_reduce_bn(Op op, int64_t M, int C, float* scratch, double* sums, Fin fin, hipStream_t st) {
     AMS_REQUIRE(C % 4 == 0 && C / 4 <= 256, "column reduce: C=%d must be a multiple of 4 (<= 1024)", C);

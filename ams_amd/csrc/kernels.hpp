@@ -296,6 +296,8 @@ int launch_image_colsum(const float* x, int B, int64_t HW, int C, int ldx, float
 size_t colstats_scratch(int64_t M, int C);
 int launch_colstats(const float* z, int64_t M, int C, const float* center, double* sums /*[2][C]*/, float* scratch,
                     hipStream_t st);
+// ... formed in f64 throughout by one thread per channel: for layers of a few rows whose variance is small against the centre's distance
+int launch_colstats_f64(const float* z, int64_t M, int C, const float* center, double* sums /*[2][C]*/, hipStream_t st);
 // BN forward coefficients from the sums; updates the moving statistics when moving_mean != nullptr.
 //   scale = gamma*rstd, shift = beta - mean*scale; save_mean, save_rstd for the backward pass.
 int launch_bn_finalize(const double* sums, double n, int C, const float* center, const float* gamma, const float* beta,

@@ -21,10 +21,12 @@ import torch
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
+sys.path.insert(0, str(ROOT / "tests"))
 
 from ams_amd import hip, spec, synth, weights  # noqa: E402
 from ams_amd.engine import StudentEngine  # noqa: E402
 from oracle.student_torch import StudentOracle  # noqa: E402
+from layer_links import layer_view  # noqa: E402  (tests/layer_links.py: the link-by-link check of the step uses the same view)
 
 CI = [0, 1, 2, 10, 11, 13]
 
@@ -39,13 +41,6 @@ def errors(spec_, g, grads_ref):
         mx = np.abs(want).max()
         out[v.name] = (np.abs(got - want).max() / max(mx, 1e-30), np.linalg.norm(got - want) / max(np.linalg.norm(want), 1e-30))
     return out
-
-
-def layer_view(eng, layer, which, B, h, w, c):
-    import ctypes as C
-    off, n = C.c_size_t(), C.c_size_t()
-    hip.check(eng.lib.ams_student_layer_tensor(eng._h, layer, which, C.byref(off), C.byref(n)))
-    return eng.arena[off.value:off.value + 4 * B * h * w * c].view(torch.float32).view(B, h, w, c).cpu().numpy().astype(np.float64)
 
 
 def layers_main():
