@@ -1,6 +1,7 @@
 // The student engine, part 4 of 4: the C ABI of include/ams_hip.h — student lifetime, the calls behind SemanticNetwork's methods, options,
 // the profiler read-out, and the kernel-level entry points (ams_k_*) the parity tests drive.
 #include "engine.hpp"
+#include "head_common.hpp"
 
 using namespace ams;
 
@@ -357,6 +358,14 @@ int ams_student_set_regularizer(ams_student* s, const uint8_t* reg_mask_dev, int
     AMS_REQUIRE(s->cfg.trainable, "set_regularizer: this student was created frozen");
     AMS_REQUIRE(n_vars > 0 && coef >= 0.f, "set_regularizer: n_vars=%d coef=%g", n_vars, (double)coef);
     s->reg_mask = reg_mask_dev; s->reg_nvars = n_vars; s->reg_coef = coef;
+    return AMS_OK;
+}
+
+int ams_student_set_kd(ams_student* s, float temperature, float alpha) {
+    AMS_REQUIRE(s, "set_kd: null student");
+    AMS_REQUIRE(s->cfg.trainable, "set_kd: this student was created frozen");
+    RUN(kd_params_check("set_kd", temperature, alpha));
+    s->kd_temperature = temperature; s->kd_alpha = alpha;
     return AMS_OK;
 }
 
@@ -883,6 +892,23 @@ int ams_k_ce_loss_grad_soft_layout(const float* logits, int32_t B, int32_t h, in
                 ce_loss_grad_scratch(B, h, w, K));
     hipStream_t st = (hipStream_t)stream;
     RUN(launch_ce_loss_grad(logits, ld, B, h, w, class_idx_host, K, H, W, teacher, NC, loss_dev, scratch, st, teacher_logits, th, tw, layout));
+    return launch_ce_combine(B, h, w, class_idx_host, K, NC, loss_dev, scratch, dlogits, ld, st);
+}
+
+int ams_k_ce_loss_grad_kd(const float* logits, int32_t B, int32_t h, int32_t w, int32_t ld, int32_t NC, const int32_t* class_idx_host, int32_t K,
+                          int32_t H, int32_t W, const uint8_t* teacher, const float* teacher_logits, int32_t th, int32_t tw, int32_t layout,
+                          double* loss_dev, float* dlogits, float* scratch, size_t scratch_floats, void* stream, float temperature, float alpha) {
+    RUN(kd_params_check("ce_loss_grad_kd", temperature, alpha));          // first: no pointer has been looked at when these two are refused
+    AMS_REQUIRE(teacher_logits, "ce_loss_grad_soft: null teacher logits");
+    AMS_REQUIRE(class_idx_host, "ce_loss_grad_soft: null class table");
+    AMS_REQUIRE(K >= 1 && K <= 32, "ce_loss_grad_soft: K=%d out of range (1..32)", K);
+    AMS_REQUIRE(layout == AMS_TLOGITS_FULL || layout == AMS_TLOGITS_SELECTED, "ce_loss_grad_soft: unknown teacher-logit layout %d", layout);
+    AMS_REQUIRE(ld >= NC && ld <= 256, "ce_loss_grad_soft: row stride %d must hold %d classes", ld, NC);
+    AMS_REQUIRE(ce_loss_grad_supported(w, W), "ce_loss_grad: %d output columns on %d source columns is outside the one-pass kernel", W, w);
+    AMS_REQUIRE(scratch && scratch_floats >= ce_loss_grad_scratch(B, h, w, K), "ce_loss_grad: scratch too small (need %zu floats)",
+                ce_loss_grad_scratch(B, h, w, K));
+    hipStream_t st = (hipStream_t)stream;
+    RUN(launch_ce_loss_grad(logits, ld, B, h, w, class_idx_host, K, H, W, teacher, NC, loss_dev, scratch, st, teacher_logits, th, tw, layout, temperature, alpha));
     return launch_ce_combine(B, h, w, class_idx_host, K, NC, loss_dev, scratch, dlogits, ld, st);
 }
 

@@ -162,6 +162,7 @@ struct ams_student {
     // train_biases_only — 0.01 * mean of the l2 losses of tvars added to the loss (:451-456; ams_student_set_regularizer)
     int f16_fallback_layers = 0;     // layers whose frozen weights are beyond fp16's range (they run the three-part bf16 form); set by freeze
     int soft_teacher = 0;
+    float kd_temperature = 1.f, kd_alpha = 1.f;      // the soft step's temperature and soft : hard mix (ams_student_set_kd; k_head.hip KD); (1, 1) = the reference's loss
     const float* teacher_logits = nullptr; int teacher_th = 0, teacher_tw = 0, teacher_layout = AMS_TLOGITS_FULL;
     const uint8_t* reg_mask = nullptr; int reg_nvars = 0; float reg_coef = 0.f;
     int nan_grads = 0;               // a batch without a valid pixel: NaN loss, ZERO gradients — what TensorFlow computes for utils/graph_utils.py:408

@@ -372,7 +372,7 @@ int loss_forward(ams_student* s, const uint8_t* teacher, int B, int32_t* labels,
         const bool soft = s->soft_teacher != 0;
         RUNK(0, 0.0, launch_ce_loss_grad(s->logits, 32, B, s->h, s->w, c.class_indices, c.n_selected, c.height, c.width, teacher, c.num_classes,
                                          s->loss_buf, s->ce_scratch, st, soft ? s->teacher_logits : nullptr, s->teacher_th, s->teacher_tw,
-                                         s->teacher_layout));
+                                         s->teacher_layout, soft ? s->kd_temperature : 1.f, soft ? s->kd_alpha : 1.f));
         return AMS_OK;
     }
     AMS_REQUIRE(labels || !s->soft_teacher, "soft_teacher: %d output columns on %d logit columns is outside the one-pass loss kernel", c.width, s->w);

@@ -3,6 +3,7 @@
 #pragma once
 #include "kernels.hpp"
 #include "cross_conf.hpp"
+#include <cmath>
 
 namespace ams {
 
@@ -65,6 +66,17 @@ struct SoftTeacher {
     float sy, sx;
     int tidx[kMaxK];
 };
+
+// The soft step's two KD knobs, by value beside SoftTeacher (ce_loss_grad_kernel<K, SOFT, KD>): 1 / T, alpha T^2, alpha T, 1 - alpha
+struct KdParams { float inv_t, at2, at, om; };
+
+// T finite and > 0 with 1 / T and T^2 finite in f32 as well, alpha in [0, 1]: checked before anything else of a call is looked at
+static inline int kd_params_check(const char* who, float temperature, float alpha) {
+    AMS_REQUIRE(std::isfinite(temperature) && temperature > 0.f && std::isfinite(1.f / temperature) && std::isfinite(temperature * temperature),
+                "%s: temperature %g must be finite and > 0", who, (double)temperature);
+    AMS_REQUIRE(alpha >= 0.f && alpha <= 1.f, "%s: alpha %g must lie in [0, 1]", who, (double)alpha);
+    return AMS_OK;
+}
 
 static inline bool tlogits_layout_ok(int layout) { return layout == AMS_TLOGITS_FULL || layout == AMS_TLOGITS_SELECTED; }
 

@@ -251,10 +251,21 @@ constexpr int kCeCB = 10;
 // SOFT: the target distribution of a pixel is the softmax of the K gathered teacher logits instead of the one-hot row of its label: per-pixel
 // loss sum_k p_k (log sum exp(z - max) - (z_k - max)) (TensorFlow's xent kernel), gradient softmax(z) - p; the mask and the mean's denominator
 // still come from the hard labels (weights = reduce_sum(filtered_labels_onehot), utils/graph_utils.py:397, 406-408).
-template <int KMAX, bool SOFT = false>
-__global__ __launch_bounds__(192) void ce_loss_grad_kernel(const float* __restrict__ logits, HeadGeom g, ClassTable ct,
+//
+// KD (SOFT only; this project's own objective, the reference has none): q = softmax(z / T), p = softmax(t / T), s = softmax(z);
+//   1, soft at T (alpha = 1): pixel = T^2 sum_k p_k (log sum exp(z/T - max/T) - (z_k - max)/T), d = T (q - p);
+//   2, mix: pixel = alpha T^2 (the same sum) + (1 - alpha) (log sum exp(z) - z_y), d = alpha T (q - p) + (1 - alpha) (s - onehot): a second
+//      exp pass over the student's K values (s beside q) and the one-hot row of the hard form.
+// The pixel's value is complete in f32 before its one rint(. 2^20), as in the two forms above; 1 / T, alpha T^2, alpha T and 1 - alpha come in kd.
+// KD = 0 compiles the code below as it was: launch_ce_loss_grad sends (T, alpha) = (1, 1) and alpha = 0 there.
+template <int KMAX, bool SOFT = false, int KD = 0>
+// The KMAX = 20 KD forms ask for two waves per SIMD (what <20, soft> has): left alone the allocator took 259 - 266 registers for them, one wave.
+// 0 = no request: every other instantiation is compiled as before.
+__global__ __launch_bounds__(192) __attribute__((amdgpu_waves_per_eu(KD != 0 && KMAX == 20 ? 2 : 0)))
+void ce_loss_grad_kernel(const float* __restrict__ logits, HeadGeom g, ClassTable ct,
                                                            const uint8_t* __restrict__ teacher, double* __restrict__ loss,
-                                                           float* __restrict__ partT, float* __restrict__ partB, SoftTeacher sft) {
+                                                           float* __restrict__ partT, float* __restrict__ partB, SoftTeacher sft, KdParams kd) {
+    static_assert(KD == 0 || SOFT, "the KD forms read the teacher logits");
     __shared__ float s_val[192][2 * KMAX + 1];
     __shared__ float s_wx[192][2];            // weight of the column towards its left / right source column
     __shared__ int s_x0[192];
@@ -340,7 +351,7 @@ __global__ __launch_bounds__(192) void ce_loss_grad_kernel(const float* __restri
                 if (k == target) zt = z[k];
             }
             float pt[SOFT ? KMAX : 1];
-            float zs[SOFT ? KMAX : 1];                    // z_k - max, kept for the soft loss
+            float zs[SOFT && KD == 0 ? KMAX : 1];         // z_k - max, kept for the soft loss
             if constexpr (SOFT) {
                 int qy0, qy1; float qty;
                 src_tap(y, sft.sy, sft.th, qy0, qy1, qty);
@@ -363,11 +374,60 @@ __global__ __launch_bounds__(192) void ce_loss_grad_kernel(const float* __restri
                 float psum = 0.f;
 #pragma unroll
                 for (int k = 0; k < KMAX; ++k)
+                    if constexpr (KD != 0) {              // selects, not guards (below): a slot beyond K holds channel tidx[0]'s logit, finite
+                        const float e = __expf((pt[k] - pmax) * kd.inv_t);
+                        pt[k] = k < g.K ? e : 0.f;
+                        psum += pt[k];
+                    } else {
                     if (k < g.K) { pt[k] = __expf(pt[k] - pmax); psum += pt[k]; } else pt[k] = 0.f;
+                    }
                 const float rp = 1.f / psum;
 #pragma unroll
                 for (int k = 0; k < KMAX; ++k) pt[k] *= rp;
             }
+            if constexpr (KD != 0) {
+                float hs[KD == 2 ? KMAX : 1];             // (1 - alpha) (s_k - [k = y])
+                float hard = 0.f;
+                if constexpr (KD == 2) {
+                    float s1 = 0.f;
+#pragma unroll
+                    for (int k = 0; k < KMAX; ++k) hs[k] = k < g.K ? __expf(z[k] - zmax) : 0.f;
+#pragma unroll
+                    for (int k = 0; k < KMAX; ++k) s1 += hs[k];
+                    const float r1 = 1.f / s1;
+                    hard = (zmax + __logf(s1)) - zt;
+#pragma unroll
+                    for (int k = 0; k < KMAX; ++k) hs[k] = kd.om * (hs[k] * r1 - (k == target ? 1.f : 0.f));
+                }
+                // sum_k p_k (lse - zq_k) as lse sum_k p_k - sum_k p_k zq_k (zq = (z - max) / T <= 0 <= lse: no cancellation either way), which
+                // needs no zq_k after the exp pass: K registers fewer.
+                // No k < K guards in the KD code, selects where a sum must leave a slot out: guarded bodies of this length became branches
+                // around every class (22 k instructions for <20, soft, T> against 12 k).  A class slot beyond K repeats class 0's logit, finite
+                // and <= max, and its p is 0
+                float qsum = 0.f, psum1 = 0.f, pz = 0.f;
+#pragma unroll
+                for (int k = 0; k < KMAX; ++k) {
+                    const float zq = (z[k] - zmax) * kd.inv_t;
+                    psum1 += pt[k];
+                    pz += pt[k] * zq;
+                    z[k] = __expf(zq);
+                }
+#pragma unroll
+                for (int k = 0; k < KMAX; ++k) qsum += k < g.K ? z[k] : 0.f;
+                const float rq = 1.f / qsum;
+                const float lp = __logf(qsum) * psum1 - pz;
+                float v = kd.at2 * lp;
+                if constexpr (KD == 2) v += kd.om * hard;
+                if (own) { my_loss += rint((double)v * 1048576.0); my_cnt += 1; }
+                const float wt = 1.f - ty;
+#pragma unroll
+                for (int k = 0; k < KMAX; ++k) {          // slots beyond K collect finite values nobody reads (the fold skips them)
+                    float d = kd.at * (z[k] * rq - pt[k]);
+                    if constexpr (KD == 2) d += hs[k];
+                    gt[k] += wt * d;
+                    gb[k] += ty * d;
+                }
+            } else {
             float ssum = 0.f;
 #pragma unroll
             for (int k = 0; k < KMAX; ++k)
@@ -393,6 +453,7 @@ __global__ __launch_bounds__(192) void ce_loss_grad_kernel(const float* __restri
                     gt[k] += wt * d;
                     gb[k] += ty * d;
                 }
+            }
           }
         }
     }
@@ -476,7 +537,9 @@ __global__ __launch_bounds__(256) void ce_loss_sum_kernel(const double* __restri
 
 // pass 1: loss[0] += CE sum, loss[1] += valid pixels (loss zeroed here), unnormalised gradient planes into scratch
 int launch_ce_loss_grad(const float* logits, int ld, int B, int h, int w, const int32_t* cls, int K, int H, int W, const uint8_t* teacher,
-                        int NC, double* loss, float* scratch, hipStream_t st, const float* soft_logits, int soft_h, int soft_w, int soft_layout) {
+                        int NC, double* loss, float* scratch, hipStream_t st, const float* soft_logits, int soft_h, int soft_w, int soft_layout,
+                        float kd_temperature, float kd_alpha) {
+    if (int rc = kd_params_check("ce_loss_grad", kd_temperature, kd_alpha)) return rc;
     ClassTable ct;
     int rc = fill_class_table(cls, K, NC, &ct);
     if (rc) return rc;
@@ -498,15 +561,31 @@ int launch_ce_loss_grad(const float* logits, int ld, int B, int h, int w, const 
         AMS_REQUIRE(tlogits_layout_ok(soft_layout), "ce_loss_grad: unknown teacher-logit layout %d", soft_layout);
         sft = soft_teacher_geom(soft_logits, soft_h, soft_w, soft_layout, ct, K, NC, H, W);
     }
-    note_kernel(soft_logits ? "ce_loss_grad_kernel<soft>" : "ce_loss_grad_kernel");
-    if (soft_logits) {
-        if (KM == 8) hipLaunchKernelGGL((ce_loss_grad_kernel<8, true>), grid, dim3(192), 0, st, logits, g, ct, teacher, blk, partT, partB, sft);
-        else if (KM == 20) hipLaunchKernelGGL((ce_loss_grad_kernel<20, true>), grid, dim3(192), 0, st, logits, g, ct, teacher, blk, partT, partB, sft);
-        else hipLaunchKernelGGL((ce_loss_grad_kernel<32, true>), grid, dim3(192), 0, st, logits, g, ct, teacher, blk, partT, partB, sft);
+    // the KD forms of the soft step: (T, alpha) = (1, 1) is the soft instantiation and alpha = 0 the hard one, the same launches as without the
+    // two parameters, so those cases are the same bits by construction
+    const int kd_form = !soft_logits || kd_alpha == 0.f ? -1 : kd_alpha == 1.f ? (kd_temperature == 1.f ? 0 : 1) : 2;
+    KdParams kd;
+    kd.inv_t = 1.f / kd_temperature;
+    kd.at2 = kd_alpha * (kd_temperature * kd_temperature);
+    kd.at = kd_alpha * kd_temperature;
+    kd.om = 1.f - kd_alpha;
+    note_kernel(kd_form == 2 ? "ce_loss_grad_kernel<soft, mix>" : kd_form == 1 ? "ce_loss_grad_kernel<soft, T>" : kd_form == 0 ? "ce_loss_grad_kernel<soft>" : "ce_loss_grad_kernel");
+    if (kd_form == 2) {
+        if (KM == 8) hipLaunchKernelGGL((ce_loss_grad_kernel<8, true, 2>), grid, dim3(192), 0, st, logits, g, ct, teacher, blk, partT, partB, sft, kd);
+        else if (KM == 20) hipLaunchKernelGGL((ce_loss_grad_kernel<20, true, 2>), grid, dim3(192), 0, st, logits, g, ct, teacher, blk, partT, partB, sft, kd);
+        else hipLaunchKernelGGL((ce_loss_grad_kernel<32, true, 2>), grid, dim3(192), 0, st, logits, g, ct, teacher, blk, partT, partB, sft, kd);
+    } else if (kd_form == 1) {
+        if (KM == 8) hipLaunchKernelGGL((ce_loss_grad_kernel<8, true, 1>), grid, dim3(192), 0, st, logits, g, ct, teacher, blk, partT, partB, sft, kd);
+        else if (KM == 20) hipLaunchKernelGGL((ce_loss_grad_kernel<20, true, 1>), grid, dim3(192), 0, st, logits, g, ct, teacher, blk, partT, partB, sft, kd);
+        else hipLaunchKernelGGL((ce_loss_grad_kernel<32, true, 1>), grid, dim3(192), 0, st, logits, g, ct, teacher, blk, partT, partB, sft, kd);
+    } else if (kd_form == 0) {
+        if (KM == 8) hipLaunchKernelGGL((ce_loss_grad_kernel<8, true>), grid, dim3(192), 0, st, logits, g, ct, teacher, blk, partT, partB, sft, kd);
+        else if (KM == 20) hipLaunchKernelGGL((ce_loss_grad_kernel<20, true>), grid, dim3(192), 0, st, logits, g, ct, teacher, blk, partT, partB, sft, kd);
+        else hipLaunchKernelGGL((ce_loss_grad_kernel<32, true>), grid, dim3(192), 0, st, logits, g, ct, teacher, blk, partT, partB, sft, kd);
     } else {
-    if (KM == 8) hipLaunchKernelGGL((ce_loss_grad_kernel<8, false>), grid, dim3(192), 0, st, logits, g, ct, teacher, blk, partT, partB, sft);
-    else if (KM == 20) hipLaunchKernelGGL((ce_loss_grad_kernel<20, false>), grid, dim3(192), 0, st, logits, g, ct, teacher, blk, partT, partB, sft);
-    else hipLaunchKernelGGL((ce_loss_grad_kernel<32, false>), grid, dim3(192), 0, st, logits, g, ct, teacher, blk, partT, partB, sft);
+    if (KM == 8) hipLaunchKernelGGL((ce_loss_grad_kernel<8, false>), grid, dim3(192), 0, st, logits, g, ct, teacher, blk, partT, partB, sft, kd);
+    else if (KM == 20) hipLaunchKernelGGL((ce_loss_grad_kernel<20, false>), grid, dim3(192), 0, st, logits, g, ct, teacher, blk, partT, partB, sft, kd);
+    else hipLaunchKernelGGL((ce_loss_grad_kernel<32, false>), grid, dim3(192), 0, st, logits, g, ct, teacher, blk, partT, partB, sft, kd);
     }
     AMS_CHECK_LAUNCH();
     hipLaunchKernelGGL(ce_loss_sum_kernel, dim3(1), dim3(256), 0, st, blk, (int)(grid.x * grid.y * grid.z), loss);

@@ -84,6 +84,7 @@ class StudentEngine:
         self.trainable = bool(trainable)
         self.num_classes = int(num_classes)
         self.soft_teacher = False
+        self.kd_temperature, self.kd_alpha = 1.0, 1.0
         self._reg_mask = self._teacher_logits_dev = None
         self._frames_b, self._frames_u8, self._frames_metric = 0, False, False
         self.class_indices = [int(c) for c in class_indices]
@@ -282,6 +283,13 @@ class StudentEngine:
         ``train_step`` then needs ``teacher_logits``."""
         hip.check(self.lib.ams_student_set_option(self._h, hip.OPT_SOFT_TEACHER, int(bool(on))), "ams_student_set_option")
         self.soft_teacher = bool(on)
+
+    def set_kd(self, temperature: float = 1.0, alpha: float = 1.0) -> None:
+        """Temperature and soft : hard mix of the soft-teacher step (this project's own; the reference's soft loss is ``(1, 1)``): per valid
+        pixel ``alpha T^2 CE(softmax(t / T), softmax(z / T)) + (1 - alpha) CE(onehot(y), softmax(z))``.  ``temperature`` finite and > 0,
+        ``alpha`` in [0, 1]; read only while ``set_soft_teacher(True)`` holds.  ``alpha = 0`` is the hard-label step."""
+        hip.check(self.lib.ams_student_set_kd(self._h, float(temperature), float(alpha)), "ams_student_set_kd")
+        self.kd_temperature, self.kd_alpha = float(temperature), float(alpha)
 
     def set_regularizer(self, on: bool, biases_only: bool = False, coef: float = 0.01) -> None:
         """create_student_v3(regularize=True[, train_biases_only=True]) (utils/graph_utils.py:451-456): loss += coef * mean over tvars of

@@ -125,6 +125,12 @@ def build_parser() -> argparse.ArgumentParser:
                    help="server: derive the hard labels of the replay memory from the teacher logits on the device instead of resizing and "
                         "uploading the source's label map (extra flag; needs --soft_teacher; not for the experiments whose labels arrive in "
                         "COCO numbering).  The edge keeps scoring against the source's labels")
+    p.add_argument("--kd_temperature", type=float, default=None,
+                   help="server: temperature T of the soft-teacher loss (extra flag; needs --soft_teacher; finite and > 0, default 1): both logit "
+                        "sets are divided by T and the soft term carries the factor T^2.  Evaluation (<results>_soft_eval.npy) keeps the T = 1 loss")
+    p.add_argument("--kd_alpha", type=float, default=None,
+                   help="server: weight of the soft term in the soft-teacher loss (extra flag; needs --soft_teacher; in [0, 1], default 1); the "
+                        "hard-label cross-entropy takes 1 - kd_alpha")
     p.add_argument("--horizon_k1s", default="16,32,64,128,256,512", help="horizon mode: training-window lengths in seconds (reference: hard-coded)")
     p.add_argument("--horizon_k2", type=int, default=256, help="horizon mode: evaluation window in seconds (reference: 256)")
     p.add_argument("--horizon_points", type=int, default=3, help="horizon mode: number of evaluation points (reference: 3)")
@@ -350,7 +356,8 @@ def train_model(ctx: Context, train_start, train_end, sampling_period, gpu_id, r
                                        masked_gradients=FLAGS.train_strategy not in ['full_model'],
                                        cross_miou_compat=FLAGS.enable_ASR, initial_variables=ctx.initial_variables,
                                        **({"device_masks": True} if getattr(FLAGS, "device_masks", False) else {}),
-                                       **({"soft_teacher": True} if soft_teacher else {}))
+                                       **({"soft_teacher": True} if soft_teacher else {}),
+                                       **{k: float(getattr(FLAGS, k)) for k in ("kd_temperature", "kd_alpha") if getattr(FLAGS, k, None) is not None})
     save_dir = ctx.save_dir(run_label + "_%d" % train_start)
     semantic_network.save_to_frozen_graph(save_dir + "_final")
     print_process("Saved model to %s_final.pb" % save_dir, 0)
@@ -660,6 +667,13 @@ def parse_flags(argv: Optional[List[str]] = None):
                      "deques carry no teacher logits)")
     if flags.labels_from_logits and not flags.soft_teacher:
         parser.error("--labels_from_logits needs --soft_teacher: the labels are derived from the teacher logits that flag caches")
+    for name in ("kd_temperature", "kd_alpha"):
+        if getattr(flags, name) is not None and not flags.soft_teacher:
+            parser.error("--%s needs --soft_teacher: it shapes the loss against the teacher logits that flag caches" % name)
+    if flags.kd_temperature is not None and not (np.isfinite(flags.kd_temperature) and flags.kd_temperature > 0):
+        parser.error("--kd_temperature must be finite and > 0 (got %r)" % flags.kd_temperature)
+    if flags.kd_alpha is not None and not 0.0 <= flags.kd_alpha <= 1.0:
+        parser.error("--kd_alpha must lie in [0, 1] (got %r)" % flags.kd_alpha)
     if flags.labels_from_logits and is_coco(video_number(flags.input_video)):
         parser.error("--labels_from_logits does not go with experiment %d: its teacher labels arrive in COCO numbering and are converted on the "
                      "way into the memory (map_coco), which an argmax over the logits' own classes cannot stand for"

@@ -148,8 +148,17 @@ class SemanticNetwork(object):
         self.train_biases_only = bool(kwargs.pop("train_biases_only", False))
         self.regularize = bool(kwargs.pop("regularize", False))
         self.soft_teacher = bool(kwargs.pop("soft_teacher", False))
+        # this project's own (the reference's soft loss has neither): temperature and soft : hard mix of the soft step (StudentEngine.set_kd).
+        # Evaluation (predict_with_soft_metric, evaluate_memory) keeps reporting the reference's T = 1 soft loss
+        self.kd_temperature = float(kwargs.pop("kd_temperature", 1.0))
+        self.kd_alpha = float(kwargs.pop("kd_alpha", 1.0))
         if frozen:                 # the reference's frozen branch never calls create_student_v3: the kwargs are accepted and unused there too
             self.soft_teacher = self.regularize = self.train_biases_only = False
+            self.kd_temperature = self.kd_alpha = 1.0
+        assert self.soft_teacher or (self.kd_temperature == 1.0 and self.kd_alpha == 1.0), \
+            "kd_temperature / kd_alpha shape the soft_teacher loss: they need soft_teacher=True"
+        assert np.isfinite(self.kd_temperature) and self.kd_temperature > 0, "kd_temperature must be finite and > 0"
+        assert 0.0 <= self.kd_alpha <= 1.0, "kd_alpha must lie in [0, 1]"
         initial_variables = kwargs.pop("initial_variables", None)
         frozen_graph = kwargs.pop("frozen_graph", None)
         max_batch = kwargs.pop("max_batch", None)
@@ -193,6 +202,8 @@ class SemanticNetwork(object):
             self._restore_dict(self._initial)
             if self.soft_teacher:
                 self.engine.set_soft_teacher(True)
+                if (self.kd_temperature, self.kd_alpha) != (1.0, 1.0):
+                    self.engine.set_kd(self.kd_temperature, self.kd_alpha)
             if self.regularize:
                 self.engine.set_regularizer(True, biases_only=self.train_biases_only)
             self.mask = None

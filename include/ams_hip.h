@@ -229,6 +229,16 @@ enum { AMS_TLOGITS_FULL = 0, AMS_TLOGITS_SELECTED = 1 };
 int ams_student_feed_teacher_logits_layout(ams_student* s, const float* teacher_logits_dev, int32_t th, int32_t tw, int32_t layout);
 int ams_student_set_regularizer(ams_student* s, const uint8_t* reg_mask_dev, int32_t n_vars, float coef);
 
+/* The two knowledge-distillation knobs of the soft-teacher step (this project's own objective; the reference has neither).  Per valid pixel,
+ * z = the student's K logits, t = the teacher's, y = the hard label's index: q = softmax(z / T), p = softmax(t / T), s = softmax(z),
+ *   pixel = alpha T^2 sum_k p_k (logsumexp(z / T) - z_k / T) + (1 - alpha) (logsumexp(z) - z_y),
+ *   d pixel / d z_k = alpha T (q_k - p_k) + (1 - alpha) (s_k - [k = y]);
+ * mask and denominator from the hard labels as before.  temperature finite and > 0 (1 / T and T^2 finite in f32), alpha in [0, 1]; anything else:
+ * AMS_E_INVALID and the student keeps what it had.  Needs a trainable student.  Read only while AMS_OPT_SOFT_TEACHER is on.  The default
+ * (1, 1) is the reference's soft loss and alpha = 0 the hard-label loss, each by the very kernel that computes it without this call.  The
+ * evaluation entries (ams_student_soft_metric, ams_k_upsample_soft_metric) keep reporting the reference's T = 1 soft loss. */
+int ams_student_set_kd(ams_student* s, float temperature, float alpha);
+
 /* ---- data-parallel split of the same step (one process per GPU) -------------------------
  * Callback form (any transport; what the gloo CPU tests and a host without RCCL use): `cb` is invoked on the host
  * whenever cross-rank sums are needed and must all-reduce (sum) `count` values of `dtype` at arena byte offset
@@ -821,6 +831,13 @@ int ams_k_ce_loss_grad_soft(const float* logits, int32_t B, int32_t h, int32_t w
 int ams_k_ce_loss_grad_soft_layout(const float* logits, int32_t B, int32_t h, int32_t w, int32_t ld, int32_t NC, const int32_t* class_idx_host,
                                    int32_t K, int32_t H, int32_t W, const uint8_t* teacher, const float* teacher_logits, int32_t th, int32_t tw,
                                    int32_t layout, double* loss_dev, float* dlogits, float* scratch, size_t scratch_floats, void* stream);
+/* The same under a temperature and a soft : hard mix (ams_student_set_kd has the objective).  temperature and alpha are checked first, before any
+ * pointer is looked at: AMS_E_INVALID, nothing launched, nothing written, ams_last_error naming the argument.  (1, 1) is
+ * ams_k_ce_loss_grad_soft_layout and alpha = 0 is ams_k_ce_loss_grad, bit for bit: the launcher sends them to those kernels. */
+int ams_k_ce_loss_grad_kd(const float* logits, int32_t B, int32_t h, int32_t w, int32_t ld, int32_t NC, const int32_t* class_idx_host,
+                          int32_t K, int32_t H, int32_t W, const uint8_t* teacher, const float* teacher_logits, int32_t th, int32_t tw,
+                          int32_t layout, double* loss_dev, float* dlogits, float* scratch, size_t scratch_floats, void* stream,
+                          float temperature, float alpha);
 
 /* K13: weight gradient of a 1x1 conv: dw[K,N] = x[M,K]^T @ dy[M,N]. scratch: >= ams_k_pointwise_wgrad_scratch floats */
 int ams_k_pointwise_wgrad(const float* x, const float* dy, int64_t M, int32_t K, int32_t N, float* dw,
