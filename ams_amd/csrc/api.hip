@@ -369,6 +369,16 @@ int ams_student_set_kd(ams_student* s, float temperature, float alpha) {
     return AMS_OK;
 }
 
+int ams_student_set_loss_weights(ams_student* s, const float* class_weights_host, int32_t n, float conf_gamma) {
+    AMS_REQUIRE(s, "set_loss_weights: null student");
+    AMS_REQUIRE(s->cfg.trainable, "set_loss_weights: this student was created frozen");
+    AMS_REQUIRE(!class_weights_host || n == s->cfg.n_selected, "set_loss_weights: %d class weights for %d selected classes", n, s->cfg.n_selected);
+    RUN(loss_weights_check("set_loss_weights", class_weights_host, n, s->cfg.n_selected, conf_gamma));
+    for (int k = 0; k < 32; ++k) s->loss_cw[k] = class_weights_host && k < n ? class_weights_host[k] : 1.f;
+    s->conf_gamma = conf_gamma;
+    return AMS_OK;
+}
+
 int ams_student_set_option(ams_student* s, int32_t option, int32_t value) {
     AMS_REQUIRE(s, "set_option: null student");
     s->dual_choice.clear();                            // any option may change the plans the autotune compared
@@ -909,6 +919,27 @@ int ams_k_ce_loss_grad_kd(const float* logits, int32_t B, int32_t h, int32_t w, 
                 ce_loss_grad_scratch(B, h, w, K));
     hipStream_t st = (hipStream_t)stream;
     RUN(launch_ce_loss_grad(logits, ld, B, h, w, class_idx_host, K, H, W, teacher, NC, loss_dev, scratch, st, teacher_logits, th, tw, layout, temperature, alpha));
+    return launch_ce_combine(B, h, w, class_idx_host, K, NC, loss_dev, scratch, dlogits, ld, st);
+}
+
+int ams_k_ce_loss_grad_weighted(const float* logits, int32_t B, int32_t h, int32_t w, int32_t ld, int32_t NC, const int32_t* class_idx_host, int32_t K,
+                                int32_t H, int32_t W, const uint8_t* teacher, const float* teacher_logits, int32_t th, int32_t tw, int32_t layout,
+                                double* loss_dev, float* dlogits, float* scratch, size_t scratch_floats, void* stream, float temperature, float alpha,
+                                const float* class_weights_host, float conf_gamma) {
+    RUN(kd_params_check("ce_loss_grad_weighted", temperature, alpha));    // first, as in the KD entry; then the two new arguments, before any other pointer
+    RUN(loss_weights_check("ce_loss_grad_weighted", class_weights_host, K, K, conf_gamma));
+    AMS_REQUIRE(teacher_logits || (conf_gamma == 0.f && alpha == 0.f),
+                "ce_loss_grad_weighted: null teacher logits with alpha %g, conf_gamma %g (they may be NULL only when both are 0)", (double)alpha, (double)conf_gamma);
+    AMS_REQUIRE(class_idx_host, "ce_loss_grad_weighted: null class table");
+    AMS_REQUIRE(K >= 1 && K <= 32, "ce_loss_grad_weighted: K=%d out of range (1..32)", K);
+    AMS_REQUIRE(layout == AMS_TLOGITS_FULL || layout == AMS_TLOGITS_SELECTED, "ce_loss_grad_weighted: unknown teacher-logit layout %d", layout);
+    AMS_REQUIRE(ld >= NC && ld <= 256, "ce_loss_grad_weighted: row stride %d must hold %d classes", ld, NC);
+    AMS_REQUIRE(ce_loss_grad_supported(w, W), "ce_loss_grad: %d output columns on %d source columns is outside the one-pass kernel", W, w);
+    AMS_REQUIRE(scratch && scratch_floats >= ce_loss_grad_scratch(B, h, w, K), "ce_loss_grad: scratch too small (need %zu floats)",
+                ce_loss_grad_scratch(B, h, w, K));
+    hipStream_t st = (hipStream_t)stream;
+    RUN(launch_ce_loss_grad(logits, ld, B, h, w, class_idx_host, K, H, W, teacher, NC, loss_dev, scratch, st, teacher_logits, th, tw, layout, temperature, alpha,
+                            class_weights_host, conf_gamma));
     return launch_ce_combine(B, h, w, class_idx_host, K, NC, loss_dev, scratch, dlogits, ld, st);
 }
 

@@ -163,6 +163,9 @@ struct ams_student {
     int f16_fallback_layers = 0;     // layers whose frozen weights are beyond fp16's range (they run the three-part bf16 form); set by freeze
     int soft_teacher = 0;
     float kd_temperature = 1.f, kd_alpha = 1.f;      // the soft step's temperature and soft : hard mix (ams_student_set_kd; k_head.hip KD); (1, 1) = the reference's loss
+    // the fine-tune loss's per-class weights and the exponent of the teacher's confidence (ams_student_set_loss_weights; k_head.hip WT); ones and 0 = the plain mean
+    float loss_cw[32] = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};
+    float conf_gamma = 0.f;
     const float* teacher_logits = nullptr; int teacher_th = 0, teacher_tw = 0, teacher_layout = AMS_TLOGITS_FULL;
     const uint8_t* reg_mask = nullptr; int reg_nvars = 0; float reg_coef = 0.f;
     int nan_grads = 0;               // a batch without a valid pixel: NaN loss, ZERO gradients — what TensorFlow computes for utils/graph_utils.py:408

@@ -1,6 +1,7 @@
 // The student engine, part 3 of 4: loss, backward and update of the fine-tune step (reference SemanticNetwork.py:253-260 _train,
 // utils/graph_utils.py:403-408 loss, :457-496 optimizer / BN update / masked assignment).
 #include "engine.hpp"
+#include "head_common.hpp"
 #include <functional>
 #include <vector>
 
@@ -367,14 +368,18 @@ int backward(ams_student* s, const void* frames, int dtype, const uint8_t* teach
 
 int loss_forward(ams_student* s, const uint8_t* teacher, int B, int32_t* labels, hipStream_t st) {
     const ams_student_config& c = s->cfg;
+    const bool weighted = !labels && !loss_weights_default(s->loss_cw, c.n_selected, s->conf_gamma);          // evaluation stays unweighted
     if (!labels && ce_loss_grad_supported(s->w, c.width)) {
         // the fine-tune step: loss sums and the unnormalised gradient in one pass over the pixels
         const bool soft = s->soft_teacher != 0;
+        AMS_REQUIRE(soft || s->conf_gamma == 0.f, "train_step: conf_gamma %g weights by the teacher's confidence: it needs soft_teacher (AMS_OPT_SOFT_TEACHER)",
+                    (double)s->conf_gamma);
         RUNK(0, 0.0, launch_ce_loss_grad(s->logits, 32, B, s->h, s->w, c.class_indices, c.n_selected, c.height, c.width, teacher, c.num_classes,
                                          s->loss_buf, s->ce_scratch, st, soft ? s->teacher_logits : nullptr, s->teacher_th, s->teacher_tw,
-                                         s->teacher_layout, soft ? s->kd_temperature : 1.f, soft ? s->kd_alpha : 1.f));
+                                         s->teacher_layout, soft ? s->kd_temperature : 1.f, soft ? s->kd_alpha : 1.f, s->loss_cw, s->conf_gamma));
         return AMS_OK;
     }
+    AMS_REQUIRE(!weighted, "loss weights: %d output columns on %d logit columns is outside the one-pass loss kernel", c.width, s->w);
     AMS_REQUIRE(labels || !s->soft_teacher, "soft_teacher: %d output columns on %d logit columns is outside the one-pass loss kernel", c.width, s->w);
     return launch_upsample_argmax(s->logits, 32, B, s->h, s->w, c.class_indices, c.n_selected, c.height, c.width, teacher,
                                   c.num_classes, labels, s->conf_buf, s->loss_buf, st);

@@ -4,6 +4,7 @@
 #include "kernels.hpp"
 #include "cross_conf.hpp"
 #include <cmath>
+#include <type_traits>
 
 namespace ams {
 
@@ -76,6 +77,37 @@ static inline int kd_params_check(const char* who, float temperature, float alph
                 "%s: temperature %g must be finite and > 0", who, (double)temperature);
     AMS_REQUIRE(alpha >= 0.f && alpha <= 1.f, "%s: alpha %g must lie in [0, 1]", who, (double)alpha);
     return AMS_OK;
+}
+
+// The weighted loss's two knobs (ce_loss_grad_kernel<K, SOFT, KD, WT = true>), by value beside KdParams: pk[label byte] = rint(cw_k 2^20) << 5 | k for the label's class k (the QUANTISED class weight,
+// at most 2^24, over the subset index that ct.lut holds), 0 for a label outside the subset or of weight 0; gamma, the exponent of the teacher's confidence.
+struct LossWeights { uint32_t pk[256]; float gamma; };
+struct NoLossWeights {};               // what the WT = false forms take in its place: nothing
+
+// class_weights (HOST, K floats, or NULL = ones): each 0 or in [2^-6, 16]; gamma finite in [0, 8]: checked before anything else of a call is looked at
+static inline int loss_weights_check(const char* who, const float* cw, int n, int K, float gamma) {
+    AMS_REQUIRE(std::isfinite(gamma) && gamma >= 0.f && gamma <= 8.f, "%s: conf_gamma %g must lie in [0, 8]", who, (double)gamma);
+    if (!cw) return AMS_OK;
+    AMS_REQUIRE(n == K && K >= 1 && K <= kMaxK, "%s: %d class weights for %d selected classes", who, n, K);
+    for (int k = 0; k < K; ++k)
+        AMS_REQUIRE(cw[k] == 0.f || (cw[k] >= 0.015625f && cw[k] <= 16.f), "%s: class_weights[%d] = %g must be 0 or lie in [2^-6, 16]", who, k, (double)cw[k]);
+    return AMS_OK;
+}
+
+static inline bool loss_weights_default(const float* cw, int K, float gamma) {
+    if (gamma != 0.f) return false;
+    if (cw) for (int k = 0; k < K; ++k) if (cw[k] != 1.f) return false;
+    return true;
+}
+
+// ct: the filled class table; cw checked (loss_weights_check).  rintf(cw 2^20) is exact in f32 for cw <= 16 (<= 2^24)
+static inline void fill_loss_weights(const ClassTable& ct, const float* cw, int K, float gamma, LossWeights* lw) {
+    for (int i = 0; i < 256; ++i) {
+        const int k = ct.lut[i];
+        const uint32_t q = k < 0 || k >= K ? 0u : (uint32_t)rintf((cw ? cw[k] : 1.f) * 1048576.f);
+        lw->pk[i] = q ? q << 5 | (uint32_t)k : 0u;
+    }
+    lw->gamma = gamma;
 }
 
 static inline bool tlogits_layout_ok(int layout) { return layout == AMS_TLOGITS_FULL || layout == AMS_TLOGITS_SELECTED; }

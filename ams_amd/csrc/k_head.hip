@@ -258,19 +258,29 @@ constexpr int kCeCB = 10;
 //      exp pass over the student's K values (s beside q) and the one-hot row of the hard form.
 // The pixel's value is complete in f32 before its one rint(. 2^20), as in the two forms above; 1 / T, alpha T^2, alpha T and 1 - alpha come in kd.
 // KD = 0 compiles the code below as it was: launch_ce_loss_grad sends (T, alpha) = (1, 1) and alpha = 0 there.
-template <int KMAX, bool SOFT = false, int KD = 0>
+//
+// WT (this project's own as well): a per-pixel weight w = cw_y c^gamma, c = max_k p_k = 1 / psum of the target softmax the SOFT forms build
+// anyway, and a weighted mean: pixel and d are multiplied by w, the block's second number is sum w instead of the count.  w is quantised ONCE,
+// w_q = rint(w 2^20) 2^-20 (an f32, exact: w <= 16), and that one value is the gradient's factor, enters the numerator as
+// rint((double)(w_q v) 2^20) and the denominator as the integer w_q 2^20: the kernel computes exactly sum w_q pixel / sum w_q, both sums
+// integer multiples of 2^-20 in f64 and so independent of order and batch split.  cw_y comes packed with the class index in lw.pk, indexed by the label BYTE where
+// the other forms read ct.lut[.] in the eight-row look-ups (no load more, no register more); a weight of 0 leaves the pixel out like an ignored label.
+// WT = false compiles the code below as it was (no argument more: NoLossWeights): launch_ce_loss_grad sends all-ones weights with gamma = 0 there.
+template <int KMAX, bool SOFT = false, int KD = 0, bool WT = false>
 // The KMAX = 20 KD forms ask for two waves per SIMD (what <20, soft> has): left alone the allocator took 259 - 266 registers for them, one wave.
 // 0 = no request: every other instantiation is compiled as before.
 __global__ __launch_bounds__(192) __attribute__((amdgpu_waves_per_eu(KD != 0 && KMAX == 20 ? 2 : 0)))
 void ce_loss_grad_kernel(const float* __restrict__ logits, HeadGeom g, ClassTable ct,
                                                            const uint8_t* __restrict__ teacher, double* __restrict__ loss,
-                                                           float* __restrict__ partT, float* __restrict__ partB, SoftTeacher sft, KdParams kd) {
+                                                           float* __restrict__ partT, float* __restrict__ partB, SoftTeacher sft, KdParams kd,
+                                                           std::conditional_t<WT, LossWeights, NoLossWeights> lw) {
     static_assert(KD == 0 || SOFT, "the KD forms read the teacher logits");
     __shared__ float s_val[192][2 * KMAX + 1];
     __shared__ float s_wx[192][2];            // weight of the column towards its left / right source column
     __shared__ int s_x0[192];
     __shared__ double s_loss[3];
     __shared__ int s_cnt[3];
+    __shared__ double s_w[WT ? 3 : 1];
     const int b = blockIdx.z, i0 = blockIdx.y, j_lo = blockIdx.x * kCeCB;
     const int i1 = i0 + 1 < g.h ? i0 + 1 : g.h - 1;
     // pixel rows of the band: floor(y * sy) == i0 (sy = 0: a single source row holds every output row)
@@ -303,6 +313,7 @@ void ce_loss_grad_kernel(const float* __restrict__ logits, HeadGeom g, ClassTabl
     for (int k = 0; k < KMAX; ++k) { gt[k] = 0.f; gb[k] = 0.f; }
     double my_loss = 0.0;                     // integer multiples of 2^-20 per pixel: exact, order-independent sums (upsample_argmax_kernel)
     int my_cnt = 0;
+    [[maybe_unused]] double my_w = 0.0;       // WT: sum of w_q 2^20, integers
     if (live) {
         const float* base = logits + (int64_t)b * g.h * g.w * g.ld;
         const float* ptl = base + ((int64_t)i0 * g.w + x0) * g.ld;
@@ -334,12 +345,17 @@ void ce_loss_grad_kernel(const float* __restrict__ logits, HeadGeom g, ClassTabl
 #pragma unroll
           for (int r = 0; r < 8; ++r) tgt[r] = tcol[(int64_t)(yb + r < yend ? yb + r : yend - 1) * g.W];
 #pragma unroll
-          for (int r = 0; r < 8; ++r) tgt[r] = ct.lut[tgt[r]];
+          for (int r = 0; r < 8; ++r)
+              if constexpr (WT) tgt[r] = (int)lw.pk[tgt[r]];       // class index and class weight in ONE word: the same two loads per row as ct.lut
+              else
+              tgt[r] = ct.lut[tgt[r]];
 #pragma unroll
           for (int r = 0; r < 8; ++r) {
             const int y = yb + r;
-            const int target = tgt[r];
+            const int target = WT ? (tgt[r] >= 32 ? tgt[r] & 31 : -1) : tgt[r];          // WT: weight 0 (or a label outside the subset) = ignored
             if (y >= yend || target < 0) continue;
+            [[maybe_unused]] float wq = 1.f;
+            if constexpr (WT) wq = (float)(tgt[r] >> 5) * (1.f / 1048576.f);    // quantised on the host (fill_loss_weights): <= 2^24, exact
             const float src = __fmul_rn((float)y, g.sy);
             const float ty = __fsub_rn(src, floorf(src));
             float z[KMAX];
@@ -384,6 +400,8 @@ void ce_loss_grad_kernel(const float* __restrict__ logits, HeadGeom g, ClassTabl
                 const float rp = 1.f / psum;
 #pragma unroll
                 for (int k = 0; k < KMAX; ++k) pt[k] *= rp;
+                // c = max_k p_k = rp (the largest entry is exp(0) = 1 before the scaling); c^gamma = exp(-gamma log psum), 1 at gamma = 0 exactly
+                if constexpr (WT) wq = rintf(wq * __expf(-lw.gamma * __logf(psum)) * 1048576.f) * (1.f / 1048576.f);
             }
             if constexpr (KD != 0) {
                 float hs[KD == 2 ? KMAX : 1];             // (1 - alpha) (s_k - [k = y])
@@ -418,12 +436,15 @@ void ce_loss_grad_kernel(const float* __restrict__ logits, HeadGeom g, ClassTabl
                 const float lp = __logf(qsum) * psum1 - pz;
                 float v = kd.at2 * lp;
                 if constexpr (KD == 2) v += kd.om * hard;
+                if constexpr (WT) { if (own) { my_loss += rint((double)(wq * v) * 1048576.0); my_w += (double)(wq * 1048576.f); } }
+                else
                 if (own) { my_loss += rint((double)v * 1048576.0); my_cnt += 1; }
                 const float wt = 1.f - ty;
 #pragma unroll
                 for (int k = 0; k < KMAX; ++k) {          // slots beyond K collect finite values nobody reads (the fold skips them)
                     float d = kd.at * (z[k] * rq - pt[k]);
                     if constexpr (KD == 2) d += hs[k];
+                    if constexpr (WT) d *= wq;
                     gt[k] += wt * d;
                     gb[k] += ty * d;
                 }
@@ -439,8 +460,12 @@ void ce_loss_grad_kernel(const float* __restrict__ logits, HeadGeom g, ClassTabl
 #pragma unroll
                 for (int k = 0; k < KMAX; ++k)
                     if (k < g.K) lp += pt[k] * (lse - zs[k]);
+                if constexpr (WT) { if (own) { my_loss += rint((double)(wq * lp) * 1048576.0); my_w += (double)(wq * 1048576.f); } }
+                else
                 if (own) { my_loss += rint((double)lp * 1048576.0); my_cnt += 1; }
             } else {
+            if constexpr (WT) { if (own) { my_loss += rint((double)(wq * ((zmax + __logf(ssum)) - zt)) * 1048576.0); my_w += (double)(wq * 1048576.f); } }
+            else
             if (own) { my_loss += rint((double)((zmax + __logf(ssum)) - zt) * 1048576.0); my_cnt += 1; }
             }
             const float wt = 1.f - ty;
@@ -449,7 +474,8 @@ void ce_loss_grad_kernel(const float* __restrict__ logits, HeadGeom g, ClassTabl
                 if (k < g.K) {
                     float want;
                     if constexpr (SOFT) want = pt[k]; else want = k == target ? 1.f : 0.f;
-                    const float d = z[k] * rs - want;
+                    float d = z[k] * rs - want;
+                    if constexpr (WT) d *= wq;
                     gt[k] += wt * d;
                     gb[k] += ty * d;
                 }
@@ -464,7 +490,8 @@ void ce_loss_grad_kernel(const float* __restrict__ logits, HeadGeom g, ClassTabl
     s_wx[threadIdx.x][1] = x1 != x0 ? tx : 0.f;       // clamped right neighbour (last source column): tx is 0 there anyway
     my_loss = wave_sum(my_loss);
     my_cnt = (int)wave_sum((float)my_cnt);
-    if ((threadIdx.x & 63) == 0) { s_loss[threadIdx.x >> 6] = my_loss; s_cnt[threadIdx.x >> 6] = my_cnt; }
+    if constexpr (WT) my_w = wave_sum(my_w);
+    if ((threadIdx.x & 63) == 0) { s_loss[threadIdx.x >> 6] = my_loss; s_cnt[threadIdx.x >> 6] = my_cnt; if constexpr (WT) s_w[threadIdx.x >> 6] = my_w; }
     __syncthreads();
     // fold the pixel columns into the cell columns: entry e = (cell column jj, plane tb, class k), columns in ascending order
     for (int e = threadIdx.x; e < kCeCB * 2 * KMAX; e += blockDim.x) {
@@ -486,6 +513,7 @@ void ce_loss_grad_kernel(const float* __restrict__ logits, HeadGeom g, ClassTabl
         for (int i = 0; i < 3; ++i) { ls += s_loss[i]; cn += s_cnt[i]; }
         double* mine = loss + 2 * (((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x);
         mine[0] = ls; mine[1] = (double)cn;
+        if constexpr (WT) mine[1] = ((s_w[0] + s_w[1]) + s_w[2]) * (1.0 / 1048576.0);      // integers below 2^46 (sum_kernel below): exact, any order
     }
 }
 
@@ -496,7 +524,7 @@ __global__ __launch_bounds__(256) void ce_combine_kernel(const float* __restrict
                                                          const double* __restrict__ loss_and_count, float* __restrict__ dlogits, int ldd,
                                                          float empty_val) {
     const double nvalid = loss_and_count[1];
-    const float inv_n = nvalid > 0.5 ? (float)(1.0 / nvalid) : 0.f;
+    const float inv_n = nvalid > 0 ? (float)(1.0 / nvalid) : 0.f;           // a weight sum can lie far below 1; for counts the same test as > 0.5
     for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < cells * ldd; e += (int64_t)gridDim.x * blockDim.x) {
         const int64_t cell = e / ldd;
         const int c = (int)(e - cell * ldd);
@@ -506,7 +534,7 @@ __global__ __launch_bounds__(256) void ce_combine_kernel(const float* __restrict
             const int i = (int)((cell / w_cells) % h_cells);
             const float t = partT[cell * KMAX + k];
             v = (i > 0 ? t + partB[cell * KMAX + k] : t) * inv_n;          // row 0 has no band above it
-            if (!(nvalid > 0.5)) v = empty_val;                             // no valid pixel: 0, or the reference's 0 / 0 (AMS_OPT_NAN_GRADS)
+            if (!(nvalid > 0)) v = empty_val;                               // no valid pixel: 0, or the reference's 0 / 0 (AMS_OPT_NAN_GRADS)
         }
         dlogits[e] = v;
     }
@@ -536,10 +564,14 @@ __global__ __launch_bounds__(256) void ce_loss_sum_kernel(const double* __restri
 }
 
 // pass 1: loss[0] += CE sum, loss[1] += valid pixels (loss zeroed here), unnormalised gradient planes into scratch
+// (under class weights or conf_gamma: loss[0] = sum of w_q pixel, loss[1] = sum of w_q, the planes weighted likewise)
 int launch_ce_loss_grad(const float* logits, int ld, int B, int h, int w, const int32_t* cls, int K, int H, int W, const uint8_t* teacher,
                         int NC, double* loss, float* scratch, hipStream_t st, const float* soft_logits, int soft_h, int soft_w, int soft_layout,
-                        float kd_temperature, float kd_alpha) {
+                        float kd_temperature, float kd_alpha, const float* class_weights, float conf_gamma) {
     if (int rc = kd_params_check("ce_loss_grad", kd_temperature, kd_alpha)) return rc;
+    if (int rc = loss_weights_check("ce_loss_grad", class_weights, K, K, conf_gamma)) return rc;
+    const bool weighted = !loss_weights_default(class_weights, K, conf_gamma);
+    AMS_REQUIRE(conf_gamma == 0.f || soft_logits, "ce_loss_grad: conf_gamma %g weights by the teacher's confidence: it needs teacher logits", (double)conf_gamma);
     ClassTable ct;
     int rc = fill_class_table(cls, K, NC, &ct);
     if (rc) return rc;
@@ -563,29 +595,39 @@ int launch_ce_loss_grad(const float* logits, int ld, int B, int h, int w, const 
     }
     // the KD forms of the soft step: (T, alpha) = (1, 1) is the soft instantiation and alpha = 0 the hard one, the same launches as without the
     // two parameters, so those cases are the same bits by construction
-    const int kd_form = !soft_logits || kd_alpha == 0.f ? -1 : kd_alpha == 1.f ? (kd_temperature == 1.f ? 0 : 1) : 2;
+    int kd_form = !soft_logits || kd_alpha == 0.f ? -1 : kd_alpha == 1.f ? (kd_temperature == 1.f ? 0 : 1) : 2;
     KdParams kd;
     kd.inv_t = 1.f / kd_temperature;
     kd.at2 = kd_alpha * (kd_temperature * kd_temperature);
     kd.at = kd_alpha * kd_temperature;
     kd.om = 1.f - kd_alpha;
-    note_kernel(kd_form == 2 ? "ce_loss_grad_kernel<soft, mix>" : kd_form == 1 ? "ce_loss_grad_kernel<soft, T>" : kd_form == 0 ? "ce_loss_grad_kernel<soft>" : "ce_loss_grad_kernel");
-    if (kd_form == 2) {
-        if (KM == 8) hipLaunchKernelGGL((ce_loss_grad_kernel<8, true, 2>), grid, dim3(192), 0, st, logits, g, ct, teacher, blk, partT, partB, sft, kd);
-        else if (KM == 20) hipLaunchKernelGGL((ce_loss_grad_kernel<20, true, 2>), grid, dim3(192), 0, st, logits, g, ct, teacher, blk, partT, partB, sft, kd);
-        else hipLaunchKernelGGL((ce_loss_grad_kernel<32, true, 2>), grid, dim3(192), 0, st, logits, g, ct, teacher, blk, partT, partB, sft, kd);
-    } else if (kd_form == 1) {
-        if (KM == 8) hipLaunchKernelGGL((ce_loss_grad_kernel<8, true, 1>), grid, dim3(192), 0, st, logits, g, ct, teacher, blk, partT, partB, sft, kd);
-        else if (KM == 20) hipLaunchKernelGGL((ce_loss_grad_kernel<20, true, 1>), grid, dim3(192), 0, st, logits, g, ct, teacher, blk, partT, partB, sft, kd);
-        else hipLaunchKernelGGL((ce_loss_grad_kernel<32, true, 1>), grid, dim3(192), 0, st, logits, g, ct, teacher, blk, partT, partB, sft, kd);
-    } else if (kd_form == 0) {
-        if (KM == 8) hipLaunchKernelGGL((ce_loss_grad_kernel<8, true>), grid, dim3(192), 0, st, logits, g, ct, teacher, blk, partT, partB, sft, kd);
-        else if (KM == 20) hipLaunchKernelGGL((ce_loss_grad_kernel<20, true>), grid, dim3(192), 0, st, logits, g, ct, teacher, blk, partT, partB, sft, kd);
-        else hipLaunchKernelGGL((ce_loss_grad_kernel<32, true>), grid, dim3(192), 0, st, logits, g, ct, teacher, blk, partT, partB, sft, kd);
+    // One launch per (KMAX tier, SOFT, KD, WT).  All-ones class weights with gamma = 0 go to the WT = false instantiations, which are compiled from
+    // the code as it was: the hard, soft and KD steps of a student that never set weights keep their bits.
+    auto go = [&](auto soft_c, auto kd_c, auto wt_c, auto lwv) {
+        constexpr bool S = decltype(soft_c)::value, Wt = decltype(wt_c)::value;
+        constexpr int D = decltype(kd_c)::value;
+        if (KM == 8) hipLaunchKernelGGL((ce_loss_grad_kernel<8, S, D, Wt>), grid, dim3(192), 0, st, logits, g, ct, teacher, blk, partT, partB, sft, kd, lwv);
+        else if (KM == 20) hipLaunchKernelGGL((ce_loss_grad_kernel<20, S, D, Wt>), grid, dim3(192), 0, st, logits, g, ct, teacher, blk, partT, partB, sft, kd, lwv);
+        else hipLaunchKernelGGL((ce_loss_grad_kernel<32, S, D, Wt>), grid, dim3(192), 0, st, logits, g, ct, teacher, blk, partT, partB, sft, kd, lwv);
+    };
+    using std::bool_constant; using std::integral_constant;
+    if (weighted) {
+        LossWeights lw;
+        fill_loss_weights(ct, class_weights, K, conf_gamma, &lw);
+        // gamma > 0 with alpha = 0: the hard form has no teacher distribution, the mix form computes p anyway (alpha T^2 = alpha T = 0, 1 - alpha = 1)
+        if (kd_form < 0 && conf_gamma > 0.f) kd_form = 2;
+        note_kernel(kd_form == 2 ? "ce_loss_grad_kernel<soft, mix, weighted>" : kd_form == 1 ? "ce_loss_grad_kernel<soft, T, weighted>" : kd_form == 0 ? "ce_loss_grad_kernel<soft, weighted>" : "ce_loss_grad_kernel<weighted>");
+        if (kd_form == 2) go(bool_constant<true>{}, integral_constant<int, 2>{}, bool_constant<true>{}, lw);
+        else if (kd_form == 1) go(bool_constant<true>{}, integral_constant<int, 1>{}, bool_constant<true>{}, lw);
+        else if (kd_form == 0) go(bool_constant<true>{}, integral_constant<int, 0>{}, bool_constant<true>{}, lw);
+        else go(bool_constant<false>{}, integral_constant<int, 0>{}, bool_constant<true>{}, lw);
     } else {
-    if (KM == 8) hipLaunchKernelGGL((ce_loss_grad_kernel<8, false>), grid, dim3(192), 0, st, logits, g, ct, teacher, blk, partT, partB, sft, kd);
-    else if (KM == 20) hipLaunchKernelGGL((ce_loss_grad_kernel<20, false>), grid, dim3(192), 0, st, logits, g, ct, teacher, blk, partT, partB, sft, kd);
-    else hipLaunchKernelGGL((ce_loss_grad_kernel<32, false>), grid, dim3(192), 0, st, logits, g, ct, teacher, blk, partT, partB, sft, kd);
+        const NoLossWeights nlw;
+        note_kernel(kd_form == 2 ? "ce_loss_grad_kernel<soft, mix>" : kd_form == 1 ? "ce_loss_grad_kernel<soft, T>" : kd_form == 0 ? "ce_loss_grad_kernel<soft>" : "ce_loss_grad_kernel");
+        if (kd_form == 2) go(bool_constant<true>{}, integral_constant<int, 2>{}, bool_constant<false>{}, nlw);
+        else if (kd_form == 1) go(bool_constant<true>{}, integral_constant<int, 1>{}, bool_constant<false>{}, nlw);
+        else if (kd_form == 0) go(bool_constant<true>{}, integral_constant<int, 0>{}, bool_constant<false>{}, nlw);
+        else go(bool_constant<false>{}, integral_constant<int, 0>{}, bool_constant<false>{}, nlw);
     }
     AMS_CHECK_LAUNCH();
     hipLaunchKernelGGL(ce_loss_sum_kernel, dim3(1), dim3(256), 0, st, blk, (int)(grid.x * grid.y * grid.z), loss);

@@ -386,9 +386,12 @@ size_t ce_loss_grad_scratch(int B, int h, int w, int K);
 // kd_temperature T, kd_alpha (soft_logits only; checked always): softmax(./T) on both logit sets with the T^2 factor, mixed alpha : 1 - alpha with the
 // hard-label CE (k_head.hip KD); (1, 1) launches the soft kernel and alpha = 0 the hard one, as without them
 // soft_layout: AMS_TLOGITS_FULL, or AMS_TLOGITS_SELECTED = [B][soft_h][soft_w][K], channel k holding class cls[k]'s logit (head_common.hpp)
+// class_weights (HOST, K floats in the order of cls, nullptr = ones), conf_gamma (needs soft_logits when > 0; both checked always): per-pixel weight
+// cw_y max_k p_k ^ gamma and a weighted mean, loss[1] = sum of the weights (k_head.hip WT); all ones with gamma = 0 launch the kernels as without them
 int launch_ce_loss_grad(const float* logits, int ld, int B, int h, int w, const int32_t* cls, int K, int H, int W, const uint8_t* teacher,
                         int NC, double* loss, float* scratch, hipStream_t st, const float* soft_logits = nullptr, int soft_h = 0, int soft_w = 0,
-                        int soft_layout = AMS_TLOGITS_FULL, float kd_temperature = 1.f, float kd_alpha = 1.f);
+                        int soft_layout = AMS_TLOGITS_FULL, float kd_temperature = 1.f, float kd_alpha = 1.f,
+                        const float* class_weights = nullptr, float conf_gamma = 0.f);
 // empty_val: every selected class's gradient when NO pixel of the (global) batch is valid: 0, or NaN = the reference's 0 / 0
 // (utils/graph_utils.py:408: loss = sum(w ce) / sum(w))
 int launch_ce_combine(int B, int h, int w, const int32_t* cls, int K, int NC, const double* loss_and_count, const float* scratch,

@@ -85,6 +85,7 @@ class StudentEngine:
         self.num_classes = int(num_classes)
         self.soft_teacher = False
         self.kd_temperature, self.kd_alpha = 1.0, 1.0
+        self.loss_class_weights, self.conf_gamma = None, 0.0
         self._reg_mask = self._teacher_logits_dev = None
         self._frames_b, self._frames_u8, self._frames_metric = 0, False, False
         self.class_indices = [int(c) for c in class_indices]
@@ -290,6 +291,18 @@ class StudentEngine:
         ``alpha`` in [0, 1]; read only while ``set_soft_teacher(True)`` holds.  ``alpha = 0`` is the hard-label step."""
         hip.check(self.lib.ams_student_set_kd(self._h, float(temperature), float(alpha)), "ams_student_set_kd")
         self.kd_temperature, self.kd_alpha = float(temperature), float(alpha)
+
+    def set_loss_weights(self, class_weights=None, conf_gamma: float = 0.0) -> None:
+        """Weights of the fine-tune loss (this project's own): ``class_weights``, K floats in the order of the class index list, each 0 or in
+        [2^-6, 16] (None = ones), and ``conf_gamma`` in [0, 8], the exponent of the teacher's confidence ``c = max_k softmax(t / T)_k`` (needs
+        ``set_soft_teacher(True)`` when > 0).  Per valid pixel ``w = cw_y c^gamma``; loss and gradient become the ``w``-weighted means, and a
+        step's second number is the sum of the weights instead of the pixel count.  Ones and 0 are the unweighted step, bit for bit."""
+        cw = None
+        if class_weights is not None:
+            cw = np.ascontiguousarray(np.asarray(class_weights, dtype=np.float32).reshape(-1))
+        hip.check(self.lib.ams_student_set_loss_weights(self._h, cw.ctypes.data_as(C.POINTER(C.c_float)) if cw is not None else None,
+                                                        int(cw.size) if cw is not None else 0, float(conf_gamma)), "ams_student_set_loss_weights")
+        self.loss_class_weights, self.conf_gamma = cw, float(conf_gamma)
 
     def set_regularizer(self, on: bool, biases_only: bool = False, coef: float = 0.01) -> None:
         """create_student_v3(regularize=True[, train_biases_only=True]) (utils/graph_utils.py:451-456): loss += coef * mean over tvars of

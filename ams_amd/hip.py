@@ -135,6 +135,7 @@ SIGNATURES = {
     "ams_student_f16_fallback_layers": (C.c_int, [_vp, C.POINTER(_i32)]),
     "ams_student_set_regularizer": (C.c_int, [_vp, _vp, _i32, _f32]),
     "ams_student_set_kd": (C.c_int, [_vp, _f32, _f32]),
+    "ams_student_set_loss_weights": (C.c_int, [_vp, C.POINTER(_f32), _i32, _f32]),
     "ams_student_profile": (C.c_int, [_vp, _i32]),
     "ams_student_profile_read": (C.c_int, [_vp, C.c_char_p, _sz, C.POINTER(_sz)]),
     "ams_student_get_adam_step": (C.c_int, [_vp, C.POINTER(_i64)]),
@@ -178,6 +179,8 @@ SIGNATURES = {
     "ams_k_ce_loss_grad_soft_layout": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i32), _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
     "ams_k_ce_loss_grad_kd": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i32), _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp,
                                         _f32, _f32]),
+    "ams_k_ce_loss_grad_weighted": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i32), _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _sz,
+                                              _vp, _f32, _f32, C.POINTER(_f32), _f32]),
     "ams_debug_launch_table_needs_attr": (C.c_int, [_i32, C.c_uint64, _sz]),
     "ams_debug_reload_knobs": (C.c_int, []),
     "ams_debug_phase_cycles": (C.c_int, [C.c_int32, C.POINTER(C.c_uint64), C.c_int32]),

@@ -415,6 +415,18 @@ class DeviceReplayMemory:
             out.append((conf_mat_, iou_, np.nanmean(iou_)))
         return out
 
+    def class_counts(self, network) -> np.ndarray:
+        """Pixels per class of the network's subset over every label map in the memory, int64 [K]: the label-confusion kernel on each slot
+        against itself has the slot's histogram on its diagonal (one launch, one copy; no kernel of its own)."""
+        n = len(self)
+        if n == 0:
+            return np.zeros(network.engine.K, dtype=np.int64)
+        phys = self.ring.physical(np.arange(n, dtype=np.int64))
+        pairs = np.ascontiguousarray(np.stack([phys, phys], axis=1), dtype=np.int32)
+        with network.process_lock:
+            conf = self._cross_confusion_pairs(network.engine, pairs)
+        return np.einsum("nkk->k", conf).astype(np.int64)
+
     def _cross_confusion_pairs(self, eng, pairs: np.ndarray) -> np.ndarray:
         n = int(pairs.shape[0])
         pairs_dev = self._upload(pairs)

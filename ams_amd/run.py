@@ -51,7 +51,8 @@ from .delta import delta_layout
 from .exp_configs import class_weights, coco_class_converter, is_coco, test_length
 from .semantic_network import FrozenGraph, SemanticNetwork
 from .synth import SyntheticVideo
-from .utils import calculate_miou, choose_frames, resize_linear, resize_nearest, string_class_iou
+from .utils import (balanced_class_weights, calculate_miou, choose_frames, label_class_counts, resize_linear, resize_nearest,
+                    string_class_iou)
 
 
 # ----------------------------------------------------------------------------------------------------------- flags
@@ -131,6 +132,14 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--kd_alpha", type=float, default=None,
                    help="server: weight of the soft term in the soft-teacher loss (extra flag; needs --soft_teacher; in [0, 1], default 1); the "
                         "hard-label cross-entropy takes 1 - kd_alpha")
+    p.add_argument("--loss_class_weights", default=None,
+                   help="server: per-class weights of the fine-tune loss with a weighted mean (extra flag): K comma-separated floats in the order "
+                        "of the experiment's classes, each 0 or in [2^-6, 16], or 'balanced' = N / (P n_k) capped to that range, recomputed at the "
+                        "start of every training phase from the labels then in the replay memory.  Also writes <results>_loss_weights.npy "
+                        "[phases, K]; evaluation stays unweighted and every other file keeps its name and format")
+    p.add_argument("--kd_conf_gamma", type=float, default=None,
+                   help="server: weight every pixel of the soft-teacher loss by the teacher's confidence (largest target probability) to this power "
+                        "(extra flag; needs --soft_teacher; in [0, 8], default 0)")
     p.add_argument("--horizon_k1s", default="16,32,64,128,256,512", help="horizon mode: training-window lengths in seconds (reference: hard-coded)")
     p.add_argument("--horizon_k2", type=int, default=256, help="horizon mode: evaluation window in seconds (reference: 256)")
     p.add_argument("--horizon_points", type=int, default=3, help="horizon mode: number of evaluation points (reference: 3)")
@@ -349,6 +358,12 @@ def train_model(ctx: Context, train_start, train_end, sampling_period, gpu_id, r
             memory_kw = dict(logits_shape=(lh, lw, nc), logits_upsample=True, logits_select=np.where(cw.reshape(-1) == 1)[0].tolist())
         device_memory = DeviceReplayMemory(mem, ctx.size[0], ctx.size[1], "cuda:%s" % gpu_id, **memory_kw)
 
+    # --loss_class_weights: K fixed weights, or 'balanced' = recomputed per phase from the memory's labels (the scene changes)
+    weights_flag = getattr(FLAGS, "loss_class_weights", None)
+    balanced = weights_flag == "balanced"
+    fixed_weights = None if weights_flag is None or balanced else parse_loss_class_weights(weights_flag, int(class_weights(exp_num).sum()))
+    conf_gamma = float(getattr(FLAGS, "kd_conf_gamma", None) or 0.0)
+    loss_weights_log = []     # --loss_class_weights, per training phase: the K weights it ran under
     semantic_network = ctx.network_cls(meta_dir=FLAGS.student_checkpoint, class_weights_exp=class_weights(exp_num),
                                        height=FLAGS.height, gpu_id=gpu_id, scale=[1], mini_batch_size=FLAGS.batch_size,
                                        lr=FLAGS.lr, mem_frac=1, coord_frac=float(FLAGS.coord_fraction),
@@ -357,7 +372,9 @@ def train_model(ctx: Context, train_start, train_end, sampling_period, gpu_id, r
                                        cross_miou_compat=FLAGS.enable_ASR, initial_variables=ctx.initial_variables,
                                        **({"device_masks": True} if getattr(FLAGS, "device_masks", False) else {}),
                                        **({"soft_teacher": True} if soft_teacher else {}),
-                                       **{k: float(getattr(FLAGS, k)) for k in ("kd_temperature", "kd_alpha") if getattr(FLAGS, k, None) is not None})
+                                       **{k: float(getattr(FLAGS, k)) for k in ("kd_temperature", "kd_alpha", "kd_conf_gamma")
+                                          if getattr(FLAGS, k, None) is not None},
+                                       **({"loss_class_weights": fixed_weights} if fixed_weights is not None else {}))
     save_dir = ctx.save_dir(run_label + "_%d" % train_start)
     semantic_network.save_to_frozen_graph(save_dir + "_final")
     print_process("Saved model to %s_final.pb" % save_dir, 0)
@@ -447,6 +464,13 @@ def train_model(ctx: Context, train_start, train_end, sampling_period, gpu_id, r
 
             if not FLAGS.no_restore:
                 semantic_network.restore_initial()
+            if balanced:
+                # the same integer histogram on either memory, so the same weights bit for bit
+                counts = device_memory.class_counts(semantic_network) if device_memory is not None \
+                    else label_class_counts(label_memory, semantic_network.class_indices_graph)
+                semantic_network.set_loss_weights(balanced_class_weights(counts), conf_gamma)
+            if weights_flag is not None:
+                loss_weights_log.append(np.asarray(semantic_network.loss_class_weights, dtype=np.float32))
             t1 = time.time()
             if device_memory is not None:
                 semantic_network.train_with_deque(device_memory, None, FLAGS.iter, FLAGS.train_strategy)
@@ -490,6 +514,8 @@ def train_model(ctx: Context, train_start, train_end, sampling_period, gpu_id, r
     np.save(final_save_dir + '_model_update_times.npy', model_save_times)
     np.save(final_save_dir + '_train_ms.npy', train_ms)
     np.save(final_save_dir + '_control.npy', np.asarray(control_log, dtype=np.float64).reshape(-1, 5))
+    if weights_flag is not None:
+        np.save(final_save_dir + '_loss_weights.npy', np.asarray(loss_weights_log, dtype=np.float32).reshape(-1, int(class_weights(exp_num).sum())))
     if soft_teacher:
         k = int(class_weights(exp_num).sum())
         np.save(final_save_dir + '_soft_eval.npy', np.asarray(soft_eval, dtype=np.float64).reshape(-1, 3 + k))
@@ -658,6 +684,19 @@ def event_times(flags, length: int) -> List[int]:
                   if t == 0 or t >= flags.memory_len or not flags.initial_fill]
 
 
+def parse_loss_class_weights(text: str, k: int) -> np.ndarray:
+    """--loss_class_weights as K comma-separated floats: f32 [K], or a ValueError that names what is wrong."""
+    try:
+        cw = np.asarray([float(t) for t in text.split(",")], dtype=np.float32)
+    except ValueError:
+        raise ValueError("--loss_class_weights must be 'balanced' or %d comma-separated floats (got %r)" % (k, text))
+    if cw.shape != (k,):
+        raise ValueError("--loss_class_weights needs one weight per class of the experiment: %d, got %d" % (k, cw.size))
+    if not np.all((cw == 0) | ((cw >= 2.0 ** -6) & (cw <= 16.0))):
+        raise ValueError("--loss_class_weights must each be 0 or lie in [2^-6, 16] (got %r)" % text)
+    return cw
+
+
 def parse_flags(argv: Optional[List[str]] = None):
     """The flags, with the combinations the soft-teacher path cannot serve refused in words."""
     parser = build_parser()
@@ -667,13 +706,20 @@ def parse_flags(argv: Optional[List[str]] = None):
                      "deques carry no teacher logits)")
     if flags.labels_from_logits and not flags.soft_teacher:
         parser.error("--labels_from_logits needs --soft_teacher: the labels are derived from the teacher logits that flag caches")
-    for name in ("kd_temperature", "kd_alpha"):
+    for name in ("kd_temperature", "kd_alpha", "kd_conf_gamma"):
         if getattr(flags, name) is not None and not flags.soft_teacher:
             parser.error("--%s needs --soft_teacher: it shapes the loss against the teacher logits that flag caches" % name)
     if flags.kd_temperature is not None and not (np.isfinite(flags.kd_temperature) and flags.kd_temperature > 0):
         parser.error("--kd_temperature must be finite and > 0 (got %r)" % flags.kd_temperature)
     if flags.kd_alpha is not None and not 0.0 <= flags.kd_alpha <= 1.0:
         parser.error("--kd_alpha must lie in [0, 1] (got %r)" % flags.kd_alpha)
+    if flags.kd_conf_gamma is not None and not (np.isfinite(flags.kd_conf_gamma) and 0.0 <= flags.kd_conf_gamma <= 8.0):
+        parser.error("--kd_conf_gamma must lie in [0, 8] (got %r)" % flags.kd_conf_gamma)
+    if flags.loss_class_weights is not None and flags.loss_class_weights != "balanced":
+        try:
+            parse_loss_class_weights(flags.loss_class_weights, int(class_weights(video_number(flags.input_video)).sum()))
+        except ValueError as e:
+            parser.error(str(e))
     if flags.labels_from_logits and is_coco(video_number(flags.input_video)):
         parser.error("--labels_from_logits does not go with experiment %d: its teacher labels arrive in COCO numbering and are converted on the "
                      "way into the memory (map_coco), which an argmax over the logits' own classes cannot stand for"

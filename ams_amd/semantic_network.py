@@ -152,9 +152,15 @@ class SemanticNetwork(object):
         # Evaluation (predict_with_soft_metric, evaluate_memory) keeps reporting the reference's T = 1 soft loss
         self.kd_temperature = float(kwargs.pop("kd_temperature", 1.0))
         self.kd_alpha = float(kwargs.pop("kd_alpha", 1.0))
+        # this project's own as well: per-class weights of the fine-tune loss and the exponent of the teacher's confidence (StudentEngine.set_loss_weights).
+        # Evaluation stays unweighted, so that runs trained under different weights stay comparable
+        self.loss_class_weights = kwargs.pop("loss_class_weights", None)
+        self.kd_conf_gamma = float(kwargs.pop("kd_conf_gamma", 0.0))
         if frozen:                 # the reference's frozen branch never calls create_student_v3: the kwargs are accepted and unused there too
             self.soft_teacher = self.regularize = self.train_biases_only = False
             self.kd_temperature = self.kd_alpha = 1.0
+            self.loss_class_weights, self.kd_conf_gamma = None, 0.0
+        self.loss_class_weights = self._checked_loss_weights(self.loss_class_weights, self.kd_conf_gamma)
         assert self.soft_teacher or (self.kd_temperature == 1.0 and self.kd_alpha == 1.0), \
             "kd_temperature / kd_alpha shape the soft_teacher loss: they need soft_teacher=True"
         assert np.isfinite(self.kd_temperature) and self.kd_temperature > 0, "kd_temperature must be finite and > 0"
@@ -204,6 +210,8 @@ class SemanticNetwork(object):
                 self.engine.set_soft_teacher(True)
                 if (self.kd_temperature, self.kd_alpha) != (1.0, 1.0):
                     self.engine.set_kd(self.kd_temperature, self.kd_alpha)
+            if self.loss_class_weights is not None or self.kd_conf_gamma != 0.0:
+                self.engine.set_loss_weights(self.loss_class_weights, self.kd_conf_gamma)
             if self.regularize:
                 self.engine.set_regularizer(True, biases_only=self.train_biases_only)
             self.mask = None
@@ -542,6 +550,26 @@ class SemanticNetwork(object):
         if feed is not None and feed.error is not None:
             raise feed.error                        # a helper's own exception (the reference would hang with the lock held)
 
+    def _checked_loss_weights(self, class_weights, conf_gamma):
+        """The K weights as f32 (or None), after the assertions of the two loss-weight arguments."""
+        assert np.isfinite(conf_gamma) and 0.0 <= conf_gamma <= 8.0, "kd_conf_gamma must lie in [0, 8]"
+        assert self.soft_teacher or conf_gamma == 0.0, "kd_conf_gamma weights by the teacher's confidence: it needs soft_teacher=True"
+        if class_weights is None:
+            return None
+        cw = np.asarray(class_weights, dtype=np.float32).reshape(-1)
+        assert cw.shape == (self.class_count,), "loss_class_weights must have one entry per selected class (%d)" % self.class_count
+        assert np.all((cw == 0) | ((cw >= 2.0 ** -6) & (cw <= 16.0))), "loss_class_weights must each be 0 or lie in [2^-6, 16]"
+        return cw
+
+    def set_loss_weights(self, class_weights=None, conf_gamma: float = 0.0) -> None:
+        """``StudentEngine.set_loss_weights`` for the phases to come: K per-class weights (None = ones) and the exponent of the teacher's
+        confidence (needs ``soft_teacher=True`` when > 0).  Training only; evaluation keeps reporting the unweighted losses."""
+        assert not self.frozen, "Can't train frozen graph!!!"
+        cw = self._checked_loss_weights(class_weights, float(conf_gamma))
+        with self.process_lock:
+            self.engine.set_loss_weights(cw, float(conf_gamma))
+        self.loss_class_weights, self.kd_conf_gamma = cw, float(conf_gamma)
+
     def _host_feed(self) -> HostBatchFeed:
         """The helper threads and pinned staging ring of training from host deques (ams_amd/batch_feed.py), kept from phase to phase; made
         on first use and again when the instance's batch geometry changed since."""
@@ -610,7 +638,7 @@ class SemanticNetwork(object):
             losses.append(loss_dev)
             if self.verbose:
                 ls = loss_dev.cpu().numpy()
-                print('Loss is %.3f at iteration %d and took %.1f ms' % (ls[0] / max(ls[1], 1), it,
+                print('Loss is %.3f at iteration %d and took %.1f ms' % (ls[0] / ls[1] if ls[1] > 0 else float('nan'), it,   # ls[1]: the weight sum, maybe < 1
                                                                          (time.time() - t1) * 1000.0))
             if on_device:
                 if it == 0 and before_dev is not None:

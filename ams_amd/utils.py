@@ -214,6 +214,31 @@ def string_class_iou(class_iou_list, population=None, headers=None, class_weight
     return "\n".join(lines) + "\n"
 
 
+def balanced_class_weights(counts):
+    """Per-class loss weights from pixel counts ``n_k`` of the subset's classes (scikit-learn's "balanced" rule, capped to what the loss kernel
+    takes): ``N / (P n_k)`` clipped to [2^-6, 16] where ``n_k > 0``, with ``N`` the sum of the counts and ``P`` the number of classes present;
+    1 for an absent class.  Computed in f64, returned as f32."""
+    n = np.asarray(counts, dtype=np.float64).reshape(-1)
+    assert n.size > 0 and np.all(n >= 0), "counts must be non-negative, one per class"
+    present = n > 0
+    cw = np.ones(n.shape, dtype=np.float64)
+    if present.any():
+        cw[present] = np.clip(n.sum() / (present.sum() * n[present]), 2.0 ** -6, 16.0)
+    return cw.astype(np.float32)
+
+
+def label_class_counts(labels, class_indices):
+    """Pixels per subset class over an iterable of label maps: int64 [K], ids truncated and folded to a byte as the engine's upload does."""
+    hist = np.zeros(256, dtype=np.int64)
+    for lab in labels:
+        a = np.asarray(lab)
+        if a.dtype != np.uint8:
+            ai = a.astype(np.float32).astype(np.int64)
+            a = np.where((ai >= 0) & (ai < 255), ai, 255)
+        hist += np.bincount(a.reshape(-1).astype(np.int64), minlength=256)
+    return hist[np.asarray(class_indices, dtype=np.int64)]
+
+
 def take_array_for(class_weights_exp):
     """Map full-label-space id -> index inside the selected subset (0 for unselected ids).
 

@@ -239,6 +239,17 @@ int ams_student_set_regularizer(ams_student* s, const uint8_t* reg_mask_dev, int
  * evaluation entries (ams_student_soft_metric, ams_k_upsample_soft_metric) keep reporting the reference's T = 1 soft loss. */
 int ams_student_set_kd(ams_student* s, float temperature, float alpha);
 
+/* Weights of the fine-tune loss (this project's own; the reference has none).  class_weights_host: HOST array of n = n_selected floats cw_k in the
+ * order of class_indices, each 0 or in [2^-6, 16]; NULL = all ones.  conf_gamma in [0, 8]: the exponent of the teacher's confidence
+ * c = max_k p_k, p = softmax(t / T) the very target distribution of ams_student_set_kd; read only on a soft-teacher step, where a step with
+ * conf_gamma > 0 and AMS_OPT_SOFT_TEACHER off is refused.  Per valid pixel w = cw_y c^gamma, quantised once to w_q = rint(w 2^20) 2^-20, and
+ *   loss = sum w_q pixel / sum w_q,   dlogits = sum w_q d / sum w_q      (pixel, d: whichever form of the loss is set),
+ * so loss_dev[1] of a step is sum w_q instead of the pixel count; a class of weight 0 is left out like an ignored label, and sum w_q = 0 is the
+ * batch without a valid pixel (NaN loss, zero gradients; AMS_OPT_NAN_GRADS).  AMS_E_INVALID, the student keeping what it had: n != n_selected;
+ * a weight that is NaN, negative, in (0, 2^-6) or above 16; conf_gamma outside [0, 8] or not finite.  Needs a trainable student.  All ones
+ * with conf_gamma = 0 (the default) run the kernels that run without this call: the same bits.  Evaluation entries stay unweighted. */
+int ams_student_set_loss_weights(ams_student* s, const float* class_weights_host /* n_selected, or NULL = ones */, int32_t n, float conf_gamma);
+
 /* ---- data-parallel split of the same step (one process per GPU) -------------------------
  * Callback form (any transport; what the gloo CPU tests and a host without RCCL use): `cb` is invoked on the host
  * whenever cross-rank sums are needed and must all-reduce (sum) `count` values of `dtype` at arena byte offset
@@ -838,6 +849,15 @@ int ams_k_ce_loss_grad_kd(const float* logits, int32_t B, int32_t h, int32_t w, 
                           int32_t K, int32_t H, int32_t W, const uint8_t* teacher, const float* teacher_logits, int32_t th, int32_t tw,
                           int32_t layout, double* loss_dev, float* dlogits, float* scratch, size_t scratch_floats, void* stream,
                           float temperature, float alpha);
+/* The same under per-class weights and the teacher-confidence weight (ams_student_set_loss_weights has the objective): loss_dev[1] = sum of the
+ * quantised weights.  class_weights_host: K floats or NULL = ones.  temperature, alpha, then class_weights_host's entries and conf_gamma are checked
+ * before any other pointer is looked at: AMS_E_INVALID, nothing launched, nothing written.  teacher_logits may be NULL when conf_gamma = 0 and
+ * alpha = 0.  conf_gamma > 0 with alpha = 0 runs the mix form, which has the teacher's distribution.  All ones with conf_gamma = 0 is
+ * ams_k_ce_loss_grad_kd, bit for bit. */
+int ams_k_ce_loss_grad_weighted(const float* logits, int32_t B, int32_t h, int32_t w, int32_t ld, int32_t NC, const int32_t* class_idx_host,
+                                int32_t K, int32_t H, int32_t W, const uint8_t* teacher, const float* teacher_logits, int32_t th, int32_t tw,
+                                int32_t layout, double* loss_dev, float* dlogits, float* scratch, size_t scratch_floats, void* stream,
+                                float temperature, float alpha, const float* class_weights_host, float conf_gamma);
 
 /* K13: weight gradient of a 1x1 conv: dw[K,N] = x[M,K]^T @ dy[M,N]. scratch: >= ams_k_pointwise_wgrad_scratch floats */
 int ams_k_pointwise_wgrad(const float* x, const float* dy, int64_t M, int32_t K, int32_t N, float* dw,
