@@ -340,11 +340,12 @@ int ams_student_f16_fallback_layers(const ams_student* s, int32_t* n_layers) {
 
 int ams_student_feed_teacher_logits_layout(ams_student* s, const float* teacher_logits_dev, int32_t th, int32_t tw, int32_t layout) {
     AMS_REQUIRE(s, "feed_teacher_logits: null student");
-    AMS_REQUIRE(layout == AMS_TLOGITS_FULL || layout == AMS_TLOGITS_SELECTED, "feed_teacher_logits: unknown teacher-logit layout %d", layout);
-    if (!teacher_logits_dev) { s->teacher_logits = nullptr; s->teacher_th = s->teacher_tw = 0; s->teacher_layout = AMS_TLOGITS_FULL; return AMS_OK; }
+    AMS_REQUIRE(tlogits_layout_ok(layout), "feed_teacher_logits: unknown teacher-logit layout %d", layout);
+    LossObjective& o = s->loss_objective;
+    if (!teacher_logits_dev) { o.teacher_logits = nullptr; o.th = o.tw = 0; o.layout = AMS_TLOGITS_FULL; return AMS_OK; }
     AMS_REQUIRE(th >= 1 && tw >= 1 && th <= s->cfg.height && tw <= s->cfg.width, "feed_teacher_logits: %d x %d teacher logits for %d x %d labels", th, tw,
                 s->cfg.height, s->cfg.width);
-    s->teacher_logits = teacher_logits_dev; s->teacher_th = th; s->teacher_tw = tw; s->teacher_layout = layout;
+    o.teacher_logits = teacher_logits_dev; o.th = th; o.tw = tw; o.layout = layout;
     return AMS_OK;
 }
 
@@ -365,7 +366,7 @@ int ams_student_set_kd(ams_student* s, float temperature, float alpha) {
     AMS_REQUIRE(s, "set_kd: null student");
     AMS_REQUIRE(s->cfg.trainable, "set_kd: this student was created frozen");
     RUN(kd_params_check("set_kd", temperature, alpha));
-    s->kd_temperature = temperature; s->kd_alpha = alpha;
+    s->loss_objective.temperature = temperature; s->loss_objective.alpha = alpha;
     return AMS_OK;
 }
 
@@ -374,8 +375,9 @@ int ams_student_set_loss_weights(ams_student* s, const float* class_weights_host
     AMS_REQUIRE(s->cfg.trainable, "set_loss_weights: this student was created frozen");
     AMS_REQUIRE(!class_weights_host || n == s->cfg.n_selected, "set_loss_weights: %d class weights for %d selected classes", n, s->cfg.n_selected);
     RUN(loss_weights_check("set_loss_weights", class_weights_host, n, s->cfg.n_selected, conf_gamma));
-    for (int k = 0; k < 32; ++k) s->loss_cw[k] = class_weights_host && k < n ? class_weights_host[k] : 1.f;
-    s->conf_gamma = conf_gamma;
+    for (int k = 0; k < n && class_weights_host; ++k) s->loss_cw[k] = class_weights_host[k];
+    s->loss_objective.class_weights = class_weights_host ? s->loss_cw : nullptr;
+    s->loss_objective.conf_gamma = conf_gamma;
     return AMS_OK;
 }
 
@@ -461,7 +463,7 @@ int ams_student_set_option(ams_student* s, int32_t option, int32_t value) {
         return AMS_OK;
     }
     if (option == AMS_OPT_SOFT_TEACHER) {
-        s->soft_teacher = value != 0;
+        s->loss_objective.soft_teacher = value != 0;
         return AMS_OK;
     }
     if (option == AMS_OPT_NAN_GRADS) {
@@ -872,75 +874,64 @@ int ams_k_ce_grad(const float* logits, int32_t B, int32_t h, int32_t w, int32_t 
 
 size_t ams_k_ce_loss_grad_scratch(int32_t B, int32_t h, int32_t w, int32_t K) { return ce_loss_grad_scratch(B, h, w, K); }
 
+// The one body of the five kernel-level loss entries.  Refused in this order: the KD parameters; the weights, before any pointer is looked at;
+// null teacher logits where the objective needs them (needs_teacher_logits: always, but for the weighted entry at alpha = 0 and gamma = 0); the
+// class table; K; layout; row stride; geometry; scratch.  Then the two launches.
+static int ce_loss_grad_entry(const char* who, const HeadCall& c, const LossObjective& o, bool needs_teacher_logits, double* loss_dev, float* dlogits,
+                              float* scratch, size_t scratch_floats, void* stream) {
+    RUN(kd_params_check(who, o.temperature, o.alpha));
+    RUN(loss_weights_check(who, o.class_weights, c.K, c.K, o.conf_gamma));
+    AMS_REQUIRE(o.teacher_logits || !needs_teacher_logits, "%s: null teacher logits (alpha %g, conf_gamma %g)", who, (double)o.alpha, (double)o.conf_gamma);
+    AMS_REQUIRE(c.cls, "%s: null class table", who);
+    AMS_REQUIRE(c.K >= 1 && c.K <= 32, "%s: K=%d out of range (1..32)", who, c.K);
+    AMS_REQUIRE(tlogits_layout_ok(o.layout), "%s: unknown teacher-logit layout %d", who, o.layout);
+    AMS_REQUIRE(c.ld >= c.NC && c.ld <= 256, "%s: row stride %d must hold %d classes", who, c.ld, c.NC);
+    AMS_REQUIRE(ce_loss_grad_supported(c.w, c.W), "%s: %d output columns on %d source columns is outside the one-pass kernel", who, c.W, c.w);
+    AMS_REQUIRE(scratch && scratch_floats >= ce_loss_grad_scratch(c.B, c.h, c.w, c.K), "%s: scratch too small (need %zu floats)", who,
+                ce_loss_grad_scratch(c.B, c.h, c.w, c.K));
+    hipStream_t st = (hipStream_t)stream;
+    RUN(launch_ce_loss_grad(c, o, loss_dev, scratch, st));
+    return launch_ce_combine(c, loss_dev, scratch, dlogits, c.ld, st);
+}
+
 int ams_k_ce_loss_grad(const float* logits, int32_t B, int32_t h, int32_t w, int32_t NC, const int32_t* class_idx_host, int32_t K, int32_t H,
                        int32_t W, const uint8_t* teacher, double* loss_dev, float* dlogits, float* scratch, size_t scratch_floats, void* stream) {
-    AMS_REQUIRE(ce_loss_grad_supported(w, W), "ce_loss_grad: %d output columns on %d source columns is outside the one-pass kernel", W, w);
-    AMS_REQUIRE(scratch && scratch_floats >= ce_loss_grad_scratch(B, h, w, K), "ce_loss_grad: scratch too small (need %zu floats)",
-                ce_loss_grad_scratch(B, h, w, K));
-    hipStream_t st = (hipStream_t)stream;
-    RUN(launch_ce_loss_grad(logits, NC, B, h, w, class_idx_host, K, H, W, teacher, NC, loss_dev, scratch, st));
-    return launch_ce_combine(B, h, w, class_idx_host, K, NC, loss_dev, scratch, dlogits, NC, st);
+    const HeadCall c{logits, NC, B, h, w, class_idx_host, K, H, W, teacher, NC};
+    return ce_loss_grad_entry("ce_loss_grad", c, LossObjective{}, false, loss_dev, dlogits, scratch, scratch_floats, stream);
 }
 
 int ams_k_ce_loss_grad_soft(const float* logits, int32_t B, int32_t h, int32_t w, int32_t NC, const int32_t* class_idx_host, int32_t K, int32_t H,
                             int32_t W, const uint8_t* teacher, const float* teacher_logits, int32_t th, int32_t tw, double* loss_dev, float* dlogits,
                             float* scratch, size_t scratch_floats, void* stream) {
-    return ams_k_ce_loss_grad_soft_layout(logits, B, h, w, NC, NC, class_idx_host, K, H, W, teacher, teacher_logits, th, tw, AMS_TLOGITS_FULL, loss_dev,
-                                          dlogits, scratch, scratch_floats, stream);
+    const HeadCall c{logits, NC, B, h, w, class_idx_host, K, H, W, teacher, NC};
+    const LossObjective o{teacher_logits, th, tw, AMS_TLOGITS_FULL};
+    return ce_loss_grad_entry("ce_loss_grad_soft", c, o, true, loss_dev, dlogits, scratch, scratch_floats, stream);
 }
 
 int ams_k_ce_loss_grad_soft_layout(const float* logits, int32_t B, int32_t h, int32_t w, int32_t ld, int32_t NC, const int32_t* class_idx_host,
                                    int32_t K, int32_t H, int32_t W, const uint8_t* teacher, const float* teacher_logits, int32_t th, int32_t tw, int32_t layout,
                                    double* loss_dev, float* dlogits, float* scratch, size_t scratch_floats, void* stream) {
-    AMS_REQUIRE(teacher_logits, "ce_loss_grad_soft: null teacher logits");
-    AMS_REQUIRE(class_idx_host, "ce_loss_grad_soft: null class table");
-    AMS_REQUIRE(K >= 1 && K <= 32, "ce_loss_grad_soft: K=%d out of range (1..32)", K);
-    AMS_REQUIRE(layout == AMS_TLOGITS_FULL || layout == AMS_TLOGITS_SELECTED, "ce_loss_grad_soft: unknown teacher-logit layout %d", layout);
-    AMS_REQUIRE(ld >= NC && ld <= 256, "ce_loss_grad_soft: row stride %d must hold %d classes", ld, NC);
-    AMS_REQUIRE(ce_loss_grad_supported(w, W), "ce_loss_grad: %d output columns on %d source columns is outside the one-pass kernel", W, w);
-    AMS_REQUIRE(scratch && scratch_floats >= ce_loss_grad_scratch(B, h, w, K), "ce_loss_grad: scratch too small (need %zu floats)",
-                ce_loss_grad_scratch(B, h, w, K));
-    hipStream_t st = (hipStream_t)stream;
-    RUN(launch_ce_loss_grad(logits, ld, B, h, w, class_idx_host, K, H, W, teacher, NC, loss_dev, scratch, st, teacher_logits, th, tw, layout));
-    return launch_ce_combine(B, h, w, class_idx_host, K, NC, loss_dev, scratch, dlogits, ld, st);
+    const HeadCall c{logits, ld, B, h, w, class_idx_host, K, H, W, teacher, NC};
+    const LossObjective o{teacher_logits, th, tw, layout};
+    return ce_loss_grad_entry("ce_loss_grad_soft_layout", c, o, true, loss_dev, dlogits, scratch, scratch_floats, stream);
 }
 
 int ams_k_ce_loss_grad_kd(const float* logits, int32_t B, int32_t h, int32_t w, int32_t ld, int32_t NC, const int32_t* class_idx_host, int32_t K,
                           int32_t H, int32_t W, const uint8_t* teacher, const float* teacher_logits, int32_t th, int32_t tw, int32_t layout,
                           double* loss_dev, float* dlogits, float* scratch, size_t scratch_floats, void* stream, float temperature, float alpha) {
-    RUN(kd_params_check("ce_loss_grad_kd", temperature, alpha));          // first: no pointer has been looked at when these two are refused
-    AMS_REQUIRE(teacher_logits, "ce_loss_grad_soft: null teacher logits");
-    AMS_REQUIRE(class_idx_host, "ce_loss_grad_soft: null class table");
-    AMS_REQUIRE(K >= 1 && K <= 32, "ce_loss_grad_soft: K=%d out of range (1..32)", K);
-    AMS_REQUIRE(layout == AMS_TLOGITS_FULL || layout == AMS_TLOGITS_SELECTED, "ce_loss_grad_soft: unknown teacher-logit layout %d", layout);
-    AMS_REQUIRE(ld >= NC && ld <= 256, "ce_loss_grad_soft: row stride %d must hold %d classes", ld, NC);
-    AMS_REQUIRE(ce_loss_grad_supported(w, W), "ce_loss_grad: %d output columns on %d source columns is outside the one-pass kernel", W, w);
-    AMS_REQUIRE(scratch && scratch_floats >= ce_loss_grad_scratch(B, h, w, K), "ce_loss_grad: scratch too small (need %zu floats)",
-                ce_loss_grad_scratch(B, h, w, K));
-    hipStream_t st = (hipStream_t)stream;
-    RUN(launch_ce_loss_grad(logits, ld, B, h, w, class_idx_host, K, H, W, teacher, NC, loss_dev, scratch, st, teacher_logits, th, tw, layout, temperature, alpha));
-    return launch_ce_combine(B, h, w, class_idx_host, K, NC, loss_dev, scratch, dlogits, ld, st);
+    const HeadCall c{logits, ld, B, h, w, class_idx_host, K, H, W, teacher, NC};
+    const LossObjective o{teacher_logits, th, tw, layout, temperature, alpha};
+    return ce_loss_grad_entry("ce_loss_grad_kd", c, o, true, loss_dev, dlogits, scratch, scratch_floats, stream);
 }
 
 int ams_k_ce_loss_grad_weighted(const float* logits, int32_t B, int32_t h, int32_t w, int32_t ld, int32_t NC, const int32_t* class_idx_host, int32_t K,
                                 int32_t H, int32_t W, const uint8_t* teacher, const float* teacher_logits, int32_t th, int32_t tw, int32_t layout,
                                 double* loss_dev, float* dlogits, float* scratch, size_t scratch_floats, void* stream, float temperature, float alpha,
                                 const float* class_weights_host, float conf_gamma) {
-    RUN(kd_params_check("ce_loss_grad_weighted", temperature, alpha));    // first, as in the KD entry; then the two new arguments, before any other pointer
-    RUN(loss_weights_check("ce_loss_grad_weighted", class_weights_host, K, K, conf_gamma));
-    AMS_REQUIRE(teacher_logits || (conf_gamma == 0.f && alpha == 0.f),
-                "ce_loss_grad_weighted: null teacher logits with alpha %g, conf_gamma %g (they may be NULL only when both are 0)", (double)alpha, (double)conf_gamma);
-    AMS_REQUIRE(class_idx_host, "ce_loss_grad_weighted: null class table");
-    AMS_REQUIRE(K >= 1 && K <= 32, "ce_loss_grad_weighted: K=%d out of range (1..32)", K);
-    AMS_REQUIRE(layout == AMS_TLOGITS_FULL || layout == AMS_TLOGITS_SELECTED, "ce_loss_grad_weighted: unknown teacher-logit layout %d", layout);
-    AMS_REQUIRE(ld >= NC && ld <= 256, "ce_loss_grad_weighted: row stride %d must hold %d classes", ld, NC);
-    AMS_REQUIRE(ce_loss_grad_supported(w, W), "ce_loss_grad: %d output columns on %d source columns is outside the one-pass kernel", W, w);
-    AMS_REQUIRE(scratch && scratch_floats >= ce_loss_grad_scratch(B, h, w, K), "ce_loss_grad: scratch too small (need %zu floats)",
-                ce_loss_grad_scratch(B, h, w, K));
-    hipStream_t st = (hipStream_t)stream;
-    RUN(launch_ce_loss_grad(logits, ld, B, h, w, class_idx_host, K, H, W, teacher, NC, loss_dev, scratch, st, teacher_logits, th, tw, layout, temperature, alpha,
-                            class_weights_host, conf_gamma));
-    return launch_ce_combine(B, h, w, class_idx_host, K, NC, loss_dev, scratch, dlogits, ld, st);
+    const HeadCall c{logits, ld, B, h, w, class_idx_host, K, H, W, teacher, NC};
+    const LossObjective o{teacher_logits, th, tw, layout, temperature, alpha, class_weights_host, conf_gamma};
+    // the one entry that takes NULL teacher logits: when neither the mix nor the weight looks at them
+    return ce_loss_grad_entry("ce_loss_grad_weighted", c, o, conf_gamma != 0.f || alpha != 0.f, loss_dev, dlogits, scratch, scratch_floats, stream);
 }
 
 size_t ams_k_pointwise_wgrad_scratch(int64_t M, int32_t K, int32_t N) { return pointwise_wgrad_scratch(M, K, N); }

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "kernels.hpp"
+#include "head_common.hpp"
 
 namespace ams {
 
@@ -161,12 +162,11 @@ struct ams_student {
     // logits)) (:375-376, 403-404), the logits fed per step (ams_student_feed_teacher_logits = feed_dict[teacher_labels_logits_pl]); regularize /
     // train_biases_only — 0.01 * mean of the l2 losses of tvars added to the loss (:451-456; ams_student_set_regularizer)
     int f16_fallback_layers = 0;     // layers whose frozen weights are beyond fp16's range (they run the three-part bf16 form); set by freeze
-    int soft_teacher = 0;
-    float kd_temperature = 1.f, kd_alpha = 1.f;      // the soft step's temperature and soft : hard mix (ams_student_set_kd; k_head.hip KD); (1, 1) = the reference's loss
-    // the fine-tune loss's per-class weights and the exponent of the teacher's confidence (ams_student_set_loss_weights; k_head.hip WT); ones and 0 = the plain mean
-    float loss_cw[32] = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};
-    float conf_gamma = 0.f;
-    const float* teacher_logits = nullptr; int teacher_th = 0, teacher_tw = 0, teacher_layout = AMS_TLOGITS_FULL;
+    // the fine-tune loss's objective: soft_teacher (AMS_OPT_SOFT_TEACHER), the logits fed per step (ams_student_feed_teacher_logits_layout), temperature and
+    // soft : hard mix (ams_student_set_kd), class weights and the exponent of the teacher's confidence (ams_student_set_loss_weights; class_weights
+    // points at loss_cw once they are set).  The defaults are the reference's loss; the step runs objective_of_step(loss_objective)
+    ams::LossObjective loss_objective;
+    float loss_cw[32];
     const uint8_t* reg_mask = nullptr; int reg_nvars = 0; float reg_coef = 0.f;
     int nan_grads = 0;               // a batch without a valid pixel: NaN loss, ZERO gradients — what TensorFlow computes for utils/graph_utils.py:408
                                      // (reduce_mean over the empty boolean_mask: its gradient is an empty tensor, densified to zeros); 1 = NaN gradients (AMS_OPT_NAN_GRADS)

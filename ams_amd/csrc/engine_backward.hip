@@ -66,6 +66,12 @@ static PwArgs dgrad_args(const float* dy, int64_t M, int N, int ldy, const float
     return a;
 }
 
+// the student's own logits (row stride 32) against a batch's labels: what both passes of the one-pass loss are given
+static HeadCall step_head_call(const ams_student* s, int B, const uint8_t* teacher) {
+    const ams_student_config& c = s->cfg;
+    return HeadCall{s->logits, 32, B, s->h, s->w, c.class_indices, c.n_selected, c.height, c.width, teacher, c.num_classes};
+}
+
 int backward(ams_student* s, const void* frames, int dtype, const uint8_t* teacher, int B, int global_B, const SyncCtx* sc,
                     hipStream_t st) {
     const ams_student_config& c = s->cfg;
@@ -81,7 +87,7 @@ int backward(ams_student* s, const void* frames, int dtype, const uint8_t* teach
     // AMS_OPT_NAN_GRADS = 1 writes NaN gradients instead (a loud failure for callers that prefer one).
     const float empty_val = s->nan_grads ? __builtin_nanf("") : 0.f;
     if (ce_loss_grad_supported(s->w, c.width))           // second pass of the one-pass loss kernel (train_step_impl ran the first)
-        RUNK(0, 0.0, launch_ce_combine(B, s->h, s->w, c.class_indices, c.n_selected, NC, s->loss_buf, s->ce_scratch, s->dlogits, 32, st, empty_val));
+        RUNK(0, 0.0, launch_ce_combine(step_head_call(s, B, teacher), s->loss_buf, s->ce_scratch, s->dlogits, 32, st, empty_val));
     else
         RUNK(0, 0.0, launch_ce_grad(s->logits, 32, B, s->h, s->w, c.class_indices, c.n_selected, c.height, c.width, teacher, NC, s->loss_buf,
                                     s->dlogits, 32, st, empty_val));
@@ -368,19 +374,18 @@ int backward(ams_student* s, const void* frames, int dtype, const uint8_t* teach
 
 int loss_forward(ams_student* s, const uint8_t* teacher, int B, int32_t* labels, hipStream_t st) {
     const ams_student_config& c = s->cfg;
-    const bool weighted = !labels && !loss_weights_default(s->loss_cw, c.n_selected, s->conf_gamma);          // evaluation stays unweighted
+    const LossObjective o = objective_of_step(s->loss_objective);
     if (!labels && ce_loss_grad_supported(s->w, c.width)) {
         // the fine-tune step: loss sums and the unnormalised gradient in one pass over the pixels
-        const bool soft = s->soft_teacher != 0;
-        AMS_REQUIRE(soft || s->conf_gamma == 0.f, "train_step: conf_gamma %g weights by the teacher's confidence: it needs soft_teacher (AMS_OPT_SOFT_TEACHER)",
-                    (double)s->conf_gamma);
-        RUNK(0, 0.0, launch_ce_loss_grad(s->logits, 32, B, s->h, s->w, c.class_indices, c.n_selected, c.height, c.width, teacher, c.num_classes,
-                                         s->loss_buf, s->ce_scratch, st, soft ? s->teacher_logits : nullptr, s->teacher_th, s->teacher_tw,
-                                         s->teacher_layout, soft ? s->kd_temperature : 1.f, soft ? s->kd_alpha : 1.f, s->loss_cw, s->conf_gamma));
+        AMS_REQUIRE(o.soft_teacher || o.conf_gamma == 0.f, "train_step: conf_gamma %g weights by the teacher's confidence: it needs soft_teacher (AMS_OPT_SOFT_TEACHER)",
+                    (double)o.conf_gamma);
+        RUNK(0, 0.0, launch_ce_loss_grad(step_head_call(s, B, teacher), o, s->loss_buf, s->ce_scratch, st));
         return AMS_OK;
     }
-    AMS_REQUIRE(!weighted, "loss weights: %d output columns on %d logit columns is outside the one-pass loss kernel", c.width, s->w);
-    AMS_REQUIRE(labels || !s->soft_teacher, "soft_teacher: %d output columns on %d logit columns is outside the one-pass loss kernel", c.width, s->w);
+    // evaluation (labels) stays unweighted
+    AMS_REQUIRE(labels || loss_weights_default(o.class_weights, c.n_selected, o.conf_gamma),
+                "loss weights: %d output columns on %d logit columns is outside the one-pass loss kernel", c.width, s->w);
+    AMS_REQUIRE(labels || !o.soft_teacher, "soft_teacher: %d output columns on %d logit columns is outside the one-pass loss kernel", c.width, s->w);
     return launch_upsample_argmax(s->logits, 32, B, s->h, s->w, c.class_indices, c.n_selected, c.height, c.width, teacher,
                                   c.num_classes, labels, s->conf_buf, s->loss_buf, st);
 }
@@ -393,7 +398,7 @@ int train_step_impl(ams_student* s, const void* frames_dev, int32_t frames_dtype
     if (!s->cfg.trainable) { set_error("train_step: this student was created frozen (trainable=0)"); return AMS_E_STATE; }
     AMS_REQUIRE(global_batch >= batch, "train_step: global batch %d < local batch %d", global_batch, batch);
     // soft_teacher=True without the feed: TensorFlow's "You must feed a value for placeholder tensor" (teacher_labels_logits_pl)
-    AMS_REQUIRE(!s->soft_teacher || s->teacher_logits, "train_step: soft_teacher is on but no teacher logits are fed (ams_student_feed_teacher_logits)");
+    AMS_REQUIRE(!s->loss_objective.soft_teacher || s->loss_objective.teacher_logits, "train_step: soft_teacher is on but no teacher logits are fed (ams_student_feed_teacher_logits)");
     hipStream_t st = (hipStream_t)stream;
     if (comm) cb = comm_as_cb;
     SyncCtx sc{cb, user, s, comm};

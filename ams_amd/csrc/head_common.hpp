@@ -112,6 +112,59 @@ static inline void fill_loss_weights(const ClassTable& ct, const float* cw, int 
 
 static inline bool tlogits_layout_ok(int layout) { return layout == AMS_TLOGITS_FULL || layout == AMS_TLOGITS_SELECTED; }
 
+// ---- one loss call, as the host describes it (launch_ce_loss_grad, launch_ce_combine, the ams_k_ce_loss_grad* entries, the student's step) ----
+// The head call: whose logits against which labels
+struct HeadCall {
+    const float* logits = nullptr;     // [B][h][w][ld] f32, the student's
+    int ld = 0, B = 0, h = 0, w = 0;
+    const int32_t* cls = nullptr;      // HOST, the K selected classes' ids
+    int K = 0;
+    int H = 0, W = 0;
+    const uint8_t* teacher = nullptr;  // the teacher's labels [B][H][W]
+    int NC = 0;
+};
+
+// The objective: what the loss of a pixel is.  The defaults are the reference's hard loss.
+struct LossObjective {
+    // != nullptr: soft-teacher targets, teacher logits [B][th][tw][NC] f32 (utils/graph_utils.py:375-376, 403-404; SoftTeacher above), th x tw at most the
+    // label size; layout AMS_TLOGITS_FULL, or AMS_TLOGITS_SELECTED = [B][th][tw][K], channel k holding class cls[k]'s logit
+    const float* teacher_logits = nullptr;
+    int th = 0, tw = 0, layout = AMS_TLOGITS_FULL;
+    // T, alpha (used with teacher logits only; checked always): softmax(./T) on both logit sets with the T^2 factor, mixed alpha : 1 - alpha with the
+    // hard-label CE (k_head.hip KD); (1, 1) launches the soft kernel and alpha = 0 the hard one, as without them
+    float temperature = 1.f, alpha = 1.f;
+    // class_weights (HOST, K floats in the order of cls, nullptr = ones), conf_gamma (needs teacher logits when > 0; both checked always): per-pixel weight
+    // cw_y max_k p_k ^ gamma and a weighted mean, loss[1] = sum of the weights (k_head.hip WT); all ones with gamma = 0 launch the kernels as without them
+    const float* class_weights = nullptr;
+    float conf_gamma = 0.f;
+    // the student's switch (AMS_OPT_SOFT_TEACHER): its step goes by objective_of_step below; the kernel-level entries go by teacher_logits alone
+    int soft_teacher = 0;
+};
+
+// soft off: no teacher logits, T = alpha = 1, whatever was fed or set (the weights stay)
+static inline LossObjective objective_of_step(LossObjective o) {
+    if (!o.soft_teacher) { o.teacher_logits = nullptr; o.temperature = o.alpha = 1.f; }
+    return o;
+}
+
+// the class tier of the one-pass loss kernels' instantiations
+static inline int ce_kmax(int K) { return K <= 8 ? 8 : K <= 20 ? 20 : 32; }
+
+// Which ce_loss_grad_kernel<KMAX, SOFT, KD, WT> an objective runs, and that form's name for the profiler.  (T, alpha) = (1, 1) is the soft form and
+// alpha = 0 the hard one, the same launches as without the two parameters, so those cases are the same bits by construction; all-ones class
+// weights with gamma = 0 go to the WT = false forms, which are compiled from the code as it was.
+struct LossForm { bool soft; int kd; bool weighted; const char* name; };
+static inline LossForm loss_form(const LossObjective& o, int K) {
+    static const char* const names[2][4] = {
+        {"ce_loss_grad_kernel", "ce_loss_grad_kernel<soft>", "ce_loss_grad_kernel<soft, T>", "ce_loss_grad_kernel<soft, mix>"},
+        {"ce_loss_grad_kernel<weighted>", "ce_loss_grad_kernel<soft, weighted>", "ce_loss_grad_kernel<soft, T, weighted>", "ce_loss_grad_kernel<soft, mix, weighted>"}};
+    const bool weighted = !loss_weights_default(o.class_weights, K, o.conf_gamma);
+    int kd = !o.teacher_logits || o.alpha == 0.f ? -1 : o.alpha == 1.f ? (o.temperature == 1.f ? 0 : 1) : 2;
+    // gamma > 0 with alpha = 0: the hard form has no teacher distribution, the mix form computes p anyway (alpha T^2 = alpha T = 0, 1 - alpha = 1)
+    if (kd < 0 && weighted && o.conf_gamma > 0.f) kd = 2;
+    return LossForm{kd >= 0, kd < 0 ? 0 : kd, weighted, names[weighted][kd + 1]};
+}
+
 // ct: the filled class table of the K selected classes (fill_class_table)
 static inline SoftTeacher soft_teacher_geom(const float* t, int th, int tw, int layout, const ClassTable& ct, int K, int NC, int H, int W) {
     SoftTeacher s;

@@ -540,6 +540,7 @@ __global__ __launch_bounds__(256) void ce_combine_kernel(const float* __restrict
     }
 }
 
+// a block's pixel columns are (CB + 1) source columns' worth
 bool ce_loss_grad_supported(int w, int W) {
     const int per_cell = w > 1 ? (W - 1 + w - 2) / (w - 1) + 1 : W;      // output columns per source column, rounded up, + 1
     return (kCeCB + 1) * per_cell + 2 <= 192;
@@ -547,7 +548,7 @@ bool ce_loss_grad_supported(int w, int W) {
 
 // two gradient planes, then the blocks' (loss, count) pairs as doubles (4 floats per block)
 size_t ce_loss_grad_scratch(int B, int h, int w, int K) {
-    return (size_t)2 * B * h * w * (K <= 8 ? 8 : K <= 20 ? 20 : 32) + 4 + (size_t)4 * cdiv(w, kCeCB) * h * B;
+    return (size_t)2 * B * h * w * ce_kmax(K) + 4 + (size_t)4 * cdiv(w, kCeCB) * h * B;
 }
 
 // loss[0] = sum of the blocks' loss sums, loss[1] = sum of their valid-pixel counts: exact (integer multiples of 2^-20 / integers in f64), so the
@@ -565,69 +566,57 @@ __global__ __launch_bounds__(256) void ce_loss_sum_kernel(const double* __restri
 
 // pass 1: loss[0] += CE sum, loss[1] += valid pixels (loss zeroed here), unnormalised gradient planes into scratch
 // (under class weights or conf_gamma: loss[0] = sum of w_q pixel, loss[1] = sum of w_q, the planes weighted likewise)
-int launch_ce_loss_grad(const float* logits, int ld, int B, int h, int w, const int32_t* cls, int K, int H, int W, const uint8_t* teacher,
-                        int NC, double* loss, float* scratch, hipStream_t st, const float* soft_logits, int soft_h, int soft_w, int soft_layout,
-                        float kd_temperature, float kd_alpha, const float* class_weights, float conf_gamma) {
-    if (int rc = kd_params_check("ce_loss_grad", kd_temperature, kd_alpha)) return rc;
-    if (int rc = loss_weights_check("ce_loss_grad", class_weights, K, K, conf_gamma)) return rc;
-    const bool weighted = !loss_weights_default(class_weights, K, conf_gamma);
-    AMS_REQUIRE(conf_gamma == 0.f || soft_logits, "ce_loss_grad: conf_gamma %g weights by the teacher's confidence: it needs teacher logits", (double)conf_gamma);
+int launch_ce_loss_grad(const HeadCall& c, const LossObjective& o, double* loss, float* scratch, hipStream_t st) {
+    if (int rc = kd_params_check("ce_loss_grad", o.temperature, o.alpha)) return rc;
+    if (int rc = loss_weights_check("ce_loss_grad", o.class_weights, c.K, c.K, o.conf_gamma)) return rc;
+    AMS_REQUIRE(o.conf_gamma == 0.f || o.teacher_logits, "ce_loss_grad: conf_gamma %g weights by the teacher's confidence: it needs teacher logits", (double)o.conf_gamma);
     ClassTable ct;
-    int rc = fill_class_table(cls, K, NC, &ct);
+    int rc = fill_class_table(c.cls, c.K, c.NC, &ct);
     if (rc) return rc;
-    AMS_REQUIRE(teacher && loss && scratch, "ce_loss_grad: null pointer");
-    const HeadGeom g = head_geom(ld, B, h, w, K, H, W, NC);
-    // a block's pixel columns: (CB + 1) source columns' worth
-    const int per_cell = w > 1 ? (W - 1 + w - 2) / (w - 1) + 1 : W;
-    AMS_REQUIRE((kCeCB + 1) * per_cell + 2 <= 192, "ce_loss_grad: %d output columns per source column do not fit a block", per_cell);
-    const int KM = K <= 8 ? 8 : K <= 20 ? 20 : 32;
+    AMS_REQUIRE(c.teacher && loss && scratch, "ce_loss_grad: null pointer");
+    const HeadGeom g = head_geom(c.ld, c.B, c.h, c.w, c.K, c.H, c.W, c.NC);
+    AMS_REQUIRE(ce_loss_grad_supported(c.w, c.W), "ce_loss_grad: %d output columns on %d source columns do not fit a block", c.W, c.w);
+    const int KM = ce_kmax(c.K);
+    const size_t planes = (size_t)2 * c.B * c.h * c.w * KM;
     float* partT = scratch;
-    float* partB = scratch + (size_t)B * h * w * KM;
-    const dim3 grid(cdiv(w, kCeCB), h, B);
-    const size_t planes = (size_t)2 * B * h * w * KM;
+    float* partB = scratch + planes / 2;
+    const dim3 grid(cdiv(c.w, kCeCB), c.h, c.B);
     double* blk = reinterpret_cast<double*>(scratch + (planes + 3) / 4 * 4);          // 16-byte aligned behind the planes
     SoftTeacher sft;
     memset(&sft, 0, sizeof(sft));
-    if (soft_logits) {
-        AMS_REQUIRE(soft_h >= 1 && soft_w >= 1 && soft_h <= H && soft_w <= W, "ce_loss_grad: teacher logits of %d x %d for labels of %d x %d", soft_h, soft_w, H, W);
-        AMS_REQUIRE(tlogits_layout_ok(soft_layout), "ce_loss_grad: unknown teacher-logit layout %d", soft_layout);
-        sft = soft_teacher_geom(soft_logits, soft_h, soft_w, soft_layout, ct, K, NC, H, W);
+    if (o.teacher_logits) {
+        AMS_REQUIRE(o.th >= 1 && o.tw >= 1 && o.th <= c.H && o.tw <= c.W, "ce_loss_grad: teacher logits of %d x %d for labels of %d x %d", o.th, o.tw, c.H, c.W);
+        AMS_REQUIRE(tlogits_layout_ok(o.layout), "ce_loss_grad: unknown teacher-logit layout %d", o.layout);
+        sft = soft_teacher_geom(o.teacher_logits, o.th, o.tw, o.layout, ct, c.K, c.NC, c.H, c.W);
     }
-    // the KD forms of the soft step: (T, alpha) = (1, 1) is the soft instantiation and alpha = 0 the hard one, the same launches as without the
-    // two parameters, so those cases are the same bits by construction
-    int kd_form = !soft_logits || kd_alpha == 0.f ? -1 : kd_alpha == 1.f ? (kd_temperature == 1.f ? 0 : 1) : 2;
     KdParams kd;
-    kd.inv_t = 1.f / kd_temperature;
-    kd.at2 = kd_alpha * (kd_temperature * kd_temperature);
-    kd.at = kd_alpha * kd_temperature;
-    kd.om = 1.f - kd_alpha;
-    // One launch per (KMAX tier, SOFT, KD, WT).  All-ones class weights with gamma = 0 go to the WT = false instantiations, which are compiled from
-    // the code as it was: the hard, soft and KD steps of a student that never set weights keep their bits.
-    auto go = [&](auto soft_c, auto kd_c, auto wt_c, auto lwv) {
-        constexpr bool S = decltype(soft_c)::value, Wt = decltype(wt_c)::value;
+    kd.inv_t = 1.f / o.temperature;
+    kd.at2 = o.alpha * (o.temperature * o.temperature);
+    kd.at = o.alpha * o.temperature;
+    kd.om = 1.f - o.alpha;
+    const LossForm f = loss_form(o, c.K);
+    note_kernel(f.name);
+    // One launch per (KMAX tier, SOFT, KD, WT): the form's three values become template arguments one after the other
+    auto launch = [&](auto soft_c, auto kd_c, auto lwv) {
+        constexpr bool S = decltype(soft_c)::value, Wt = std::is_same<decltype(lwv), LossWeights>::value;
         constexpr int D = decltype(kd_c)::value;
-        if (KM == 8) hipLaunchKernelGGL((ce_loss_grad_kernel<8, S, D, Wt>), grid, dim3(192), 0, st, logits, g, ct, teacher, blk, partT, partB, sft, kd, lwv);
-        else if (KM == 20) hipLaunchKernelGGL((ce_loss_grad_kernel<20, S, D, Wt>), grid, dim3(192), 0, st, logits, g, ct, teacher, blk, partT, partB, sft, kd, lwv);
-        else hipLaunchKernelGGL((ce_loss_grad_kernel<32, S, D, Wt>), grid, dim3(192), 0, st, logits, g, ct, teacher, blk, partT, partB, sft, kd, lwv);
+        if (KM == 8) hipLaunchKernelGGL((ce_loss_grad_kernel<8, S, D, Wt>), grid, dim3(192), 0, st, c.logits, g, ct, c.teacher, blk, partT, partB, sft, kd, lwv);
+        else if (KM == 20) hipLaunchKernelGGL((ce_loss_grad_kernel<20, S, D, Wt>), grid, dim3(192), 0, st, c.logits, g, ct, c.teacher, blk, partT, partB, sft, kd, lwv);
+        else hipLaunchKernelGGL((ce_loss_grad_kernel<32, S, D, Wt>), grid, dim3(192), 0, st, c.logits, g, ct, c.teacher, blk, partT, partB, sft, kd, lwv);
     };
-    using std::bool_constant; using std::integral_constant;
-    if (weighted) {
+    auto of_form = [&](auto lwv) {
+        using std::bool_constant; using std::integral_constant;
+        if (f.kd == 2) launch(bool_constant<true>{}, integral_constant<int, 2>{}, lwv);
+        else if (f.kd == 1) launch(bool_constant<true>{}, integral_constant<int, 1>{}, lwv);
+        else if (f.soft) launch(bool_constant<true>{}, integral_constant<int, 0>{}, lwv);
+        else launch(bool_constant<false>{}, integral_constant<int, 0>{}, lwv);
+    };
+    if (f.weighted) {
         LossWeights lw;
-        fill_loss_weights(ct, class_weights, K, conf_gamma, &lw);
-        // gamma > 0 with alpha = 0: the hard form has no teacher distribution, the mix form computes p anyway (alpha T^2 = alpha T = 0, 1 - alpha = 1)
-        if (kd_form < 0 && conf_gamma > 0.f) kd_form = 2;
-        note_kernel(kd_form == 2 ? "ce_loss_grad_kernel<soft, mix, weighted>" : kd_form == 1 ? "ce_loss_grad_kernel<soft, T, weighted>" : kd_form == 0 ? "ce_loss_grad_kernel<soft, weighted>" : "ce_loss_grad_kernel<weighted>");
-        if (kd_form == 2) go(bool_constant<true>{}, integral_constant<int, 2>{}, bool_constant<true>{}, lw);
-        else if (kd_form == 1) go(bool_constant<true>{}, integral_constant<int, 1>{}, bool_constant<true>{}, lw);
-        else if (kd_form == 0) go(bool_constant<true>{}, integral_constant<int, 0>{}, bool_constant<true>{}, lw);
-        else go(bool_constant<false>{}, integral_constant<int, 0>{}, bool_constant<true>{}, lw);
+        fill_loss_weights(ct, o.class_weights, c.K, o.conf_gamma, &lw);
+        of_form(lw);
     } else {
-        const NoLossWeights nlw;
-        note_kernel(kd_form == 2 ? "ce_loss_grad_kernel<soft, mix>" : kd_form == 1 ? "ce_loss_grad_kernel<soft, T>" : kd_form == 0 ? "ce_loss_grad_kernel<soft>" : "ce_loss_grad_kernel");
-        if (kd_form == 2) go(bool_constant<true>{}, integral_constant<int, 2>{}, bool_constant<false>{}, nlw);
-        else if (kd_form == 1) go(bool_constant<true>{}, integral_constant<int, 1>{}, bool_constant<false>{}, nlw);
-        else if (kd_form == 0) go(bool_constant<true>{}, integral_constant<int, 0>{}, bool_constant<false>{}, nlw);
-        else go(bool_constant<false>{}, integral_constant<int, 0>{}, bool_constant<false>{}, nlw);
+        of_form(NoLossWeights{});
     }
     AMS_CHECK_LAUNCH();
     hipLaunchKernelGGL(ce_loss_sum_kernel, dim3(1), dim3(256), 0, st, blk, (int)(grid.x * grid.y * grid.z), loss);
@@ -635,21 +624,20 @@ int launch_ce_loss_grad(const float* logits, int ld, int B, int h, int w, const 
     return AMS_OK;
 }
 
-// pass 2 (after the valid-pixel count is final, i.e. after its cross-rank sum in a data-parallel step)
-int launch_ce_combine(int B, int h, int w, const int32_t* cls, int K, int NC, const double* loss_and_count, const float* scratch,
-                      float* dlogits, int ldd, hipStream_t st, float empty_val) {
+// pass 2 (after the valid-pixel count is final, i.e. after its cross-rank sum in a data-parallel step); of c, the cells and the class list count
+int launch_ce_combine(const HeadCall& c, const double* loss_and_count, const float* scratch, float* dlogits, int ldd, hipStream_t st, float empty_val) {
     ClassTable ct;
-    int rc = fill_class_table(cls, K, NC, &ct);
+    int rc = fill_class_table(c.cls, c.K, c.NC, &ct);
     if (rc) return rc;
-    AMS_REQUIRE(ldd >= NC && ldd <= 256, "ce_combine: ldd=%d must hold %d classes", ldd, NC);
-    const int KM = K <= 8 ? 8 : K <= 20 ? 20 : 32;
-    const int64_t cells = (int64_t)B * h * w;
+    AMS_REQUIRE(ldd >= c.NC && ldd <= 256, "ce_combine: ldd=%d must hold %d classes", ldd, c.NC);
+    const int KM = ce_kmax(c.K);
+    const int64_t cells = (int64_t)c.B * c.h * c.w;
     const float* partT = scratch;
     const float* partB = scratch + (size_t)cells * KM;
     const int grid = (int)(cdiv64(cells * ldd, 256) < 2048 ? cdiv64(cells * ldd, 256) : 2048);
-    if (KM == 8) hipLaunchKernelGGL(ce_combine_kernel<8>, dim3(grid), dim3(256), 0, st, partT, partB, cells, w, h, ct, K, loss_and_count, dlogits, ldd, empty_val);
-    else if (KM == 20) hipLaunchKernelGGL(ce_combine_kernel<20>, dim3(grid), dim3(256), 0, st, partT, partB, cells, w, h, ct, K, loss_and_count, dlogits, ldd, empty_val);
-    else hipLaunchKernelGGL(ce_combine_kernel<32>, dim3(grid), dim3(256), 0, st, partT, partB, cells, w, h, ct, K, loss_and_count, dlogits, ldd, empty_val);
+    if (KM == 8) hipLaunchKernelGGL(ce_combine_kernel<8>, dim3(grid), dim3(256), 0, st, partT, partB, cells, c.w, c.h, ct, c.K, loss_and_count, dlogits, ldd, empty_val);
+    else if (KM == 20) hipLaunchKernelGGL(ce_combine_kernel<20>, dim3(grid), dim3(256), 0, st, partT, partB, cells, c.w, c.h, ct, c.K, loss_and_count, dlogits, ldd, empty_val);
+    else hipLaunchKernelGGL(ce_combine_kernel<32>, dim3(grid), dim3(256), 0, st, partT, partB, cells, c.w, c.h, ct, c.K, loss_and_count, dlogits, ldd, empty_val);
     AMS_CHECK_LAUNCH();
     return AMS_OK;
 }

@@ -382,20 +382,14 @@ int launch_ce_grad(const float* logits, int ld, int B, int h, int w, const int32
 // scratch (ce_loss_grad_scratch floats); pass 2 scales by 1 / count (after its cross-rank sum) and writes dlogits [B*h*w, ldd]
 bool ce_loss_grad_supported(int w, int W);
 size_t ce_loss_grad_scratch(int B, int h, int w, int K);
-// soft_logits != nullptr: soft-teacher targets, teacher logits [B][soft_h][soft_w][NC] f32 (utils/graph_utils.py:375-376, 403-404; k_head.hip SoftTeacher)
-// kd_temperature T, kd_alpha (soft_logits only; checked always): softmax(./T) on both logit sets with the T^2 factor, mixed alpha : 1 - alpha with the
-// hard-label CE (k_head.hip KD); (1, 1) launches the soft kernel and alpha = 0 the hard one, as without them
-// soft_layout: AMS_TLOGITS_FULL, or AMS_TLOGITS_SELECTED = [B][soft_h][soft_w][K], channel k holding class cls[k]'s logit (head_common.hpp)
-// class_weights (HOST, K floats in the order of cls, nullptr = ones), conf_gamma (needs soft_logits when > 0; both checked always): per-pixel weight
-// cw_y max_k p_k ^ gamma and a weighted mean, loss[1] = sum of the weights (k_head.hip WT); all ones with gamma = 0 launch the kernels as without them
-int launch_ce_loss_grad(const float* logits, int ld, int B, int h, int w, const int32_t* cls, int K, int H, int W, const uint8_t* teacher,
-                        int NC, double* loss, float* scratch, hipStream_t st, const float* soft_logits = nullptr, int soft_h = 0, int soft_w = 0,
-                        int soft_layout = AMS_TLOGITS_FULL, float kd_temperature = 1.f, float kd_alpha = 1.f,
-                        const float* class_weights = nullptr, float conf_gamma = 0.f);
+// what is computed on which tensors: HeadCall and LossObjective, head_common.hpp
+struct HeadCall;
+struct LossObjective;
+int launch_ce_loss_grad(const HeadCall& c, const LossObjective& o, double* loss, float* scratch, hipStream_t st);
 // empty_val: every selected class's gradient when NO pixel of the (global) batch is valid: 0, or NaN = the reference's 0 / 0
 // (utils/graph_utils.py:408: loss = sum(w ce) / sum(w))
-int launch_ce_combine(int B, int h, int w, const int32_t* cls, int K, int NC, const double* loss_and_count, const float* scratch,
-                      float* dlogits, int ldd, hipStream_t st, float empty_val = 0.f);
+int launch_ce_combine(const HeadCall& c, const double* loss_and_count, const float* scratch, float* dlogits, int ldd, hipStream_t st,
+                      float empty_val = 0.f);
 // freeze-time range check of the fp16 product form: over_host[j] = 1 when any |w| of job j is > limit or not finite, or when no |w| of job j
 // reaches `low` (every weight so small that its fp16 parts are subnormal: split1_f16 keeps 22 bits only for normal parts).  Synchronises `st`.
 struct WeightRange { const float* w; int64_t n; };

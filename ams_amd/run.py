@@ -51,8 +51,8 @@ from .delta import delta_layout
 from .exp_configs import class_weights, coco_class_converter, is_coco, test_length
 from .semantic_network import FrozenGraph, SemanticNetwork
 from .synth import SyntheticVideo
-from .utils import (balanced_class_weights, calculate_miou, choose_frames, label_class_counts, resize_linear, resize_nearest,
-                    string_class_iou)
+from .utils import (balanced_class_weights, calculate_miou, choose_frames, label_class_counts, loss_knobs_problem, resize_linear,
+                    resize_nearest, string_class_iou)
 
 
 # ----------------------------------------------------------------------------------------------------------- flags
@@ -690,10 +690,9 @@ def parse_loss_class_weights(text: str, k: int) -> np.ndarray:
         cw = np.asarray([float(t) for t in text.split(",")], dtype=np.float32)
     except ValueError:
         raise ValueError("--loss_class_weights must be 'balanced' or %d comma-separated floats (got %r)" % (k, text))
-    if cw.shape != (k,):
-        raise ValueError("--loss_class_weights needs one weight per class of the experiment: %d, got %d" % (k, cw.size))
-    if not np.all((cw == 0) | ((cw >= 2.0 ** -6) & (cw <= 16.0))):
-        raise ValueError("--loss_class_weights must each be 0 or lie in [2^-6, 16] (got %r)" % text)
+    problem = loss_knobs_problem(True, loss_class_weights=cw, class_count=k, dash="--")
+    if problem:
+        raise ValueError(problem)
     return cw
 
 
@@ -709,12 +708,10 @@ def parse_flags(argv: Optional[List[str]] = None):
     for name in ("kd_temperature", "kd_alpha", "kd_conf_gamma"):
         if getattr(flags, name) is not None and not flags.soft_teacher:
             parser.error("--%s needs --soft_teacher: it shapes the loss against the teacher logits that flag caches" % name)
-    if flags.kd_temperature is not None and not (np.isfinite(flags.kd_temperature) and flags.kd_temperature > 0):
-        parser.error("--kd_temperature must be finite and > 0 (got %r)" % flags.kd_temperature)
-    if flags.kd_alpha is not None and not 0.0 <= flags.kd_alpha <= 1.0:
-        parser.error("--kd_alpha must lie in [0, 1] (got %r)" % flags.kd_alpha)
-    if flags.kd_conf_gamma is not None and not (np.isfinite(flags.kd_conf_gamma) and 0.0 <= flags.kd_conf_gamma <= 8.0):
-        parser.error("--kd_conf_gamma must lie in [0, 8] (got %r)" % flags.kd_conf_gamma)
+    problem = loss_knobs_problem(flags.soft_teacher, dash="--", **{name: getattr(flags, name) for name in ("kd_temperature", "kd_alpha", "kd_conf_gamma")
+                                                                   if getattr(flags, name) is not None})
+    if problem:
+        parser.error(problem)
     if flags.loss_class_weights is not None and flags.loss_class_weights != "balanced":
         try:
             parse_loss_class_weights(flags.loss_class_weights, int(class_weights(video_number(flags.input_video)).sum()))

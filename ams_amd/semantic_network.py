@@ -44,7 +44,7 @@ from .engine import StudentEngine
 from .render import VIEWS as RENDER_VIEWS, DeviceRenderer
 from .replay import LOW_RES_LOGITS, SAMPLE_FIELDS, DeviceReplayMemory, draw_samples
 from .soft_metric import SoftMetric
-from .utils import calculate_miou, colormap
+from .utils import calculate_miou, colormap, loss_knobs_problem
 from .weights import load_npy
 
 FROZEN_MAGIC = b"AMSF\x01"
@@ -161,10 +161,6 @@ class SemanticNetwork(object):
             self.kd_temperature = self.kd_alpha = 1.0
             self.loss_class_weights, self.kd_conf_gamma = None, 0.0
         self.loss_class_weights = self._checked_loss_weights(self.loss_class_weights, self.kd_conf_gamma)
-        assert self.soft_teacher or (self.kd_temperature == 1.0 and self.kd_alpha == 1.0), \
-            "kd_temperature / kd_alpha shape the soft_teacher loss: they need soft_teacher=True"
-        assert np.isfinite(self.kd_temperature) and self.kd_temperature > 0, "kd_temperature must be finite and > 0"
-        assert 0.0 <= self.kd_alpha <= 1.0, "kd_alpha must lie in [0, 1]"
         initial_variables = kwargs.pop("initial_variables", None)
         frozen_graph = kwargs.pop("frozen_graph", None)
         max_batch = kwargs.pop("max_batch", None)
@@ -551,15 +547,10 @@ class SemanticNetwork(object):
             raise feed.error                        # a helper's own exception (the reference would hang with the lock held)
 
     def _checked_loss_weights(self, class_weights, conf_gamma):
-        """The K weights as f32 (or None), after the assertions of the two loss-weight arguments."""
-        assert np.isfinite(conf_gamma) and 0.0 <= conf_gamma <= 8.0, "kd_conf_gamma must lie in [0, 8]"
-        assert self.soft_teacher or conf_gamma == 0.0, "kd_conf_gamma weights by the teacher's confidence: it needs soft_teacher=True"
-        if class_weights is None:
-            return None
-        cw = np.asarray(class_weights, dtype=np.float32).reshape(-1)
-        assert cw.shape == (self.class_count,), "loss_class_weights must have one entry per selected class (%d)" % self.class_count
-        assert np.all((cw == 0) | ((cw >= 2.0 ** -6) & (cw <= 16.0))), "loss_class_weights must each be 0 or lie in [2^-6, 16]"
-        return cw
+        """The K weights as f32 (or None), after the assertion that the loss's knobs (these two, kd_temperature, kd_alpha) can be served."""
+        problem = loss_knobs_problem(self.soft_teacher, self.kd_temperature, self.kd_alpha, conf_gamma, class_weights, self.class_count)
+        assert problem is None, problem
+        return None if class_weights is None else np.asarray(class_weights, dtype=np.float32).reshape(-1)
 
     def set_loss_weights(self, class_weights=None, conf_gamma: float = 0.0) -> None:
         """``StudentEngine.set_loss_weights`` for the phases to come: K per-class weights (None = ones) and the exponent of the teacher's

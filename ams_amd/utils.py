@@ -227,6 +227,28 @@ def balanced_class_weights(counts):
     return cw.astype(np.float32)
 
 
+def loss_knobs_problem(soft_teacher, kd_temperature=1.0, kd_alpha=1.0, kd_conf_gamma=0.0, loss_class_weights=None, class_count=None, dash=""):
+    """What is wrong with a setting of the fine-tune loss's knobs, in words, or None: the ranges the C library holds them to (head_common.hpp:
+    kd_params_check, loss_weights_check), and that the three KD knobs shape a loss which only ``soft_teacher`` computes.  ``loss_class_weights``:
+    ``class_count`` numbers or None.  ``dash``: what stands in front of a knob's name (run.py's parser passes "--")."""
+    if not (np.isfinite(kd_temperature) and kd_temperature > 0):
+        return "%skd_temperature must be finite and > 0 (got %r)" % (dash, kd_temperature)
+    if not 0.0 <= kd_alpha <= 1.0:
+        return "%skd_alpha must lie in [0, 1] (got %r)" % (dash, kd_alpha)
+    if not (np.isfinite(kd_conf_gamma) and 0.0 <= kd_conf_gamma <= 8.0):
+        return "%skd_conf_gamma must lie in [0, 8] (got %r)" % (dash, kd_conf_gamma)
+    for name, value, default in (("kd_temperature", kd_temperature, 1.0), ("kd_alpha", kd_alpha, 1.0), ("kd_conf_gamma", kd_conf_gamma, 0.0)):
+        if value != default and not soft_teacher:
+            return "%s%s needs %ssoft_teacher: it shapes the loss against the teacher logits" % (dash, name, dash)
+    if loss_class_weights is not None:
+        cw = np.asarray(loss_class_weights, dtype=np.float32).reshape(-1)
+        if cw.size != class_count:
+            return "%sloss_class_weights needs one weight per class: %d, got %d" % (dash, class_count, cw.size)
+        if not np.all((cw == 0) | ((cw >= 2.0 ** -6) & (cw <= 16.0))):
+            return "%sloss_class_weights must each be 0 or lie in [2^-6, 16] (got %r)" % (dash, cw.tolist())
+    return None
+
+
 def label_class_counts(labels, class_indices):
     """Pixels per subset class over an iterable of label maps: int64 [K], ids truncated and folded to a byte as the engine's upload does."""
     hist = np.zeros(256, dtype=np.int64)

@@ -5,81 +5,23 @@ alpha = 1).  Per valid pixel, z the student's K upsampled logits, t the teacher'
 
 Kernel level (ams_k_ce_loss_grad_kd) against f64 autograd of that formula, the identities with the two existing kernels bit for bit, one
 fine-tune step against the f64 oracle's network under the formula, and the SemanticNetwork surface on a DeviceReplayMemory."""
-import ctypes as C
-import random
-
 import numpy as np
 import pytest
 import torch
 
+import loss_ref as LR
 from ams_amd import exp_configs, hip, spec as S, synth, weights as Wt
 from ams_amd.engine import StudentEngine
-from ams_amd.replay import DeviceReplayMemory, draw_samples
+from ams_amd.replay import draw_samples
 from ams_amd.semantic_network import SemanticNetwork
+from loss_ref import CI, DEV, rel_err
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-CI = [0, 1, 2, 10, 11, 13]
-
-
-def P(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def rel_err(got, want):
-    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
-    return np.abs(got - want).max() / max(np.abs(want).max(), 1e-30)
-
-
-def kd_objective(z, t, y, valid, T, alpha):
-    """The formula of the module's head: z, t [..., K] (t carries no gradient), y int64 [...], valid bool [...]."""
-    p = torch.softmax(t.detach() / T, -1)
-    soft = T * T * (p * (torch.logsumexp(z / T, -1, keepdim=True) - z / T)).sum(-1)
-    hard = torch.logsumexp(z, -1) - torch.gather(z, -1, y.unsqueeze(-1)).squeeze(-1)
-    return (alpha * soft + (1 - alpha) * hard)[valid].mean()
-
-
-def _teacher_logits(labels, rng, nc=19, th=None, tw=None, sharp=3.0):
-    """tests/test_gpu_soft_teacher.py's: noise + a bump of 3 on the class of the label map, optionally sampled down to th x tw."""
-    B, H, W = labels.shape
-    t = rng.standard_normal((B, H, W, nc)).astype(np.float32)
-    ok = labels < nc
-    bi, yi, xi = np.nonzero(ok)
-    t[bi, yi, xi, labels[ok]] += sharp
-    if th is not None:
-        ys = np.round(np.linspace(0, H - 1, th)).astype(int)
-        xs = np.round(np.linspace(0, W - 1, tw)).astype(int)
-        t = np.ascontiguousarray(t[:, ys][:, :, xs])
-    return t
-
-
-def _material(h, w, H, W, NC, th, tw, seed):
-    rng = np.random.default_rng(seed)
-    B = 2
-    logits = (rng.standard_normal((B, h, w, NC)) * 2).astype(np.float32)
-    teacher = rng.integers(0, NC, (B, H, W)).astype(np.uint8)
-    teacher[rng.random((B, H, W)) < 0.1] = 255
-    tl = _teacher_logits(np.where(teacher < NC, teacher, 0).astype(np.int64), rng, nc=NC, th=th if (th, tw) != (H, W) else None, tw=tw)
-    assert tl.shape == (B, th, tw, NC)
-    return logits, teacher, tl
-
 
 def _kd_call(lib, ld, td, tld, cls, NC, H, W, th, tw, T, alpha, layout=hip.TLOGITS_FULL):
-    B, h, w, _ = ld.shape
-    K = len(cls)
-    ci = (C.c_int32 * K)(*cls)
-    n = lib.ams_k_ce_loss_grad_scratch(B, h, w, K)
-    scr = torch.full((n,), np.nan, device=DEV)
-    loss = torch.full((2,), np.nan, dtype=torch.float64, device=DEV)
-    dl = torch.full((B, h, w, NC), np.nan, device=DEV)
-    hip.check(lib.ams_k_ce_loss_grad_kd(P(ld), B, h, w, NC, NC, ci, K, H, W, P(td), P(tld), th, tw, layout, P(loss), P(dl), P(scr), n, stream(),
-                                        C.c_float(T), C.c_float(alpha)))
-    return loss.cpu().numpy(), dl.cpu().numpy()
+    assert tuple(tld.shape[1:3]) == (th, tw)
+    return LR.loss_call(lib, "kd", ld, td, tld, cls, NC, H, W, T, alpha, layout=layout)
 
 
 SHAPE0 = (5, 9, 64, 128, 19, CI, 64, 128)
@@ -96,18 +38,15 @@ def test_kd_loss_and_gradient_kernel(h, w, H, W, NC, cls, th, tw, T, alpha):
     2^-20 fixed-point loss): count, mean loss rel 2e-5, max |d - d64| / max |d64| < 3e-5, unselected columns exactly 0, run-to-run identical."""
     from oracle.student_torch import resize_bilinear_align_corners
     lib = hip.lib()
-    logits, teacher, tl = _material(h, w, H, W, NC, th, tw, seed=h * w + th)
+    logits, teacher, tl = LR.material(h, w, H, W, NC, th, tw, seed=h * w + th)
     K = len(cls)
-    lut = np.full(256, -1)
-    lut[cls] = np.arange(K)
-    valid = torch.as_tensor(lut[teacher] >= 0)
-    y = torch.as_tensor(np.where(lut[teacher] >= 0, lut[teacher], 0).astype(np.int64))
+    valid, y = (torch.as_tensor(a) for a in LR.targets(teacher, cls))
     lt = torch.as_tensor(logits).double().requires_grad_(True)
     zf = resize_bilinear_align_corners(lt, H, W)[..., cls]
     tf_ = torch.as_tensor(tl).double()
     if (th, tw) != (H, W):
         tf_ = resize_bilinear_align_corners(tf_, H, W)
-    objective = kd_objective(zf, tf_[..., cls], y, valid, T, alpha)
+    objective, _ = LR.objective(zf, tf_[..., cls], y, valid, T, alpha)
     objective.backward()
     want = float(objective.detach())
     ld, td, tld = torch.as_tensor(logits).to(DEV), torch.as_tensor(teacher).to(DEV), torch.as_tensor(tl).to(DEV)
@@ -127,21 +66,11 @@ def test_kd_identities_bit_for_bit():
     """(1, 1) is ams_k_ce_loss_grad_soft, alpha = 0 is ams_k_ce_loss_grad at any T, and the selected teacher layout is the full one."""
     lib = hip.lib()
     h, w, H, W, NC, cls, th, tw = SHAPE0
-    logits, teacher, tl = _material(h, w, H, W, NC, th, tw, seed=h * w + th)
-    B, K = 2, len(cls)
-    ci = (C.c_int32 * K)(*cls)
+    logits, teacher, tl = LR.material(h, w, H, W, NC, th, tw, seed=h * w + th)
     ld, td, tld = torch.as_tensor(logits).to(DEV), torch.as_tensor(teacher).to(DEV), torch.as_tensor(tl).to(DEV)
-    n = lib.ams_k_ce_loss_grad_scratch(B, h, w, K)
-    scr = torch.full((n,), np.nan, device=DEV)
 
     def existing(soft):
-        loss = torch.full((2,), np.nan, dtype=torch.float64, device=DEV)
-        dl = torch.full((B, h, w, NC), np.nan, device=DEV)
-        if soft:
-            hip.check(lib.ams_k_ce_loss_grad_soft(P(ld), B, h, w, NC, ci, K, H, W, P(td), P(tld), th, tw, P(loss), P(dl), P(scr), n, stream()))
-        else:
-            hip.check(lib.ams_k_ce_loss_grad(P(ld), B, h, w, NC, ci, K, H, W, P(td), P(loss), P(dl), P(scr), n, stream()))
-        return loss.cpu().numpy(), dl.cpu().numpy()
+        return LR.loss_call(lib, "soft" if soft else "hard", ld, td, tld if soft else None, cls, NC, H, W)
 
     def same(a, b):
         return np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
@@ -165,22 +94,6 @@ def W0():
     return Wt.synthetic_weights(S.build_spec(), seed=0)
 
 
-def _oracle_kd_gradients(o, frames, labels, tl, T, alpha):
-    """Loss and gradients of the formula on the oracle's own network (StudentOracle.logits_full in training mode), by autograd."""
-    params, leaves = dict(o.vars), {}
-    for v in o.spec.trainable:
-        leaves[v.name] = params[v.name] = o.vars[v.name].clone().requires_grad_(True)
-    z = o.reduced_logits(o.logits_full(frames, "train", params))
-    y, weight = o.label_targets(labels)
-    t = torch.as_tensor(tl).to(o.dtype)
-    if t.shape[1:3] != z.shape[1:3]:
-        from oracle.student_torch import resize_bilinear_align_corners
-        t = resize_bilinear_align_corners(t, z.shape[1], z.shape[2])
-    loss = kd_objective(z, o.reduced_logits(t), y, weight > 0, T, alpha)
-    grads = torch.autograd.grad(loss, list(leaves.values()))
-    return float(loss.detach()), dict(zip(leaves, grads))
-
-
 @pytest.mark.parametrize("low_res", [False, True])
 def test_kd_step_matches_f64_oracle(W0, low_res):
     """One step at 64 x 128 under set_kd(2, 0.5), teacher logits at the label size and on 9 x 17: the bars of
@@ -188,10 +101,10 @@ def test_kd_step_matches_f64_oracle(W0, low_res):
     from oracle.student_torch import StudentOracle
     H, B, lr, T, alpha = 64, 4, 1e-3, 2.0, 0.5
     frames, labels = synth.SyntheticVideo(H, B, CI, seed=5).clip()
-    tl = _teacher_logits(labels.astype(np.int64), np.random.default_rng(17), th=9 if low_res else None, tw=17)
+    tl = LR.teacher_logits(labels.astype(np.int64), np.random.default_rng(17), th=9 if low_res else None, tw=17)
     f32 = frames.astype(np.float32)
-    loss_o, grads_o = _oracle_kd_gradients(StudentOracle(W0, CI, dtype=torch.float64), f32, labels, tl, T, alpha)
-    _, grads_32 = _oracle_kd_gradients(StudentOracle(W0, CI), f32, labels, tl, T, alpha)
+    loss_o, _, grads_o = LR.oracle_gradients(StudentOracle(W0, CI, dtype=torch.float64), f32, labels, tl, T, alpha)
+    _, _, grads_32 = LR.oracle_gradients(StudentOracle(W0, CI), f32, labels, tl, T, alpha)
     loss_soft, _ = StudentOracle(W0, CI, dtype=torch.float64).gradients(f32, labels, teacher_logits=tl)
     assert abs(loss_o - loss_soft) > 1e-2 * abs(loss_soft)
     eng = StudentEngine(CI, H, 2 * H, max_batch=B, trainable=True)
@@ -243,42 +156,19 @@ def test_kd_step_matches_f64_oracle(W0, low_res):
 H, BATCH, ITERS, SLOTS, SEED, GRID = 64, 2, 3, 4, 3, (9, 17)
 
 
-def _seed(seed):
-    np.random.seed(seed)
-    random.seed(seed)
-
-
-def _memory(rng):
-    src = (H, 2 * H)
-    frames = [rng.integers(0, 256, src + (3,), dtype=np.uint8) for _ in range(SLOTS)]
-    labels = [np.repeat(np.repeat(rng.integers(0, 19, (H // 8, 2 * H // 8), dtype=np.uint8), 8, axis=0), 8, axis=1) for _ in range(SLOTS)]
-    ys = np.rint(np.linspace(0, src[0] - 1, GRID[0])).astype(np.int64)
-    xs = np.rint(np.linspace(0, src[1] - 1, GRID[1])).astype(np.int64)
-    logits = []
-    for l in labels:
-        t = rng.standard_normal(GRID + (19,)).astype(np.float32)
-        cls = l[ys][:, xs][..., None].astype(np.int64)
-        np.put_along_axis(t, cls, np.take_along_axis(t, cls, 2) + 3.0, axis=2)
-        logits.append(t)
-    mem = DeviceReplayMemory(SLOTS, src[0], src[1], DEV, logits_shape=GRID + (19,))
-    for f, l, t in zip(frames, labels, logits):
-        mem.append(f, l, t)
-    return mem, np.stack(frames), np.stack(labels), np.stack(logits)
-
-
 @pytest.mark.parametrize("kd", [(2.0, 0.5), None], ids=["kd_2_0.5", "default"])
 def test_semantic_network_kd_phase_equals_hand_made_steps(W0, kd):
     """SemanticNetwork(soft_teacher=True[, kd_temperature=2, kd_alpha=0.5]) for three iterations on a replay memory of four 64 x 128 slots with
     9 x 17 teacher logits, against engine.train_step on the same draws — on an engine under set_kd(2, 0.5), or, without the two kwargs, on one
     that never called set_kd: every variable and last_losses equal bit for bit."""
-    mem, frames, labels, logits = _memory(np.random.default_rng(12))
+    mem, frames, labels, logits = LR.memory(np.random.default_rng(12), H, SLOTS, GRID)
     kw = dict(class_weights_exp=exp_configs.class_weights(25), height=H, scale=[1], mini_batch_size=BATCH, lr=1e-3, initial_variables=W0,
               soft_teacher=True)
     net = SemanticNetwork("unused", **kw, **(dict(kd_temperature=kd[0], kd_alpha=kd[1]) if kd else {}))
-    _seed(SEED)
+    LR.seed(SEED)
     net.train_with_deque(mem, None, ITERS)
     assert len(net.last_losses) == ITERS and all(np.isfinite(net.last_losses))
-    _seed(SEED)
+    LR.seed(SEED)
     desc = draw_samples(len(mem), (H, 2 * H), [H, 2 * H], [1], BATCH, ITERS, flip=False)
     ci = net.class_indices_graph.tolist()
     eng = StudentEngine(ci, H, 2 * H, max_batch=BATCH, trainable=True)
@@ -322,7 +212,7 @@ def test_scheduler_run_with_kd_flags_writes_the_same_files_with_other_losses(tmp
     for tag, extra in (("soft", []), ("kd", ["--kd_temperature", "2", "--kd_alpha", "0.5"])):
         out[tag] = str(tmp_path / tag) + "/"
         os.makedirs(out[tag])
-        _seed(1)
+        LR.seed(1)
         summary = R.main(["--input_video", "synthetic:25-synth:seconds=8:fps=2", "--student_checkpoint", "synthetic:0", "--output_dir", out[tag],
                           "--gpu", "0", "--mode", "simple", "--height", "32", "--batch_size", "2", "--iter", "1", "--send_period", "2",
                           "--train_period", "2", "--first_train_time", "2", "--memory_len", "4", "--device_memory", "--soft_teacher"] + extra)

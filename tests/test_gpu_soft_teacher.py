@@ -12,43 +12,14 @@ import torch
 from ams_amd import exp_configs, hip, spec as S, synth, weights as Wt
 from ams_amd.engine import StudentEngine
 from ams_amd.semantic_network import SemanticNetwork
+from loss_ref import CI, DEV, P, material, rel_err, stream, teacher_logits as _teacher_logits
 
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda:0"
-CI = [0, 1, 2, 10, 11, 13]
-
-
-def P(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def rel_err(got, want):
-    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
-    return np.abs(got - want).max() / max(np.abs(want).max(), 1e-30)
 
 
 @pytest.fixture(scope="module")
 def W0():
     return Wt.synthetic_weights(S.build_spec(), seed=0)
-
-
-def _teacher_logits(labels, rng, nc=19, th=None, tw=None, sharp=3.0):
-    """Synthetic cached teacher logits: noise + a bump on the class of the label map (what a teacher whose argmax gave those labels looks like)."""
-    B, H, W = labels.shape
-    t = rng.standard_normal((B, H, W, nc)).astype(np.float32)
-    ok = labels < nc
-    bi, yi, xi = np.nonzero(ok)
-    t[bi, yi, xi, labels[ok]] += sharp
-    if th is not None:
-        ys = np.round(np.linspace(0, H - 1, th)).astype(int)
-        xs = np.round(np.linspace(0, W - 1, tw)).astype(int)
-        t = np.ascontiguousarray(t[:, ys][:, :, xs])
-    return t
 
 
 @pytest.mark.parametrize("h,w,H,W,cls,th,tw", [(5, 9, 64, 128, CI, 64, 128), (3, 5, 32, 64, [2, 8, 9, 10, 11, 13], 32, 64),
@@ -59,13 +30,8 @@ def test_soft_teacher_loss_and_gradient_kernel(h, w, H, W, cls, th, tw):
     teacher logits at the label size (the reference's feed) and on smaller grids (resized like the student's logits); run-to-run identical."""
     from oracle.student_torch import resize_bilinear_align_corners
     lib = hip.lib()
-    rng = np.random.default_rng(h * w + th)
     B, NC, K = 2, 19, len(cls)
-    logits = (rng.standard_normal((B, h, w, NC)) * 2).astype(np.float32)
-    teacher = rng.integers(0, 19, (B, H, W)).astype(np.uint8)
-    teacher[rng.random((B, H, W)) < 0.1] = 255
-    tl = _teacher_logits(np.where(teacher < 19, teacher, 0).astype(np.int64), rng, th=th if (th, tw) != (H, W) else None, tw=tw)
-    assert tl.shape == (B, th, tw, NC)
+    logits, teacher, tl = material(h, w, H, W, NC, th, tw, seed=h * w + th)
     ci = (C.c_int32 * K)(*cls)
     ld, td, tld = torch.as_tensor(logits).to(DEV), torch.as_tensor(teacher).to(DEV), torch.as_tensor(tl).to(DEV)
     lut = np.full(256, -1)

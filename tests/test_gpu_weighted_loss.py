@@ -6,73 +6,33 @@ pixel, with pixel and d whatever the chosen form (hard, soft, soft at T, mix) co
 Kernel level (ams_k_ce_loss_grad_weighted) against f64 autograd of that formula (for gamma = 0 on the hard form: torch's own weighted
 cross_entropy), identities bit for bit, batch-split exactness of the loss pair, weight sums below 0.5, one fine-tune step against the f64
 oracle's network, and the SemanticNetwork / scheduler surface."""
-import ctypes as C
 import glob
 import os
-import random
 
 import numpy as np
 import pytest
 import torch
 
-import weighted_loss_ref as WR
+import loss_ref as LR
 from ams_amd import exp_configs, hip, spec as S, synth, weights as Wt
 from ams_amd.engine import StudentEngine
-from ams_amd.replay import DeviceReplayMemory, draw_samples
+from ams_amd.replay import draw_samples
 from ams_amd.semantic_network import SemanticNetwork
+from loss_ref import CI, CW6, Q, rel_err, same
 
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda:0"
-CI, CW6, Q = WR.CI, WR.CW6, WR.Q
-
-
-def P(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def rel_err(got, want):
-    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
-    return np.abs(got - want).max() / max(np.abs(want).max(), 1e-30)
-
-
-def same(a, b):
-    return np.array_equal(a[0], b[0], equal_nan=True) and np.array_equal(a[1], b[1], equal_nan=True)
 
 
 def _call(lib, logits, teacher, tl, cls, NC, H, W, T, alpha, cw, gamma, layout=hip.TLOGITS_FULL):
     """ams_k_ce_loss_grad_weighted on host arrays: (loss pair, dlogits).  tl None = NULL teacher logits."""
-    ld, td = torch.as_tensor(logits).to(DEV), torch.as_tensor(teacher).to(DEV)
-    tld = torch.as_tensor(tl).to(DEV) if tl is not None else None
-    th, tw = (tl.shape[1], tl.shape[2]) if tl is not None else (0, 0)
-    B, h, w, _ = ld.shape
-    K = len(cls)
-    ci = (C.c_int32 * K)(*cls)
-    n = lib.ams_k_ce_loss_grad_scratch(B, h, w, K)
-    scr = torch.full((n,), np.nan, device=DEV)
-    loss = torch.full((2,), np.nan, dtype=torch.float64, device=DEV)
-    dl = torch.full((B, h, w, NC), np.nan, device=DEV)
-    cwp = (C.c_float * K)(*[float(v) for v in cw]) if cw is not None else None
-    hip.check(lib.ams_k_ce_loss_grad_weighted(P(ld), B, h, w, NC, NC, ci, K, H, W, P(td), P(tld), th, tw, layout, P(loss), P(dl), P(scr), n, stream(),
-                                              C.c_float(T), C.c_float(alpha), cwp, C.c_float(gamma)))
-    return loss.cpu().numpy(), dl.cpu().numpy()
-
-
-def _targets(teacher, cls):
-    lut = np.full(256, -1)
-    lut[cls] = np.arange(len(cls))
-    return lut[teacher] >= 0, np.where(lut[teacher] >= 0, lut[teacher], 0).astype(np.int64)
+    return LR.loss_call(lib, "weighted", logits, teacher, tl, cls, NC, H, W, T, alpha, cw, gamma, layout)
 
 
 def _reference(logits, teacher, tl, cls, H, W, T, alpha, cw, gamma):
     """f64 autograd of the module head's formula: loss, d loss / d low-res logits, f64 sum of the quantised weights, and the summed absolute
     error of the weights an f32 NumPy restatement forms (0 at gamma = 0: the class weights are exact)."""
     from oracle.student_torch import resize_bilinear_align_corners
-    valid_np, y_np = _targets(teacher, cls)
+    valid_np, y_np = LR.targets(teacher, cls)
     valid, y = torch.as_tensor(valid_np), torch.as_tensor(y_np)
     lt = torch.as_tensor(logits).double().requires_grad_(True)
     z = resize_bilinear_align_corners(lt, H, W)[..., cls]
@@ -83,15 +43,15 @@ def _reference(logits, teacher, tl, cls, H, W, T, alpha, cw, gamma):
             t = resize_bilinear_align_corners(t, H, W)
         t = t[..., cls]
     cwt = torch.as_tensor(np.asarray(cw, dtype=np.float64))
-    loss, _ = WR.weighted_objective(z, t, y, valid, T, alpha, cwt, gamma)
+    loss, _ = LR.objective(z, t, y, valid, T, alpha, cwt, gamma)
     loss.backward()
-    w64 = WR.pixel_weights(t, y, cwt, T, gamma).numpy()[valid_np]
-    sum_wq = float(WR.quantised(w64).sum())
+    w64 = LR.pixel_weights(t, y, cwt, T, gamma).numpy()[valid_np]
+    sum_wq = float(LR.quantised(w64).sum())
     err32 = 0.0
     if gamma:
         # the f32 restatement starts from the teacher logits as an f32 program has them at the pixel: the f64 interpolation rounded to f32
-        w32 = WR.weights_f32(t.numpy().astype(np.float32), y_np, cw, T, gamma)[valid_np]
-        err32 = float(np.abs(WR.quantised(w32) - WR.quantised(w64)).sum())
+        w32 = LR.weights_f32(t.numpy().astype(np.float32), y_np, cw, T, gamma)[valid_np]
+        err32 = float(np.abs(LR.quantised(w32) - LR.quantised(w64)).sum())
     return float(loss.detach()), lt.grad.numpy(), sum_wq, err32, int(valid_np.sum())
 
 
@@ -125,7 +85,7 @@ def test_weighted_loss_and_gradient_kernel(shape, form, T, alpha, cw, gamma):
     summed weight error of an f32 NumPy restatement on the same inputs (both figures are printed)."""
     h, w, H, W, NC, cls, th, tw = shape
     lib = hip.lib()
-    logits, teacher, tl = WR.material(h, w, H, W, NC, th, tw, seed=h * w + th)
+    logits, teacher, tl = LR.material(h, w, H, W, NC, th, tw, seed=h * w + th)
     feed = tl if form == "soft" else None
     want, d64, sum_wq, err32, nvalid = _reference(logits, teacher, feed, cls, H, W, T, alpha, cw, gamma)
     outs = [_call(lib, logits, teacher, feed, cls, NC, H, W, T, alpha, cw, gamma) for _ in range(2)]
@@ -150,8 +110,8 @@ def test_hard_form_is_torchs_weighted_cross_entropy():
     """gamma = 0 on the hard form against torch.nn.functional.cross_entropy(weight=cw, ignore_index, reduction='mean') in f64."""
     from oracle.student_torch import resize_bilinear_align_corners
     h, w, H, W, NC, cls, th, tw = SHAPE0
-    logits, teacher, _ = WR.material(h, w, H, W, NC, th, tw, seed=h * w + th)
-    valid, y = _targets(teacher, cls)
+    logits, teacher, _ = LR.material(h, w, H, W, NC, th, tw, seed=h * w + th)
+    valid, y = LR.targets(teacher, cls)
     lt = torch.as_tensor(logits).double().requires_grad_(True)
     z = resize_bilinear_align_corners(lt, H, W)[..., cls]
     target = torch.as_tensor(np.where(valid, y, -100))
@@ -167,24 +127,8 @@ def test_hard_form_is_torchs_weighted_cross_entropy():
 
 
 def _existing(lib, logits, teacher, tl, cls, NC, H, W, kind, T=1.0, alpha=1.0):
-    ld, td = torch.as_tensor(logits).to(DEV), torch.as_tensor(teacher).to(DEV)
-    tld = torch.as_tensor(tl).to(DEV)
-    B, h, w, _ = ld.shape
-    K = len(cls)
-    ci = (C.c_int32 * K)(*cls)
-    n = lib.ams_k_ce_loss_grad_scratch(B, h, w, K)
-    scr = torch.full((n,), np.nan, device=DEV)
-    loss = torch.full((2,), np.nan, dtype=torch.float64, device=DEV)
-    dl = torch.full((B, h, w, NC), np.nan, device=DEV)
-    th, tw = tl.shape[1], tl.shape[2]
-    if kind == "hard":
-        hip.check(lib.ams_k_ce_loss_grad(P(ld), B, h, w, NC, ci, K, H, W, P(td), P(loss), P(dl), P(scr), n, stream()))
-    elif kind == "soft":
-        hip.check(lib.ams_k_ce_loss_grad_soft(P(ld), B, h, w, NC, ci, K, H, W, P(td), P(tld), th, tw, P(loss), P(dl), P(scr), n, stream()))
-    else:
-        hip.check(lib.ams_k_ce_loss_grad_kd(P(ld), B, h, w, NC, NC, ci, K, H, W, P(td), P(tld), th, tw, hip.TLOGITS_FULL, P(loss), P(dl), P(scr), n,
-                                            stream(), C.c_float(T), C.c_float(alpha)))
-    return loss.cpu().numpy(), dl.cpu().numpy()
+    """The entry that served the form before the weighted one: ams_k_ce_loss_grad, _soft or _kd."""
+    return LR.loss_call(lib, kind, logits, teacher, tl if kind != "hard" else None, cls, NC, H, W, T, alpha)
 
 
 FORMS = [("hard", 1.0, 0.0), ("soft", 1.0, 1.0), ("kd", 2.0, 1.0), ("kd", 2.0, 0.5)]
@@ -196,7 +140,7 @@ def test_identities_bit_for_bit():
     is the same call with class k's labels rewritten to 255; the selected teacher layout is the full one under weights."""
     lib = hip.lib()
     h, w, H, W, NC, cls, th, tw = SHAPE0
-    logits, teacher, tl = WR.material(h, w, H, W, NC, th, tw, seed=h * w + th)
+    logits, teacher, tl = LR.material(h, w, H, W, NC, th, tw, seed=h * w + th)
     a = (lib, logits, teacher, tl, cls, NC, H, W)
     for kind, T, alpha in FORMS:
         old = _existing(*a, kind, T, alpha)
@@ -226,7 +170,7 @@ def test_loss_pair_is_exact_under_a_batch_split(T, alpha, gamma):
     """The pair of B = 2 equals the f64 sum of the two B = 1 pairs exactly: both members are sums of integer multiples of 2^-20."""
     lib = hip.lib()
     h, w, H, W, NC, cls, th, tw = SHAPE0
-    logits, teacher, tl = WR.material(h, w, H, W, NC, th, tw, seed=h * w + th)
+    logits, teacher, tl = LR.material(h, w, H, W, NC, th, tw, seed=h * w + th)
     both = _call(lib, logits, teacher, tl, cls, NC, H, W, T, alpha, CW6, gamma)[0]
     parts = [_call(lib, logits[b:b + 1], teacher[b:b + 1], tl[b:b + 1], cls, NC, H, W, T, alpha, CW6, gamma)[0] for b in range(2)]
     assert np.array_equal(both, parts[0] + parts[1])
@@ -238,7 +182,7 @@ def test_weight_sums_below_one_half():
     and a gradient that holds to the f64 reference.  All class weights 0: NaN loss and all-zero dlogits."""
     lib = hip.lib()
     h, w, H, W, NC, cls, th, tw = SHAPE0
-    logits, teacher, tl = WR.material(h, w, H, W, NC, th, tw, seed=h * w + th)
+    logits, teacher, tl = LR.material(h, w, H, W, NC, th, tw, seed=h * w + th)
     one = np.full_like(teacher, 255)
     one[1, 37, 71] = cls[4]
     flat = np.zeros_like(tl)
@@ -262,22 +206,6 @@ def W0():
     return Wt.synthetic_weights(S.build_spec(), seed=0)
 
 
-def _oracle_gradients(o, frames, labels, tl, T, alpha, cw, gamma):
-    """Loss and gradients of the formula on the oracle's own network (StudentOracle.logits_full in training mode), by autograd."""
-    params, leaves = dict(o.vars), {}
-    for v in o.spec.trainable:
-        leaves[v.name] = params[v.name] = o.vars[v.name].clone().requires_grad_(True)
-    z = o.reduced_logits(o.logits_full(frames, "train", params))
-    y, weight = o.label_targets(labels)
-    t = torch.as_tensor(tl).to(o.dtype)
-    if t.shape[1:3] != z.shape[1:3]:
-        from oracle.student_torch import resize_bilinear_align_corners
-        t = resize_bilinear_align_corners(t, z.shape[1], z.shape[2])
-    loss, sum_w = WR.weighted_objective(z, o.reduced_logits(t), y, weight > 0, T, alpha, torch.as_tensor(np.asarray(cw)).to(o.dtype), gamma)
-    grads = torch.autograd.grad(loss, list(leaves.values()))
-    return float(loss.detach()), float(sum_w.detach()), dict(zip(leaves, grads))
-
-
 @pytest.mark.parametrize("low_res", [False, True])
 def test_weighted_step_matches_f64_oracle(W0, low_res):
     """One step at 64 x 128, B = 2, under set_loss_weights(cw, 2) + set_kd(2, 0.5), teacher logits at the label size and on 9 x 17, with the bars of
@@ -285,11 +213,11 @@ def test_weighted_step_matches_f64_oracle(W0, low_res):
     from oracle.student_torch import StudentOracle
     H, B, lr, T, alpha, gamma = 64, 2, 1e-3, 2.0, 0.5, 2.0
     frames, labels = synth.SyntheticVideo(H, B, CI, seed=5).clip()
-    tl = WR.teacher_logits(labels.astype(np.int64), np.random.default_rng(17), th=9 if low_res else None, tw=17)
+    tl = LR.teacher_logits(labels.astype(np.int64), np.random.default_rng(17), th=9 if low_res else None, tw=17)
     f32 = frames.astype(np.float32)
-    loss_o, sum_w, grads_o = _oracle_gradients(StudentOracle(W0, CI, dtype=torch.float64), f32, labels, tl, T, alpha, CW6, gamma)
-    _, _, grads_32 = _oracle_gradients(StudentOracle(W0, CI), f32, labels, tl, T, alpha, CW6, gamma)
-    loss_plain, _, _ = _oracle_gradients(StudentOracle(W0, CI, dtype=torch.float64), f32, labels, tl, T, alpha, [1.0] * 6, 0.0)
+    loss_o, sum_w, grads_o = LR.oracle_gradients(StudentOracle(W0, CI, dtype=torch.float64), f32, labels, tl, T, alpha, CW6, gamma)
+    _, _, grads_32 = LR.oracle_gradients(StudentOracle(W0, CI), f32, labels, tl, T, alpha, CW6, gamma)
+    loss_plain, _, _ = LR.oracle_gradients(StudentOracle(W0, CI, dtype=torch.float64), f32, labels, tl, T, alpha, [1.0] * 6, 0.0)
     eng = StudentEngine(CI, H, 2 * H, max_batch=B, trainable=True)
     eng.load_variables(W0)
     eng.set_soft_teacher(True)
@@ -347,45 +275,22 @@ def test_weighted_step_matches_f64_oracle(W0, low_res):
 H, BATCH, ITERS, SLOTS, SEED, GRID = 64, 2, 3, 4, 3, (9, 17)
 
 
-def _seed(seed):
-    np.random.seed(seed)
-    random.seed(seed)
-
-
-def _memory(rng):
-    src = (H, 2 * H)
-    frames = [rng.integers(0, 256, src + (3,), dtype=np.uint8) for _ in range(SLOTS)]
-    labels = [np.repeat(np.repeat(rng.integers(0, 19, (H // 8, 2 * H // 8), dtype=np.uint8), 8, axis=0), 8, axis=1) for _ in range(SLOTS)]
-    ys = np.rint(np.linspace(0, src[0] - 1, GRID[0])).astype(np.int64)
-    xs = np.rint(np.linspace(0, src[1] - 1, GRID[1])).astype(np.int64)
-    logits = []
-    for l in labels:
-        t = rng.standard_normal(GRID + (19,)).astype(np.float32)
-        cls = l[ys][:, xs][..., None].astype(np.int64)
-        np.put_along_axis(t, cls, np.take_along_axis(t, cls, 2) + 3.0, axis=2)
-        logits.append(t)
-    mem = DeviceReplayMemory(SLOTS, src[0], src[1], DEV, logits_shape=GRID + (19,))
-    for f, l, t in zip(frames, labels, logits):
-        mem.append(f, l, t)
-    return mem, np.stack(frames), np.stack(labels), np.stack(logits)
-
-
 @pytest.mark.parametrize("weighted", [True, False], ids=["cw_gamma_2", "default"])
 def test_semantic_network_weighted_phase_equals_hand_made_steps(W0, weighted):
     """SemanticNetwork(soft_teacher=True[, loss_class_weights=cw, kd_conf_gamma=2]) for three iterations on a replay memory of four 64 x 128 slots
     with 9 x 17 teacher logits, against engine.train_step on the same draws — on an engine under set_loss_weights(cw, 2), or, without the two
     kwargs, on one that never called the setter: every variable and last_losses equal bit for bit.  The memory's class histogram is the labels'."""
-    mem, frames, labels, logits = _memory(np.random.default_rng(12))
+    mem, frames, labels, logits = LR.memory(np.random.default_rng(12), H, SLOTS, GRID)
     kw = dict(class_weights_exp=exp_configs.class_weights(25), height=H, scale=[1], mini_batch_size=BATCH, lr=1e-3, initial_variables=W0,
               soft_teacher=True)
     net = SemanticNetwork("unused", **kw, **(dict(loss_class_weights=CW6, kd_conf_gamma=2) if weighted else {}))
     from ams_amd.utils import label_class_counts
     counts = mem.class_counts(net)
     assert counts.dtype == np.int64 and np.array_equal(counts, label_class_counts(list(labels), net.class_indices_graph)) and counts.sum() > 0
-    _seed(SEED)
+    LR.seed(SEED)
     net.train_with_deque(mem, None, ITERS)
     assert len(net.last_losses) == ITERS and all(np.isfinite(net.last_losses))
-    _seed(SEED)
+    LR.seed(SEED)
     desc = draw_samples(len(mem), (H, 2 * H), [H, 2 * H], [1], BATCH, ITERS, flip=False)
     eng = StudentEngine(net.class_indices_graph.tolist(), H, 2 * H, max_batch=BATCH, trainable=True)
     eng.load_variables(W0)
@@ -419,7 +324,7 @@ def test_scheduler_balanced_weights_on_host_deques_and_device_memory(tmp_path):
     for tag, extra in (("plain", []), ("host", ["--loss_class_weights", "balanced"]), ("device", ["--loss_class_weights", "balanced", "--device_memory"])):
         out[tag] = str(tmp_path / tag) + "/"
         os.makedirs(out[tag])
-        _seed(1)
+        LR.seed(1)
         summary = R.main(["--input_video", "synthetic:25-synth:seconds=8:fps=2", "--student_checkpoint", "synthetic:0", "--output_dir", out[tag],
                           "--gpu", "0", "--mode", "simple", "--height", "32", "--batch_size", "2", "--iter", "1", "--send_period", "2",
                           "--train_period", "2", "--first_train_time", "2", "--memory_len", "4"] + extra)
@@ -449,7 +354,7 @@ def test_scheduler_soft_teacher_run_with_balanced_weights_and_gamma(tmp_path):
     from ams_amd import run as R
     out = str(tmp_path / "soft") + "/"
     os.makedirs(out)
-    _seed(1)
+    LR.seed(1)
     summary = R.main(["--input_video", "synthetic:25-synth:seconds=8:fps=2", "--student_checkpoint", "synthetic:0", "--output_dir", out,
                       "--gpu", "0", "--mode", "simple", "--height", "32", "--batch_size", "2", "--iter", "1", "--send_period", "2",
                       "--train_period", "2", "--first_train_time", "2", "--memory_len", "4", "--device_memory", "--soft_teacher",

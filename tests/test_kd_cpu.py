@@ -10,6 +10,7 @@ import pytest
 
 from ams_amd import exp_configs, hip, run as R
 from ams_amd.semantic_network import SemanticNetwork
+from loss_ref import header_prototype
 
 ROOT = Path(__file__).resolve().parent.parent
 NULL = C.c_void_p(0)
@@ -53,27 +54,9 @@ def test_set_kd_on_a_null_student_fails_cleanly():
     assert b"null student" in lib.ams_last_error()
 
 
-C_TYPES = {"float": C.c_float, "int32_t": C.c_int32, "size_t": C.c_size_t, "int": C.c_int}
-
-
-def _header_prototype(name):
-    text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "ams_hip.h").read_text(), flags=re.S)
-    ret, args = re.search(r"\b(\w+)\s+%s\s*\(([^)]*)\)\s*;" % name, text).groups()
-    out = []
-    for a in args.split(","):
-        a = a.strip()
-        if a.replace(" ", "").startswith("constint32_t*"):
-            out.append(C.POINTER(C.c_int32))
-        elif "*" in a:
-            out.append(C.c_void_p)
-        else:
-            out.append(C_TYPES[a.split()[-2]])
-    return C_TYPES[ret], out
-
-
 @pytest.mark.parametrize("name", ["ams_student_set_kd", "ams_k_ce_loss_grad_kd"])
 def test_header_and_binding_agree_on_the_prototypes(name):
-    assert _header_prototype(name) == tuple(hip.SIGNATURES[name])
+    assert header_prototype(name) == tuple(hip.SIGNATURES[name])
     fn = getattr(hip.lib(), name)
     assert fn.restype is hip.SIGNATURES[name][0] and list(fn.argtypes) == hip.SIGNATURES[name][1]
     # the kd entry is the soft-layout entry with the two floats behind it

@@ -11,6 +11,7 @@ import pytest
 
 from ams_amd import exp_configs, hip, run as R
 from ams_amd.semantic_network import SemanticNetwork
+from loss_ref import header_prototype
 from ams_amd.utils import balanced_class_weights, label_class_counts
 
 ROOT = Path(__file__).resolve().parent.parent
@@ -33,30 +34,9 @@ def test_error_code_is_the_headers():
     assert int(re.search(r"\bAMS_E_INVALID\s*=\s*(-?\d+)", text).group(1)) == E_INVALID
 
 
-C_TYPES = {"float": C.c_float, "int32_t": C.c_int32, "size_t": C.c_size_t, "int": C.c_int}
-
-
-def _header_prototype(name):
-    text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "ams_hip.h").read_text(), flags=re.S)
-    ret, args = re.search(r"\b(\w+)\s+%s\s*\(([^)]*)\)\s*;" % name, text).groups()
-    out = []
-    for a in args.split(","):
-        a = a.strip()
-        flat = a.replace(" ", "")
-        if flat.startswith("constint32_t*"):
-            out.append(C.POINTER(C.c_int32))
-        elif flat.startswith("constfloat*class_weights_host"):
-            out.append(C.POINTER(C.c_float))
-        elif "*" in a:
-            out.append(C.c_void_p)
-        else:
-            out.append(C_TYPES[a.split()[-2]])
-    return C_TYPES[ret], out
-
-
 @pytest.mark.parametrize("name", ["ams_student_set_loss_weights", "ams_k_ce_loss_grad_weighted"])
 def test_header_and_binding_agree_on_the_prototypes(name):
-    assert _header_prototype(name) == tuple(hip.SIGNATURES[name])
+    assert header_prototype(name) == tuple(hip.SIGNATURES[name])
     fn = getattr(hip.lib(), name)
     assert fn.restype is hip.SIGNATURES[name][0] and list(fn.argtypes) == hip.SIGNATURES[name][1]
     # the weighted entry is the kd entry with the weight table and gamma behind it
@@ -188,7 +168,7 @@ def test_weighted_objective_values_of_the_kernel_tests_first_shape_are_far_apart
     (ones, 0), (cw, 0) and (cw, 2), for the hard, soft and mix forms: every pair that a form can tell apart differs by more than ten times the 2e-5
     loss bar, so a kernel that ignored a knob could not pass."""
     import torch
-    import weighted_loss_ref as WR
+    import loss_ref as WR
     from oracle.student_torch import resize_bilinear_align_corners
     h, w, H, W, NC, cls = 5, 9, 64, 128, 19, WR.CI
     logits, teacher, tl = WR.material(h, w, H, W, NC, H, W, seed=h * w + H)
@@ -200,7 +180,7 @@ def test_weighted_objective_values_of_the_kernel_tests_first_shape_are_far_apart
     t = torch.as_tensor(tl).double()[..., cls]
     ones, cw = torch.ones(len(cls), dtype=torch.float64), torch.tensor(WR.CW6, dtype=torch.float64)
     for T, alpha in ((1.0, 0.0), (1.0, 1.0), (2.0, 0.5)):
-        vals = [float(WR.weighted_objective(z, t, y, valid, T, alpha, c, g)[0]) for c, g in ((ones, 0.0), (cw, 0.0), (cw, 2.0))]
+        vals = [float(WR.objective(z, t, y, valid, T, alpha, c, g)[0]) for c, g in ((ones, 0.0), (cw, 0.0), (cw, 2.0))]
         for i, a in enumerate(vals):
             for b in vals[i + 1:]:
                 assert abs(a - b) > 10 * 2e-5 * max(a, b), (T, alpha, vals)
