@@ -126,7 +126,18 @@ int ams_student_lowres_size(const ams_student* s, int32_t* h, int32_t* w);
  * and element count of a per-layer training tensor of a TRAINABLE student, NHWC [max_batch, Hout, Wout, cout] — which = 0 raw conv output z,
  * 1 activated output a (= the next layer's input), 2 gradient wrt a (after a fine-tune step it holds dz where the step computed dz in
  * place), 3 gradient wrt z of a backbone layer (in place over 2, or a tensor of its own where 2 is read again as a skip gradient).  layer is 1-based (ams_layer_desc order).  Which of them a step actually writes depends on the fusion options: with every
- * AMS_OPT_TRAIN_* / FUSE_* fine-tune option at 0 all of them are. */
+ * AMS_OPT_TRAIN_* / FUSE_* fine-tune option at 0 all of them are.
+ * The DEFAULT step (train_recompute 2, fuse_dgrad_bn 3, fuse_gemm_red 3, fuse_operand_bn 1) writes, with their plain meaning:
+ *   z   of every layer but the expand layers of expanded_conv_1 .. _6 (those blocks go from their input straight to the depthwise z);
+ *   a   of the project layers and of image_pooling, aspp0, concat_projection only (the stem's, the expand layers' and the depthwise layers'
+ *       activations are applied on the consumer's loads of z and never stored);
+ *   3   (dz) of the project layers, of the expand layers of expanded_conv_7 .. _16, of the depthwise layers of expanded_conv .. _6, of aspp0
+ *       and concat_projection;
+ *   2   (da) of the project layers that close a residual block.
+ * 3 of a depthwise layer of expanded_conv_7 .. _16 holds dy = da * act'(BN(z)) where the apply pass ran inside the depthwise backward
+ * kernel (from 256 rows = batch * pixels of that layer on, where the project layer's input-gradient GEMM fuses the BN-backward sums), and dz
+ * below that; 2 / 3 of the stem and of the expand layers of expanded_conv_1 .. _6 are never written
+ * (tests/layer_links.py default_step_stored gives the rule and the source line behind each entry). */
 int ams_student_layer_tensor(const ams_student* s, int32_t layer, int32_t which, size_t* offset_bytes, size_t* n_elems);
 
 /* ---- server -> edge hand-off: replaces save_to_frozen_graph / trim_graph_frozen / convert_batchnorms -----

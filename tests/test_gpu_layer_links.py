@@ -15,6 +15,13 @@ tests/test_gpu_kernels.py uses that bar: conv_stem 1e-5 (test_stem_conv), conv_d
 kernel tests measure reduced quantities against max|ref|, not against the sum of the absolute terms): its bar is 4 x the worst error of
 the f32 CPU oracle's own step on that kind over the same sizes, computed here from the reference, never from the engine.  No bar
 exceeds 1e-4.
+
+THE DEFAULT STEP is held by two plans that together name all 164 gradient tensors and all 108 moving statistics: default_step_plan (the
+links whose inputs and outputs the step stores) at the bars above, and layer_links.composite_plan (the links that close across a tensor
+the step does not store: everything inside the recompute blocks, the first block, the depthwise and project layers' operand transforms,
+the late expand layers' BN backward) at 4 x the f32 CPU oracle's own error on the same composite links with the same tensors withheld.
+Which tensors the step stores depends on the size (layer_links.default_step_stored): from 256 rows in the stride-16 GEMMs on, the late
+depthwise layers' dz handle holds dy and their backward runs through the fused kernels; 128x256 x 2 is the case that holds that path.
 """
 import pytest
 import torch
@@ -86,54 +93,7 @@ def test_image_pooling_statistics_of_two_similar_frames(bars):
     _hold("image pooling, 64x128 x 2", res, bars)
 
 
-def default_step_plan(links):
-    """The links whose inputs and outputs the DEFAULT (fused) step provably writes with their plain meaning.
-
-    Recompute blocks = expanded_conv_1 .. _6 (block input <= 32 channels, xdw_train_supported); "late" blocks = expanded_conv_7 .. _16.
-
-    Covered
-      F1  the stem (frames -> z, launch_stem); the expand layers of the late blocks (x = the previous project layer's a, always
-          written: engine_forward.hip:696-698 act_pass is true for a project layer); image_pooling, aspp0, concat_projection, logits
-      F2  every project layer (its a and its residual source, another project layer's a, are written); image_pooling, aspp0,
-          concat_projection
-      F3  every layer whose z is written: all but the expand layers of the recompute blocks
-      L   loss sums from AMS_REGION_LOGITS
-      B1  logits (weights and bias), concat_projection, aspp0, image_pooling; the expand layers of the late blocks (x = a stored project a,
-          dz written in place by launch_bn_bwd_apply, engine_backward.hip:216)
-      B2  concat_projection, aspp0, image_pooling; the last backbone layer (engine_backward.hip:219: first iteration, plain bn_backward);
-          every project layer that feeds a late block (its consumers' dz are the late expand layer's, and the stored da of the residual
-          project layer; its own dz goes to dzp or in place through launch_bn_bwd_apply, :216)
-      DA  the residual project layers of the late blocks but the last (da written by the expand layer's input-gradient GEMM with the skip
-          gradient added, engine_backward.hip:340-352; dz goes to dzp, so da survives)
-    Not covered
-      F1 / F2 / F3 / B1 / B2 of the recompute blocks' expand layers: z_e, a_e, da_e, dz_e are never stored (engine_forward.hip:632-667,
-          engine_backward.hip:221-275)
-      F1 of every depthwise layer, F2 of every expand layer and of the stem: the expand layer's / the stem's a is applied on the depthwise
-          kernel's tap loads and not written (engine_forward.hip:627, :670-679, :697)
-      F1 and B1 of every project layer, F2 of every depthwise layer: the depthwise a is applied on the project GEMM's operand loads and not
-          written (operand_bn_act, engine_forward.hip:685-689, engine_backward.hip:331)
-      B1 / B2 of every depthwise layer: with the apply pass folded into the depthwise backward kernel its dz is never formed, the da buffer
-          keeps dy = da * mask (engine_backward.hip:206-216, :305-308); the recompute blocks' depthwise dz is formed but its consumer's
-          tensors are not
-      B2 of the late expand layers: their consumer's dz (depthwise) is not stored; their da buffer holds dy before dz overwrites it
-          (launch_depthwise_dgrad_bn, engine_backward.hip:311)
-      B2 of the project layers that feed a recompute block or the first block, and B1 / B2 of the stem: the consumer's dz is not stored
-          (engine_backward.hip:237-250, :277-294)
-    """
-    sp = links.spec
-    recompute_expand = {l.idx for l in links.backbone if l.scope.endswith("/expand") and 8 <= l.cin <= 32 and l.cin % 4 == 0}
-    late_expand = {l.idx for l in links.backbone if l.scope.endswith("/expand")} - recompute_expand
-    project = {l.idx for l in links.backbone if l.scope.endswith("/project")}
-    head = [links.lp.idx, links.la.idx, links.lc.idx]
-    plan = [("L", 0), ("F1", 1)]
-    plan += [("F1", i) for i in sorted(late_expand) + head + [links.ll.idx]]
-    plan += [("F2", i) for i in sorted(project) + head]
-    plan += [("F3", l.idx) for l in sp.layers if l.bn_eps is not None and l.idx not in recompute_expand]
-    plan += [("B1", i) for i in sorted(late_expand) + head + [links.ll.idx]]
-    feeds_late = sorted(i for i in project if i + 1 in late_expand)
-    plan += [("B2", i) for i in feeds_late + [links.nb] + head]
-    plan += [("DA", i) for i in feeds_late if links.by_idx[i].residual_from is not None]
-    return plan
+default_step_plan = LL.default_step_plan          # the plan lives beside composite_plan
 
 
 @pytest.mark.parametrize("H,B", [(64, 2), (62, 3)])
@@ -144,3 +104,62 @@ def test_links_of_the_default_step(bars, H, B):
     assert len(plan) == len(set(plan)) == 1 + 15 + 20 + 48 + 14 + 14 + 7
     res = links.close(plan)
     _hold("default step %dx%d x %d" % (H, 2 * H, B), res, bars)
+
+
+@pytest.fixture(scope="module")
+def composite():
+    """bars and bands of the composite links: from the f32 CPU oracle's own step with the default step's tensors withheld, over the sizes"""
+    levels = LL.f32_composite_levels()
+    bands = LL.f32_bands()
+    print("f32 CPU composite levels: %s\nbands (tau per layer): %s" % (levels, bands))
+    return LL.composite_bars(levels), bands
+
+
+def _hold_composite(tag, H, B, run, composite_bars, bands, late=False):
+    sp = LL.S.build_spec()
+    stored = LL.default_step_stored(sp, H, B)
+    links = LL.Links(run, stored=stored, bands=bands)
+    plan = LL.composite_plan(sp)
+    # the two plans together name every gradient tensor and every moving statistic of the step
+    both = LL.plan_names(sp, plan) | LL.plan_names(sp, default_step_plan(links))
+    assert both == {v.name for v in sp.trainable} | {v.name for v in sp.stats} and len(sp.trainable) == 164
+    assert not set(plan) & set(default_step_plan(links))
+    try:
+        res = links.close(LL.late_plan(plan) if late else plan)
+    finally:
+        print("%s: masks of the activations that are not stored\n%s" % (tag, LL.ambiguity_report(links)))
+    _hold(tag, res, composite_bars)
+    return res
+
+
+@pytest.mark.parametrize("H,B", LL.SIZES)
+def test_every_link_of_the_default_step(composite, H, B):
+    """What production runs, on the links default_step_plan leaves out: each closes in f64 across the tensors the default step does not
+    store (layer_links.default_step_stored), the masks of the withheld activations resolved element by element (Links.resolved_mask),
+    at 4 x the f32 CPU oracle's own error on the same composite links.  At these sizes the stride-16 GEMMs have 64 .. 96 rows, so the
+    late depthwise layers' dz is written in place by the unfused BN backward and is checked as dz; the fused path of those blocks is
+    test_late_blocks_of_the_default_step_with_fused_gemms."""
+    res = _hold_composite("default step, composite links, %dx%d x %d" % (H, 2 * H, B), H, B, _engine_run(H, B, layerwise=False), *composite)
+    assert not [r for r in res if r.name.endswith(" (dy)")]
+
+
+def test_every_link_of_the_default_step_soft_teacher(composite):
+    """The same with the soft-teacher feed on the 9 x 17 grid: the plan does not depend on the form of the loss."""
+    _hold_composite("default step, composite links, soft teacher 64x128 x 2", 64, 2, _engine_run(64, 2, soft=True, layerwise=False), *composite)
+
+
+def test_late_blocks_of_the_default_step_with_fused_gemms():
+    """128x256 x 2: the smallest case whose stride-16 GEMMs have 256 rows, from which live_pointwise takes the split-product kernels
+    (split_pays).  Only there does the project layers' input-gradient GEMM apply act' and leave the BN-backward sums (red_mode 2), and only
+    then does fold_apply send the depthwise layer's apply pass through launch_depthwise_dgrad_bn2 with cA / cB / cC, the expand layer's
+    scale / shift / mean / rstd and the layer's own partial rows: what production runs for expanded_conv_7 .. _16.  default_step_stored
+    lists every late depthwise handle as dy for this size, and B2 checks it as dy only: a step that fell back to the unfused path fails.
+    The composite links of the stride-16 blocks (one engine step; the f64 side works on 8 x 16 maps), bars and bands from the f32 CPU
+    oracle's own step at this size."""
+    H, B = LL.FUSED_SIZE
+    sizes = (LL.FUSED_SIZE,)
+    levels, bands = LL.f32_composite_levels(sizes, late=True), LL.f32_bands(sizes)
+    print("f32 CPU composite levels, stride-16 blocks: %s" % levels)
+    res = _hold_composite("default step, stride-16 blocks, %dx%d x %d" % (H, 2 * H, B), H, B, _engine_run(H, B, layerwise=False),
+                          LL.composite_bars(levels), bands, late=True)
+    assert len([r for r in res if r.name.endswith(" (dy)")]) == 10                # every late depthwise handle was checked as dy

@@ -5,6 +5,9 @@
 (b) The same on the f32 oracle's step gives the f32 reference level of every link kind; 4 x that level is the bar of every kind that has no
     kernel-level f64 bar of its own (tests/test_gpu_layer_links.py).
 (c) Negative controls: five wrong wires, each made on a copy of the f64 run's tensors, fail the link they belong to at those bars.
+(d) The default step: the same runs with every tensor the default (fused) step does not store withheld (LL.default_step_stored).  Both
+    plans together close to 1e-10 across the withheld tensors; the f32 run gives the levels of the composite links and the band of every
+    withheld activation; six more wrong wires and two planted mask bits fail or pass as they must.
 
 Sizes: 64x128 x 2 frames and 62x124 x 3 frames (even and odd block inputs pad differently under SAME).
 """
@@ -115,3 +118,213 @@ def test_negative_controls(runs64, bars, H, B):
     bad = LL.copy_run(run)
     bad["grads"][gname], bad["grads"][bname] = run["grads"][bname], run["grads"][gname]
     assert _fails(bad, bars, {("B2", gname), ("B2", bname)}, e) == {("B2", gname), ("B2", bname)}
+
+
+# ---------------------------------------------------------------------------------------------------------
+# the default step: the same runs with the tensors it does not store withheld (LL.default_step_stored)
+# ---------------------------------------------------------------------------------------------------------
+SPEC = LL.S.build_spec()
+ALL_SIZES = SIZES + (LL.FUSED_SIZE,)
+STORED = {(H, B): LL.default_step_stored(SPEC, H, B) for H, B in ALL_SIZES}
+
+
+@pytest.fixture(scope="module")
+def fused64():
+    """the f64 oracle's step at the size from which the stride-16 GEMMs fuse their sums and the late depthwise handles hold dy"""
+    H, B = LL.FUSED_SIZE
+    frames, labels = LL.case_clip(H, B)
+    return LL.oracle_run(LL.case_weights(), LL.CI, frames, labels, torch.float64)
+
+
+@pytest.fixture(scope="module")
+def composite():
+    """(bars, bands) of the composite links as the GPU test takes them: f32 levels and bands over all of its sizes"""
+    return LL.composite_bars(LL.f32_composite_levels()), LL.f32_bands()
+
+
+_default_plan = LL.default_step_plan
+
+
+def test_the_two_plans_name_every_gradient_and_statistic(runs64):
+    links = LL.Links(runs64[SIZES[0]])
+    a, b = LL.composite_plan(SPEC), _default_plan(links)
+    assert not set(a) & set(b) and len(a) == len(set(a)) == 34 + 6 + 41 + 40 + 3
+    assert LL.plan_names(SPEC, a) | LL.plan_names(SPEC, b) == {v.name for v in SPEC.trainable} | {v.name for v in SPEC.stats}
+    assert len(SPEC.trainable) == 164 and len(SPEC.stats) == 108
+    # the special case: a late depthwise handle holds dy from 256 rows in the stride-16 GEMMs on, dz below; never both, never neither
+    late_dw = {l.idx for l in links.backbone if l.kind == "dw" and l.idx >= 23}
+    for (H, B), stored in STORED.items():
+        dy, dz = {i for k, i in stored if k == "dy"}, {i for k, i in stored if k == "dz"}
+        assert (dy, dz & late_dw) == ((late_dw, set()) if (H // 16) * (H // 8) * B >= 256 else (set(), late_dw)), (H, B)
+        assert not {i for k, i in stored if k == "z"} & LL.recompute_expand(SPEC)
+    assert LL.recompute_expand(SPEC) == {4, 7, 10, 13, 16, 19}
+    assert {(k, i) for k, i in LL.late_plan(a)} == {(k, i) for k, i in a if i >= 22}
+
+
+@pytest.mark.parametrize("H,B", SIZES)
+def test_the_default_plan_closes_on_the_f64_oracle_step_with_tensors_withheld(runs64, composite, H, B):
+    stored = STORED[(H, B)]
+    links = LL.Links(LL.withhold(runs64[(H, B)], stored), stored=stored, bands=composite[1])
+    res = links.close(_default_plan(links) + LL.composite_plan(SPEC))
+    print(LL.report(res))
+    print(LL.ambiguity_report(links))
+    assert {r.kind for r in res} == set(LL.KINDS) - {"dlogits"}
+    bad = [r for r in res if not r.err <= 1e-10]
+    assert not bad, bad
+    assert not [r for r in res if r.name.endswith(" (dy)")]                         # under 256 rows: the late depthwise handles hold dz
+    assert not any(d["resolved"] for d in links.ambiguous.values())                 # the f64 run's masks are the f64 masks
+    assert len(links.ambiguous) == 34 and all(d["tau"] > 0 for d in links.ambiguous.values())
+
+
+def test_f32_oracle_step_gives_the_composite_levels_and_bands(composite):
+    """The f32 CPU oracle's own step with the default step's tensors withheld: the level of every kind of composite link (4 x that is its
+    bar; composite_bars asserts the cap), the band of every withheld activation and how many elements fall into it."""
+    bars, bands = composite
+    for H, B in LL.SIZES:
+        res, links = LL.f32_composite_results(H, B)
+        print("f32 CPU oracle, composite links, %dx%d x %d:\n%s\n%s" % (H, 2 * H, B, LL.report(res, bars), LL.ambiguity_report(links)))
+        assert not LL.failures(res, bars)
+    print("bands: %s" % {SPEC.layers[i - 1].scope: "%.2e" % t for i, t in sorted(bands.items())})
+    assert set(bars) == set(LL.KINDS) - {"conv_stem", "bn_act", "loss", "dlogits"}
+    assert all(0 < b <= LL.BAR_CAP for b, _ in bars.values())
+    assert len(bands) == 34 and all(0 < t < 1e-4 for t in bands.values())
+
+
+def test_the_stride_16_blocks_close_where_the_handles_hold_dy(fused64):
+    """At LL.FUSED_SIZE every late depthwise handle holds dy: the links of the stride-16 blocks of both plans close on the f64 step, each
+    handle is checked as dy, and the two ways a step can betray the declaration fail that layer's B2 and nothing else: dy left unmasked
+    (da where da * act' belongs), and dz written in place (the unfused path) where dy is declared."""
+    stored = STORED[LL.FUSED_SIZE]
+    bands = LL.f32_bands((LL.FUSED_SIZE,))
+    bars = LL.composite_bars(LL.f32_composite_levels((LL.FUSED_SIZE,), late=True))
+    good = LL.withhold(fused64, stored)
+    links = LL.Links(good, stored=stored, bands=bands)
+    plan = LL.late_plan(LL.composite_plan(SPEC))
+    res = links.close(plan + LL.late_plan(_default_plan(links)))
+    bad = [r for r in res if not r.err <= 1e-10]
+    assert not bad, bad
+    assert len([r for r in res if r.name.endswith(" (dy)")]) == 10
+    d = [l for l in SPEC.layers if l.scope == "MobilenetV2/expanded_conv_8/depthwise"][0]
+    full = LL.Links(fused64)
+    for wrong in (full.cot_a(d.idx), fused64["dz"][d.idx]):
+        run = LL.copy_run(good)
+        run["dz"][d.idx] = wrong
+        got = LL.failures(LL.Links(run, stored=stored, bands=bands).close(plan), bars)
+        assert {(r.link, r.name) for r in got} == {("B2", d.scope + " (dy)")}, got
+
+
+def _failing(run_w, composite, bars, around, bands=None, plan=None):
+    """{(link, name)} of the links of both plans on the layers within three of ``around`` that fail on the withheld run"""
+    links = LL.Links(run_w, stored=STORED[(run_w["frames"].shape[1], run_w["frames"].shape[0])], bands=composite[1] if bands is None else bands)
+    near = lambda p: [(k, i) for k, i in p if abs(i - around.idx) <= 3]  # noqa: E731
+    cplan = near(LL.composite_plan(SPEC)) if plan is None else plan
+    bad = LL.failures(links.close(cplan), composite[0])
+    if plan is None:
+        bad += LL.failures(links.close(near(_default_plan(links))), bars)
+    return {(r.link, r.name) for r in bad}, links
+
+
+@pytest.mark.parametrize("H,B", SIZES)
+def test_negative_controls_with_tensors_withheld(runs64, composite, bars, H, B):
+    run = runs64[(H, B)]
+    full = LL.Links(run)
+    good = LL.withhold(run, STORED[(H, B)])
+    L = {l.scope: l for l in SPEC.layers}
+
+    # 1. the expand weight gradient of a recompute block scaled by 1 + 1e-4
+    e = L["MobilenetV2/expanded_conv_3/expand"]
+    bad = LL.copy_run(good)
+    bad["grads"][e.weight_name] = good["grads"][e.weight_name] * (1 + 1e-4)
+    assert _failing(bad, composite, bars, e)[0] == {("B1", e.weight_name)}
+
+    # 2. dgamma of a recompute block's expand layer with the variance over n - 1 samples
+    e = L["MobilenetV2/expanded_conv_5/expand"]
+    gname = e.scope + "/BatchNorm/gamma:0"
+    z, g = run["z"][e.idx], LL._leaf(run["params"][gname])
+    n = z.numel() // z.shape[1]
+    mu = z.mean(dim=(0, 2, 3), keepdim=True)
+    y = (z - mu) * torch.rsqrt(((z - mu) ** 2).sum(dim=(0, 2, 3), keepdim=True) / (n - 1) + e.bn_eps) * g.view(1, -1, 1, 1)
+    bad = LL.copy_run(good)
+    bad["grads"][gname] = torch.autograd.grad((y * full.mask(e) * full.cot_a(e.idx)).sum(), g)[0]
+    assert _failing(bad, composite, bars, e)[0] == {("B2", gname)}
+
+    # 3. the skip gradient into a recompute block's input gradient taken from the neighbouring block (blocks 4 and 5: same shape)
+    a, b = L["MobilenetV2/expanded_conv_4/project"], L["MobilenetV2/expanded_conv_5/project"]
+    src = full.by_idx[a.residual_from]
+    bad = LL.copy_run(good)
+    bad["da"][a.idx] = good["da"][b.idx]
+    got = _failing(bad, composite, bars, a)[0]
+    assert {("DA", a.scope), ("B2", src.scope)} <= got <= {("DA", a.scope), ("B2", src.scope), ("B2", src.scope + "/BatchNorm/gamma:0"),
+                                                            ("B2", src.scope + "/BatchNorm/beta:0")}, got
+
+    # 4. a stride-2 recompute block's depthwise dz rolled by one pixel: every link that reads it, and no other
+    d, e, p = (L["MobilenetV2/expanded_conv_3/" + s] for s in ("depthwise", "expand", "project"))
+    assert d.stride == 2 and e.idx in LL.recompute_expand(SPEC)
+    bad = LL.copy_run(good)
+    bad["dz"][d.idx] = torch.roll(good["dz"][d.idx], 1, dims=3)
+    got = _failing(bad, composite, bars, d)[0]
+    front = full.by_idx[e.idx - 1]
+    assert {("B1", d.weight_name), ("B2", d.scope), ("B1", e.weight_name), ("B2", e.scope + "/BatchNorm/gamma:0"), ("B2", front.scope),
+            ("DA", front.scope)} <= got, got
+    assert all(name.startswith((d.scope, e.scope, front.scope)) for _, name in got), got
+
+    # 5. the stem weight gradient built from the first block's dz of the wrong frame
+    stem = L["MobilenetV2/Conv"]
+    wrong = LL.copy_run(good)
+    wrong["dz"][2] = torch.roll(good["dz"][2], 1, dims=0)
+    dz_stem = LL.Links(wrong, stored=STORED[(H, B)], bands=composite[1]).dz(stem.idx)
+    bad = LL.copy_run(good)
+    w = LL._leaf(full.P(stem.weight_name))
+    bad["grads"][stem.weight_name] = torch.autograd.grad((full.conv(stem, full.x_in(stem), w) * dz_stem).sum(), w)[0]
+    assert _failing(bad, composite, bars, stem)[0] == {("B1", stem.weight_name)}
+
+    # 6. (dy of a late depthwise layer left unmasked: test_the_stride_16_blocks_close_where_the_handles_hold_dy, at the size where it is dy)
+
+
+@pytest.mark.parametrize("H,B", SIZES[:1])
+def test_mask_controls(runs64, composite, bars, H, B):
+    """One mask bit of a withheld activation planted the other way round, with everything the step derives from it (the layer's dz, dgamma,
+    dbeta and weight gradient, the input gradient and the BN backward of the layer in front): far outside the band it fails, inside the
+    band it is resolved, reported, and every quantity passes under the resolved mask."""
+    run = runs64[(H, B)]
+    good = LL.withhold(run, STORED[(H, B)])
+    e = [l for l in SPEC.layers if l.scope == "MobilenetV2/expanded_conv_3/expand"][0]
+    front = SPEC.layers[e.idx - 2]
+    assert front.residual_from is not None                                       # its da is stored: the input gradient is checked on its own
+    plan = [("B1", e.idx), ("B2", e.idx), ("DA", front.idx), ("B2", front.idx)]
+    ref = LL.Links(good, stored=STORED[(H, B)], bands=composite[1])
+    y = ref._bn(e, ref.z(e.idx), *ref._gb(e))[0]
+    dist = torch.minimum(y.abs(), (y - 6).abs())
+    cot = ref.cot_a(e.idx)
+
+    def planted(where):
+        pl = LL.Links(good, stored=STORED[(H, B)], bands=composite[1])
+        mk = ref.mask(e).clone()
+        mk[where] = 1.0 - mk[where]
+        pl._cache[("mask", e.idx)] = mk                                          # the step's own mask: this one bit the other way round
+        bad = LL.copy_run(good)
+        dz, dg, db, _, _ = pl._bn_backward(e, pl.cot_a(e.idx))
+        w = LL._leaf(pl.P(e.weight_name))
+        bad["grads"][e.weight_name] = torch.autograd.grad((pl.conv(e, pl.x_in(e), w) * dz).sum(), w)[0]
+        bad["grads"][e.scope + "/BatchNorm/gamma:0"], bad["grads"][e.scope + "/BatchNorm/beta:0"] = dg, db
+        bad["da"][front.idx] = pl.cot_a(front.idx)
+        dz, dg, db, _, _ = pl._bn_backward(front, bad["da"][front.idx])
+        bad["dz"][front.idx] = dz
+        bad["grads"][front.scope + "/BatchNorm/gamma:0"], bad["grads"][front.scope + "/BatchNorm/beta:0"] = dg, db
+        return bad
+
+    inside = cot.abs() * ((y - 3).abs() < 2)                                     # the largest cotangent on an element well between the knees
+    far = tuple(torch.nonzero(inside == inside.max())[0].tolist())
+    assert dist[far] > 0.5
+    got, links = _failing(planted(far), composite, bars, e, plan=plan)
+    assert ("B2", e.scope + "/BatchNorm/beta:0") in got and links.ambiguous[e.idx]["resolved"] == 0, got
+
+    near = tuple(torch.nonzero(dist == dist.min())[0].tolist())
+    bands = dict(composite[1])
+    bands[e.idx] = max(bands[e.idx], 2 * float(dist[near]))                       # this control's own band: the nearest element is inside it
+    got, links = _failing(planted(near), composite, bars, e, bands=bands, plan=plan)
+    print(LL.ambiguity_report(links))
+    assert not got and links.ambiguous[e.idx]["resolved"] == 1, (got, links.ambiguous[e.idx])
+    # ... and without the band the same run fails: the bit is no rounding
+    bands[e.idx] = 0.0
+    assert _failing(planted(near), composite, bars, e, bands=bands, plan=plan)[0]
