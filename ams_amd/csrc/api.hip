@@ -174,70 +174,51 @@ int ams_student_freeze(ams_student* s, void* stream) {
     return AMS_OK;
 }
 
-int ams_student_predict(ams_student* s, const void* frames_dev, int32_t frames_dtype, int32_t batch, int32_t mode,
-                        int32_t* labels_out_dev, void* stream) {
+// The one body of the four predict entries.  metric: 0 none, 1 when teacher labels come, 2 required; labels: int32, or uint8 when labels_u8
+static int student_predict(const char* who, ams_student* s, const void* frames_dev, int32_t frames_dtype, int32_t batch, int32_t mode, const uint8_t* teacher_dev,
+                           int metric, void* labels_out_dev, int64_t* conf_dev, double* loss_dev, void* stream, int per_frame, int labels_u8) {
     RUN(check_call(s, frames_dev, frames_dtype, batch));
-    AMS_REQUIRE(labels_out_dev, "predict: null output");
+    if (metric == 2) AMS_REQUIRE(teacher_dev && labels_out_dev && conf_dev && loss_dev, "%s: null pointer", who);
+    AMS_REQUIRE(labels_out_dev, "%s: null output", who);
+    AMS_REQUIRE(teacher_dev == nullptr || (conf_dev && loss_dev), "%s: metrics need conf and loss buffers", who);
     hipStream_t st = (hipStream_t)stream;
     RUN(run_forward(s, frames_dev, frames_dtype, batch, mode, st));
-    const ams_student_config& c = s->cfg;
-    return launch_upsample_argmax(s->logits, 32, batch, s->h, s->w, c.class_indices, c.n_selected, c.height, c.width, nullptr,
-                                  c.num_classes, labels_out_dev, nullptr, nullptr, st);
+    return launch_upsample_argmax(student_head_call(s, batch, teacher_dev), static_cast<int32_t*>(labels_out_dev), conf_dev, loss_dev, st, per_frame, labels_u8);
+}
+
+int ams_student_predict(ams_student* s, const void* frames_dev, int32_t frames_dtype, int32_t batch, int32_t mode,
+                        int32_t* labels_out_dev, void* stream) {
+    return student_predict("predict", s, frames_dev, frames_dtype, batch, mode, nullptr, 0, labels_out_dev, nullptr, nullptr, stream, 0, 0);
 }
 
 int ams_student_predict_with_metric(ams_student* s, const void* frames_dev, int32_t frames_dtype, int32_t batch, int32_t mode,
                                     const uint8_t* teacher_dev, int32_t* labels_out_dev, int64_t* conf_mat_dev, double* loss_dev,
                                     void* stream) {
-    RUN(check_call(s, frames_dev, frames_dtype, batch));
-    AMS_REQUIRE(teacher_dev && labels_out_dev && conf_mat_dev && loss_dev, "predict_with_metric: null pointer");
-    hipStream_t st = (hipStream_t)stream;
-    RUN(run_forward(s, frames_dev, frames_dtype, batch, mode, st));
-    const ams_student_config& c = s->cfg;
-    return launch_upsample_argmax(s->logits, 32, batch, s->h, s->w, c.class_indices, c.n_selected, c.height, c.width, teacher_dev,
-                                  c.num_classes, labels_out_dev, conf_mat_dev, loss_dev, st);
+    return student_predict("predict_with_metric", s, frames_dev, frames_dtype, batch, mode, teacher_dev, 2, labels_out_dev, conf_mat_dev, loss_dev, stream, 0, 0);
 }
 
 int ams_student_predict_frames(ams_student* s, const void* frames_dev, int32_t frames_dtype, int32_t batch, int32_t mode, const uint8_t* teacher_dev,
                                int32_t* labels_out_dev, int64_t* conf_mats_dev, double* losses_dev, void* stream) {
-    RUN(check_call(s, frames_dev, frames_dtype, batch));
-    AMS_REQUIRE(labels_out_dev, "predict_frames: null output");
-    AMS_REQUIRE(teacher_dev == nullptr || (conf_mats_dev && losses_dev), "predict_frames: metrics need conf and loss buffers");
-    hipStream_t st = (hipStream_t)stream;
-    RUN(run_forward(s, frames_dev, frames_dtype, batch, mode, st));
-    const ams_student_config& c = s->cfg;
-    return launch_upsample_argmax(s->logits, 32, batch, s->h, s->w, c.class_indices, c.n_selected, c.height, c.width, teacher_dev, c.num_classes,
-                                  labels_out_dev, teacher_dev ? conf_mats_dev : nullptr, teacher_dev ? losses_dev : nullptr, st, /*per_frame=*/1);
+    return student_predict("predict_frames", s, frames_dev, frames_dtype, batch, mode, teacher_dev, 1, labels_out_dev, conf_mats_dev, losses_dev, stream, 1, 0);
 }
 
 int ams_student_predict_frames_u8(ams_student* s, const void* frames_dev, int32_t frames_dtype, int32_t batch, int32_t mode, const uint8_t* teacher_dev,
                                   uint8_t* labels_out_dev, int64_t* conf_mats_dev, double* losses_dev, void* stream) {
-    RUN(check_call(s, frames_dev, frames_dtype, batch));
-    AMS_REQUIRE(labels_out_dev, "predict_frames_u8: null output");
-    AMS_REQUIRE(teacher_dev == nullptr || (conf_mats_dev && losses_dev), "predict_frames_u8: metrics need conf and loss buffers");
-    hipStream_t st = (hipStream_t)stream;
-    RUN(run_forward(s, frames_dev, frames_dtype, batch, mode, st));
-    const ams_student_config& c = s->cfg;
-    return launch_upsample_argmax(s->logits, 32, batch, s->h, s->w, c.class_indices, c.n_selected, c.height, c.width, teacher_dev, c.num_classes,
-                                  reinterpret_cast<int32_t*>(labels_out_dev), teacher_dev ? conf_mats_dev : nullptr, teacher_dev ? losses_dev : nullptr, st,
-                                  /*per_frame=*/1, /*labels_u8=*/1);
+    return student_predict("predict_frames_u8", s, frames_dev, frames_dtype, batch, mode, teacher_dev, 1, labels_out_dev, conf_mats_dev, losses_dev, stream, 1, 1);
 }
 
 int ams_student_confidence(ams_student* s, int32_t batch, const uint8_t* teacher_dev, uint8_t* conf_u8, float* conf_f32, int64_t* stats, void* stream) {
     AMS_REQUIRE(s, "confidence: null student");
     AMS_REQUIRE(batch >= 1 && batch <= s->cfg.max_batch, "confidence: batch %d outside 1..%d", batch, s->cfg.max_batch);
-    const ams_student_config& c = s->cfg;
-    return launch_upsample_confidence(s->logits, 32, batch, s->h, s->w, c.class_indices, c.n_selected, c.height, c.width, teacher_dev, c.num_classes,
-                                      conf_u8, conf_f32, stats, (hipStream_t)stream);
+    return launch_upsample_confidence(student_head_call(s, batch, teacher_dev), conf_u8, conf_f32, stats, (hipStream_t)stream);
 }
 
 int ams_student_soft_metric_layout(ams_student* s, int32_t batch, const uint8_t* teacher_dev, const float* teacher_logits_dev, int32_t th, int32_t tw,
                                    int64_t* stats, float* p_f32, float* ce_f32, void* stream, int32_t layout) {
     AMS_REQUIRE(s, "soft_metric: null student");
     AMS_REQUIRE(batch >= 1 && batch <= s->cfg.max_batch, "soft_metric: batch %d outside 1..%d", batch, s->cfg.max_batch);
-    AMS_REQUIRE(layout == AMS_TLOGITS_FULL || layout == AMS_TLOGITS_SELECTED, "soft_metric: unknown teacher-logit layout %d", layout);
-    const ams_student_config& c = s->cfg;
-    return launch_upsample_soft_metric(s->logits, 32, batch, s->h, s->w, c.class_indices, c.n_selected, c.height, c.width, teacher_dev, c.num_classes,
-                                       teacher_logits_dev, th, tw, stats, p_f32, ce_f32, (hipStream_t)stream, layout);
+    return launch_upsample_soft_metric(student_head_call(s, batch, teacher_dev), LossObjective{teacher_logits_dev, th, tw, layout}, stats, p_f32, ce_f32,
+                                       (hipStream_t)stream);
 }
 
 int ams_student_soft_metric(ams_student* s, int32_t batch, const uint8_t* teacher_dev, const float* teacher_logits_dev, int32_t th, int32_t tw,
@@ -245,23 +226,26 @@ int ams_student_soft_metric(ams_student* s, int32_t batch, const uint8_t* teache
     return ams_student_soft_metric_layout(s, batch, teacher_dev, teacher_logits_dev, th, tw, stats, p_f32, ce_f32, stream, AMS_TLOGITS_FULL);
 }
 
+// teacher id -> the student's subset index, -1 = ignored
+struct StudentLut {
+    int32_t lut[256];
+    explicit StudentLut(const ams_student* s) {
+        for (int i = 0; i < 256; ++i) lut[i] = -1;
+        for (int k = 0; k < s->cfg.n_selected; ++k) lut[s->cfg.class_indices[k]] = k;
+    }
+};
+
 int ams_cross_confusion(const ams_student* s, const uint8_t* labels_dev, int64_t n_pixels, int64_t* conf_mat_dev, void* stream) {
     AMS_REQUIRE(s && labels_dev && conf_mat_dev && n_pixels > 0, "cross_confusion: bad argument");
-    int32_t lut[256];
-    for (int i = 0; i < 256; ++i) lut[i] = -1;
-    for (int k = 0; k < s->cfg.n_selected; ++k) lut[s->cfg.class_indices[k]] = k;
-    return launch_cross_confusion(labels_dev, labels_dev + n_pixels, n_pixels, lut, s->cfg.n_selected, conf_mat_dev,
+    return launch_cross_confusion(labels_dev, labels_dev + n_pixels, n_pixels, StudentLut(s).lut, s->cfg.n_selected, conf_mat_dev,
                                   (hipStream_t)stream);
 }
 
 int ams_cross_confusion_pairs(const ams_student* s, const uint8_t* label_slots_dev, int64_t label_slot_stride, int32_t capacity, int64_t n_pixels,
                               const int32_t* pairs_dev, const int32_t* pairs_host, int32_t n_pairs, int64_t* conf_mats_dev, void* stream) {
     AMS_REQUIRE(s, "cross_confusion_pairs: null student");
-    int32_t lut[256];
-    for (int i = 0; i < 256; ++i) lut[i] = -1;
-    for (int k = 0; k < s->cfg.n_selected; ++k) lut[s->cfg.class_indices[k]] = k;
-    return launch_cross_confusion_pairs(label_slots_dev, label_slot_stride, capacity, n_pixels, pairs_dev, pairs_host, n_pairs, lut, s->cfg.n_selected,
-                                        conf_mats_dev, (hipStream_t)stream);
+    return launch_cross_confusion_pairs(label_slots_dev, label_slot_stride, capacity, n_pixels, pairs_dev, pairs_host, n_pairs, StudentLut(s).lut,
+                                        s->cfg.n_selected, conf_mats_dev, (hipStream_t)stream);
 }
 
 int ams_replay_gather(const uint8_t* frame_slots_dev, int64_t frame_slot_stride, const uint8_t* label_slots_dev, int64_t label_slot_stride,
@@ -558,11 +542,17 @@ static int64_t delta_mask_bytes(const ams_student* s, const ams_delta_var* vars,
     return mask;
 }
 
-size_t ams_student_apply_delta_scratch(const ams_delta_var* vars_host, int32_t n_vars) {
-    if (!vars_host || n_vars < 1 || n_vars > AMS_DELTA_MAX_VARS) return 0;
+// the mask section of a delta over these variables, in bytes: one bit per element, each variable on a byte of its own; -1: no such table
+static int64_t delta_mask_sum(const ams_delta_var* vars_host, int32_t n_vars) {
+    if (!vars_host || n_vars < 1 || n_vars > AMS_DELTA_MAX_VARS) return -1;
     int64_t mask = 0;
     for (int32_t i = 0; i < n_vars; ++i) mask += vars_host[i].count > 0 ? (vars_host[i].count + 7) / 8 : 0;
-    return (size_t)(4 * (int64_t)n_vars + delta_segments(mask));
+    return mask;
+}
+
+size_t ams_student_apply_delta_scratch(const ams_delta_var* vars_host, int32_t n_vars) {
+    const int64_t mask = delta_mask_sum(vars_host, n_vars);
+    return mask < 0 ? 0 : (size_t)(4 * (int64_t)n_vars + delta_segments(mask));
 }
 
 int ams_student_apply_delta(ams_student* s, const uint8_t* payload_dev, int64_t payload_bytes, const ams_delta_var* vars_host,
@@ -607,10 +597,8 @@ int ams_select_apply(float* params_dev, const float* before_dev, int64_t n, floa
 }
 
 size_t ams_student_encode_delta_scratch(const ams_delta_var* vars_host, int32_t n_vars) {
-    if (!vars_host || n_vars < 1 || n_vars > AMS_DELTA_MAX_VARS) return 0;
-    int64_t mask = 0;
-    for (int32_t i = 0; i < n_vars; ++i) mask += vars_host[i].count > 0 ? (vars_host[i].count + 7) / 8 : 0;
-    return (size_t)(5 * (int64_t)n_vars + 2 + encode_segments(mask));
+    const int64_t mask = delta_mask_sum(vars_host, n_vars);
+    return mask < 0 ? 0 : (size_t)(5 * (int64_t)n_vars + 2 + encode_segments(mask));
 }
 
 int ams_student_encode_delta(ams_student* s, const uint8_t* mask_dev, const ams_delta_var* vars_host, int32_t n_vars, uint8_t* payload_dev,
@@ -839,37 +827,36 @@ size_t ams_k_global_mean_scratch(int32_t B, int32_t C) { return image_colsum_scr
 int ams_k_upsample_argmax(const float* logits, int32_t B, int32_t h, int32_t w, int32_t NC, const int32_t* class_idx_host, int32_t K,
                           int32_t H, int32_t W, const uint8_t* teacher, int32_t* labels_out, int64_t* conf_mat, double* loss,
                           void* stream) {
-    return launch_upsample_argmax(logits, NC, B, h, w, class_idx_host, K, H, W, teacher, NC, labels_out, conf_mat, loss,
-                                  (hipStream_t)stream);
+    const HeadCall c{logits, NC, B, h, w, class_idx_host, K, H, W, teacher, NC};
+    return launch_upsample_argmax(c, labels_out, conf_mat, loss, (hipStream_t)stream);
 }
 
 int ams_k_upsample_confidence(const float* logits, int32_t B, int32_t h, int32_t w, int32_t NC, const int32_t* class_idx_host, int32_t K,
                               int32_t H, int32_t W, const uint8_t* teacher, uint8_t* conf_u8, float* conf_f32, int64_t* stats, void* stream) {
-    return launch_upsample_confidence(logits, NC, B, h, w, class_idx_host, K, H, W, teacher, NC, conf_u8, conf_f32, stats, (hipStream_t)stream);
+    const HeadCall c{logits, NC, B, h, w, class_idx_host, K, H, W, teacher, NC};
+    return launch_upsample_confidence(c, conf_u8, conf_f32, stats, (hipStream_t)stream);
 }
 size_t ams_confidence_stats_len(void) { return (size_t)confidence_stats_len(); }
 
 int ams_k_upsample_soft_metric_layout(const float* logits, int32_t B, int32_t h, int32_t w, int32_t ld, int32_t NC, const int32_t* class_idx_host,
                                       int32_t K, int32_t H, int32_t W, const uint8_t* teacher, const float* teacher_logits, int32_t th, int32_t tw,
                                       int32_t layout, int64_t* stats, float* p_f32, float* ce_f32, void* stream) {
-    AMS_REQUIRE(class_idx_host, "soft_metric: null class table");
-    AMS_REQUIRE(layout == AMS_TLOGITS_FULL || layout == AMS_TLOGITS_SELECTED, "soft_metric: unknown teacher-logit layout %d", layout);
-    return launch_upsample_soft_metric(logits, ld, B, h, w, class_idx_host, K, H, W, teacher, NC, teacher_logits, th, tw, stats, p_f32, ce_f32,
-                                       (hipStream_t)stream, layout);
+    const HeadCall c{logits, ld, B, h, w, class_idx_host, K, H, W, teacher, NC};
+    return launch_upsample_soft_metric(c, LossObjective{teacher_logits, th, tw, layout}, stats, p_f32, ce_f32, (hipStream_t)stream);
 }
 
 int ams_k_upsample_soft_metric(const float* logits, int32_t B, int32_t h, int32_t w, int32_t NC, const int32_t* class_idx_host, int32_t K,
                                int32_t H, int32_t W, const uint8_t* teacher, const float* teacher_logits, int32_t th, int32_t tw, int64_t* stats,
                                float* p_f32, float* ce_f32, void* stream) {
-    return launch_upsample_soft_metric(logits, NC, B, h, w, class_idx_host, K, H, W, teacher, NC, teacher_logits, th, tw, stats, p_f32, ce_f32,
-                                       (hipStream_t)stream, AMS_TLOGITS_FULL);
+    return ams_k_upsample_soft_metric_layout(logits, B, h, w, NC, NC, class_idx_host, K, H, W, teacher, teacher_logits, th, tw, AMS_TLOGITS_FULL, stats, p_f32,
+                                             ce_f32, stream);
 }
 size_t ams_soft_metric_stats_len(int32_t K) { return K >= 1 && K <= 32 ? (size_t)soft_metric_stats_len(K) : 0; }
 
 int ams_k_ce_grad(const float* logits, int32_t B, int32_t h, int32_t w, int32_t NC, const int32_t* class_idx_host, int32_t K, int32_t H,
                   int32_t W, const uint8_t* teacher, const double* loss_and_count_dev, float* dlogits, void* stream) {
-    return launch_ce_grad(logits, NC, B, h, w, class_idx_host, K, H, W, teacher, NC, loss_and_count_dev, dlogits, NC,
-                          (hipStream_t)stream);
+    const HeadCall c{logits, NC, B, h, w, class_idx_host, K, H, W, teacher, NC};
+    return launch_ce_grad(c, loss_and_count_dev, dlogits, NC, (hipStream_t)stream);
 }
 
 size_t ams_k_ce_loss_grad_scratch(int32_t B, int32_t h, int32_t w, int32_t K) { return ce_loss_grad_scratch(B, h, w, K); }

@@ -253,6 +253,12 @@ static inline double pw_bytes(const PwArgs& a) {
 }
 static inline double dw_bytes(const LayerRt& l, int B) { return 4.0 * ((double)B * (l.px_in + l.px_out) * l.d.cin + 9.0 * l.d.cin); }
 
+// the student's own logits (row stride 32) of B frames against their labels (or none): what every head launcher is given
+static inline HeadCall student_head_call(const ams_student* s, int B, const uint8_t* teacher) {
+    const ams_student_config& c = s->cfg;
+    return HeadCall{s->logits, 32, B, s->h, s->w, c.class_indices, c.n_selected, c.height, c.width, teacher, c.num_classes};
+}
+
 // cross-rank sums of the data-parallel step: through the library's RCCL communicator on the launch stream (comm), or through a
 // host callback (cb: the gloo test hook / any other transport).  `cb` doubles as "a sync is configured" for the callers below.
 struct SyncCtx { ams_allreduce_cb cb; void* user; ams_student* s; ams_comm* comm; };

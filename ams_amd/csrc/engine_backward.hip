@@ -66,12 +66,6 @@ static PwArgs dgrad_args(const float* dy, int64_t M, int N, int ldy, const float
     return a;
 }
 
-// the student's own logits (row stride 32) against a batch's labels: what both passes of the one-pass loss are given
-static HeadCall step_head_call(const ams_student* s, int B, const uint8_t* teacher) {
-    const ams_student_config& c = s->cfg;
-    return HeadCall{s->logits, 32, B, s->h, s->w, c.class_indices, c.n_selected, c.height, c.width, teacher, c.num_classes};
-}
-
 int backward(ams_student* s, const void* frames, int dtype, const uint8_t* teacher, int B, int global_B, const SyncCtx* sc,
                     hipStream_t st) {
     const ams_student_config& c = s->cfg;
@@ -87,10 +81,9 @@ int backward(ams_student* s, const void* frames, int dtype, const uint8_t* teach
     // AMS_OPT_NAN_GRADS = 1 writes NaN gradients instead (a loud failure for callers that prefer one).
     const float empty_val = s->nan_grads ? __builtin_nanf("") : 0.f;
     if (ce_loss_grad_supported(s->w, c.width))           // second pass of the one-pass loss kernel (train_step_impl ran the first)
-        RUNK(0, 0.0, launch_ce_combine(step_head_call(s, B, teacher), s->loss_buf, s->ce_scratch, s->dlogits, 32, st, empty_val));
+        RUNK(0, 0.0, launch_ce_combine(student_head_call(s, B, teacher), s->loss_buf, s->ce_scratch, s->dlogits, 32, st, empty_val));
     else
-        RUNK(0, 0.0, launch_ce_grad(s->logits, 32, B, s->h, s->w, c.class_indices, c.n_selected, c.height, c.width, teacher, NC, s->loss_buf,
-                                    s->dlogits, 32, st, empty_val));
+        RUNK(0, 0.0, launch_ce_grad(student_head_call(s, B, teacher), s->loss_buf, s->dlogits, 32, st, empty_val));
     // A layer's weight gradient only feeds the optimizer: it runs on the side stream while the main stream goes on with the input gradient
     // and the next layer's BN backward (many of these kernels are latency-bound at 8 frames and share the chip well).  Nothing the side
     // stream reads is overwritten inside the step (every dz lives in per-layer memory — in the head too: in place over da), so the main
@@ -379,15 +372,14 @@ int loss_forward(ams_student* s, const uint8_t* teacher, int B, int32_t* labels,
         // the fine-tune step: loss sums and the unnormalised gradient in one pass over the pixels
         AMS_REQUIRE(o.soft_teacher || o.conf_gamma == 0.f, "train_step: conf_gamma %g weights by the teacher's confidence: it needs soft_teacher (AMS_OPT_SOFT_TEACHER)",
                     (double)o.conf_gamma);
-        RUNK(0, 0.0, launch_ce_loss_grad(step_head_call(s, B, teacher), o, s->loss_buf, s->ce_scratch, st));
+        RUNK(0, 0.0, launch_ce_loss_grad(student_head_call(s, B, teacher), o, s->loss_buf, s->ce_scratch, st));
         return AMS_OK;
     }
     // evaluation (labels) stays unweighted
     AMS_REQUIRE(labels || loss_weights_default(o.class_weights, c.n_selected, o.conf_gamma),
                 "loss weights: %d output columns on %d logit columns is outside the one-pass loss kernel", c.width, s->w);
     AMS_REQUIRE(labels || !o.soft_teacher, "soft_teacher: %d output columns on %d logit columns is outside the one-pass loss kernel", c.width, s->w);
-    return launch_upsample_argmax(s->logits, 32, B, s->h, s->w, c.class_indices, c.n_selected, c.height, c.width, teacher,
-                                  c.num_classes, labels, s->conf_buf, s->loss_buf, st);
+    return launch_upsample_argmax(student_head_call(s, B, teacher), labels, s->conf_buf, s->loss_buf, st);
 }
 
 int train_step_impl(ams_student* s, const void* frames_dev, int32_t frames_dtype, const uint8_t* teacher_dev,

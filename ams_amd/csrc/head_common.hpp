@@ -30,18 +30,6 @@ __device__ __forceinline__ float bilerp(float tl, float tr, float bl, float br, 
     return __fadd_rn(top, __fmul_rn(__fsub_rn(bot, top), ty));
 }
 
-static inline int fill_class_table(const int32_t* cls_host, int K, int NC, ClassTable* ct) {
-    AMS_REQUIRE(K > 0 && K <= kMaxK, "head: K=%d out of range (1..%d)", K, kMaxK);
-    for (int i = 0; i < 256; ++i) ct->lut[i] = -1;
-    for (int k = 0; k < kMaxK; ++k) ct->idx[k] = 0;
-    for (int k = 0; k < K; ++k) {
-        AMS_REQUIRE(cls_host[k] >= 0 && cls_host[k] < NC && cls_host[k] < 256, "head: class id %d out of range", cls_host[k]);
-        ct->idx[k] = cls_host[k];
-        ct->lut[cls_host[k]] = k;
-    }
-    return AMS_OK;
-}
-
 // the scale of an align-corners resize of n_in samples to n_out, as f32 (TF: CalculateResizeScale with align_corners)
 static inline float align_corners_scale(int n_in, int n_out) { return n_out > 1 ? (float)(n_in - 1) / (float)(n_out - 1) : 0.f; }
 
@@ -112,7 +100,7 @@ static inline void fill_loss_weights(const ClassTable& ct, const float* cw, int 
 
 static inline bool tlogits_layout_ok(int layout) { return layout == AMS_TLOGITS_FULL || layout == AMS_TLOGITS_SELECTED; }
 
-// ---- one loss call, as the host describes it (launch_ce_loss_grad, launch_ce_combine, the ams_k_ce_loss_grad* entries, the student's step) ----
+// ---- one head call, as the host describes it (every head launcher, the ams_k_* head and loss entries, the student: student_head_call) ----
 // The head call: whose logits against which labels
 struct HeadCall {
     const float* logits = nullptr;     // [B][h][w][ld] f32, the student's
@@ -123,6 +111,24 @@ struct HeadCall {
     const uint8_t* teacher = nullptr;  // the teacher's labels [B][H][W]
     int NC = 0;
 };
+
+// What every head launcher refuses first, in this order, and what it gets in return: the class table and the geometry of the call.  After it
+// come the launcher's own conditions and, last, in front of its first memset or launch, the null checks of the pointers it reads.
+static inline int head_call_check(const char* who, const HeadCall& c, ClassTable* ct, HeadGeom* g) {
+    AMS_REQUIRE(c.cls, "%s: null class table", who);
+    AMS_REQUIRE(c.K > 0 && c.K <= kMaxK, "%s: K=%d out of range (1..%d)", who, c.K, kMaxK);
+    for (int i = 0; i < 256; ++i) ct->lut[i] = -1;
+    for (int k = 0; k < kMaxK; ++k) ct->idx[k] = 0;
+    for (int k = 0; k < c.K; ++k) {
+        AMS_REQUIRE(c.cls[k] >= 0 && c.cls[k] < c.NC && c.cls[k] < 256, "%s: class id %d out of range", who, c.cls[k]);
+        ct->idx[k] = c.cls[k];
+        ct->lut[c.cls[k]] = k;
+    }
+    AMS_REQUIRE(c.B > 0 && c.h > 0 && c.w > 0 && c.H > 0 && c.W > 0, "%s: no pixels: B=%d, %d x %d -> %d x %d", who, c.B, c.h, c.w, c.H, c.W);
+    AMS_REQUIRE(c.ld >= c.NC, "%s: row stride %d below %d classes", who, c.ld, c.NC);
+    *g = head_geom(c.ld, c.B, c.h, c.w, c.K, c.H, c.W, c.NC);
+    return AMS_OK;
+}
 
 // The objective: what the loss of a pixel is.  The defaults are the reference's hard loss.
 struct LossObjective {

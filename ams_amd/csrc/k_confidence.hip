@@ -142,24 +142,21 @@ __global__ __launch_bounds__(256) void upsample_confidence_kernel(const float* _
     }
 }
 
-// cls: HOST pointer to the K selected class ids.  Every output pointer may be null: nothing is written there.
-int launch_upsample_confidence(const float* logits, int ld, int B, int h, int w, const int32_t* cls, int K, int H, int W, const uint8_t* teacher,
-                               int NC, uint8_t* conf_u8, float* conf_f32, int64_t* stats, hipStream_t st) {
+// Every output pointer may be null: nothing is written there.
+int launch_upsample_confidence(const HeadCall& c, uint8_t* conf_u8, float* conf_f32, int64_t* stats, hipStream_t st) {
     ClassTable ct;
-    int rc = fill_class_table(cls, K, NC, &ct);
-    if (rc) return rc;
-    AMS_REQUIRE(logits && B > 0 && h > 0 && w > 0 && H > 0 && W > 0, "confidence: B=%d, %d x %d -> %d x %d", B, h, w, H, W);
-    AMS_REQUIRE(ld >= NC, "confidence: row stride %d below %d classes", ld, NC);
-    const HeadGeom g = head_geom(ld, B, h, w, K, H, W, NC);
-    const dim3 grid = head_band_grid(B, H, W);
+    HeadGeom g;
+    if (int rc = head_call_check("confidence", c, &ct, &g)) return rc;
+    const dim3 grid = head_band_grid(c.B, c.H, c.W);
     // a block's pixel counts per bin live in 21-bit fields
-    AMS_REQUIRE((int64_t)cdiv(H, (int)grid.y) * 256 < (1 << kConfPackBits), "confidence: %d rows per band overflow a block's counters", cdiv(H, (int)grid.y));
-    if (stats) AMS_CHECK_HIP(hipMemsetAsync(stats, 0, sizeof(int64_t) * kConfStatsLen * B, st));
+    AMS_REQUIRE((int64_t)cdiv(c.H, (int)grid.y) * 256 < (1 << kConfPackBits), "confidence: %d rows per band overflow a block's counters", cdiv(c.H, (int)grid.y));
+    AMS_REQUIRE(c.logits, "confidence: null pointer");
+    if (stats) AMS_CHECK_HIP(hipMemsetAsync(stats, 0, sizeof(int64_t) * kConfStatsLen * c.B, st));
     note_kernel("upsample_confidence_kernel");
-    if (K <= 8)
-        hipLaunchKernelGGL(upsample_confidence_kernel<8>, grid, dim3(256), 0, st, logits, g, ct, teacher, conf_u8, conf_f32, (unsigned long long*)stats);
+    if (c.K <= 8)
+        hipLaunchKernelGGL(upsample_confidence_kernel<8>, grid, dim3(256), 0, st, c.logits, g, ct, c.teacher, conf_u8, conf_f32, (unsigned long long*)stats);
     else
-        hipLaunchKernelGGL(upsample_confidence_kernel<0>, grid, dim3(256), 0, st, logits, g, ct, teacher, conf_u8, conf_f32, (unsigned long long*)stats);
+        hipLaunchKernelGGL(upsample_confidence_kernel<0>, grid, dim3(256), 0, st, c.logits, g, ct, c.teacher, conf_u8, conf_f32, (unsigned long long*)stats);
     AMS_CHECK_LAUNCH();
     return AMS_OK;
 }

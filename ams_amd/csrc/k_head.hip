@@ -107,27 +107,26 @@ __global__ __launch_bounds__(256) void upsample_argmax_kernel(const float* __res
     }
 }
 
-// cls: HOST pointer to the K selected class ids (they travel to the kernel by value)
-int launch_upsample_argmax(const float* logits, int ld, int B, int h, int w, const int32_t* cls, int K, int H, int W,
-                           const uint8_t* teacher, int NC, int32_t* labels, int64_t* conf, double* loss, hipStream_t st, int per_frame, int labels_u8) {
+// per_frame != 0: conf [B][K][K] and loss [B][2] instead of the batch totals; labels_u8 != 0: labels as uint8 [B][H][W] through the same pointer
+int launch_upsample_argmax(const HeadCall& c, int32_t* labels, int64_t* conf, double* loss, hipStream_t st, int per_frame, int labels_u8) {
     ClassTable ct;
-    int rc = fill_class_table(cls, K, NC, &ct);
-    if (rc) return rc;
-    AMS_REQUIRE(teacher == nullptr || (conf != nullptr && loss != nullptr), "head: metrics need conf and loss buffers");
-    const int nm = per_frame ? B : 1;
-    if (teacher) {
-        AMS_CHECK_HIP(hipMemsetAsync(conf, 0, sizeof(int64_t) * K * K * nm, st));
+    HeadGeom g;
+    if (int rc = head_call_check("upsample_argmax", c, &ct, &g)) return rc;
+    AMS_REQUIRE(c.teacher == nullptr || (conf != nullptr && loss != nullptr), "upsample_argmax: metrics need conf and loss buffers");
+    AMS_REQUIRE(c.logits, "upsample_argmax: null pointer");
+    const int nm = per_frame ? c.B : 1;
+    if (c.teacher) {
+        AMS_CHECK_HIP(hipMemsetAsync(conf, 0, sizeof(int64_t) * c.K * c.K * nm, st));
         AMS_CHECK_HIP(hipMemsetAsync(loss, 0, sizeof(double) * 2 * nm, st));
     }
-    HeadGeom g = head_geom(ld, B, h, w, K, H, W, NC);
     g.per_frame = per_frame;
     g.labels_u8 = labels_u8;
     note_kernel("upsample_argmax_kernel");
-    const dim3 grid = head_band_grid(B, H, W);      // bands of consecutive rows per block
-    if (K <= 8)
-        hipLaunchKernelGGL(upsample_argmax_kernel<8>, grid, dim3(256), 0, st, logits, g, ct, teacher, labels, (unsigned long long*)conf, loss);
+    const dim3 grid = head_band_grid(c.B, c.H, c.W);      // bands of consecutive rows per block
+    if (c.K <= 8)
+        hipLaunchKernelGGL(upsample_argmax_kernel<8>, grid, dim3(256), 0, st, c.logits, g, ct, c.teacher, labels, (unsigned long long*)conf, loss);
     else
-        hipLaunchKernelGGL(upsample_argmax_kernel<0>, grid, dim3(256), 0, st, logits, g, ct, teacher, labels, (unsigned long long*)conf, loss);
+        hipLaunchKernelGGL(upsample_argmax_kernel<0>, grid, dim3(256), 0, st, c.logits, g, ct, c.teacher, labels, (unsigned long long*)conf, loss);
     AMS_CHECK_LAUNCH();
     return AMS_OK;
 }
@@ -213,22 +212,20 @@ __global__ __launch_bounds__(256) void ce_grad_kernel(const float* __restrict__ 
     }
 }
 
-int launch_ce_grad(const float* logits, int ld, int B, int h, int w, const int32_t* cls, int K, int H, int W,
-                   const uint8_t* teacher, int NC, const double* loss_and_count, float* dlogits, int ldd, hipStream_t st, float empty_val) {
+int launch_ce_grad(const HeadCall& c, const double* loss_and_count, float* dlogits, int ldd, hipStream_t st, float empty_val) {
     ClassTable ct;
-    int rc = fill_class_table(cls, K, NC, &ct);
-    if (rc) return rc;
-    AMS_REQUIRE(teacher && loss_and_count && dlogits, "ce_grad: null pointer");
-    AMS_REQUIRE(ldd >= NC && ldd <= 256, "ce_grad: ldd=%d must hold %d classes", ldd, NC);
-    const HeadGeom g = head_geom(ld, B, h, w, K, H, W, NC);
-    const dim3 grid(w, h, B);
-    note_kernel(K <= 8 ? "ce_grad_kernel<8>" : K <= 20 ? "ce_grad_kernel<20>" : "ce_grad_kernel<32>");
-    if (K <= 8)
-        hipLaunchKernelGGL(ce_grad_kernel<8>, grid, dim3(256), 0, st, logits, g, ct, teacher, loss_and_count, dlogits, ldd, empty_val);
-    else if (K <= 20)
-        hipLaunchKernelGGL(ce_grad_kernel<20>, grid, dim3(256), 0, st, logits, g, ct, teacher, loss_and_count, dlogits, ldd, empty_val);
+    HeadGeom g;
+    if (int rc = head_call_check("ce_grad", c, &ct, &g)) return rc;
+    AMS_REQUIRE(ldd >= c.NC && ldd <= 256, "ce_grad: ldd=%d must hold %d classes", ldd, c.NC);
+    AMS_REQUIRE(c.logits && c.teacher && loss_and_count && dlogits, "ce_grad: null pointer");
+    const dim3 grid(c.w, c.h, c.B);
+    note_kernel(c.K <= 8 ? "ce_grad_kernel<8>" : c.K <= 20 ? "ce_grad_kernel<20>" : "ce_grad_kernel<32>");
+    if (c.K <= 8)
+        hipLaunchKernelGGL(ce_grad_kernel<8>, grid, dim3(256), 0, st, c.logits, g, ct, c.teacher, loss_and_count, dlogits, ldd, empty_val);
+    else if (c.K <= 20)
+        hipLaunchKernelGGL(ce_grad_kernel<20>, grid, dim3(256), 0, st, c.logits, g, ct, c.teacher, loss_and_count, dlogits, ldd, empty_val);
     else
-        hipLaunchKernelGGL(ce_grad_kernel<32>, grid, dim3(256), 0, st, logits, g, ct, teacher, loss_and_count, dlogits, ldd, empty_val);
+        hipLaunchKernelGGL(ce_grad_kernel<32>, grid, dim3(256), 0, st, c.logits, g, ct, c.teacher, loss_and_count, dlogits, ldd, empty_val);
     AMS_CHECK_LAUNCH();
     return AMS_OK;
 }
@@ -571,10 +568,9 @@ int launch_ce_loss_grad(const HeadCall& c, const LossObjective& o, double* loss,
     if (int rc = loss_weights_check("ce_loss_grad", o.class_weights, c.K, c.K, o.conf_gamma)) return rc;
     AMS_REQUIRE(o.conf_gamma == 0.f || o.teacher_logits, "ce_loss_grad: conf_gamma %g weights by the teacher's confidence: it needs teacher logits", (double)o.conf_gamma);
     ClassTable ct;
-    int rc = fill_class_table(c.cls, c.K, c.NC, &ct);
-    if (rc) return rc;
-    AMS_REQUIRE(c.teacher && loss && scratch, "ce_loss_grad: null pointer");
-    const HeadGeom g = head_geom(c.ld, c.B, c.h, c.w, c.K, c.H, c.W, c.NC);
+    HeadGeom g;
+    if (int rc = head_call_check("ce_loss_grad", c, &ct, &g)) return rc;
+    AMS_REQUIRE(c.logits && c.teacher && loss && scratch, "ce_loss_grad: null pointer");
     AMS_REQUIRE(ce_loss_grad_supported(c.w, c.W), "ce_loss_grad: %d output columns on %d source columns do not fit a block", c.W, c.w);
     const int KM = ce_kmax(c.K);
     const size_t planes = (size_t)2 * c.B * c.h * c.w * KM;
@@ -624,11 +620,12 @@ int launch_ce_loss_grad(const HeadCall& c, const LossObjective& o, double* loss,
     return AMS_OK;
 }
 
-// pass 2 (after the valid-pixel count is final, i.e. after its cross-rank sum in a data-parallel step); of c, the cells and the class list count
+// pass 2 (after the valid-pixel count is final, i.e. after its cross-rank sum in a data-parallel step); c is checked whole (head_call_check), the
+// cells and the class list are what the launch reads
 int launch_ce_combine(const HeadCall& c, const double* loss_and_count, const float* scratch, float* dlogits, int ldd, hipStream_t st, float empty_val) {
     ClassTable ct;
-    int rc = fill_class_table(c.cls, c.K, c.NC, &ct);
-    if (rc) return rc;
+    HeadGeom g;
+    if (int rc = head_call_check("ce_combine", c, &ct, &g)) return rc;
     AMS_REQUIRE(ldd >= c.NC && ldd <= 256, "ce_combine: ldd=%d must hold %d classes", ldd, c.NC);
     const int KM = ce_kmax(c.K);
     const int64_t cells = (int64_t)c.B * c.h * c.w;

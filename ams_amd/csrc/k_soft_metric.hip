@@ -182,26 +182,24 @@ __global__ __launch_bounds__(256) void upsample_soft_metric_kernel(const float* 
     }
 }
 
-// cls: HOST pointer to the K selected class ids.  Every output pointer may be null: nothing is written there.  A refused call writes nothing.
-int launch_upsample_soft_metric(const float* logits, int ld, int B, int h, int w, const int32_t* cls, int K, int H, int W, const uint8_t* teacher,
-                                int NC, const float* teacher_logits, int th, int tw, int64_t* stats, float* p_f32, float* ce_f32, hipStream_t st, int layout) {
+// o: the teacher logits, their grid and their layout (nothing else of it is read).  Every output pointer may be null: nothing is written there.
+// A refused call writes nothing.
+int launch_upsample_soft_metric(const HeadCall& c, const LossObjective& o, int64_t* stats, float* p_f32, float* ce_f32, hipStream_t st) {
     ClassTable ct;
-    int rc = fill_class_table(cls, K, NC, &ct);
-    if (rc) return rc;
-    AMS_REQUIRE(logits && teacher_logits && B > 0 && h > 0 && w > 0 && H > 0 && W > 0, "soft_metric: B=%d, %d x %d -> %d x %d", B, h, w, H, W);
-    AMS_REQUIRE(ld >= NC, "soft_metric: row stride %d below %d classes", ld, NC);
-    AMS_REQUIRE(tlogits_layout_ok(layout), "soft_metric: unknown teacher-logit layout %d", layout);
-    AMS_REQUIRE(th >= 1 && tw >= 1 && th <= H && tw <= W, "soft_metric: teacher logits of %d x %d for labels of %d x %d", th, tw, H, W);
-    const HeadGeom g = head_geom(ld, B, h, w, K, H, W, NC);
-    const dim3 grid = head_band_grid(B, H, W);
-    AMS_REQUIRE(cdiv(H, (int)grid.y) <= kSoftMaxBandRows, "soft_metric: %d rows per band overflow a thread's column sums", cdiv(H, (int)grid.y));
-    const SoftTeacher sft = soft_teacher_geom(teacher_logits, th, tw, layout, ct, K, NC, H, W);
-    if (stats) AMS_CHECK_HIP(hipMemsetAsync(stats, 0, sizeof(int64_t) * soft_metric_stats_len(K) * B, st));
+    HeadGeom g;
+    if (int rc = head_call_check("soft_metric", c, &ct, &g)) return rc;
+    AMS_REQUIRE(tlogits_layout_ok(o.layout), "soft_metric: unknown teacher-logit layout %d", o.layout);
+    AMS_REQUIRE(o.th >= 1 && o.tw >= 1 && o.th <= c.H && o.tw <= c.W, "soft_metric: teacher logits of %d x %d for labels of %d x %d", o.th, o.tw, c.H, c.W);
+    const dim3 grid = head_band_grid(c.B, c.H, c.W);
+    AMS_REQUIRE(cdiv(c.H, (int)grid.y) <= kSoftMaxBandRows, "soft_metric: %d rows per band overflow a thread's column sums", cdiv(c.H, (int)grid.y));
+    AMS_REQUIRE(c.logits && o.teacher_logits, "soft_metric: null pointer");
+    const SoftTeacher sft = soft_teacher_geom(o.teacher_logits, o.th, o.tw, o.layout, ct, c.K, c.NC, c.H, c.W);
+    if (stats) AMS_CHECK_HIP(hipMemsetAsync(stats, 0, sizeof(int64_t) * soft_metric_stats_len(c.K) * c.B, st));
     note_kernel("upsample_soft_metric_kernel");
-    if (K <= 8)
-        hipLaunchKernelGGL(upsample_soft_metric_kernel<8>, grid, dim3(256), 0, st, logits, g, ct, teacher, sft, (unsigned long long*)stats, p_f32, ce_f32);
+    if (c.K <= 8)
+        hipLaunchKernelGGL(upsample_soft_metric_kernel<8>, grid, dim3(256), 0, st, c.logits, g, ct, c.teacher, sft, (unsigned long long*)stats, p_f32, ce_f32);
     else
-        hipLaunchKernelGGL(upsample_soft_metric_kernel<0>, grid, dim3(256), 0, st, logits, g, ct, teacher, sft, (unsigned long long*)stats, p_f32, ce_f32);
+        hipLaunchKernelGGL(upsample_soft_metric_kernel<0>, grid, dim3(256), 0, st, c.logits, g, ct, c.teacher, sft, (unsigned long long*)stats, p_f32, ce_f32);
     AMS_CHECK_LAUNCH();
     return AMS_OK;
 }

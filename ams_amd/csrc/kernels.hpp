@@ -372,19 +372,18 @@ int launch_encode_delta(const uint8_t* mask, const int64_t* table_dev, int n_var
                         int64_t* work, uint8_t* payload, int64_t cap, int64_t* payload_bytes, hipStream_t st);
 
 // ---- k_head.hip : fused upsample + argmax + metrics, CE gradient, phi-score confusion --------------------
+// what is computed on which tensors: HeadCall and LossObjective, head_common.hpp.  Every launcher below that takes a HeadCall goes through
+// head_call_check first (one order of refusal), then its own conditions, then the null checks of what it reads
+struct HeadCall;
+struct LossObjective;
 // per_frame != 0: conf [B][K][K] and loss [B][2] (one confusion matrix / loss pair per frame) instead of the batch totals
-int launch_upsample_argmax(const float* logits, int ld, int B, int h, int w, const int32_t* cls, int K, int H, int W,
-                           const uint8_t* teacher, int NC, int32_t* labels, int64_t* conf, double* loss, hipStream_t st, int per_frame = 0,
+int launch_upsample_argmax(const HeadCall& c, int32_t* labels, int64_t* conf, double* loss, hipStream_t st, int per_frame = 0,
                            int labels_u8 = 0 /* labels as uint8 [B][H][W] through the same pointer */);
-int launch_ce_grad(const float* logits, int ld, int B, int h, int w, const int32_t* cls, int K, int H, int W,
-                   const uint8_t* teacher, int NC, const double* loss_and_count, float* dlogits, int ldd, hipStream_t st, float empty_val = 0.f);
+int launch_ce_grad(const HeadCall& c, const double* loss_and_count, float* dlogits, int ldd, hipStream_t st, float empty_val = 0.f);
 // loss + gradient in one pass (fine-tune step): pass 1 leaves the CE sum / valid count in loss[2] and the unnormalised gradient in
 // scratch (ce_loss_grad_scratch floats); pass 2 scales by 1 / count (after its cross-rank sum) and writes dlogits [B*h*w, ldd]
 bool ce_loss_grad_supported(int w, int W);
 size_t ce_loss_grad_scratch(int B, int h, int w, int K);
-// what is computed on which tensors: HeadCall and LossObjective, head_common.hpp
-struct HeadCall;
-struct LossObjective;
 int launch_ce_loss_grad(const HeadCall& c, const LossObjective& o, double* loss, float* scratch, hipStream_t st);
 // empty_val: every selected class's gradient when NO pixel of the (global) batch is valid: 0, or NaN = the reference's 0 / 0
 // (utils/graph_utils.py:408: loss = sum(w ce) / sum(w))
@@ -403,16 +402,13 @@ int launch_cross_confusion(const uint8_t* a, const uint8_t* b, int64_t n, const 
 // ---- k_confidence.hip : the student's per-pixel certainty (max softmax) and its statistics, the same walk as upsample_argmax ----
 // conf_u8 [B][H][W], conf_f32 [B][H][W], stats [B][confidence_stats_len()] (layout: include/ams_hip.h); each may be null
 int confidence_stats_len();
-int launch_upsample_confidence(const float* logits, int ld, int B, int h, int w, const int32_t* cls, int K, int H, int W, const uint8_t* teacher,
-                               int NC, uint8_t* conf_u8, float* conf_f32, int64_t* stats, hipStream_t st);
+int launch_upsample_confidence(const HeadCall& c, uint8_t* conf_u8, float* conf_f32, int64_t* stats, hipStream_t st);
 
 // ---- k_soft_metric.hip : the soft-teacher loss and the probabilistic confusion matrices (prob_confmat, prob_confmat_star), the same walk ----
-// teacher uint8 [B][H][W] or null (every pixel valid), teacher_logits f32 [B][th][tw][NC] (th <= H, tw <= W); stats [B][soft_metric_stats_len(K)],
-// p_f32 [B][H][W][K], ce_f32 [B][H][W] (layout: include/ams_hip.h); each output may be null
+// c.teacher uint8 [B][H][W] or null (every pixel valid); of o, teacher_logits f32 [B][th][tw][NC] (th <= H, tw <= W; layout AMS_TLOGITS_SELECTED:
+// [B][th][tw][K]); stats [B][soft_metric_stats_len(K)], p_f32 [B][H][W][K], ce_f32 [B][H][W] (layout: include/ams_hip.h); each output may be null
 int soft_metric_stats_len(int K);
-int launch_upsample_soft_metric(const float* logits, int ld, int B, int h, int w, const int32_t* cls, int K, int H, int W, const uint8_t* teacher,
-                                int NC, const float* teacher_logits, int th, int tw, int64_t* stats, float* p_f32, float* ce_f32, hipStream_t st,
-                                int layout = AMS_TLOGITS_FULL /* AMS_TLOGITS_SELECTED: teacher_logits [B][th][tw][K] */);
+int launch_upsample_soft_metric(const HeadCall& c, const LossObjective& o, int64_t* stats, float* p_f32, float* ce_f32, hipStream_t st);
 
 // ---- k_replay.hip : the replay memory on the device: a mini-batch in one launch, cached teacher logits, the phi-score pairs ----
 // samples_host / pairs_host: the host copies of the device tables, checked before anything is launched

@@ -22,10 +22,13 @@ NB = Cf.NB
 NC = 19
 SENTINEL = 0x5A
 
-# (h, w, H, W, classes): the head test's shapes (K <= 8 in registers; 19 classes = the per-pixel path; H, W no multiples of block and band)
-# and one with two column strips, the second ragged
-SHAPES = [(5, 9, 64, 128, [0, 1, 2, 10, 11, 13]), (3, 5, 32, 64, [2, 8, 9, 10, 11, 13]), (9, 17, 128, 256, list(range(19))),
-          (4, 7, 50, 90, [0, 15]), (3, 5, 40, 300, [0, 1, 2, 5, 8, 10, 11, 13])]
+# (h, w, H, W, classes, batch): the head test's shapes (K <= 8 in registers; 19 classes = the per-pixel path; H, W no multiples of block and
+# band) and one with two column strips, the second ragged; then the smallest shapes at which the walk down the columns can go wrong: a
+# second strip that is mostly dead threads with fewer rows than bands, three frames, in both forms; a scale of 0 on either axis; the identity
+SHAPES = [(5, 9, 64, 128, [0, 1, 2, 10, 11, 13], 2), (3, 5, 32, 64, [2, 8, 9, 10, 11, 13], 2), (9, 17, 128, 256, list(range(19)), 2),
+          (4, 7, 50, 90, [0, 15], 2), (3, 5, 40, 300, [0, 1, 2, 5, 8, 10, 11, 13], 2),
+          (3, 5, 7, 300, [0, 1, 2, 10, 11, 13], 3), (3, 5, 7, 300, list(range(19)), 3), (1, 4, 9, 33, [0, 1, 2, 10, 11, 13], 2),
+          (4, 1, 33, 9, list(range(19)), 2), (5, 9, 5, 9, [0, 15], 2)]
 
 
 @pytest.fixture(scope="module")
@@ -73,11 +76,12 @@ def test_stats_length(lib):
     assert int(lib.ams_confidence_stats_len()) == Cf.STATS_LEN == 4 * NB + 2 * 32 + 1 and hip.CONFIDENCE_BINS == NB
 
 
-@pytest.mark.parametrize("h,w,H,W,cls", SHAPES, ids=lambda v: "x".join(map(str, v)) if isinstance(v, list) else str(v))
-def test_kernel_against_the_reference(lib, h, w, H, W, cls):
+@pytest.mark.parametrize("h,w,H,W,cls,B", SHAPES, ids=["-".join(map(str, s[:4])) + "-" + "x".join(map(str, s[4])) + ("" if s[5] == 2 else "-B%d" % s[5])
+                                                       for s in SHAPES])
+def test_kernel_against_the_reference(lib, h, w, H, W, cls, B):
     """Largest |conf_f32 - f64 reference| seen on MI355X over these shapes: 2.6e-7 (the bound is the head test's 1e-5)."""
-    B, K = 2, len(cls)
-    logits, teacher = _inputs(h, w, H, W)
+    K = len(cls)
+    logits, teacher = _inputs(h, w, H, W, B)
     shape = (B, h, w, H, W)
     ld, td = torch.from_numpy(logits).to(DEV), torch.from_numpy(teacher).to(DEV)
     u8, f32, stats = (t.cpu().numpy() for t in _confidence(lib, ld, shape, cls, td))
@@ -114,7 +118,7 @@ def test_kernel_against_the_reference(lib, h, w, H, W, cls):
 
 
 def test_all_ignored_teacher_and_no_teacher(lib):
-    h, w, H, W, cls = SHAPES[0]
+    h, w, H, W, cls, _ = SHAPES[0]
     logits, _ = _inputs(h, w, H, W)
     ld = torch.from_numpy(logits).to(DEV)
     blank = torch.full((2, H, W), 255, dtype=torch.uint8, device=DEV)
@@ -126,7 +130,7 @@ def test_all_ignored_teacher_and_no_teacher(lib):
 
 
 def test_null_outputs_write_nothing_else(lib):
-    h, w, H, W, cls = SHAPES[3]
+    h, w, H, W, cls, _ = SHAPES[3]
     K, B = len(cls), 2
     logits, teacher = _inputs(h, w, H, W)
     ld, td = torch.from_numpy(logits).to(DEV), torch.from_numpy(teacher).to(DEV)

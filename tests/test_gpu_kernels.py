@@ -922,6 +922,48 @@ def test_upsample_argmax_metrics_and_ce_grad(lib, h, w, H, W, cls):
     assert np.array_equal(d1, outs[1][1])
 
 
+# the smallest shapes at which the walk down the columns can go wrong: a second 256-column strip that is mostly dead threads with
+# fewer rows than bands, three frames, K = 6 (registers) and K = 19 (per pixel); a scale of 0 on either axis; the identity (every t = 0)
+@pytest.mark.parametrize("h,w,H,W,cls,B", [(3, 5, 7, 300, [0, 1, 2, 10, 11, 13], 3), (3, 5, 7, 300, list(range(19)), 3),
+                                           (1, 4, 9, 33, [0, 1, 2, 10, 11, 13], 2), (4, 1, 33, 9, list(range(19)), 2),
+                                           (5, 9, 5, 9, [0, 1, 2, 10, 11, 13], 2), (5, 9, 5, 9, list(range(19)), 2)])
+def test_upsample_argmax_at_the_edges_of_the_walk(lib, h, w, H, W, cls, B):
+    rng = np.random.default_rng(h * w + H)
+    NC, K = 19, len(cls)
+    logits = (rng.standard_normal((B, h, w, NC)) * 2).astype(np.float32)
+    teacher = rng.integers(0, 19, (B, H, W)).astype(np.uint8)
+    teacher[rng.random((B, H, W)) < 0.1] = 255
+    ci = (C.c_int32 * K)(*cls)
+    ld, td = dev(logits), torch.as_tensor(teacher).to(DEV)
+    labels = torch.full((B, H, W), -1, dtype=torch.int32, device=DEV)
+    conf = torch.empty(K * K, dtype=torch.int64, device=DEV)
+    loss = torch.empty(2, dtype=torch.float64, device=DEV)
+    hip.check(lib.ams_k_upsample_argmax(P(ld), B, h, w, NC, ci, K, H, W, P(td), P(labels), P(conf), P(loss), stream()))
+    full = _np_bilinear(logits, H, W)[..., cls]                       # f32, same unfused lerp order as the kernel
+    if (h, w) == (H, W):
+        assert np.array_equal(full, logits[..., cls])                  # the identity: the logits themselves
+    want_lab = np.argmax(full, axis=-1)
+    assert np.array_equal(labels.cpu().numpy(), want_lab)              # bit-exact label map, every pixel written
+    lut = np.full(256, -1)
+    lut[cls] = np.arange(K)
+    tgt = lut[teacher]
+    valid = tgt >= 0
+    cm = np.zeros((K, K), dtype=np.int64)
+    np.add.at(cm, (tgt[valid], want_lab[valid]), 1)
+    assert np.array_equal(conf.cpu().numpy().reshape(K, K), cm)
+    z = full.astype(np.float64)
+    lse = np.log(np.exp(z - z.max(-1, keepdims=True)).sum(-1)) + z.max(-1)
+    pix = lse - np.take_along_axis(z, np.maximum(tgt, 0)[..., None], -1)[..., 0]
+    got = loss.cpu().numpy()
+    assert got[1] == valid.sum() > 0
+    assert got[0] / got[1] == pytest.approx(pix[valid].mean(), rel=1e-5)
+    # a frame alone gives that frame's labels
+    one = torch.full((1, H, W), -1, dtype=torch.int32, device=DEV)
+    last = ld[B - 1:].contiguous()
+    hip.check(lib.ams_k_upsample_argmax(P(last), 1, h, w, NC, ci, K, H, W, None, P(one), None, None, stream()))
+    assert torch.equal(one[0], labels[B - 1])
+
+
 def test_upsample_all_ignored_gives_zero_count(lib):
     B, h, w, H, W, NC = 1, 3, 5, 32, 64, 19
     cls = [0, 1]

@@ -25,6 +25,13 @@ CASES = [
     (5, 9, 64, 128, list(range(19)), 19, 2, (9, 17), True),                      # the KMAX = 0 form; two rows per band, a third grid
     (2, 3, 17, 40, [0, 1, 2, 5, 8, 10, 11, 13], 19, 1, None, True),              # the edge of the register form
     (3, 5, 33, 65, list(range(32)), 32, 1, None, True),
+    # the smallest shapes at which the walk down the columns can go wrong: a second column strip that is mostly dead threads with fewer rows
+    # than bands, three frames, in both forms; a scale of 0 on either axis; the identity
+    (3, 5, 7, 300, CI6, 19, 3, None, True), (3, 5, 7, 300, list(range(19)), 19, 3, (3, 5), True),
+    (1, 4, 9, 33, CI6, 19, 1, None, True), (4, 1, 33, 9, list(range(19)), 19, 1, (4, 1), True), (5, 9, 5, 9, CI6, 19, 1, None, True),
+    # a tenth field: the row stride of the student's logits, fed through ams_k_upsample_soft_metric_layout (32 = the student's own: its 19
+    # logits lie in rows of 32 floats, the rest filled with a value no output may show), in both forms
+    (5, 9, 64, 128, CI6, 19, 2, None, True, 32), (5, 9, 64, 128, list(range(19)), 19, 2, (9, 17), True, 32),
 ]
 
 
@@ -55,13 +62,22 @@ def _inputs(h, w, H, W, cls, NC, B, grid):
     return logits, tlog, ids
 
 
-def _soft(lib, ld, tld, ids_dev, shape, cls, stats=True, maps=True):
+def _soft(lib, ld, tld, ids_dev, shape, cls, stats=True, maps=True, stride=None):
     B, h, w, H, W = shape
     K = len(cls)
     n = int(lib.ams_soft_metric_stats_len(K))
     out_stats = torch.full((B, n), -1, dtype=torch.int64, device=DEV) if stats else None
     out_p = torch.full((B, H, W, K), -7.0, dtype=torch.float32, device=DEV) if maps else None
     out_ce = torch.full((B, H, W), -7.0, dtype=torch.float32, device=DEV) if maps else None
+    if stride is not None:
+        NC = ld.shape[-1]
+        wide = torch.full((B, h, w, stride), 1e30, dtype=torch.float32, device=DEV)
+        wide[..., :NC] = ld
+        hip.check(lib.ams_k_upsample_soft_metric_layout(P(wide), B, h, w, stride, NC, (C.c_int32 * K)(*cls), K, H, W, P(ids_dev), P(tld), tld.shape[1],
+                                                        tld.shape[2], hip.TLOGITS_FULL, P(out_stats), P(out_p), P(out_ce), stream()),
+                  "ams_k_upsample_soft_metric_layout")
+        torch.cuda.synchronize()
+        return out_stats, out_p, out_ce
     hip.check(lib.ams_k_upsample_soft_metric(P(ld), B, h, w, ld.shape[-1], (C.c_int32 * K)(*cls), K, H, W, P(ids_dev), P(tld), tld.shape[1], tld.shape[2],
                                              P(out_stats), P(out_p), P(out_ce), stream()), "ams_k_upsample_soft_metric")
     return out_stats, out_p, out_ce
@@ -84,17 +100,22 @@ def test_stats_length(lib):
         assert int(lib.ams_soft_metric_stats_len(K)) == SM.stats_len(K) == 2 + 2 * K * K
 
 
-@pytest.mark.parametrize("case", CASES, ids=lambda c: "%dx%d-%dx%d-K%dof%d-B%d-%s-%s" % (c[0], c[1], c[2], c[3], len(c[4]), c[5], c[6],
-                                                                                        "full" if c[7] is None else "%dx%d" % c[7], "ids" if c[8] else "noids"))
+@pytest.mark.parametrize("case", CASES, ids=lambda c: "%dx%d-%dx%d-K%dof%d-B%d-%s-%s%s" % (c[0], c[1], c[2], c[3], len(c[4]), c[5], c[6],
+                                                                                          "full" if c[7] is None else "%dx%d" % c[7], "ids" if c[8] else "noids",
+                                                                                          "-ld%d" % c[9] if len(c) > 9 else ""))
 def test_kernel_against_the_reference_and_its_own_maps(lib, case):
     """Largest |p_f32 - f64| and |ce_f32 - f64| seen on MI355X per shape: DESIGN.md 4.9 (the bound is the head test's 1e-5)."""
-    h, w, H, W, cls, NC, B, grid, with_ids = case
+    h, w, H, W, cls, NC, B, grid, with_ids = case[:9]
+    stride = case[9] if len(case) > 9 else None
     K = len(cls)
     logits, tlog, ids = _inputs(h, w, H, W, cls, NC, B, grid)
     shape = (B, h, w, H, W)
     ld, tld = torch.from_numpy(logits).to(DEV), torch.from_numpy(tlog).to(DEV)
     idd = torch.from_numpy(ids).to(DEV) if with_ids else None
-    stats, p, ce = (t.cpu().numpy() for t in _soft(lib, ld, tld, idd, shape, cls))
+    stats, p, ce = (t.cpu().numpy() for t in _soft(lib, ld, tld, idd, shape, cls, stride=stride))
+    if stride is not None:                                                       # the same bits as from rows of NC floats
+        for got, want in zip((stats, p, ce), _soft(lib, ld, tld, idd, shape, cls)):
+            assert np.array_equal(got, want.cpu().numpy(), equal_nan=True)
     ref, p_ref, ce_ref, arg_ref = SM.soft_metric_reference(logits, tlog, ids if with_ids else None, cls, H, W)
     labels = _labels(lib, ld, shape, cls)[0]
     assert np.array_equal(arg_ref, labels)                                       # the shared arithmetic: the label kernel's argmax, exactly
@@ -116,7 +137,7 @@ def test_kernel_against_the_reference_and_its_own_maps(lib, case):
     if B > 1:
         for b in range(B):
             alone = _soft(lib, ld[b:b + 1].contiguous(), tld[b:b + 1].contiguous(), idd[b:b + 1].contiguous() if with_ids else None,
-                          (1, h, w, H, W), cls, maps=False)[0].cpu().numpy()
+                          (1, h, w, H, W), cls, maps=False, stride=stride)[0].cpu().numpy()
             assert np.array_equal(alone[0], stats[b]), b
 
 
