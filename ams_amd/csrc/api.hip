@@ -776,6 +776,65 @@ int ams_k_block_fused_f16(const float* x, int32_t B, int32_t H, int32_t W, int32
                               scale_p, shift_p, AMS_ACT_NONE, Cout, residual != 0, y, st, nullptr, nullptr, 0, he, pe, hp, pp, kp_p);
 }
 
+// ---- the first block (k_first_block.hip; the tile-per-wave form of k_block.hip).  One check for both entries and the plan query, in the order the
+// header states (has_form / has_panels: whether the entry takes the argument at all)
+static_assert(sizeof(ams_first_block_plan) == sizeof(FirstBlockPlan) && sizeof(FirstBlockPlan) == 15 * sizeof(int32_t), "ams_first_block_plan is FirstBlockPlan, field by field");
+static size_t first_block_scratch(int form) { return form == 1 ? 3 * 32 * 32 : (form == 2 ? 2 * 32 * 32 + 2 * 16 * 32 : 0); }
+static int first_block_call_check(const char* who, int dtype, int B, int H, int W, bool has_form, int form, bool has_panels, const uint16_t* panels,
+                                  size_t panel_elems) {
+    AMS_REQUIRE(dtype == AMS_DT_U8 || dtype == AMS_DT_F32, "%s: frames must be uint8 or float32", who);
+    AMS_REQUIRE(B > 0 && H > 0 && W > 0, "%s: no pixels: B=%d, %d x %d", who, B, H, W);
+    AMS_REQUIRE(!has_form || (form >= 0 && form <= 2), "%s: unknown form %d", who, form);
+    AMS_REQUIRE(!has_panels || form == 0 || (panels && panel_elems >= first_block_scratch(form)), "%s: panel scratch too small (need %zu)", who,
+                first_block_scratch(form));
+    return AMS_OK;
+}
+
+size_t ams_k_first_block_scratch(int32_t form) { return first_block_scratch(form); }
+
+int ams_k_first_block_plan(int32_t frames_dtype, int32_t B, int32_t H, int32_t W, int32_t form, const int32_t* occupancy, ams_first_block_plan* plan_out) {
+    RUN(first_block_call_check("first_block_plan", frames_dtype, B, H, W, true, form, false, nullptr, 0));
+    AMS_REQUIRE(!occupancy || (occupancy[0] > 0 && occupancy[1] > 0 && occupancy[2] > 0), "first_block_plan: occupancy figures must be positive");
+    AMS_REQUIRE(plan_out, "first_block_plan: null pointer");
+    FirstBlockPlan p;
+    RUN(first_block_plan(frames_dtype, B, H, W, form == 2, occupancy, &p));
+    memcpy(plan_out, &p, sizeof(p));
+    return AMS_OK;
+}
+
+int ams_k_first_block(const void* frames, int32_t frames_dtype, int32_t B, int32_t H, int32_t W, float pixel_scale, const float* w_stem,
+                      const float* scale_s, const float* shift_s, const float* w_dw, const float* scale_d, const float* shift_d, const float* w_proj,
+                      const float* scale_p, const float* shift_p, float* y, int32_t form, uint16_t* panels, size_t panel_elems,
+                      ams_first_block_plan* plan_out, void* stream) {
+    RUN(first_block_call_check("first_block", frames_dtype, B, H, W, true, form, true, panels, panel_elems));
+    AMS_REQUIRE(frames && w_stem && scale_s && shift_s && w_dw && scale_d && shift_d && w_proj && scale_p && shift_p && y, "first_block: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t ps = 32 * 32, pj = 16 * 32;       // planes of the stem's [32 channels][32 k] and the project layer's [16][32] panels
+    const uint16_t *w3 = nullptr, *hs = nullptr, *hj = nullptr;
+    if (form == 1) {                                // as ams_student_freeze for layer 1: [27][32] -> three bf16 parts [32][32], k = tap * 3 + channel
+        RUN(launch_split_weights3(w_stem, 32, 1, 27, 32, 32, panels, panels + ps, panels + 2 * ps, st));
+        w3 = panels;
+    } else if (form == 2) {                         // ... and for layers 1 and 3: two fp16 parts each
+        RUN(launch_split_weights_f16(w_stem, 32, 1, 27, 32, 32, panels, panels + ps, st));
+        RUN(launch_split_weights_f16(w_proj, 16, 1, 32, 16, 32, panels + 2 * ps, panels + 2 * ps + pj, st));
+        hs = panels; hj = panels + 2 * ps;
+    }
+    FirstBlockPlan p;
+    RUN(launch_first_block(frames, frames_dtype, B, H, W, pixel_scale, w_stem, scale_s, shift_s, AMS_ACT_RELU6, w_dw, scale_d, shift_d, AMS_ACT_RELU6,
+                           w_proj, scale_p, shift_p, AMS_ACT_NONE, y, st, w3, ps, hs, ps, hj, pj, &p));
+    if (plan_out) memcpy(plan_out, &p, sizeof(p));
+    return AMS_OK;
+}
+
+int ams_k_first_block_tiles(const void* frames, int32_t frames_dtype, int32_t B, int32_t H, int32_t W, float pixel_scale, const float* w_stem,
+                            const float* scale_s, const float* shift_s, const float* w_dw, const float* scale_d, const float* shift_d,
+                            const float* w_proj, const float* scale_p, const float* shift_p, float* y, void* stream) {
+    RUN(first_block_call_check("first_block_tiles", frames_dtype, B, H, W, false, 0, false, nullptr, 0));
+    AMS_REQUIRE(frames && w_stem && scale_s && shift_s && w_dw && scale_d && shift_d && w_proj && scale_p && shift_p && y, "first_block_tiles: null pointer");
+    return launch_first_block_tiles(frames, frames_dtype, B, H, W, pixel_scale, w_stem, scale_s, shift_s, AMS_ACT_RELU6, w_dw, scale_d, shift_d, AMS_ACT_RELU6,
+                                    w_proj, scale_p, shift_p, AMS_ACT_NONE, y, (hipStream_t)stream, nullptr);
+}
+
 int ams_k_expand_dw(const float* x, int32_t B, int32_t H, int32_t W, int32_t Cin, const float* w_exp, const float* scale_e,
                     const float* shift_e, int32_t Cexp, const float* w_dw, int32_t stride, int32_t rate, const float* scale_d,
                     const float* shift_d, float* y, void* stream) {

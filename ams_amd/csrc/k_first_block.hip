@@ -735,11 +735,75 @@ __global__ __launch_bounds__(256, BORDER ? 2 : 3) void first_block_walk_kernel(F
     }
 }
 
+// The launch plan of launch_first_block: which tiles the walking kernel takes, which the border launch, and on how many blocks each.
+// Interior tiles (first_block_walk_kernel's header) form a rectangle: the conditions are separate in y and x.
+int first_block_plan(int dtype, int B, int H, int W, bool h16, const int* occupancy, FirstBlockPlan* p) {
+    memset(p, 0, sizeof(*p));
+    same_pad(H + 1, 3, 2, 1, &p->Ho, &p->pt);
+    same_pad(W + 1, 3, 2, 1, &p->Wo, &p->pl);
+    p->tiles_x = cdiv(p->Wo, 16);
+    p->tiles_y = cdiv(p->Ho, 8);
+    const int64_t nblocks = (int64_t)p->tiles_x * p->tiles_y * B;
+    AMS_REQUIRE(nblocks > 0 && nblocks < 0x7fffffffLL, "first_block: bad grid");
+    p->border_tiles = p->border_grid = (int)nblocks;                      // the one-tile kernel on every tile, unless the walk below runs
+    if (!(h16 && dtype == AMS_DT_U8 && knobs().fb_walk != 0 && (int64_t)B * H * W * 3 + 16 < 0x7fffffffLL)) return AMS_OK;
+    auto range = [](int tiles, int T, int Osize, int pad, int Isize, int* first, int* count) {
+        *first = 0; *count = 0;
+        for (int t = 0; t < tiles; ++t) {
+            const int o0 = t * T;
+            const bool in = o0 >= 1 && o0 + T < Osize && (o0 - 1) * 2 - pad >= 0 && (o0 + T) * 2 - pad + 2 <= Isize - 1;
+            if (in) { if (!*count) *first = t; ++*count; }
+        }
+    };
+    range(p->tiles_y, 8, p->Ho, p->pt, H, &p->ity0, &p->niy);
+    range(p->tiles_x, 16, p->Wo, p->pl, W, &p->itx0, &p->nix);
+    // The walking kernel loads a position's taps as 8-byte pieces, and the piece of the third window row (k = 24 .. 31) ends 5 bytes behind the
+    // window.  Everywhere else those bytes are the next pixels of the frame or of the next frame and meet the panels' zero rows; behind the last
+    // pixel of the batch's last frame they are out of the buffer's range, and the range check then zeroes the whole dword, taps 24 .. 26 with it
+    // (one wrong stem position per batch: tests/test_gpu_first_block.py at 34 x 66, where both directions end exactly at the frame's edge).
+    // A last interior tile whose last window ends that close to the frame's end leaves its column of tiles to the border launch, which clamps.
+    if (p->niy > 0 && p->nix > 0) {
+        const int iy0 = (p->ity0 + p->niy) * 8 * 2 - p->pt, ix0 = (p->itx0 + p->nix) * 16 * 2 - p->pl;      // window of its last halo position
+        if (((int64_t)(iy0 + 2) * W + ix0) * 3 + 6 + 8 > (int64_t)H * W * 3) --p->nix;
+    }
+    const int64_t n_in = (int64_t)B * p->niy * p->nix;
+    if (n_in <= 0) return AMS_OK;
+    int per_cu = 1, bper_cu = 1, cus = 256;
+    if (occupancy) { per_cu = occupancy[0]; bper_cu = occupancy[1]; cus = occupancy[2]; }
+    else {
+        RUN_RC(func_blocks_per_cu((const void*)first_block_walk_kernel<0>, 256, 0, &per_cu));
+        RUN_RC(device_cus(&cus));
+    }
+    const int64_t slots = (int64_t)per_cu * cus;
+    int64_t rounds = cdiv(n_in, slots);
+    if (knobs().fb_walk > 0 && rounds > knobs().fb_walk) rounds = knobs().fb_walk;      // AMS_FB_WALK=<n>: at most n tiles per block
+    int64_t grid = cdiv(cdiv(n_in, rounds), 8) * 8;           // equal shares; a multiple of 8: a block's tiles stay on its XCD's share
+    if (grid > n_in) grid = n_in;
+    p->interior_tiles = (int)n_in; p->interior_grid = (int)grid;
+    const int64_t n_border = nblocks - n_in;
+    p->border_tiles = p->border_grid = (int)n_border;
+    if (n_border > 0 && knobs().fb_walk != -2) {              // AMS_FB_WALK=-2: the border tiles on the one-tile kernel (A/B of the two border forms)
+        if (!occupancy) RUN_RC(func_blocks_per_cu((const void*)first_block_walk_kernel<0, true>, 256, 0, &bper_cu));
+        const int64_t bslots = (int64_t)bper_cu * cus;
+        int64_t brounds = cdiv(n_border, bslots);
+        if (knobs().fb_walk > 0 && brounds > knobs().fb_walk) brounds = knobs().fb_walk;
+        int64_t bgrid = cdiv(cdiv(n_border, brounds), 8) * 8;
+        if (bgrid > n_border) bgrid = n_border;
+        p->border_grid = (int)bgrid;
+        p->border_walks = 1;
+    }
+    return AMS_OK;
+}
+
 int launch_first_block(const void* frames, int dtype, int B, int H, int W, float pixel_scale, const float* w_stem,
                        const float* sc_s, const float* sh_s, int act_s, const float* w_dw, const float* sc_d, const float* sh_d,
                        int act_d, const float* w_pj, const float* sc_p, const float* sh_p, int act_p, float* y, hipStream_t st,
-                       const uint16_t* w_parts, int64_t w_plane, const uint16_t* h_stem, int64_t h_stem_plane, const uint16_t* h_pj, int64_t h_pj_plane) {
+                       const uint16_t* w_parts, int64_t w_plane, const uint16_t* h_stem, int64_t h_stem_plane, const uint16_t* h_pj, int64_t h_pj_plane,
+                       FirstBlockPlan* plan_out) {
     AMS_REQUIRE(dtype == AMS_DT_U8 || dtype == AMS_DT_F32, "first_block: frames must be uint8 or float32");
+    FirstBlockPlan pl;
+    RUN_RC(first_block_plan(dtype, B, H, W, h_stem && h_pj, nullptr, &pl));
+    if (plan_out) *plan_out = pl;
     FirstBlockArgs a;
     memset(&a, 0, sizeof(a));
     a.frames = frames; a.B = B; a.H = H; a.W = W; a.ps = pixel_scale;
@@ -747,67 +811,35 @@ int launch_first_block(const void* frames, int dtype, int B, int H, int W, float
     a.w_dw = w_dw; a.sc_d = sc_d; a.sh_d = sh_d; a.act_d = act_d;
     a.w_pj = w_pj; a.sc_p = sc_p; a.sh_p = sh_p; a.act_p = act_p; a.y = y;
     a.w_parts = w_parts; a.w_plane = w_plane;
-    same_pad(H + 1, 3, 2, 1, &a.Ho, &a.pt);
-    same_pad(W + 1, 3, 2, 1, &a.Wo, &a.pl);
-    a.tiles_x = cdiv(a.Wo, 16);
-    a.tiles_y = cdiv(a.Ho, 8);
+    a.Ho = pl.Ho; a.Wo = pl.Wo; a.pt = pl.pt; a.pl = pl.pl;
+    a.tiles_x = pl.tiles_x; a.tiles_y = pl.tiles_y;
+    a.ity0 = pl.ity0; a.itx0 = pl.itx0; a.niy = pl.niy; a.nix = pl.nix;
     const int64_t nblocks = (int64_t)a.tiles_x * a.tiles_y * B;
-    AMS_REQUIRE(nblocks > 0 && nblocks < 0x7fffffffLL, "first_block: bad grid");
     if (h_stem && h_pj) {                           // two fp16 parts in the stem and the project layer (takes precedence over w_parts)
         a.hs = h_stem; a.hs_plane = h_stem_plane; a.hj = h_pj; a.hj_plane = h_pj_plane;
-        if (dtype == AMS_DT_U8 && knobs().fb_walk != 0 && (int64_t)B * H * W * 3 + 16 < 0x7fffffffLL) {
-            // interior tiles (first_block_walk_kernel's header) form a rectangle: the conditions are separate in y and x
-            auto range = [](int tiles, int T, int Osize, int pad, int Isize, int* first, int* count) {
-                *first = 0; *count = 0;
-                for (int t = 0; t < tiles; ++t) {
-                    const int o0 = t * T;
-                    const bool in = o0 >= 1 && o0 + T < Osize && (o0 - 1) * 2 - pad >= 0 && (o0 + T) * 2 - pad + 2 <= Isize - 1;
-                    if (in) { if (!*count) *first = t; ++*count; }
-                }
-            };
-            range(a.tiles_y, 8, a.Ho, a.pt, H, &a.ity0, &a.niy);
-            range(a.tiles_x, 16, a.Wo, a.pl, W, &a.itx0, &a.nix);
-            const int64_t n_in = (int64_t)B * a.niy * a.nix;
-            if (n_in > 0) {
-                int per_cu = 1, cus = 256;
-                RUN_RC(func_blocks_per_cu((const void*)first_block_walk_kernel<0>, 256, 0, &per_cu));
-                RUN_RC(device_cus(&cus));
-                const int64_t slots = (int64_t)per_cu * cus;
-                int64_t rounds = cdiv(n_in, slots);
-                if (knobs().fb_walk > 0 && rounds > knobs().fb_walk) rounds = knobs().fb_walk;      // AMS_FB_WALK=<n>: at most n tiles per block
-                int64_t grid = cdiv(cdiv(n_in, rounds), 8) * 8;           // equal shares; a multiple of 8: a block's tiles stay on its XCD's share
-                if (grid > n_in) grid = n_in;
-                note_kernel("first_block_walk_kernel<0>");                // (a profiled launch bracket covers the border launch below as well)
+        if (pl.interior_tiles > 0) {
+            const unsigned grid = (unsigned)pl.interior_grid, n_in = (unsigned)pl.interior_tiles;
+            note_kernel("first_block_walk_kernel<0>");                // (a profiled launch bracket covers the border launch below as well)
 #ifdef AMS_MEASURE
-                switch (knobs().fb_abl) {           // MEASUREMENT BUILD ONLY (libams_hip_measure.so: tools/sweep_fb_abl.sh, tools/fb_phases.py)
-#define FB_A(A_) case A_: hipLaunchKernelGGL(first_block_walk_kernel<A_>, dim3((unsigned)grid), dim3(256), 0, st, a, (unsigned)n_in); break;
-                    FB_A(1) FB_A(2) FB_A(4) FB_A(8) FB_A(16) FB_A(6) FB_A(14) FB_A(30) FB_A(31) FB_A(32) FB_A(33) FB_A(34) FB_A(36) FB_A(40) FB_A(48) FB_A(63)
+            switch (knobs().fb_abl) {           // MEASUREMENT BUILD ONLY (libams_hip_measure.so: tools/sweep_fb_abl.sh, tools/fb_phases.py)
+#define FB_A(A_) case A_: hipLaunchKernelGGL(first_block_walk_kernel<A_>, dim3(grid), dim3(256), 0, st, a, n_in); break;
+                FB_A(1) FB_A(2) FB_A(4) FB_A(8) FB_A(16) FB_A(6) FB_A(14) FB_A(30) FB_A(31) FB_A(32) FB_A(33) FB_A(34) FB_A(36) FB_A(40) FB_A(48) FB_A(63)
 #undef FB_A
-                    default: hipLaunchKernelGGL(first_block_walk_kernel<0>, dim3((unsigned)grid), dim3(256), 0, st, a, (unsigned)n_in);
-                }
-#else
-                hipLaunchKernelGGL(first_block_walk_kernel<0>, dim3((unsigned)grid), dim3(256), 0, st, a, (unsigned)n_in);
-#endif
-                AMS_CHECK_LAUNCH();
-                const int64_t n_border = nblocks - n_in;
-                if (n_border > 0) {
-                    a.border_only = 1;
-                    if (knobs().fb_walk == -2)          // AMS_FB_WALK=-2: the border tiles on the one-tile kernel (A/B of the two border forms)
-                        hipLaunchKernelGGL((first_block_kernel<uint8_t, false, true>), dim3((unsigned)n_border), dim3(256), 0, st, a, (unsigned)n_border);
-                    else {
-                        int bper_cu = 1;
-                        RUN_RC(func_blocks_per_cu((const void*)first_block_walk_kernel<0, true>, 256, 0, &bper_cu));
-                        const int64_t bslots = (int64_t)bper_cu * cus;
-                        int64_t brounds = cdiv(n_border, bslots);
-                        if (knobs().fb_walk > 0 && brounds > knobs().fb_walk) brounds = knobs().fb_walk;
-                        int64_t bgrid = cdiv(cdiv(n_border, brounds), 8) * 8;
-                        if (bgrid > n_border) bgrid = n_border;
-                        hipLaunchKernelGGL((first_block_walk_kernel<0, true>), dim3((unsigned)bgrid), dim3(256), 0, st, a, (unsigned)n_border);
-                    }
-                    AMS_CHECK_LAUNCH();
-                }
-                return AMS_OK;
+                default: hipLaunchKernelGGL(first_block_walk_kernel<0>, dim3(grid), dim3(256), 0, st, a, n_in);
             }
+#else
+            hipLaunchKernelGGL(first_block_walk_kernel<0>, dim3(grid), dim3(256), 0, st, a, n_in);
+#endif
+            AMS_CHECK_LAUNCH();
+            if (pl.border_tiles > 0) {
+                a.border_only = 1;
+                if (pl.border_walks)
+                    hipLaunchKernelGGL((first_block_walk_kernel<0, true>), dim3((unsigned)pl.border_grid), dim3(256), 0, st, a, (unsigned)pl.border_tiles);
+                else
+                    hipLaunchKernelGGL((first_block_kernel<uint8_t, false, true>), dim3((unsigned)pl.border_grid), dim3(256), 0, st, a, (unsigned)pl.border_tiles);
+                AMS_CHECK_LAUNCH();
+            }
+            return AMS_OK;
         }
         note_kernel(dtype == AMS_DT_U8 ? "first_block_kernel<unsigned char, false, true>" : "first_block_kernel<float, false, true>");
         if (dtype == AMS_DT_U8) hipLaunchKernelGGL((first_block_kernel<uint8_t, false, true>), dim3((unsigned)nblocks), dim3(256), 0, st, a, (unsigned)nblocks);

@@ -161,11 +161,25 @@ size_t pointwise_wgrad_scratch(int64_t M, int K, int N);
 int launch_pointwise_wgrad(const WgArgs& a, hipStream_t st);
 
 // ---- k_first_block.hip : stem + depthwise + project of the first block in one kernel (frozen inference; 3 -> 32 -> 32 -> 16)
+// What launch_first_block launches for a batch (ams_first_block_plan of include/ams_hip.h is this, field by field): the output grid and its
+// 8 x 16 tiles, the rectangle of interior tiles, and the tiles and blocks of the two launches.  interior_tiles = 0: the walking form does not
+// run, and the border launch is the one-tile kernel over every tile.
+struct FirstBlockPlan {
+    int Ho, Wo, pt, pl;                     // stem output size and its SAME padding on the 127.5-padded frame
+    int tiles_y, tiles_x;
+    int ity0, itx0, niy, nix;               // interior tiles [ity0, ity0 + niy) x [itx0, itx0 + nix); niy * nix = 0: none
+    int interior_tiles, interior_grid;      // first_block_walk_kernel<0>: tiles over the batch, blocks
+    int border_tiles, border_grid;          // every other tile: tiles over the batch, blocks
+    int border_walks;                       // 1: the border launch is first_block_walk_kernel<0, true>, 0: first_block_kernel (a tile per block)
+};
+// occupancy: null = ask the device (blocks per CU of the two walking kernels, CUs); else {interior blocks per CU, border blocks per CU, CUs}:
+// pure host arithmetic, no device call
+int first_block_plan(int dtype, int B, int H, int W, bool h16, const int* occupancy, FirstBlockPlan* plan);
 int launch_first_block(const void* frames, int dtype, int B, int H, int W, float pixel_scale, const float* w_stem,
                        const float* sc_s, const float* sh_s, int act_s, const float* w_dw, const float* sc_d, const float* sh_d,
                        int act_d, const float* w_pj, const float* sc_p, const float* sh_p, int act_p, float* y, hipStream_t st,
                        const uint16_t* w_parts = nullptr, int64_t w_plane = 0, const uint16_t* h_stem = nullptr, int64_t h_stem_plane = 0,
-                       const uint16_t* h_pj = nullptr, int64_t h_pj_plane = 0);
+                       const uint16_t* h_pj = nullptr, int64_t h_pj_plane = 0, FirstBlockPlan* plan_out = nullptr);
 // h_stem / h_pj: optional fp16 panels (hi | lo 2^11) of the stem [part][32][32] and of the project layer [part][16][32]: with both, the stem's and
 // the project layer's products run as 3 fp16 MFMAs each (AMS_MATMUL_SPLIT_F16; takes precedence over w_parts)
 // w_parts: optional three-part bf16 panels [part][32][32] of the stem weights (k = tap * 3 + channel, zero-padded 27 -> 32): with them and

@@ -79,6 +79,12 @@ class RenderOut(C.Structure):
                 ("ignore_mask", C.c_void_p), ("cross_mask", C.c_void_p)]
 
 
+class FirstBlockPlan(C.Structure):
+    """ams_first_block_plan: what ams_k_first_block launched (or ams_k_first_block_plan says it would)."""
+    _fields_ = [(n, C.c_int32) for n in ("out_h", "out_w", "pad_top", "pad_left", "tiles_y", "tiles_x", "ity0", "itx0", "niy", "nix",
+                                         "interior_tiles", "interior_grid", "border_tiles", "border_grid", "border_walks")]
+
+
 RENDER_VIEWS = tuple(f[0] for f in RenderOut._fields_)
 RENDER_TABLE_BYTES = 1120
 CONFIDENCE_BINS = 32          # AMS_CONFIDENCE_BINS
@@ -161,6 +167,11 @@ SIGNATURES = {
     "ams_k_dw_project": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ams_k_block_fused": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _sz, _vp]),
     "ams_k_block_fused_f16": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _sz, _vp]),
+    "ams_k_first_block_scratch": (_sz, [_i32]),
+    "ams_k_first_block": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _sz,
+                                    C.POINTER(FirstBlockPlan), _vp]),
+    "ams_k_first_block_tiles": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ams_k_first_block_plan": (C.c_int, [_i32, _i32, _i32, _i32, _i32, C.POINTER(_i32), C.POINTER(FirstBlockPlan)]),
     "ams_k_expand_dw": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ams_k_expand_dw_stream": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _sz, _i32, _i32, _vp]),
     "ams_k_global_mean": (C.c_int, [_vp, _i32, _i64, _i32, _vp, _vp, _sz, _vp]),

@@ -760,6 +760,37 @@ int ams_k_dw_project(const float* e, int32_t B, int32_t H, int32_t W, int32_t C,
                      const float* scale_d, const float* shift_d, const float* w_proj, int32_t N, const float* scale_p,
                      const float* shift_p, const float* res, float* y, uint16_t* panels, size_t panel_elems, void* stream);
 
+/* The first block of the frozen path in one kernel (k_first_block.hip): frames [B,H,W,3] (frames_dtype AMS_DT_U8 | AMS_DT_F32) -> one row and one
+ * column of 127.5 -> x * pixel_scale - 1 -> stem 3x3 s2 (w_stem [3,3,3,32]) + BN + ReLU6 -> depthwise 3x3 (w_dw [3,3,32,1]) + BN + ReLU6 -> project
+ * 1x1 (w_proj [32,16]) + BN = y [B, ceil((H+1)/2), ceil((W+1)/2), 16].  form 0: exact f32 products, the same bits as ams_k_stem_conv ->
+ * ams_k_depthwise3x3 -> ams_k_pointwise; 1: the stem's products on three bf16 parts (six MFMAs); 2: the stem's and the project layer's on two fp16
+ * parts (three MFMAs each; what the engine runs by default: uint8 frames walk the interior tiles, see ams_first_block_plan).  panels: scratch of
+ * >= ams_k_first_block_scratch(form) uint16, into which the entry splits the weights as ams_student_freeze does (unused, may be NULL, for form 0).
+ * plan_out (optional): what was launched.  Refused with AMS_E_INVALID before any launch, in this order: a frames_dtype other than the two; B, H or W
+ * below 1; an unknown form; panels too small; a null pointer. */
+typedef struct ams_first_block_plan {
+    int32_t out_h, out_w, pad_top, pad_left;   /* y's grid; the stem's SAME padding in front of the (H+1) x (W+1) padded frame */
+    int32_t tiles_y, tiles_x;                  /* 8 x 16 output tiles per frame */
+    int32_t ity0, itx0, niy, nix;              /* interior tiles (every stem position of the tile + 1-pixel halo exists, every tap and every byte the
+                                                  walking kernel loads for it lies inside the unpadded frame): rows [ity0, ity0 + niy), columns
+                                                  [itx0, itx0 + nix); niy * nix = 0: none */
+    int32_t interior_tiles, interior_grid;     /* the walking launch: tiles over the batch, blocks (0, 0: not launched) */
+    int32_t border_tiles, border_grid;         /* the launch of all other tiles (with interior_tiles = 0: every tile, one per block) */
+    int32_t border_walks;                      /* 1: that launch is the walking border kernel, 0: the one-tile kernel */
+} ams_first_block_plan;
+size_t ams_k_first_block_scratch(int32_t form);
+int ams_k_first_block(const void* frames, int32_t frames_dtype, int32_t B, int32_t H, int32_t W, float pixel_scale, const float* w_stem,
+                      const float* scale_s, const float* shift_s, const float* w_dw, const float* scale_d, const float* shift_d, const float* w_proj,
+                      const float* scale_p, const float* shift_p, float* y, int32_t form, uint16_t* panels, size_t panel_elems,
+                      ams_first_block_plan* plan_out, void* stream);
+/* The same block as one tile per wave (k_block.hip; exact f32, the same bits as form 0; AMS_OPT_FUSE_FIRST_BLOCK = 2). */
+int ams_k_first_block_tiles(const void* frames, int32_t frames_dtype, int32_t B, int32_t H, int32_t W, float pixel_scale, const float* w_stem,
+                            const float* scale_s, const float* shift_s, const float* w_dw, const float* scale_d, const float* shift_d,
+                            const float* w_proj, const float* scale_p, const float* shift_p, float* y, void* stream);
+/* The plan ams_k_first_block would hand back, without a launch.  occupancy NULL: the blocks per CU of the two walking kernels and the CU count are
+ * asked of the current device; else {interior blocks per CU, border blocks per CU, CUs}: pure host arithmetic, no GPU needed. */
+int ams_k_first_block_plan(int32_t frames_dtype, int32_t B, int32_t H, int32_t W, int32_t form, const int32_t* occupancy, ams_first_block_plan* plan_out);
+
 /* Frame ingest (reference run.py:179-183, :415-421: cv2.resize of the decoded frame to [H, 2H] + BGR->RGB; INTER_NEAREST for
  * the teacher label map).  src [Hs,Ws,C] uint8 -> dst [H,W,C] uint8, both device memory.  mode AMS_RESIZE_NEAREST |
  * AMS_RESIZE_LINEAR (OpenCV's 8-bit fixed-point INTER_LINEAR: 11-bit weights, integer passes, the 2x box-average shortcut; bit-identical
