@@ -699,101 +699,92 @@ int ams_k_pointwise_split_f16(const float* x, int64_t M, int32_t K, const float*
     return launch_pointwise_split_f16(a, panels, (int64_t)plane, Kp, st);
 }
 
-int ams_k_expand_dw_stream_f16(const float* x, int32_t B, int32_t H, int32_t W, int32_t Cin, const float* w_exp, const float* scale_e,
-                               const float* shift_e, int32_t Cexp, const float* w_dw, int32_t rate, const float* scale_d, const float* shift_d,
-                               float* y, uint16_t* panels, size_t panel_elems, int32_t presplit, int32_t y_h2i, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    if (!expand_dw_stream_supported(Cin, Cexp, 1, rate) || Cin < 64) {
-        set_error("expand_dw_stream_f16: unsupported shape Cin=%d Cexp=%d rate=%d", Cin, Cexp, rate);
-        return AMS_E_INVALID;
-    }
-    const size_t plane = (size_t)Cexp * Cin, xplane = (size_t)B * H * W * Cin;
-    AMS_REQUIRE(panels && panel_elems >= 2 * plane + (presplit ? 2 * xplane : 0), "expand_dw_stream_f16: panel scratch too small (need %zu)",
-                2 * plane + (presplit ? 2 * xplane : 0));
-    RUN(launch_split_weights_f16(w_exp, Cexp, 1, Cin, Cexp, Cin, panels, panels + plane, st));
-    const uint16_t* xp = nullptr;
-    if (presplit) {                                // the operand as two fp16 part planes, as a producing GEMM leaves it (PwArgs::ysplit_fmt 1)
-        uint16_t* xq = panels + 2 * plane;
-        RUN(launch_split_weights_f16(x, 1, Cin, Cin, (int)((int64_t)B * H * W), Cin, xq, xq + xplane, st));
-        xp = xq;
-    }
-    if (presplit == 2)
-        return launch_expand_dw_wreg(xp, (int64_t)xplane, B, H, W, Cin, panels, (int64_t)plane, AMS_NP_F16, scale_e, shift_e, AMS_ACT_RELU6, Cexp, w_dw,
-                                     rate, scale_d, shift_d, AMS_ACT_RELU6, y, st, y_h2i ? 1 : 0);
-    return launch_expand_dw_stream(x, xp, (int64_t)xplane, B, H, W, Cin, nullptr, panels, (int64_t)plane, AMS_NP_F16, scale_e, shift_e, AMS_ACT_RELU6,
-                                   Cexp, w_dw, 1, rate, scale_d, shift_d, AMS_ACT_RELU6, y, st, y_h2i ? 1 : 0);
-}
-
 int ams_ingest_resize_u8(const uint8_t* src, int32_t Hs, int32_t Ws, int32_t Cn, int32_t mode, int32_t swap_rb, uint8_t* dst, int32_t H,
                          int32_t W, void* stream) {
     return launch_resize_u8(src, Hs, Ws, Cn, mode, swap_rb, dst, H, W, (hipStream_t)stream);
 }
 
+// ---- the frozen blocks (block_call.hpp).  Each entry fills the description, has it checked whole in front of its first launch (block_call_check, with
+// the entry's name and its scratch), splits the weights into `panels` as ams_student_freeze does and hands the description to the launcher
+static void set_panels(ConvLayer* l, const uint16_t* panels, int64_t plane, int np, int Kp) { l->panels = panels; l->plane = plane; l->np = np; l->Kp = Kp; }
+
 int ams_k_dw_project(const float* e, int32_t B, int32_t H, int32_t W, int32_t Cc, const float* w_dw, int32_t rate, const float* scale_d,
                      const float* shift_d, const float* w_proj, int32_t N, const float* scale_p, const float* shift_p,
                      const float* res, float* y, uint16_t* panels, size_t panel_elems, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    if (!dw_project_supported(Cc, N, 1, rate)) { set_error("dw_project: unsupported shape C=%d N=%d rate=%d", Cc, N, rate); return AMS_E_INVALID; }
-    AMS_REQUIRE(panels && panel_elems >= (size_t)2 * N * Cc, "dw_project: panel scratch too small (need %zu)", (size_t)2 * N * Cc);
-    uint16_t* hi = panels;
-    uint16_t* lo = panels + (size_t)N * Cc;
-    RUN(launch_split_weights(w_proj, N, 1, Cc, N, Cc, hi, lo, st));
-    PwArgs a = pw_args(nullptr, (int64_t)B * H * W, Cc, Cc, w_proj, N, y, N);
-    a.scale = scale_p; a.shift = shift_p; a.act = AMS_ACT_NONE;
-    if (res) { a.res = res; a.ldr = N; }
-    return launch_dw_project(e, B, H, W, Cc, w_dw, rate, scale_d, shift_d, AMS_ACT_RELU6, a, hi, lo, Cc, st);
+    const int64_t plane = (int64_t)N * Cc;
+    BlockCall c;
+    c.x = e; c.B = B; c.H = H; c.W = W; c.Cexp = Cc; c.rate = rate; c.Cout = N; c.residual = res != nullptr; c.res = res; c.y = y;
+    c.dw = ConvLayer{w_dw, scale_d, shift_d, AMS_ACT_RELU6};
+    c.project = ConvLayer{w_proj, scale_p, shift_p, AMS_ACT_NONE, panels, plane, 2, Cc};
+    const EntryScratch sc{panels, panel_elems, (size_t)(2 * plane)};
+    RUN(block_call_check("dw_project", BK_DW_PROJECT, c, &sc));
+    RUN(launch_split_weights(w_proj, N, 1, Cc, N, Cc, panels, panels + plane, st));
+    return launch_dw_project(c, st);
+}
+
+// ams_k_block_fused (exact f32; with panels the expand layer as three bf16 parts [part][Cexp][32]) and ams_k_block_fused_f16 (expand and project
+// layers as two fp16 parts)
+static int block_fused_entry(const char* who, bool f16, const float* x, int32_t B, int32_t H, int32_t W, int32_t Cin, const float* w_exp,
+                             const float* scale_e, const float* shift_e, int32_t Cexp, const float* w_dw, int32_t stride, const float* scale_d,
+                             const float* shift_d, const float* w_proj, int32_t Cout, const float* scale_p, const float* shift_p, int32_t residual,
+                             float* y, uint16_t* panels, size_t panel_elems, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    const int kp_p = (Cexp + 31) / 32 * 32;
+    const int64_t pe = (int64_t)Cexp * 32, pp = (int64_t)Cout * kp_p;
+    BlockCall c;
+    c.x = x; c.B = B; c.H = H; c.W = W; c.Cin = Cin; c.Cexp = Cexp; c.stride = stride; c.Cout = Cout; c.residual = residual != 0; c.y = y;
+    c.expand = ConvLayer{w_exp, scale_e, shift_e, AMS_ACT_RELU6};
+    c.dw = ConvLayer{w_dw, scale_d, shift_d, AMS_ACT_RELU6};
+    c.project = ConvLayer{w_proj, scale_p, shift_p, AMS_ACT_NONE};
+    uint16_t* hp = panels ? panels + 2 * pe : nullptr;
+    if (f16) { set_panels(&c.expand, panels, pe, AMS_NP_F16, 32); set_panels(&c.project, hp, pp, AMS_NP_F16, kp_p); }
+    else if (panels) set_panels(&c.expand, panels, pe, 3, 32);
+    const EntryScratch sc{panels, panel_elems, (size_t)(f16 ? 2 * pe + 2 * pp : panels ? 3 * pe : 0)};
+    RUN(block_call_check(who, BK_WHOLE, c, &sc));
+    if (f16) {
+        RUN(launch_split_weights_f16(w_exp, Cexp, 1, Cin, Cexp, 32, panels, panels + pe, st));
+        RUN(launch_split_weights_f16(w_proj, Cout, 1, Cexp, Cout, kp_p, hp, hp + pp, st));
+    } else if (panels)
+        RUN(launch_split_weights3(w_exp, Cexp, 1, Cin, Cexp, 32, panels, panels + pe, panels + 2 * pe, st));
+    return launch_block_fused(c, st);
 }
 
 int ams_k_block_fused(const float* x, int32_t B, int32_t H, int32_t W, int32_t Cin, const float* w_exp, const float* scale_e, const float* shift_e,
                       int32_t Cexp, const float* w_dw, int32_t stride, const float* scale_d, const float* shift_d, const float* w_proj, int32_t Cout,
                       const float* scale_p, const float* shift_p, int32_t residual, float* y, uint16_t* panels, size_t panel_elems, void* stream) {
-    if (!block_fused_supported(Cin, Cexp, Cout, stride, 1, residual != 0)) { set_error("block_fused: unsupported shape"); return AMS_E_INVALID; }
-    hipStream_t st = (hipStream_t)stream;
-    const uint16_t* wparts = nullptr;
-    const int64_t plane = (int64_t)Cexp * 32;
-    if (panels) {                                  // three-part split of the expand weights into [part][Cexp][32]
-        AMS_REQUIRE(Cin <= 32 && panel_elems >= (size_t)3 * plane, "block_fused: panel scratch too small (need %zu)", (size_t)3 * plane);
-        RUN(launch_split_weights3(w_exp, Cexp, 1, Cin, Cexp, 32, panels, panels + plane, panels + 2 * plane, st));
-        wparts = panels;
-    }
-    return launch_block_fused(x, B, H, W, Cin, w_exp, scale_e, shift_e, AMS_ACT_RELU6, Cexp, w_dw, stride, scale_d, shift_d, AMS_ACT_RELU6, w_proj,
-                              scale_p, shift_p, AMS_ACT_NONE, Cout, residual != 0, y, st, nullptr, wparts, plane);
+    return block_fused_entry("block_fused", false, x, B, H, W, Cin, w_exp, scale_e, shift_e, Cexp, w_dw, stride, scale_d, shift_d, w_proj, Cout, scale_p,
+                             shift_p, residual, y, panels, panel_elems, stream);
 }
 
 int ams_k_block_fused_f16(const float* x, int32_t B, int32_t H, int32_t W, int32_t Cin, const float* w_exp, const float* scale_e, const float* shift_e,
                           int32_t Cexp, const float* w_dw, int32_t stride, const float* scale_d, const float* shift_d, const float* w_proj, int32_t Cout,
                           const float* scale_p, const float* shift_p, int32_t residual, float* y, uint16_t* panels, size_t panel_elems, void* stream) {
-    if (!block_fused_supported(Cin, Cexp, Cout, stride, 1, residual != 0)) { set_error("block_fused_f16: unsupported shape"); return AMS_E_INVALID; }
-    hipStream_t st = (hipStream_t)stream;
-    const int kp_p = (Cexp + 31) / 32 * 32;
-    const int64_t pe = (int64_t)Cexp * 32, pp = (int64_t)Cout * kp_p;
-    AMS_REQUIRE(panels && Cin <= 32 && panel_elems >= (size_t)(2 * pe + 2 * pp), "block_fused_f16: panel scratch too small (need %zu)", (size_t)(2 * pe + 2 * pp));
-    uint16_t* he = panels;
-    uint16_t* hp = panels + 2 * pe;
-    RUN(launch_split_weights_f16(w_exp, Cexp, 1, Cin, Cexp, 32, he, he + pe, st));
-    RUN(launch_split_weights_f16(w_proj, Cout, 1, Cexp, Cout, kp_p, hp, hp + pp, st));
-    return launch_block_fused(x, B, H, W, Cin, w_exp, scale_e, shift_e, AMS_ACT_RELU6, Cexp, w_dw, stride, scale_d, shift_d, AMS_ACT_RELU6, w_proj,
-                              scale_p, shift_p, AMS_ACT_NONE, Cout, residual != 0, y, st, nullptr, nullptr, 0, he, pe, hp, pp, kp_p);
+    return block_fused_entry("block_fused_f16", true, x, B, H, W, Cin, w_exp, scale_e, shift_e, Cexp, w_dw, stride, scale_d, shift_d, w_proj, Cout, scale_p,
+                             shift_p, residual, y, panels, panel_elems, stream);
 }
 
-// ---- the first block (k_first_block.hip; the tile-per-wave form of k_block.hip).  One check for both entries and the plan query, in the order the
-// header states (has_form / has_panels: whether the entry takes the argument at all)
+// ---- the first block (k_first_block.hip; the tile-per-wave form of k_block.hip): both entries and the plan query go through block_call_check
 static_assert(sizeof(ams_first_block_plan) == sizeof(FirstBlockPlan) && sizeof(FirstBlockPlan) == 15 * sizeof(int32_t), "ams_first_block_plan is FirstBlockPlan, field by field");
 static size_t first_block_scratch(int form) { return form == 1 ? 3 * 32 * 32 : (form == 2 ? 2 * 32 * 32 + 2 * 16 * 32 : 0); }
-static int first_block_call_check(const char* who, int dtype, int B, int H, int W, bool has_form, int form, bool has_panels, const uint16_t* panels,
-                                  size_t panel_elems) {
-    AMS_REQUIRE(dtype == AMS_DT_U8 || dtype == AMS_DT_F32, "%s: frames must be uint8 or float32", who);
-    AMS_REQUIRE(B > 0 && H > 0 && W > 0, "%s: no pixels: B=%d, %d x %d", who, B, H, W);
-    AMS_REQUIRE(!has_form || (form >= 0 && form <= 2), "%s: unknown form %d", who, form);
-    AMS_REQUIRE(!has_panels || form == 0 || (panels && panel_elems >= first_block_scratch(form)), "%s: panel scratch too small (need %zu)", who,
-                first_block_scratch(form));
-    return AMS_OK;
+static BlockCall first_block_call(const void* frames, int dtype, int B, int H, int W, float pixel_scale, const float* w_stem, const float* scale_s,
+                                  const float* shift_s, const float* w_dw, const float* scale_d, const float* shift_d, const float* w_proj,
+                                  const float* scale_p, const float* shift_p, float* y) {
+    BlockCall c;
+    c.frames = frames; c.dtype = dtype; c.pixel_scale = pixel_scale; c.B = B; c.H = H; c.W = W; c.Cin = 3; c.Cexp = 32; c.Cout = 16; c.y = y;
+    c.expand = ConvLayer{w_stem, scale_s, shift_s, AMS_ACT_RELU6};
+    c.dw = ConvLayer{w_dw, scale_d, shift_d, AMS_ACT_RELU6};
+    c.project = ConvLayer{w_proj, scale_p, shift_p, AMS_ACT_NONE};
+    return c;
 }
 
 size_t ams_k_first_block_scratch(int32_t form) { return first_block_scratch(form); }
 
 int ams_k_first_block_plan(int32_t frames_dtype, int32_t B, int32_t H, int32_t W, int32_t form, const int32_t* occupancy, ams_first_block_plan* plan_out) {
-    RUN(first_block_call_check("first_block_plan", frames_dtype, B, H, W, true, form, false, nullptr, 0));
+    BlockCall c;
+    c.dtype = frames_dtype; c.B = B; c.H = H; c.W = W;
+    const EntryScratch sc{nullptr, 0, 0, form, 3};
+    RUN(block_call_check("first_block_plan", BK_FIRST_PLAN, c, &sc));
     AMS_REQUIRE(!occupancy || (occupancy[0] > 0 && occupancy[1] > 0 && occupancy[2] > 0), "first_block_plan: occupancy figures must be positive");
     AMS_REQUIRE(plan_out, "first_block_plan: null pointer");
     FirstBlockPlan p;
@@ -806,22 +797,22 @@ int ams_k_first_block(const void* frames, int32_t frames_dtype, int32_t B, int32
                       const float* scale_s, const float* shift_s, const float* w_dw, const float* scale_d, const float* shift_d, const float* w_proj,
                       const float* scale_p, const float* shift_p, float* y, int32_t form, uint16_t* panels, size_t panel_elems,
                       ams_first_block_plan* plan_out, void* stream) {
-    RUN(first_block_call_check("first_block", frames_dtype, B, H, W, true, form, true, panels, panel_elems));
-    AMS_REQUIRE(frames && w_stem && scale_s && shift_s && w_dw && scale_d && shift_d && w_proj && scale_p && shift_p && y, "first_block: null pointer");
     hipStream_t st = (hipStream_t)stream;
     const int64_t ps = 32 * 32, pj = 16 * 32;       // planes of the stem's [32 channels][32 k] and the project layer's [16][32] panels
-    const uint16_t *w3 = nullptr, *hs = nullptr, *hj = nullptr;
-    if (form == 1) {                                // as ams_student_freeze for layer 1: [27][32] -> three bf16 parts [32][32], k = tap * 3 + channel
+    BlockCall c = first_block_call(frames, frames_dtype, B, H, W, pixel_scale, w_stem, scale_s, shift_s, w_dw, scale_d, shift_d, w_proj, scale_p, shift_p, y);
+    uint16_t* hj = panels ? panels + 2 * ps : nullptr;
+    if (form == 1) set_panels(&c.expand, panels, ps, 3, 32);
+    else if (form == 2) { set_panels(&c.expand, panels, ps, AMS_NP_F16, 32); set_panels(&c.project, hj, pj, AMS_NP_F16, 32); }
+    const EntryScratch sc{panels, panel_elems, first_block_scratch(form), form, 3};
+    RUN(block_call_check("first_block", BK_FIRST, c, &sc));
+    if (form == 1)                                  // as ams_student_freeze for layer 1: [27][32] -> three bf16 parts [32][32], k = tap * 3 + channel
         RUN(launch_split_weights3(w_stem, 32, 1, 27, 32, 32, panels, panels + ps, panels + 2 * ps, st));
-        w3 = panels;
-    } else if (form == 2) {                         // ... and for layers 1 and 3: two fp16 parts each
+    else if (form == 2) {                           // ... and for layers 1 and 3: two fp16 parts each
         RUN(launch_split_weights_f16(w_stem, 32, 1, 27, 32, 32, panels, panels + ps, st));
-        RUN(launch_split_weights_f16(w_proj, 16, 1, 32, 16, 32, panels + 2 * ps, panels + 2 * ps + pj, st));
-        hs = panels; hj = panels + 2 * ps;
+        RUN(launch_split_weights_f16(w_proj, 16, 1, 32, 16, 32, hj, hj + pj, st));
     }
     FirstBlockPlan p;
-    RUN(launch_first_block(frames, frames_dtype, B, H, W, pixel_scale, w_stem, scale_s, shift_s, AMS_ACT_RELU6, w_dw, scale_d, shift_d, AMS_ACT_RELU6,
-                           w_proj, scale_p, shift_p, AMS_ACT_NONE, y, st, w3, ps, hs, ps, hj, pj, &p));
+    RUN(launch_first_block(c, st, &p));
     if (plan_out) memcpy(plan_out, &p, sizeof(p));
     return AMS_OK;
 }
@@ -829,50 +820,67 @@ int ams_k_first_block(const void* frames, int32_t frames_dtype, int32_t B, int32
 int ams_k_first_block_tiles(const void* frames, int32_t frames_dtype, int32_t B, int32_t H, int32_t W, float pixel_scale, const float* w_stem,
                             const float* scale_s, const float* shift_s, const float* w_dw, const float* scale_d, const float* shift_d,
                             const float* w_proj, const float* scale_p, const float* shift_p, float* y, void* stream) {
-    RUN(first_block_call_check("first_block_tiles", frames_dtype, B, H, W, false, 0, false, nullptr, 0));
-    AMS_REQUIRE(frames && w_stem && scale_s && shift_s && w_dw && scale_d && shift_d && w_proj && scale_p && shift_p && y, "first_block_tiles: null pointer");
-    return launch_first_block_tiles(frames, frames_dtype, B, H, W, pixel_scale, w_stem, scale_s, shift_s, AMS_ACT_RELU6, w_dw, scale_d, shift_d, AMS_ACT_RELU6,
-                                    w_proj, scale_p, shift_p, AMS_ACT_NONE, y, (hipStream_t)stream, nullptr);
+    return launch_first_block_tiles(first_block_call(frames, frames_dtype, B, H, W, pixel_scale, w_stem, scale_s, shift_s, w_dw, scale_d, shift_d, w_proj,
+                                                     scale_p, shift_p, y), (hipStream_t)stream);
 }
 
 int ams_k_expand_dw(const float* x, int32_t B, int32_t H, int32_t W, int32_t Cin, const float* w_exp, const float* scale_e,
                     const float* shift_e, int32_t Cexp, const float* w_dw, int32_t stride, int32_t rate, const float* scale_d,
                     const float* shift_d, float* y, void* stream) {
-    if (!expand_dw_supported(Cin, Cexp, stride, rate)) { set_error("expand_dw: unsupported shape"); return AMS_E_INVALID; }
-    return launch_expand_dw(x, B, H, W, Cin, w_exp, scale_e, shift_e, AMS_ACT_RELU6, Cexp, w_dw, stride, rate, scale_d, shift_d,
-                            AMS_ACT_RELU6, y, (hipStream_t)stream);
+    BlockCall c;
+    c.x = x; c.B = B; c.H = H; c.W = W; c.Cin = Cin; c.Cexp = Cexp; c.stride = stride; c.rate = rate; c.y = y;
+    c.expand = ConvLayer{w_exp, scale_e, shift_e, AMS_ACT_RELU6};
+    c.dw = ConvLayer{w_dw, scale_d, shift_d, AMS_ACT_RELU6};
+    return launch_expand_dw(c, (hipStream_t)stream);
+}
+
+// ams_k_expand_dw_stream (f16 = false: `parts` = 2 | 3 of the three bf16 parts it splits; Cin <= 32: the exact-f32 form, where panels, parts and presplit
+// are unused and rate = -2 selects stride 2) and ams_k_expand_dw_stream_f16 (the two fp16 parts).  presplit: x as parts behind the weight panels, 2 =
+// the weight-register form (k_xdw_wreg.hip)
+static int expand_dw_stream_entry(const char* who, bool f16, const float* x, int32_t B, int32_t H, int32_t W, int32_t Cin, const float* w_exp,
+                                  const float* scale_e, const float* shift_e, int32_t Cexp, const float* w_dw, int32_t rate, const float* scale_d,
+                                  const float* shift_d, float* y, uint16_t* panels, size_t panel_elems, int32_t parts, int32_t presplit, int32_t y_h2i,
+                                  void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    const bool f32 = !f16 && Cin <= 32;
+    const int ns = f16 ? 2 : 3;                     // planes the entry splits
+    const size_t plane = (size_t)Cexp * Cin, xplane = (size_t)B * H * W * Cin;
+    BlockCall c;
+    c.x = x; c.B = B; c.H = H; c.W = W; c.Cin = Cin; c.Cexp = Cexp; c.rate = rate; c.y = y; c.y_fmt = y_h2i ? 1 : 0;
+    c.expand = ConvLayer{w_exp, scale_e, shift_e, AMS_ACT_RELU6};
+    c.dw = ConvLayer{w_dw, scale_d, shift_d, AMS_ACT_RELU6};
+    if (f32 && rate < 0) { c.stride = -rate; c.rate = 1; }
+    const EntryScratch sc{panels, panel_elems, f32 ? 0 : ns * plane + (presplit ? ns * xplane : 0), 0, 1, f16 ? Cin >= 64 : (parts == 2 || parts == 3)};
+    uint16_t* xq = panels && presplit ? panels + ns * plane : nullptr;      // the operand as parts, as a producing GEMM leaves it (PwArgs::ysplit)
+    if (!f32) {
+        set_panels(&c.expand, panels, (int64_t)plane, f16 ? AMS_NP_F16 : parts, Cin);
+        c.x_parts = xq; c.x_plane = (int64_t)xplane;
+    }
+    const bool wreg = !f32 && presplit == 2;
+    RUN(block_call_check(who, wreg ? BK_WREG : BK_STREAM, c, &sc));
+    AMS_REQUIRE(x, "%s: null pointer", who);        // the weight-register form reads the parts only; the entry splits them from x
+    if (!f32) {
+        const int M = (int)((int64_t)B * H * W);
+        if (f16) RUN(launch_split_weights_f16(w_exp, Cexp, 1, Cin, Cexp, Cin, panels, panels + plane, st));
+        else RUN(launch_split_weights3(w_exp, Cexp, 1, Cin, Cexp, Cin, panels, panels + plane, panels + 2 * plane, st));
+        if (xq && f16) RUN(launch_split_weights_f16(x, 1, Cin, Cin, M, Cin, xq, xq + xplane, st));
+        else if (xq) RUN(launch_split_weights3(x, 1, Cin, Cin, M, Cin, xq, xq + xplane, xq + 2 * xplane, st));
+    }
+    return wreg ? launch_expand_dw_wreg(c, st) : launch_expand_dw_stream(c, st);
 }
 
 int ams_k_expand_dw_stream(const float* x, int32_t B, int32_t H, int32_t W, int32_t Cin, const float* w_exp, const float* scale_e,
                            const float* shift_e, int32_t Cexp, const float* w_dw, int32_t rate, const float* scale_d, const float* shift_d,
                            float* y, uint16_t* panels, size_t panel_elems, int32_t parts, int32_t presplit, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    int stride = 1;
-    if (rate < 0) { stride = -rate; rate = 1; }          // rate = -2 selects stride 2 (Cin <= 32 only)
-    if (!expand_dw_stream_supported(Cin, Cexp, stride, rate) || (parts != 2 && parts != 3)) {
-        set_error("expand_dw_stream: unsupported shape Cin=%d Cexp=%d rate=%d parts=%d", Cin, Cexp, rate, parts);
-        return AMS_E_INVALID;
-    }
-    if (Cin <= 32)           // exact-f32 form: no panels
-        return launch_expand_dw_stream(x, nullptr, 0, B, H, W, Cin, w_exp, nullptr, 0, 0, scale_e, shift_e, AMS_ACT_RELU6, Cexp, w_dw, stride, rate,
-                                       scale_d, shift_d, AMS_ACT_RELU6, y, st);
-    const size_t plane = (size_t)Cexp * Cin;
-    AMS_REQUIRE(panels && panel_elems >= 3 * plane, "expand_dw_stream: panel scratch too small (need %zu)", 3 * plane);
-    RUN(launch_split_weights3(w_exp, Cexp, 1, Cin, Cexp, Cin, panels, panels + plane, panels + 2 * plane, st));
-    const uint16_t* xp = nullptr;
-    const size_t xplane = (size_t)B * H * W * Cin;
-    if (presplit) {          // the operand as bf16 parts, as a producing GEMM would leave it (PwArgs::ysplit)
-        AMS_REQUIRE(panel_elems >= 3 * plane + 3 * xplane, "expand_dw_stream: panel scratch too small for the pre-split operand (need %zu)",
-                    3 * plane + 3 * xplane);
-        uint16_t* xq = panels + 3 * plane;
-        RUN(launch_split_weights3(x, 1, Cin, Cin, (int)((int64_t)B * H * W), Cin, xq, xq + xplane, xq + 2 * xplane, st));
-        xp = xq;
-    }
-    if (presplit == 2)       // the weight-register form (k_xdw_wreg.hip)
-        return launch_expand_dw_wreg(xp, (int64_t)xplane, B, H, W, Cin, panels, (int64_t)plane, parts, scale_e, shift_e, AMS_ACT_RELU6, Cexp, w_dw,
-                                     rate, scale_d, shift_d, AMS_ACT_RELU6, y, st);
-    return launch_expand_dw_stream(x, xp, (int64_t)xplane, B, H, W, Cin, nullptr, panels, (int64_t)plane, parts, scale_e, shift_e, AMS_ACT_RELU6,
-                                   Cexp, w_dw, 1, rate, scale_d, shift_d, AMS_ACT_RELU6, y, st);
+    return expand_dw_stream_entry("expand_dw_stream", false, x, B, H, W, Cin, w_exp, scale_e, shift_e, Cexp, w_dw, rate, scale_d, shift_d, y, panels, panel_elems,
+                                  parts, presplit, 0, stream);
+}
+
+int ams_k_expand_dw_stream_f16(const float* x, int32_t B, int32_t H, int32_t W, int32_t Cin, const float* w_exp, const float* scale_e,
+                               const float* shift_e, int32_t Cexp, const float* w_dw, int32_t rate, const float* scale_d, const float* shift_d,
+                               float* y, uint16_t* panels, size_t panel_elems, int32_t presplit, int32_t y_h2i, void* stream) {
+    return expand_dw_stream_entry("expand_dw_stream_f16", true, x, B, H, W, Cin, w_exp, scale_e, shift_e, Cexp, w_dw, rate, scale_d, shift_d, y, panels,
+                                  panel_elems, 2, presplit, y_h2i, stream);
 }
 
 int ams_k_global_mean(const float* x, int32_t B, int64_t HW, int32_t C, float* y, float* scratch, size_t scratch_floats,

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "kernels.hpp"
+#include "block_call.hpp"
 #include "head_common.hpp"
 
 namespace ams {
@@ -225,13 +226,6 @@ void prof_begin(ams_student* s, hipStream_t st);
 void prof_end(ams_student* s, hipStream_t st, int layer, double bytes);
 
 // ---- helpers ------------------------------------------------------------------------------------------
-static inline PwArgs pw_args(const float* x, int64_t M, int K, int ldx, const float* w, int N, float* y, int ldy) {
-    PwArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x = x; a.M = M; a.K = K; a.Kw = K; a.ldx = ldx; a.w = w; a.w_sk = N; a.w_sn = 1; a.N = N;
-    a.rows_per_img = 1; a.act = AMS_ACT_NONE; a.y = y; a.ldy = ldy;
-    return a;
-}
 
 #define RUN(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
 

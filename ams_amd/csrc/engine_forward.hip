@@ -117,6 +117,29 @@ static PwArgs layer_args(const ams_student* s, int layer, int B, const float* x,
     return a;
 }
 
+// Layer l as a block kernel reads it (block_call.hpp): weights in `params`, BN as scale / shift, and the panels picked for it: np = 0 none,
+// 1 .. 3 the bf16 parts, AMS_NP_F16 the two fp16 parts
+static ConvLayer conv_layer(const LayerRt& l, const float* params, const float* scale, const float* shift, int np = 0) {
+    ConvLayer c;
+    c.w = params + l.d.w_off; c.scale = scale; c.shift = shift; c.act = l.d.act;
+    c.np = np; c.Kp = l.Kp;
+    if (np == AMS_NP_F16) { c.panels = l.whf; c.plane = (int64_t)l.d.cout * l.Kp; }
+    else if (np) { c.panels = l.whi; c.plane = (int64_t)(l.wlo - l.whi); }
+    return c;
+}
+static ConvLayer frozen_layer(const ams_student* s, int i, int np = 0) { return conv_layer(s->L[i], s->fparams, s->L[i].fscale, s->L[i].fshift, np); }
+// the block call of expand (or stem) layer ie, depthwise layer ie + 1 and, with_project, project layer ie + 2, over the B frames of x
+static BlockCall frozen_block(const ams_student* s, int ie, int np, bool with_project, int B, const float* x, float* y) {
+    const LayerRt &le = s->L[ie], &ld = s->L[ie + 1];
+    BlockCall c;
+    c.x = x; c.B = B; c.H = le.Hin; c.W = le.Win; c.Cin = le.d.cin; c.Cexp = le.d.cout; c.stride = ld.d.stride; c.rate = ld.d.rate; c.y = y; c.vecs = le.blk_vecs;
+    c.expand = frozen_layer(s, ie, np);
+    c.dw = frozen_layer(s, ie + 1);
+    if (!with_project) return c;
+    c.project = frozen_layer(s, ie + 2, np == AMS_NP_F16 ? np : 0); c.Cout = s->L[ie + 2].d.cout; c.residual = s->L[ie + 2].d.residual_from != 0;
+    return c;
+}
+
 // frozen 1x1 layer: late layers (few rows, wide K/N: matrix-pipe bound) go through the split kernels, in the matmul mode's form; a layer
 // whose fp16 panels did not survive the freeze's range check runs three bf16 parts.  `streamable`: see plan_block
 static PwForm pointwise_form(const ams_student* s, int layer, const PwArgs& a, bool streamable) {
@@ -253,7 +276,6 @@ static int frozen_pointwise(ams_student* s, int layer, const PwArgs& a, PwForm f
 // ---- the launches: each form builds its arguments from the plan and advances the cursor ------------------------------------------------
 static int run_first_block(ams_student* s, const FrozenView& v, int dtype, Cursor& c, hipStream_t st) {
     const ams_student_config& cf = s->cfg;
-    const float* P = s->fparams;
     const int B = v.B;
     float* y = v.act[0];
     const LayerRt& l = s->L[1];
@@ -266,22 +288,16 @@ static int run_first_block(ams_student* s, const FrozenView& v, int dtype, Curso
         !lj.d.residual_from) {
         // stem + depthwise + project of the first block in one kernel: the 32-channel half-resolution tensor stays in LDS
         const double bytes = in_bytes + 4.0 * B * lj.px_out * lj.d.cout + 4.0 * (27 * 32 + 9 * 32 + 32 * 16);
-        if (s->fuse_first_block >= 2)
-            RUNK(3, bytes, launch_first_block_tiles(v.frames, dtype, B, cf.height, cf.width, cf.pixel_scale, P + l.d.w_off, l.fscale, l.fshift,
-                                                    l.d.act, P + ld.d.w_off, ld.fscale, ld.fshift, ld.d.act, P + lj.d.w_off, lj.fscale,
-                                                    lj.fshift, lj.d.act, y, st, l.blk_vecs));
-        else {
-            const bool h16 = s->block_x6 && s->matmul_mode == AMS_MATMUL_SPLIT_F16 && l.whf && lj.whf && lj.Kp == 32;
-            const bool x6 = !h16 && s->block_x6 && s->matmul_mode != AMS_MATMUL_F32 && l.whi;
-            RUNK(3, bytes, launch_first_block(v.frames, dtype, B, cf.height, cf.width, cf.pixel_scale, P + l.d.w_off, l.fscale, l.fshift,
-                                              l.d.act, P + ld.d.w_off, ld.fscale, ld.fshift, ld.d.act, P + lj.d.w_off, lj.fscale,
-                                              lj.fshift, lj.d.act, y, st, x6 ? l.whi : nullptr, 32 * 32, h16 ? l.whf : nullptr, 32 * 32,
-                                              h16 ? lj.whf : nullptr, (int64_t)lj.d.cout * lj.Kp));
-        }
+        const bool h16 = s->fuse_first_block < 2 && s->block_x6 && s->matmul_mode == AMS_MATMUL_SPLIT_F16 && l.whf && lj.whf && lj.Kp == 32;
+        const bool x6 = s->fuse_first_block < 2 && !h16 && s->block_x6 && s->matmul_mode != AMS_MATMUL_F32 && l.whi;
+        BlockCall b = frozen_block(s, 1, h16 ? AMS_NP_F16 : x6 ? 3 : 0, true, B, nullptr, y);
+        b.frames = v.frames; b.dtype = dtype; b.pixel_scale = cf.pixel_scale; b.H = cf.height; b.W = cf.width; b.Cin = 3;
+        if (s->fuse_first_block >= 2) RUNK(3, bytes, launch_first_block_tiles(b, st));
+        else RUNK(3, bytes, launch_first_block(b, st));
         c.i = 4;
     } else {
         const double bytes = in_bytes + 4.0 * B * l.px_out * l.d.cout;
-        RUNK(1, bytes, launch_stem(v.frames, dtype, B, cf.height, cf.width, P + l.d.w_off, l.d.cout, l.fscale, l.fshift, l.d.act,
+        RUNK(1, bytes, launch_stem(v.frames, dtype, B, cf.height, cf.width, s->fparams + l.d.w_off, l.d.cout, l.fscale, l.fshift, l.d.act,
                                    cf.pixel_scale, y, st));
     }
     c.cur = y; c.cur_i = 0; c.parts = PartsFmt();
@@ -305,7 +321,6 @@ static int run_project(ams_student* s, const FrozenView& v, Cursor& c, const Blo
 }
 
 static int run_block_whole(ams_student* s, const FrozenView& v, Cursor& c, const BlockPlan& p, hipStream_t st) {
-    const float* P = s->fparams;
     const int B = v.B, i = c.i;
     const LayerRt& le = s->L[i];
     const LayerRt& ld = s->L[i + 1];
@@ -318,18 +333,13 @@ static int run_block_whole(ams_student* s, const FrozenView& v, Cursor& c, const
     const double fl_e = 2.0 * B * (double)le.px_in * le.d.cin * le.d.cout, fl_p = 2.0 * B * (double)lj.px_out * lj.d.cin * lj.d.cout;
     s->prof_flops = 2.0 * B * (double)ld.px_out * 9.0 * ld.d.cin + (p.h16 ? 0.0 : fl_p) + (p.x6 || p.h16 ? 0.0 : fl_e);
     s->prof_flops_x6 = p.h16 ? fl_e + fl_p : p.x6 ? fl_e : 0.0;
-    RUNK(i + 2, bytes, launch_block_fused(c.cur, B, le.Hin, le.Win, le.d.cin, P + le.d.w_off, le.fscale, le.fshift, le.d.act, le.d.cout,
-                                          P + ld.d.w_off, ld.d.stride, ld.fscale, ld.fshift, ld.d.act, P + lj.d.w_off, lj.fscale, lj.fshift,
-                                          lj.d.act, lj.d.cout, res, v.act[o], st, le.blk_vecs, p.x6 ? le.whi : nullptr,
-                                          (int64_t)(le.wlo - le.whi), p.h16 ? le.whf : nullptr, (int64_t)le.d.cout * le.Kp, p.h16 ? lj.whf : nullptr,
-                                          (int64_t)lj.d.cout * lj.Kp, lj.Kp));
+    RUNK(i + 2, bytes, launch_block_fused(frozen_block(s, i, p.h16 ? AMS_NP_F16 : p.x6 ? 3 : 0, true, B, c.cur, v.act[o]), st));
     c.cur = v.act[o]; c.cur_i = o; c.i = i + 3; c.parts = PartsFmt();
     return AMS_OK;
 }
 
 // expand + depthwise in one kernel (tiled or streamed), then the project GEMM
 static int run_block_expand_dw(ams_student* s, const FrozenView& v, Cursor& c, const BlockPlan& p, hipStream_t st) {
-    const float* P = s->fparams;
     const int B = v.B, i = c.i;
     const LayerRt& le = s->L[i];
     const LayerRt& ld = s->L[i + 1];
@@ -340,17 +350,14 @@ static int run_block_expand_dw(ams_student* s, const FrozenView& v, Cursor& c, c
     // a block input left as part planes only (BlockPlan::out_parts_only): c.cur names its buffer, but only the planes may be read
     AMS_REQUIRE(c.cur_f32 || (x_parts && (p.form == BLOCK_WREG || (p.form == BLOCK_STREAM && le.d.cin > 32))),
                 "engine: block at layer %d reads an f32 input that was left as part planes only", i);
-    if (p.form == BLOCK_TILED)
-        RUNK(i + 1, bytes, launch_expand_dw(c.cur, B, le.Hin, le.Win, le.d.cin, P + le.d.w_off, le.fscale, le.fshift, le.d.act, le.d.cout,
-                                            P + ld.d.w_off, ld.d.stride, ld.d.rate, ld.fscale, ld.fshift, ld.d.act, v.act[o], st));
-    else if (p.form == BLOCK_WREG)
-        RUNK(i + 1, bytes, launch_expand_dw_wreg(x_parts, xplane, B, le.Hin, le.Win, le.d.cin, p.wparts, p.wplane, p.np, le.fscale,
-                                                 le.fshift, le.d.act, le.d.cout, P + ld.d.w_off, ld.d.rate, ld.fscale, ld.fshift, ld.d.act,
-                                                 v.act[o], st, p.d_h2i ? 1 : 0));
-    else
-        RUNK(i + 1, bytes, launch_expand_dw_stream(c.cur, x_parts, xplane, B, le.Hin, le.Win, le.d.cin, P + le.d.w_off, p.wparts, p.wplane, p.np, le.fscale,
-                                                   le.fshift, le.d.act, le.d.cout, P + ld.d.w_off, ld.d.stride, ld.d.rate, ld.fscale, ld.fshift, ld.d.act,
-                                                   v.act[o], st, p.d_h2i ? 1 : 0));
+    BlockCall b = frozen_block(s, i, 0, false, B, c.cur, v.act[o]);
+    if (p.form == BLOCK_TILED) RUNK(i + 1, bytes, launch_expand_dw(b, st));
+    else {
+        b.expand.panels = p.wparts; b.expand.plane = p.wplane; b.expand.np = p.np;      // the plan's choice
+        b.x_parts = x_parts; b.x_plane = xplane; b.y_fmt = p.d_h2i ? 1 : 0;
+        if (p.form == BLOCK_WREG) RUNK(i + 1, bytes, launch_expand_dw_wreg(b, st));
+        else RUNK(i + 1, bytes, launch_expand_dw_stream(b, st));
+    }
     if (p.form != BLOCK_TILED && s->emulate_bf16_storage && ld.px_out == (int64_t)s->h * s->w)
         RUN(launch_round_bf16(v.act[o], (int64_t)B * ld.px_out * ld.d.cout, st));          // d as bf16 storage would hold it
     return run_project(s, v, c, p, i + 2, v.act[o], o, st);
@@ -372,11 +379,13 @@ static int run_block_layers(ams_student* s, const FrozenView& v, Cursor& c, cons
     const int o = other(v, c.cur_i, x_i);
     if (p.dw_project) {
         const LayerRt& lpj = s->L[i + 1];
-        const PwArgs a = layer_args(s, i + 1, B, nullptr, v.act[o], c.cur);
-        const double bytes = 4.0 * ((double)B * (l.px_in * l.d.cin + lpj.px_out * lpj.d.cout * (a.res ? 2 : 1)) +
+        BlockCall b;
+        b.x = x; b.B = B; b.H = l.Hin; b.W = l.Win; b.Cexp = l.d.cin; b.stride = l.d.stride; b.rate = l.d.rate; b.Cout = lpj.d.cout; b.y = v.act[o];
+        b.dw = frozen_layer(s, i);
+        b.project = frozen_layer(s, i + 1, 2); b.residual = lpj.d.residual_from != 0; b.res = c.cur;
+        const double bytes = 4.0 * ((double)B * (l.px_in * l.d.cin + lpj.px_out * lpj.d.cout * (b.residual ? 2 : 1)) +
                                     (double)lpj.d.cin * lpj.d.cout + 9.0 * l.d.cin);
-        RUNK(i + 1, bytes, launch_dw_project(x, B, l.Hin, l.Win, l.d.cin, P + l.d.w_off, l.d.rate, l.fscale, l.fshift, l.d.act, a,
-                                             lpj.whi, lpj.wlo, lpj.Kp, st));
+        RUNK(i + 1, bytes, launch_dw_project(b, st));
         c.cur = v.act[o]; c.cur_i = o; c.i = i + 2; c.parts = PartsFmt();
         return AMS_OK;
     }
@@ -451,9 +460,10 @@ static int run_head(ams_student* s, const FrozenView& v, const Cursor& c, hipStr
         const double bytes = 4.0 * M * (la.d.cin + 32) + 4.0 * ((double)la.Kp * la.d.cout + (double)lc.Kp * lc.d.cout + (double)ll.Kp * ll.d.cout) +
                              4.0 * (2.0 * la.d.cout + 2.0 * lc.d.cout + ll.d.cout + (double)B * lc.d.cout);
         s->prof_flops_x6 = 2.0 * M * ((double)la.d.cin * la.d.cout + (double)la.d.cout * lc.d.cout + (double)lc.d.cout * ll.d.cout);
-        RUNK(s->iLogits, bytes, launch_head_chain(c.cur, M, la.d.cin, la.whf, (int64_t)la.d.cout * la.Kp, la.fscale, la.fshift, la.d.act,
-                                                  lc.whf, (int64_t)lc.d.cout * lc.Kp, lc.fscale, lc.fshift, lc.d.act, v.img_bias, HW,
-                                                  ll.whf, (int64_t)ll.d.cout * ll.Kp, d.shift, d.act, ll.d.cout, v.logits, st));
+        ConvLayer lg = frozen_layer(s, s->iLogits, AMS_NP_F16);
+        lg.scale = nullptr; lg.shift = d.shift; lg.act = d.act;      // biases
+        RUNK(s->iLogits, bytes, launch_head_chain(c.cur, M, la.d.cin, frozen_layer(s, s->iAspp, AMS_NP_F16), frozen_layer(s, s->iProj, AMS_NP_F16), lg,
+                                                  v.img_bias, HW, ll.d.cout, v.logits, st));
         return AMS_OK;
     }
     RUN(frozen_pointwise(s, s->iAspp, a, fa, st));
@@ -657,10 +667,12 @@ int forward_live(ams_student* s, const void* frames, int dtype, int B, int globa
             // ... which leaves the statistics of that raw output behind as one partial row per tile (no separate pass over z_d)
             int d_rows = 0;
             const bool d_stats = (s->fuse_gemm_red & 1) && expand_dw_stats_scratch(B, l.Hin, l.Win, l.d.cout, ld.d.stride) <= s->scratch_floats;
+            BlockCall xdw;                       // the live weights with the batch statistics; the depthwise layer's raw output
+            xdw.x = x; xdw.B = B; xdw.H = l.Hin; xdw.W = l.Win; xdw.Cin = l.d.cin; xdw.Cexp = l.d.cout; xdw.stride = ld.d.stride; xdw.rate = ld.d.rate; xdw.y = ld.z;
+            xdw.expand = conv_layer(l, P, l.scale, l.shift);
+            xdw.dw = conv_layer(ld, P, s->vec_ones, s->vec_zeros); xdw.dw.act = AMS_ACT_NONE;
             RUNK(i + 1, 4.0 * ((double)B * (l.px_in * l.d.cin + ld.px_out * ld.d.cout)),
-                 launch_expand_dw(x, B, l.Hin, l.Win, l.d.cin, P + l.d.w_off, l.scale, l.shift, l.d.act, l.d.cout, P + ld.d.w_off, ld.d.stride,
-                                  ld.d.rate, s->vec_ones, s->vec_zeros, AMS_ACT_NONE, ld.z, st, d_stats ? s->stats + ld.d.mean_off : nullptr,
-                                  d_stats ? s->scratch : nullptr, d_stats ? &d_rows : nullptr));
+                 launch_expand_dw(xdw, st, d_stats ? s->stats + ld.d.mean_off : nullptr, d_stats ? s->scratch : nullptr, d_stats ? &d_rows : nullptr));
             RUN(bn_train(s, ld, (int64_t)B * ld.px_out, (double)global_B * ld.px_out, update_ema, sc, nullptr, st, d_rows, !operand_bn_act(s, i + 1)));
             ++i;
             continue;

@@ -24,6 +24,7 @@
 
 #include "pw_common.hpp"
 #include "split_bf16.hpp"
+#include "block_call.hpp"
 
 namespace ams {
 
@@ -608,21 +609,27 @@ bool block_fused_supported(int Cin, int Cexp, int Cout, int stride, int rate, bo
     return blk_pick_tile(Cexp, Cout, stride, false, &th, &tw) && blk_pick_tile(Cexp, Cout, stride, true, &th, &tw);
 }
 
-int launch_block_fused(const float* x, int B, int H, int W, int Cin, const float* w_exp, const float* sc_e, const float* sh_e, int act_e, int Cexp,
-                       const float* w_dw, int stride, const float* sc_d, const float* sh_d, int act_d, const float* w_pj, const float* sc_p,
-                       const float* sh_p, int act_p, int Cout, bool residual, float* y, hipStream_t st, const float* vecs, const uint16_t* wparts,
-                       int64_t wplane, const uint16_t* h_exp, int64_t h_exp_plane, const uint16_t* h_pj, int64_t h_pj_plane, int h_pj_kp) {
-    AMS_REQUIRE(block_fused_supported(Cin, Cexp, Cout, stride, 1, residual), "block kernel: unsupported shape Cin=%d Cexp=%d Cout=%d s=%d", Cin, Cexp,
-                Cout, stride);
+// the three layers of a block call into the device arguments (both launchers below)
+static void blk_layers(const BlockCall& c, BlkArgs* a) {
+    const ConvLayer &e = c.expand, &d = c.dw, &p = c.project;
+    a->w_exp = e.w; a->sc_e = e.scale; a->sh_e = e.shift; a->act_e = e.act; a->Cexp = c.Cexp;
+    a->w_dw = d.w; a->sc_d = d.scale; a->sh_d = d.shift; a->act_d = d.act;
+    a->w_pj = p.w; a->sc_p = p.scale; a->sh_p = p.shift; a->act_p = p.act; a->Cout = c.Cout;
+    a->residual = c.residual ? 1 : 0; a->y = c.y; a->vecs = c.vecs;
+}
+
+int launch_block_fused(const BlockCall& c, hipStream_t st) {
+    RUN_RC(block_call_check("block_fused", BK_WHOLE, c));
+    const int Cexp = c.Cexp, Cout = c.Cout, stride = c.stride;
     BlkArgs a;
     memset(&a, 0, sizeof(a));
-    a.x = x; a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.w_exp = w_exp; a.sc_e = sc_e; a.sh_e = sh_e; a.act_e = act_e; a.Cexp = Cexp;
-    a.w_dw = w_dw; a.sc_d = sc_d; a.sh_d = sh_d; a.act_d = act_d; a.w_pj = w_pj; a.sc_p = sc_p; a.sh_p = sh_p; a.act_p = act_p; a.Cout = Cout;
-    a.residual = residual ? 1 : 0; a.y = y; a.vecs = vecs; a.timed = knobs().blk_timed;
-    if (h_exp && h_pj) { a.he = h_exp; a.he_plane = h_exp_plane; a.hp = h_pj; a.hp_plane = h_pj_plane; a.kp_p = h_pj_kp; }      // fp16 form: expand and project
-    else if (wparts && Cin > 16) { a.wparts = wparts; a.wplane = wplane; }      // X6 pays from K = 24 on (at K = 16 half of every bf16 MFMA is padding)
-    same_pad(H, 3, stride, 1, &a.Ho, &a.pt);
-    same_pad(W, 3, stride, 1, &a.Wo, &a.pl);
+    a.x = c.x; a.B = c.B; a.H = c.H; a.W = c.W; a.Cin = c.Cin;
+    blk_layers(c, &a);
+    a.timed = knobs().blk_timed;
+    if (c.expand.np == AMS_NP_F16) { a.he = c.expand.panels; a.he_plane = c.expand.plane; a.hp = c.project.panels; a.hp_plane = c.project.plane; a.kp_p = c.project.Kp; }      // fp16 form: expand and project
+    else if (c.expand.np && c.Cin > 16) { a.wparts = c.expand.panels; a.wplane = c.expand.plane; }      // X6 pays from K = 24 on (at K = 16 half of every bf16 MFMA is padding)
+    same_pad(c.H, 3, stride, 1, &a.Ho, &a.pt);
+    same_pad(c.W, 3, stride, 1, &a.Wo, &a.pl);
     // tile of output pixels per WAVE: the measured choice, or the next smaller one that fits LDS (blk_pick_tile)
     int th, tw;
     AMS_REQUIRE(blk_pick_tile(Cexp, Cout, stride, a.wparts != nullptr || a.he != nullptr, &th, &tw), "block kernel: no tile fits LDS for Cexp=%d", Cexp);
@@ -638,20 +645,16 @@ int launch_block_fused(const float* x, int B, int H, int W, int Cin, const float
 
 // First block of the network in the same form: frames -> pad 127.5 -> x * ps - 1 -> stem 3x3 s2 (3 -> 32) + BN + ReLU6 -> depthwise 3x3 (32)
 // + BN + ReLU6 -> project 1x1 (32 -> 16) + BN.  `vecs` = [13][32] table (stem BN | depthwise BN | depthwise taps) or null.
-int launch_first_block_tiles(const void* frames, int dtype, int B, int H, int W, float pixel_scale, const float* w_stem, const float* sc_s,
-                             const float* sh_s, int act_s, const float* w_dw, const float* sc_d, const float* sh_d, int act_d, const float* w_pj,
-                             const float* sc_p, const float* sh_p, int act_p, float* y, hipStream_t st, const float* vecs) {
-    AMS_REQUIRE(dtype == AMS_DT_U8 || dtype == AMS_DT_F32, "first_block: frames must be uint8 or float32");
+int launch_first_block_tiles(const BlockCall& c, hipStream_t st) {
+    RUN_RC(block_call_check("first_block_tiles", BK_FIRST_TILES, c));
     BlkArgs a;
     memset(&a, 0, sizeof(a));
-    a.x = reinterpret_cast<const float*>(frames); a.B = B; a.fH = H; a.fW = W; a.ps = pixel_scale; a.Cin = 27;
-    a.w_exp = w_stem; a.sc_e = sc_s; a.sh_e = sh_s; a.act_e = act_s; a.Cexp = 32;
-    a.w_dw = w_dw; a.sc_d = sc_d; a.sh_d = sh_d; a.act_d = act_d; a.w_pj = w_pj; a.sc_p = sc_p; a.sh_p = sh_p; a.act_p = act_p; a.Cout = 16;
-    a.residual = 0; a.y = y; a.vecs = vecs;
-    same_pad(H + 1, 3, 2, 1, &a.H, &a.spt);           // the stem's output grid = the depthwise conv's input grid
-    same_pad(W + 1, 3, 2, 1, &a.W, &a.spl);
+    a.x = reinterpret_cast<const float*>(c.frames); a.B = c.B; a.fH = c.H; a.fW = c.W; a.ps = c.pixel_scale; a.Cin = 27;
+    blk_layers(c, &a);
+    same_pad(c.H + 1, 3, 2, 1, &a.H, &a.spt);         // the stem's output grid = the depthwise conv's input grid
+    same_pad(c.W + 1, 3, 2, 1, &a.W, &a.spl);
     a.Ho = a.H; a.Wo = a.W; a.pt = 1; a.pl = 1;        // depthwise 3x3, stride 1, SAME
-    if (dtype == AMS_DT_U8) return launch_blk_k<1, 2, 1, 8, 8, uint8_t>(a, st);
+    if (c.dtype == AMS_DT_U8) return launch_blk_k<1, 2, 1, 8, 8, uint8_t>(a, st);
     return launch_blk_k<1, 2, 1, 8, 8, float>(a, st);
 }
 

@@ -13,6 +13,7 @@
 // image — loading the 9 taps per lane instead costs 72 registers of prefetch and 5x the L2 traffic), the project-weight
 // pieces and the depthwise weights / BN of the chunk (single buffers, two barriers per chunk: up to three blocks per CU).
 #include "pw_common.hpp"
+#include "block_call.hpp"
 
 namespace ams {
 
@@ -237,17 +238,18 @@ static int launch_dwp_t(DwpArgs a, hipStream_t st) {
     return AMS_OK;
 }
 
-// e: [B,H,W,C] -> y: [B,H,W,N]; p carries the project layer (N, scale, shift, act, res, ldr, y, ldy); whi/wlo: its
-// weights as bf16 panels [N][C]
-int launch_dw_project(const float* e, int B, int H, int W, int C, const float* w_dw, int rate, const float* sc_d, const float* sh_d,
-                      int act_d, const PwArgs& p, const uint16_t* whi, const uint16_t* wlo, int Kp, hipStream_t st) {
-    AMS_REQUIRE(dw_project_supported(C, p.N, 1, rate), "dw_project: unsupported shape C=%d N=%d rate=%d", C, p.N, rate);
-    AMS_REQUIRE(Kp == C && p.K == C, "dw_project: the panels must be [N][C] (Kp=%d, K=%d, C=%d)", Kp, p.K, C);
-    AMS_REQUIRE((p.ldy & 3) == 0 && (!p.res || (p.ldr & 3) == 0) && !p.img_bias, "dw_project: layout");
+// c.x = e: [B,H,W,C] -> y: [B,H,W,N], C = c.Cexp, N = c.Cout; the project layer's epilogue (scale, shift, act, + c.res) rides in the embedded
+// PwArgs, dense rows; its weights as two-part bf16 panels [N][C]
+int launch_dw_project(const BlockCall& c, hipStream_t st) {
+    RUN_RC(block_call_check("dw_project", BK_DW_PROJECT, c));
+    const int C = c.Cexp, rate = c.rate;
+    PwArgs p = pw_args(nullptr, (int64_t)c.B * c.H * c.W, C, C, c.project.w, c.Cout, c.y, c.Cout);
+    p.scale = c.project.scale; p.shift = c.project.shift; p.act = c.project.act;
+    if (c.residual) { p.res = c.res; p.ldr = c.Cout; }
     DwpArgs a;
     memset(&a, 0, sizeof(a));
-    a.e = e; a.B = B; a.H = H; a.W = W; a.C = C; a.w_dw = w_dw; a.sc_d = sc_d; a.sh_d = sh_d; a.act_d = act_d; a.rate = rate;
-    a.p = p; a.whi = whi; a.plane = (int64_t)(wlo - whi);
+    a.e = c.x; a.B = c.B; a.H = c.H; a.W = c.W; a.C = C; a.w_dw = c.dw.w; a.sc_d = c.dw.scale; a.sh_d = c.dw.shift; a.act_d = c.dw.act; a.rate = rate;
+    a.p = p; a.whi = c.project.panels; a.plane = c.project.plane;
     const int nt = dwp_pick_nt(p.N);
 #define DWP(NT_) if (nt == NT_) return rate == 1 ? launch_dwp_t<NT_, 1>(a, st) : launch_dwp_t<NT_, 2>(a, st);
     DWP(1) DWP(2) DWP(3) DWP(4) DWP(5) DWP(6) DWP(8) DWP(10)

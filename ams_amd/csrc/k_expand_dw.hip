@@ -10,6 +10,7 @@
 // The expanded activation never reaches HBM.  Costs: the halo is recomputed per tile (x1.27 GEMM work for 16x16 tiles,
 // stride 1) and every channel chunk re-reads the small input tile from L2.
 #include "pw_common.hpp"
+#include "block_call.hpp"
 
 namespace ams {
 
@@ -287,10 +288,9 @@ size_t expand_dw_stats_scratch(int B, int H, int W, int Cexp, int stride) {
     return (size_t)B * cdiv(Ho, th) * cdiv(Wo, tw) * 2 * (size_t)Cexp;
 }
 
-int launch_expand_dw(const float* x, int B, int H, int W, int Cin, const float* w_exp, const float* sc_e, const float* sh_e, int act_e,
-                     int Cexp, const float* w_dw, int stride, int rate, const float* sc_d, const float* sh_d, int act_d, float* y,
-                     hipStream_t st, const float* stats_center, float* stats_part, int* stats_rows) {
-    AMS_REQUIRE(expand_dw_supported(Cin, Cexp, stride, rate), "expand_dw: unsupported shape Cin=%d Cexp=%d s=%d r=%d", Cin, Cexp, stride, rate);
+int launch_expand_dw(const BlockCall& c, hipStream_t st, const float* stats_center, float* stats_part, int* stats_rows) {
+    RUN_RC(block_call_check("expand_dw", BK_TILED, c));
+    const int B = c.B, H = c.H, W = c.W, Cexp = c.Cexp, stride = c.stride, rate = c.rate;
     XdwArgs a;
     memset(&a, 0, sizeof(a));
     a.center = stats_center; a.part = stats_part;
@@ -302,8 +302,8 @@ int launch_expand_dw(const float* x, int B, int H, int W, int Cin, const float* 
         same_pad(W, 3, stride, rate, &Wo, &pp);
         *stats_rows = B * cdiv(Ho, th) * cdiv(Wo, tw);
     }
-    a.x = x; a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.w_exp = w_exp; a.sc_e = sc_e; a.sh_e = sh_e; a.act_e = act_e;
-    a.Cexp = Cexp; a.w_dw = w_dw; a.sc_d = sc_d; a.sh_d = sh_d; a.act_d = act_d; a.y = y;
+    a.x = c.x; a.B = B; a.H = H; a.W = W; a.Cin = c.Cin; a.w_exp = c.expand.w; a.sc_e = c.expand.scale; a.sh_e = c.expand.shift; a.act_e = c.expand.act;
+    a.Cexp = Cexp; a.w_dw = c.dw.w; a.sc_d = c.dw.scale; a.sh_d = c.dw.shift; a.act_d = c.dw.act; a.y = c.y;
     same_pad(H, 3, stride, rate, &a.Ho, &a.pt);
     same_pad(W, 3, stride, rate, &a.Wo, &a.pl);
     const bool nt2 = Cexp % 32 == 0;

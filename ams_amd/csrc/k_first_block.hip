@@ -15,6 +15,7 @@
 // Arithmetic per element is the same as in the three separate kernels (same tap order, same MFMA chunking).
 #include "pw_common.hpp"
 #include "split_bf16.hpp"
+#include "block_call.hpp"
 
 namespace ams {
 
@@ -795,28 +796,28 @@ int first_block_plan(int dtype, int B, int H, int W, bool h16, const int* occupa
     return AMS_OK;
 }
 
-int launch_first_block(const void* frames, int dtype, int B, int H, int W, float pixel_scale, const float* w_stem,
-                       const float* sc_s, const float* sh_s, int act_s, const float* w_dw, const float* sc_d, const float* sh_d,
-                       int act_d, const float* w_pj, const float* sc_p, const float* sh_p, int act_p, float* y, hipStream_t st,
-                       const uint16_t* w_parts, int64_t w_plane, const uint16_t* h_stem, int64_t h_stem_plane, const uint16_t* h_pj, int64_t h_pj_plane,
-                       FirstBlockPlan* plan_out) {
-    AMS_REQUIRE(dtype == AMS_DT_U8 || dtype == AMS_DT_F32, "first_block: frames must be uint8 or float32");
+int launch_first_block(const BlockCall& c, hipStream_t st, FirstBlockPlan* plan_out) {
+    RUN_RC(block_call_check("first_block", BK_FIRST, c));
+    const ConvLayer &s = c.expand, &d = c.dw, &p = c.project;
+    const int dtype = c.dtype, B = c.B;
+    const bool h16 = s.np == AMS_NP_F16;
+    const uint16_t* w_parts = s.np == 3 ? s.panels : nullptr;
     FirstBlockPlan pl;
-    RUN_RC(first_block_plan(dtype, B, H, W, h_stem && h_pj, nullptr, &pl));
+    RUN_RC(first_block_plan(dtype, B, c.H, c.W, h16, nullptr, &pl));
     if (plan_out) *plan_out = pl;
     FirstBlockArgs a;
     memset(&a, 0, sizeof(a));
-    a.frames = frames; a.B = B; a.H = H; a.W = W; a.ps = pixel_scale;
-    a.w_stem = w_stem; a.sc_s = sc_s; a.sh_s = sh_s; a.act_s = act_s;
-    a.w_dw = w_dw; a.sc_d = sc_d; a.sh_d = sh_d; a.act_d = act_d;
-    a.w_pj = w_pj; a.sc_p = sc_p; a.sh_p = sh_p; a.act_p = act_p; a.y = y;
-    a.w_parts = w_parts; a.w_plane = w_plane;
+    a.frames = c.frames; a.B = B; a.H = c.H; a.W = c.W; a.ps = c.pixel_scale;
+    a.w_stem = s.w; a.sc_s = s.scale; a.sh_s = s.shift; a.act_s = s.act;
+    a.w_dw = d.w; a.sc_d = d.scale; a.sh_d = d.shift; a.act_d = d.act;
+    a.w_pj = p.w; a.sc_p = p.scale; a.sh_p = p.shift; a.act_p = p.act; a.y = c.y;
+    a.w_parts = w_parts; a.w_plane = 32 * 32;         // [part][32][32]
     a.Ho = pl.Ho; a.Wo = pl.Wo; a.pt = pl.pt; a.pl = pl.pl;
     a.tiles_x = pl.tiles_x; a.tiles_y = pl.tiles_y;
     a.ity0 = pl.ity0; a.itx0 = pl.itx0; a.niy = pl.niy; a.nix = pl.nix;
     const int64_t nblocks = (int64_t)a.tiles_x * a.tiles_y * B;
-    if (h_stem && h_pj) {                           // two fp16 parts in the stem and the project layer (takes precedence over w_parts)
-        a.hs = h_stem; a.hs_plane = h_stem_plane; a.hj = h_pj; a.hj_plane = h_pj_plane;
+    if (h16) {                                      // two fp16 parts in the stem and the project layer
+        a.hs = s.panels; a.hs_plane = s.plane; a.hj = p.panels; a.hj_plane = p.plane;
         if (pl.interior_tiles > 0) {
             const unsigned grid = (unsigned)pl.interior_grid, n_in = (unsigned)pl.interior_tiles;
             note_kernel("first_block_walk_kernel<0>");                // (a profiled launch bracket covers the border launch below as well)

@@ -24,6 +24,7 @@
 // fragment reads (128 KB at 256 B/clk).
 #include "pw_common.hpp"
 #include "split_bf16.hpp"
+#include "block_call.hpp"
 
 namespace ams {
 
@@ -295,18 +296,17 @@ bool head_chain_supported(int KA, int NA, int KB, int NB, int KC, int NC) {
 }
 
 // logits[M][32] = C(B(A(x))) with A = aspp0, B = concat_projection (+ img_bias per image), C = logits; panels as launch_pointwise_split_f16 takes them
-int launch_head_chain(const float* x, int64_t M, int KA, const uint16_t* wA, int64_t planeA, const float* scA, const float* shA, int actA,
-                      const uint16_t* wB, int64_t planeB, const float* scB, const float* shB, int actB, const float* img_bias, int64_t rows_per_img,
-                      const uint16_t* wC, int64_t planeC, const float* biasC, int actC, int NC, float* y, hipStream_t st) {
-    AMS_REQUIRE(M > 0 && rows_per_img > 0 && x && wA && wB && wC && img_bias && y && head_chain_supported(KA, HC_N, HC_N, HC_N, HC_N, NC),
+int launch_head_chain(const float* x, int64_t M, int KA, const ConvLayer& A, const ConvLayer& B, const ConvLayer& C, const float* img_bias,
+                      int64_t rows_per_img, int NC, float* y, hipStream_t st) {
+    AMS_REQUIRE(M > 0 && rows_per_img > 0 && x && A.panels && B.panels && C.panels && img_bias && y && head_chain_supported(KA, HC_N, HC_N, HC_N, HC_N, NC),
                 "head_chain: bad problem (M %lld KA %d NC %d)", (long long)M, KA, NC);
     HeadChainArgs a;
     a.x = x; a.M = M; a.KA = KA; a.pitch = hc_slab_pitch(KA);
     const size_t lds = hc_lds(KA);
-    a.wA = wA; a.wB = wB; a.wC = wC; a.planeA = planeA; a.planeB = planeB; a.planeC = planeC;
-    a.scA = scA; a.shA = shA; a.scB = scB; a.shB = shB; a.biasC = biasC;
+    a.wA = A.panels; a.wB = B.panels; a.wC = C.panels; a.planeA = A.plane; a.planeB = B.plane; a.planeC = C.plane;
+    a.scA = A.scale; a.shA = A.shift; a.scB = B.scale; a.shB = B.shift; a.biasC = C.shift;
     a.img_bias = img_bias; a.rows_per_img = rows_per_img;
-    a.actA = actA; a.actB = actB; a.actC = actC; a.NC = NC;
+    a.actA = A.act; a.actB = B.act; a.actC = C.act; a.NC = NC;
     a.y = y;
     RUN_RC(func_allow_lds((const void*)head_chain_kernel, lds));
     note_kernel("head_chain_kernel");

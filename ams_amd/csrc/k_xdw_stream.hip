@@ -18,6 +18,7 @@
 // The 6x-expanded tensor is never written; what reaches HBM is the depthwise output (the project GEMM's operand).
 #include "pw_common.hpp"
 #include "split_bf16.hpp"
+#include "block_call.hpp"
 
 namespace ams {
 
@@ -576,29 +577,24 @@ static int launch_xds_ks(const XdsArgs& a, const XdsPlan& p, int np, hipStream_t
     return np == 3 ? launch_xds_w<KS, 2, 3>(a, p, st) : np == 1 ? launch_xds_w<KS, 2, 1>(a, p, st) : launch_xds_w<KS, 2, 2>(a, p, st);
 }
 
-// w_f32: the expand weights [Cin][Cexp] for the exact-f32 form (Cin <= 32; w_parts / np / x_parts are then unused).
-// x_parts (optional): x as bf16 parts [part][B*H*W][Cin], x_plane apart, exactly what split8 makes of x (the producing GEMM writes
+// c.expand.w: the expand weights [Cin][Cexp] for the exact-f32 form (Cin <= 32; the panels, np and c.x_parts are then unused).
+// c.x_parts (optional): x as bf16 parts [part][B*H*W][Cin], x_plane apart, exactly what split8 makes of x (the producing GEMM writes
 // them, PwArgs::ysplit): the E-waves then load their operands ready-made instead of splitting them once per channel chunk.
-// w_parts: the expand layer's bf16 panels [part][Cexp][Cin] (np = 2: hi, lo; np = 3: hi, mid, lo), part p at w_parts + p * plane
-int launch_expand_dw_stream(const float* x, const uint16_t* x_parts, int64_t x_plane, int B, int H, int W, int Cin, const float* w_f32,
-                            const uint16_t* w_parts, int64_t plane, int np,
-                            const float* sc_e, const float* sh_e, int act_e, int Cexp, const float* w_dw, int stride, int rate, const float* sc_d,
-                            const float* sh_d, int act_d, float* y, hipStream_t st, int y_fmt) {
+// c.expand.panels: the expand layer's bf16 panels [part][Cexp][Cin] (np = 2: hi, lo; np = 3: hi, mid, lo), part p at panels + p * plane
+int launch_expand_dw_stream(const BlockCall& c, hipStream_t st) {
+    RUN_RC(block_call_check("expand_dw_stream", BK_STREAM, c));
+    const int B = c.B, H = c.H, W = c.W, Cin = c.Cin, Cexp = c.Cexp, stride = c.stride, rate = c.rate;
     const bool f32 = Cin <= 32;
-    const bool h16 = !f32 && np == AMS_NP_F16;       // two fp16 parts
-    if (h16) np = 2;
-    AMS_REQUIRE(y_fmt == 0 || (h16 && Cexp % 8 == 0 && stride == 1), "expand_dw_stream: the fp16-pair output needs the fp16 form and Cexp %% 8 == 0");
-    AMS_REQUIRE(expand_dw_stream_supported(Cin, Cexp, stride, rate) && (f32 ? w_f32 != nullptr : (w_parts && np >= 1 && np <= 3)),
-                "expand_dw_stream: unsupported shape Cin=%d Cexp=%d rate=%d", Cin, Cexp, rate);
-    if (f32) { np = 0; x_parts = nullptr; }
-    AMS_REQUIRE(B > 0 && H > 0 && W > 0, "expand_dw_stream: empty input");
+    const bool h16 = !f32 && c.expand.np == AMS_NP_F16;       // two fp16 parts
+    const int np = f32 ? 0 : h16 ? 2 : c.expand.np;
     AMS_REQUIRE((int64_t)H * W * Cexp * 4 < 0x7fffffffLL, "expand_dw_stream: a frame of the output exceeds 2 GiB");
     XdsPlan p;
     AMS_REQUIRE(xds_plan(B, H, W, Cin, Cexp, rate, np, &p), "expand_dw_stream: no segment geometry fits LDS (W=%d rate=%d)", W, rate);
     XdsArgs a;
     memset(&a, 0, sizeof(a));
-    a.x = x; a.xs = x_parts; a.xs_plane = x_plane; a.wf = w_f32; a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.wp = w_parts; a.plane = plane; a.sc_e = sc_e; a.sh_e = sh_e; a.act_e = act_e;
-    a.Cexp = Cexp; a.w_dw = w_dw; a.sc_d = sc_d; a.sh_d = sh_d; a.act_d = act_d; a.y = y; a.rate = rate;
+    a.x = c.x; a.xs = f32 ? nullptr : c.x_parts; a.xs_plane = c.x_plane; a.wf = c.expand.w; a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.wp = c.expand.panels; a.plane = c.expand.plane;
+    a.sc_e = c.expand.scale; a.sh_e = c.expand.shift; a.act_e = c.expand.act;
+    a.Cexp = Cexp; a.w_dw = c.dw.w; a.sc_d = c.dw.scale; a.sh_d = c.dw.shift; a.act_d = c.dw.act; a.y = c.y; a.rate = rate;
     a.stride = stride;
     if (stride == 2) {
         int pt, pl;
@@ -610,7 +606,7 @@ int launch_expand_dw_stream(const float* x, const uint16_t* x_parts, int64_t x_p
     a.SH = p.SH; a.SW = p.SW; a.Wp = p.SW + 2; a.T = ((p.SH + 2) * a.Wp + step - 1) / step; a.ring = p.ring;
     a.nsy = p.nsy; a.nsx = p.nsx; a.chunks = (Cexp + 16 * p.nt - 1) / (16 * p.nt);
     a.items = B * rate * rate * p.nsy * p.nsx; a.groups = p.groups;
-    a.y_fmt = y_fmt;
+    a.y_fmt = c.y_fmt;
     a.timed = knobs().xwr_timed;
     if (h16) {
         AMS_REQUIRE(p.nwe == 4 && p.nwd == 4, "expand_dw_stream: the fp16 form runs with 4 + 4 waves");

@@ -13,6 +13,7 @@
 //     k_xdw_stream.hip (same products in the same order, same depthwise order: bit-identical to it and to the unfused pair).
 #include "pw_common.hpp"
 #include "split_bf16.hpp"
+#include "block_call.hpp"
 
 namespace ams {
 
@@ -484,17 +485,13 @@ static int launch_xwr_w(const XwrArgs& a, int nwe, int nrg, size_t lds, hipStrea
     return launch_xwr_k<KS, NP, 4, 4, 1, H16>(a, lds, st);
 }
 
-// the weight-register form; x_parts is required (bf16 parts of the input, np of them).  AMS_XWR_FORCE = "E-waves (4|8),row
+// the weight-register form; c.x_parts is required (bf16 parts of the input, np of them).  AMS_XWR_FORCE = "E-waves (4|8),row
 // segments,column strips,blocks per channel group,row groups per E-wave and step (1|2; 2 only with 4 E-waves)" (0 = automatic).
-int launch_expand_dw_wreg(const uint16_t* x_parts, int64_t x_plane, int B, int H, int W, int Cin, const uint16_t* w_parts, int64_t plane,
-                          int np, const float* sc_e, const float* sh_e, int act_e, int Cexp, const float* w_dw, int rate, const float* sc_d,
-                          const float* sh_d, int act_d, float* y, hipStream_t st, int y_fmt) {
-    const bool h16 = np == AMS_NP_F16;               // two fp16 parts (split_bf16.hpp)
-    if (h16) np = 2;
-    AMS_REQUIRE(expand_dw_stream_supported(Cin, Cexp, 1, rate) && Cin >= 64 && np >= 1 && np <= 3 && x_parts, "expand_dw_wreg: unsupported shape Cin=%d Cexp=%d rate=%d",
-                Cin, Cexp, rate);
-    AMS_REQUIRE(y_fmt == 0 || (h16 && Cexp % 8 == 0), "expand_dw_wreg: the fp16-pair output needs the fp16 form and Cexp %% 8 == 0");
-    AMS_REQUIRE(B > 0 && H > 0 && W > 0, "expand_dw_wreg: empty input");
+int launch_expand_dw_wreg(const BlockCall& c, hipStream_t st) {
+    RUN_RC(block_call_check("expand_dw_wreg", BK_WREG, c));
+    const int B = c.B, H = c.H, W = c.W, Cin = c.Cin, Cexp = c.Cexp, rate = c.rate;
+    const bool h16 = c.expand.np == AMS_NP_F16;      // two fp16 parts (split_bf16.hpp)
+    const int np = h16 ? 2 : c.expand.np;
     AMS_REQUIRE((int64_t)H * W * Cexp * 4 < 0x7fffffffLL, "expand_dw_wreg: a frame of the output exceeds 2 GiB");
     int nwe = 4, nsy_force = 0, nsx_force = 0, groups_force = 0, nrg = 2;
     if (knobs().xwr_set) { const int* f = knobs().xwr; nwe = f[0]; nsy_force = f[1]; nsx_force = f[2]; groups_force = f[3]; nrg = f[4]; }
@@ -519,12 +516,12 @@ int launch_expand_dw_wreg(const uint16_t* x_parts, int64_t x_plane, int B, int H
         while ((int64_t)B * rate * rate * cgroups * nsx * nsy < 512 && (Hs + nsy - 1) / nsy > 8) ++nsy;
     XwrArgs a;
     memset(&a, 0, sizeof(a));
-    a.xs = x_parts; a.xs_plane = x_plane; a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.wp = w_parts; a.plane = plane; a.sc_e = sc_e; a.sh_e = sh_e;
-    a.act_e = act_e; a.Cexp = Cexp; a.w_dw = w_dw; a.sc_d = sc_d; a.sh_d = sh_d; a.act_d = act_d; a.y = y; a.rate = rate;
+    a.xs = c.x_parts; a.xs_plane = c.x_plane; a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.wp = c.expand.panels; a.plane = c.expand.plane; a.sc_e = c.expand.scale;
+    a.sh_e = c.expand.shift; a.act_e = c.expand.act; a.Cexp = Cexp; a.w_dw = c.dw.w; a.sc_d = c.dw.scale; a.sh_d = c.dw.shift; a.act_d = c.dw.act; a.y = c.y; a.rate = rate;
     a.SH = (Hs + nsy - 1) / nsy; a.SW = SW; a.Wp = SW + 2; a.T = ((a.SH + 2) * a.Wp + step - 1) / step; a.ring = ring;
     a.nsy = nsy; a.nsx = nsx; a.cgroups = cgroups;
     a.items = B * rate * rate * nsy * nsx;
-    a.y_fmt = y_fmt;
+    a.y_fmt = c.y_fmt;
     int64_t groups = groups_force > 0 ? groups_force : (512 + cgroups - 1) / cgroups;      // one block per CU (LDS), twice over
     if (groups > a.items) groups = a.items;
     a.groups = (int)groups;

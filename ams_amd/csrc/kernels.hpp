@@ -8,6 +8,11 @@ struct ams_comm;
 
 namespace ams {
 
+// block_call.hpp: a frozen conv layer and a frozen block as the host describes them, and block_call_check, which every launcher that takes
+// a BlockCall goes through first (one order of refusal)
+struct ConvLayer;
+struct BlockCall;
+
 // ---- runtime.hip : per-device launch bookkeeping, environment knobs (read once) --------------------------
 // allow `lds` bytes of dynamic LDS for kernel `fn` on the CURRENT device (no-op up to 64 KB; set once per device and size)
 int func_allow_lds(const void* fn, size_t lds);
@@ -103,6 +108,14 @@ struct PwArgs {
     const float* x_v0; const float* x_v1; const float* x_v2; const float* x2;
     float* x_tmp;
 };
+// dense [M][K] x [K][N] -> [M][ldy], no epilogue: the starting point of every PwArgs
+static inline PwArgs pw_args(const float* x, int64_t M, int K, int ldx, const float* w, int N, float* y, int ldy) {
+    PwArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = x; a.M = M; a.K = K; a.Kw = K; a.ldx = ldx; a.w = w; a.w_sk = N; a.w_sn = 1; a.N = N;
+    a.rows_per_img = 1; a.act = AMS_ACT_NONE; a.y = y; a.ldy = ldy;
+    return a;
+}
 int launch_pointwise(const PwArgs& a, hipStream_t st);
 // x' of PwArgs::x_mode written to a.x_tmp by the elementwise kernels the transform replaces; on return *b is `a` without the transform
 int pointwise_materialize_x(const PwArgs& a, PwArgs* b, hipStream_t st);
@@ -132,9 +145,9 @@ bool pointwise_split_writes_parts(const PwArgs& a);      // the split kernels wi
 // the frozen head's three GEMMs (aspp0 -> concat_projection + per-image bias -> logits) as one kernel on the same fp16 panels, bit-identical to
 // the three launch_pointwise_split_f16 calls it replaces (k_head_chain.hip); y [M][32], NC <= 32 columns written
 bool head_chain_supported(int KA, int NA, int KB, int NB, int KC, int NC);
-int launch_head_chain(const float* x, int64_t M, int KA, const uint16_t* wA, int64_t planeA, const float* scA, const float* shA, int actA,
-                      const uint16_t* wB, int64_t planeB, const float* scB, const float* shB, int actB, const float* img_bias, int64_t rows_per_img,
-                      const uint16_t* wC, int64_t planeC, const float* biasC, int actC, int NC, float* y, hipStream_t st);
+// A, B, C: the layers' fp16 panels, planes, BN vectors (C: shift = its bias, no scale) and activations
+int launch_head_chain(const float* x, int64_t M, int KA, const ConvLayer& A, const ConvLayer& B, const ConvLayer& C, const float* img_bias,
+                      int64_t rows_per_img, int NC, float* y, hipStream_t st);
 
 // dw[K,N] = x[M,K]^T @ dy[M,N];  scratch holds the per-split partial products.
 struct WgArgs {
@@ -152,8 +165,8 @@ struct WgArgs {
 };
 // fused depthwise 3x3 (+BN+act) -> project 1x1 (+BN, +residual), frozen inference, split-bf16 GEMM (k_dw_project.hip)
 bool dw_project_supported(int C, int N, int stride, int rate);
-int launch_dw_project(const float* e, int B, int H, int W, int C, const float* w_dw, int rate, const float* sc_d, const float* sh_d,
-                      int act_d, const PwArgs& p, const uint16_t* whi, const uint16_t* wlo, int Kp, hipStream_t st);
+// c.x: the expanded tensor [B][H][W][Cexp]; the project layer's two-part bf16 panels [Cout][Cexp]; c.res with c.residual
+int launch_dw_project(const BlockCall& c, hipStream_t st);
 bool pointwise_wgrad_x6_applies(int64_t M, int K, int N, int ldx, int ldy);
 int wgrad_x6_splits(int64_t M, int K, int N);
 int launch_pointwise_wgrad_x6(const WgArgs& a, int splits, hipStream_t st);
@@ -175,15 +188,11 @@ struct FirstBlockPlan {
 // occupancy: null = ask the device (blocks per CU of the two walking kernels, CUs); else {interior blocks per CU, border blocks per CU, CUs}:
 // pure host arithmetic, no device call
 int first_block_plan(int dtype, int B, int H, int W, bool h16, const int* occupancy, FirstBlockPlan* plan);
-int launch_first_block(const void* frames, int dtype, int B, int H, int W, float pixel_scale, const float* w_stem,
-                       const float* sc_s, const float* sh_s, int act_s, const float* w_dw, const float* sc_d, const float* sh_d,
-                       int act_d, const float* w_pj, const float* sc_p, const float* sh_p, int act_p, float* y, hipStream_t st,
-                       const uint16_t* w_parts = nullptr, int64_t w_plane = 0, const uint16_t* h_stem = nullptr, int64_t h_stem_plane = 0,
-                       const uint16_t* h_pj = nullptr, int64_t h_pj_plane = 0, FirstBlockPlan* plan_out = nullptr);
-// h_stem / h_pj: optional fp16 panels (hi | lo 2^11) of the stem [part][32][32] and of the project layer [part][16][32]: with both, the stem's and
-// the project layer's products run as 3 fp16 MFMAs each (AMS_MATMUL_SPLIT_F16; takes precedence over w_parts)
-// w_parts: optional three-part bf16 panels [part][32][32] of the stem weights (k = tap * 3 + channel, zero-padded 27 -> 32): with them and
-// uint8 frames the stem's products run as six bf16 MFMAs, operands from a 258-entry table of the normalised byte values (f32-level)
+int launch_first_block(const BlockCall& c, hipStream_t st, FirstBlockPlan* plan_out = nullptr);
+// c.expand = the stem.  Panels of the stem and the project layer as fp16 parts (hi | lo 2^11; [part][32][32] and [part][16][32]): the stem's and
+// the project layer's products run as 3 fp16 MFMAs each (AMS_MATMUL_SPLIT_F16)
+// three-part bf16 panels [part][32][32] of the stem alone (k = tap * 3 + channel, zero-padded 27 -> 32): with them and uint8 frames the
+// stem's products run as six bf16 MFMAs, operands from a 258-entry table of the normalised byte values (f32-level)
 
 // ---- k_ingest.hip : frame / label resize on the device (run.py:179-183)
 int launch_resize_u8(const uint8_t* src, int Hs, int Ws, int C, int mode, int swap_rb, uint8_t* dst, int H, int W, hipStream_t st);
@@ -222,12 +231,10 @@ int launch_depthwise_wgrad(const float* x, const float* dy, int B, int H, int W,
 
 // ---- k_expand_dw.hip : fused expand (1x1+BN+ReLU6) -> depthwise 3x3 (+BN+ReLU6), frozen inference ------------
 bool expand_dw_supported(int Cin, int Cexp, int stride, int rate);
-// stats_part != nullptr (fine-tune forward; sc_d / sh_d / act_d then describe what is WRITTEN, normally the identity): partial rows
+// stats_part != nullptr (fine-tune forward; c.dw's scale / shift / act then describe what is WRITTEN, normally the identity): partial rows
 // [*stats_rows][2][Cexp] of sum(y - center), sum((y - center)^2) of the written values, expand_dw_stats_scratch floats
 size_t expand_dw_stats_scratch(int B, int H, int W, int Cexp, int stride);
-int launch_expand_dw(const float* x, int B, int H, int W, int Cin, const float* w_exp, const float* sc_e, const float* sh_e, int act_e,
-                     int Cexp, const float* w_dw, int stride, int rate, const float* sc_d, const float* sh_d, int act_d, float* y,
-                     hipStream_t st, const float* stats_center = nullptr, float* stats_part = nullptr, int* stats_rows = nullptr);
+int launch_expand_dw(const BlockCall& c, hipStream_t st, const float* stats_center = nullptr, float* stats_part = nullptr, int* stats_rows = nullptr);
 
 // ---- k_xdw_train.hip : fine-tune step of the early blocks (Cin <= 32) without the 6x-expanded tensors: every consumer recomputes
 // z_e = x . W_e from the block input (see the file header)
@@ -267,36 +274,25 @@ int launch_expand_stats(const double* xx64, int Cin, const float* w_exp, int Cex
 
 // ---- k_block.hip : a whole early inverted-residual block (expand -> depthwise -> project [+ input]) in one kernel ----
 bool block_fused_supported(int Cin, int Cexp, int Cout, int stride, int rate, bool residual);
-int launch_block_fused(const float* x, int B, int H, int W, int Cin, const float* w_exp, const float* sc_e, const float* sh_e, int act_e, int Cexp,
-                       const float* w_dw, int stride, const float* sc_d, const float* sh_d, int act_d, const float* w_pj, const float* sc_p,
-                       const float* sh_p, int act_p, int Cout, bool residual, float* y, hipStream_t st, const float* vecs = nullptr,
-                       const uint16_t* wparts = nullptr, int64_t wplane = 0, const uint16_t* h_exp = nullptr, int64_t h_exp_plane = 0,
-                       const uint16_t* h_pj = nullptr, int64_t h_pj_plane = 0, int h_pj_kp = 0);
-// h_exp / h_pj: optional fp16 panels (hi | lo 2^11, `plane` apart) of the expand layer [part][Cexp][32] and the project layer
-// [part][Cout][h_pj_kp]: with both, the expand and the project products run as 3 fp16 MFMAs each (AMS_MATMUL_SPLIT_F16; takes precedence over wparts)
-// wparts: optional three-part bf16 panels [part][Cexp][32] of the expand weights (parts `wplane` apart): with them the expand products of
-// a block with Cin 24 / 32 run as six bf16 MFMAs (f32-level) instead of eight exact-f32 MFMAs
-// vecs: optional [13][Cexp] table (sc_e | sh_e | sc_d | sh_d | w_dw[9]) built once by launch_block_pack (the engine: at freeze)
-int launch_first_block_tiles(const void* frames, int dtype, int B, int H, int W, float pixel_scale, const float* w_stem, const float* sc_s,
-                             const float* sh_s, int act_s, const float* w_dw, const float* sc_d, const float* sh_d, int act_d, const float* w_pj,
-                             const float* sc_p, const float* sh_p, int act_p, float* y, hipStream_t st, const float* vecs = nullptr);
+int launch_block_fused(const BlockCall& c, hipStream_t st);
+// fp16 panels (hi | lo 2^11) of the expand layer [part][Cexp][32] and the project layer [part][Cout][Kp]: the expand and the project
+// products run as 3 fp16 MFMAs each (AMS_MATMUL_SPLIT_F16)
+// three-part bf16 panels [part][Cexp][32] of the expand layer alone: the expand products of a block with Cin 24 / 32 run as six bf16 MFMAs
+// (f32-level) instead of eight exact-f32 MFMAs
+// c.vecs: optional [13][Cexp] table (sc_e | sh_e | sc_d | sh_d | w_dw[9]) built once by launch_block_pack (the engine: at freeze)
+int launch_first_block_tiles(const BlockCall& c, hipStream_t st);
 int launch_block_pack(const float* sc_e, const float* sh_e, const float* sc_d, const float* sh_d, const float* w_dw, int Cexp, float* out, hipStream_t st);
 
-constexpr int AMS_NP_F16 = 4;   // `np` of the streaming launchers: the two fp16 parts of split_bf16.hpp
+constexpr int AMS_NP_F16 = 4;   // ConvLayer::np: the two fp16 parts of split_bf16.hpp
 // ---- k_xdw_stream.hip : the same fusion for the stride-16 blocks (Cin 64 / 96 / 160, stride 1, rate 1 | 2): raster-order
 // streaming through an LDS ring, split-bf16 products from the expand layer's bf16 panels (np = 2 | 3 parts, `plane` apart)
 bool expand_dw_stream_supported(int Cin, int Cexp, int stride, int rate);
-int launch_expand_dw_stream(const float* x, const uint16_t* x_parts, int64_t x_plane, int B, int H, int W, int Cin, const float* w_f32,
-                            const uint16_t* w_parts, int64_t plane, int np,
-                            const float* sc_e, const float* sh_e, int act_e, int Cexp, const float* w_dw, int stride, int rate, const float* sc_d,
-                            const float* sh_d, int act_d, float* y, hipStream_t st, int y_fmt = 0);
+int launch_expand_dw_stream(const BlockCall& c, hipStream_t st);
 
 // ---- k_xdw_wreg.hip : the streaming fusion with the expand weights in registers and the operand staged in LDS (160 -> 960)
-int launch_expand_dw_wreg(const uint16_t* x_parts, int64_t x_plane, int B, int H, int W, int Cin, const uint16_t* w_parts, int64_t plane,
-                          int np, const float* sc_e, const float* sh_e, int act_e, int Cexp, const float* w_dw, int rate, const float* sc_d,
-                          const float* sh_d, int act_d, float* y, hipStream_t st, int y_fmt = 0);
-// np of the two streaming launchers: 1 .. 3 bf16 parts, or AMS_NP_F16 = the two fp16 parts of split_bf16.hpp (hi | lo 2^11; planes as for
-// np = 2).  y_fmt 1 (fp16 form only): the result as fp16 pairs interleaved per 8 channels (PwArgs::x_fmt 1) instead of f32
+int launch_expand_dw_wreg(const BlockCall& c, hipStream_t st);
+// c.expand.np of the two streaming launchers: 1 .. 3 bf16 parts, or AMS_NP_F16 = the two fp16 parts of split_bf16.hpp (hi | lo 2^11; planes as
+// for np = 2).  c.y_fmt 1 (fp16 form only): the result as fp16 pairs interleaved per 8 channels (PwArgs::x_fmt 1) instead of f32
 
 
 // ---- k_elementwise.hip : BN pieces, pooling, reductions, Adam ------------------------------------------

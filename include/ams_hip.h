@@ -698,6 +698,10 @@ int ams_k_pointwise_split3(const float* x, int64_t M, int32_t K, const float* w,
                            const float* shift, int32_t act, const float* res, float* y, uint16_t* panels,
                            size_t panel_elems, void* stream);
 
+/* The frozen-block entries (ams_k_expand_dw, ams_k_block_fused[_f16], ams_k_expand_dw_stream[_f16], ams_k_dw_project, ams_k_first_block[_tiles])
+ * refuse with AMS_E_INVALID, in this order and in front of their first launch: (first block) frames that are not uint8 / float32; B, H or W <= 0;
+ * an unsupported shape, unknown form or number of parts; panels == NULL or panel_elems below what the call needs in all ("need N"); a NULL
+ * tensor, weight or BN vector (res may be NULL: no residual). */
 /* K4+K3 fused (frozen inference): y = relu6(bn_d(dw3x3(relu6(bn_e(x @ w_exp))))) for an inverted-residual block whose
  * input has Cin <= 64 channels; the expanded tensor never reaches HBM.  x [B,H,W,Cin], w_exp [Cin,Cexp], w_dw [3,3,Cexp,1],
  * y [B,Ho,Wo,Cexp] (SAME, stride 1|2, rate 1).  Cexp % 32 == 0 or % 48 == 0. */

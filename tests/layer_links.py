@@ -430,7 +430,7 @@ class Links:
 # what the default (fused) step stores, and the links that close across what it does not
 # ---------------------------------------------------------------------------------------------------------
 def recompute_expand(spec) -> set:
-    """idx of the expand layers of the recompute blocks, expanded_conv_1 .. _6 (train_recompute_block, engine_forward.hip:498-506:
+    """idx of the expand layers of the recompute blocks, expanded_conv_1 .. _6 (train_recompute_block, engine_forward.hip:508-516:
     xdw_train_supported = block input of 8 .. 32 channels, a multiple of 4)"""
     return {l.idx for l in spec.layers if l.scope.startswith("MobilenetV2") and l.scope.endswith("/expand") and 8 <= l.cin <= 32 and l.cin % 4 == 0}
 
@@ -440,13 +440,13 @@ def default_step_stored(spec, H: int, B: int) -> frozenset:
     mode) writes with their plain meaning on B frames of H x 2H, from the layer table and the case's size alone.  Each rule mirrors a
     predicate of the engine (scratch sizes are taken to fit):
 
-      z   every BN layer but the recompute blocks' expand layers: train_recompute_block (engine_forward.hip:498-506) sends the block
-          through launch_expand_dw, which writes the depthwise z only (:631-666)
-      a   the project layers (:696 act_pass: role project, and operand_bn_act is false for them) and image_pooling, aspp0,
-          concat_projection (:706, :713, :717).  NOT the stem (stem_fused_train :520-525 makes dw_fused_train_fwd(2) true, :626), NOT the
-          late expand layers (dw_fused_train :511-517 / dw_fused_train_fwd :526-530: stride-1 depthwise behind an expand layer outside a
-          recompute block, :696), NOT any depthwise layer (operand_bn_act :534-539: a depthwise layer in front of a project layer whose
-          channels are a multiple of 4, :664, :696)
+      z   every BN layer but the recompute blocks' expand layers: train_recompute_block (engine_forward.hip:508-516) sends the block
+          through launch_expand_dw, which writes the depthwise z only (:641-678)
+      a   the project layers (:708 act_pass: role project, and operand_bn_act is false for them) and image_pooling, aspp0,
+          concat_projection (:718, :725, :729).  NOT the stem (stem_fused_train :530-535 makes dw_fused_train_fwd(2) true, :636), NOT the
+          late expand layers (dw_fused_train :521-527 / dw_fused_train_fwd :536-540: stride-1 depthwise behind an expand layer outside a
+          recompute block, :708), NOT any depthwise layer (operand_bn_act :544-549: a depthwise layer in front of a project layer whose
+          channels are a multiple of 4, :676, :708)
       dz  the project layers (dzp for the residual ones, engine_plan.hip:266, else in place: engine_backward.hip:210, :223, :226); the late
           expand layers (in place behind launch_depthwise_dgrad_bn's rows, :215-223); the depthwise layers of the recompute blocks and of
           the first block (fold_apply needs dw_fused_train, false for them: :213, so :223 or :226 writes dz in place); aspp0 and
@@ -487,7 +487,7 @@ def default_step_plan(links):
 
     Covered
       F1  the stem (frames -> z, launch_stem); the expand layers of the late blocks (x = the previous project layer's a, always
-          written: engine_forward.hip:696-698 act_pass is true for a project layer); image_pooling, aspp0, concat_projection, logits
+          written: engine_forward.hip:708-710 act_pass is true for a project layer); image_pooling, aspp0, concat_projection, logits
       F2  every project layer (its a and its residual source, another project layer's a, are written); image_pooling, aspp0,
           concat_projection
       F3  every layer whose z is written: all but the expand layers of the recompute blocks
@@ -501,12 +501,12 @@ def default_step_plan(links):
           gradient added, engine_backward.hip:340-352; dz goes to dzp, so da survives)
     Covered by the composite plan (layer_links.composite_plan, test_every_link_of_the_default_step: the links close across the tensors
     that are not stored, from the nearest stored one)
-      F1 / F2 / F3 / B1 / B2 of the recompute blocks' expand layers: z_e, a_e, da_e, dz_e are never stored (engine_forward.hip:632-667,
+      F1 / F2 / F3 / B1 / B2 of the recompute blocks' expand layers: z_e, a_e, da_e, dz_e are never stored (engine_forward.hip:642-679,
           engine_backward.hip:221-275)
       F1 of every depthwise layer, F2 of every expand layer and of the stem: the expand layer's / the stem's a is applied on the depthwise
-          kernel's tap loads and not written (engine_forward.hip:627, :670-679, :697)
+          kernel's tap loads and not written (engine_forward.hip:637, :682-691, :709)
       F1 and B1 of every project layer, F2 of every depthwise layer: the depthwise a is applied on the project GEMM's operand loads and not
-          written (operand_bn_act, engine_forward.hip:685-689, engine_backward.hip:331)
+          written (operand_bn_act, engine_forward.hip:697-701, engine_backward.hip:331)
       B1 / B2 of every depthwise layer: with the apply pass folded into the depthwise backward kernel its dz is never formed, the da buffer
           keeps dy = da * mask (engine_backward.hip:206-216, :305-308); the recompute blocks' depthwise dz is formed but its consumer's
           tensors are not
