@@ -365,6 +365,32 @@ int ams_student_set_loss_weights(ams_student* s, const float* class_weights_host
     return AMS_OK;
 }
 
+int ams_student_set_loss_mining(ams_student* s, float top_k, void* scratch_dev, size_t scratch_bytes) {
+    AMS_REQUIRE(s, "set_loss_mining: null student");
+    AMS_REQUIRE(s->cfg.trainable, "set_loss_mining: this student was created frozen");
+    RUN(mining_top_k_check("set_loss_mining", top_k));
+    if (top_k < 1.f) {
+        const ams_student_config& c = s->cfg;
+        AMS_REQUIRE(ce_loss_grad_supported(s->w, c.width), "set_loss_mining: %d output columns on %d logit columns is outside the one-pass loss kernel", c.width, s->w);
+        const size_t need = loss_mining_scratch(c.max_batch, c.height, c.width);
+        AMS_REQUIRE(scratch_dev && ((uintptr_t)scratch_dev & 15) == 0 && scratch_bytes >= need,
+                    "set_loss_mining: scratch NULL, misaligned or too small (need %zu bytes, 16-byte aligned)", need);
+    }
+    s->mining_top_k = top_k;
+    if (scratch_dev != s->mining_scratch) s->mining_ran = false;       // another block: nothing of a mined step in it yet
+    s->mining_scratch = scratch_dev;
+    return AMS_OK;
+}
+
+int ams_student_mining_result(ams_student* s, ams_mining_result* out_host, void* stream) {
+    AMS_REQUIRE(s && out_host, "mining_result: null pointer");
+    if (!s->mining_ran || !s->mining_scratch) { set_error("mining_result: no mined step has run (ams_student_set_loss_mining with top_k < 1)"); return AMS_E_STATE; }
+    const MiningBuffers m = loss_mining_buffers(s->mining_scratch, s->cfg.max_batch, s->cfg.height, s->cfg.width);
+    AMS_CHECK_HIP(hipMemcpyAsync(out_host, m.result, sizeof(ams_mining_result), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    AMS_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
+    return AMS_OK;
+}
+
 int ams_student_set_option(ams_student* s, int32_t option, int32_t value) {
     AMS_REQUIRE(s, "set_option: null student");
     s->dual_choice.clear();                            // any option may change the plans the autotune compared
@@ -986,6 +1012,52 @@ int ams_k_ce_loss_grad_weighted(const float* logits, int32_t B, int32_t h, int32
     const LossObjective o{teacher_logits, th, tw, layout, temperature, alpha, class_weights_host, conf_gamma};
     // the one entry that takes NULL teacher logits: when neither the mix nor the weight looks at them
     return ce_loss_grad_entry("ce_loss_grad_weighted", c, o, conf_gamma != 0.f || alpha != 0.f, loss_dev, dlogits, scratch, scratch_floats, stream);
+}
+
+size_t ams_k_loss_mining_scratch(int32_t B, int32_t H, int32_t W) { return loss_mining_scratch(B, H, W); }
+
+// The weighted entry's refusals in its order (ce_loss_grad_entry), then top_k, the mining scratch and the outputs; then steps 1 - 3 and the weighted
+// entry's two launches on the mined map
+int ams_k_ce_loss_grad_mined(const float* logits, int32_t B, int32_t h, int32_t w, int32_t ld, int32_t NC, const int32_t* class_idx_host, int32_t K,
+                             int32_t H, int32_t W, const uint8_t* teacher, const float* teacher_logits, int32_t th, int32_t tw, int32_t layout,
+                             double* loss_dev, float* dlogits, float* scratch, size_t scratch_floats, void* stream, float temperature, float alpha,
+                             const float* class_weights_host, float conf_gamma, float top_k, uint8_t* labels_out_dev, float* key_out_dev,
+                             ams_mining_result* result_dev, void* mining_scratch_dev, size_t mining_scratch_bytes) {
+    const char* who = "ce_loss_grad_mined";
+    HeadCall c{logits, ld, B, h, w, class_idx_host, K, H, W, teacher, NC};
+    const LossObjective o{teacher_logits, th, tw, layout, temperature, alpha, class_weights_host, conf_gamma};
+    RUN(kd_params_check(who, o.temperature, o.alpha));
+    RUN(loss_weights_check(who, o.class_weights, c.K, c.K, o.conf_gamma));
+    AMS_REQUIRE(o.teacher_logits || (conf_gamma == 0.f && alpha == 0.f), "%s: null teacher logits (alpha %g, conf_gamma %g)", who, (double)o.alpha, (double)o.conf_gamma);
+    AMS_REQUIRE(c.cls, "%s: null class table", who);
+    AMS_REQUIRE(c.K >= 1 && c.K <= 32, "%s: K=%d out of range (1..32)", who, c.K);
+    AMS_REQUIRE(tlogits_layout_ok(o.layout), "%s: unknown teacher-logit layout %d", who, o.layout);
+    AMS_REQUIRE(c.ld >= c.NC && c.ld <= 256, "%s: row stride %d must hold %d classes", who, c.ld, c.NC);
+    AMS_REQUIRE(ce_loss_grad_supported(c.w, c.W), "%s: %d output columns on %d source columns is outside the one-pass kernel", who, c.W, c.w);
+    AMS_REQUIRE(scratch && scratch_floats >= ce_loss_grad_scratch(c.B, c.h, c.w, c.K), "%s: scratch too small (need %zu floats)", who,
+                ce_loss_grad_scratch(c.B, c.h, c.w, c.K));
+    RUN(mining_top_k_check(who, top_k));
+    hipStream_t st = (hipStream_t)stream;
+    if (top_k < 1.f) {
+        AMS_REQUIRE(B >= 1 && H >= 1 && W >= 1, "%s: no pixels: B=%d, %d x %d", who, B, H, W);
+        AMS_REQUIRE(mining_scratch_dev && ((uintptr_t)mining_scratch_dev & 15) == 0 && mining_scratch_bytes >= loss_mining_scratch(B, H, W),
+                    "%s: mining scratch NULL, misaligned or too small (need %zu bytes, 16-byte aligned)", who, loss_mining_scratch(B, H, W));
+        AMS_REQUIRE(labels_out_dev && result_dev, "%s: null output (mined labels, result)", who);
+        AMS_REQUIRE(((uintptr_t)result_dev & 7) == 0 && ((uintptr_t)key_out_dev & 3) == 0, "%s: misaligned output", who);
+        MiningBuffers m = loss_mining_buffers(mining_scratch_dev, B, H, W);
+        m.labels = labels_out_dev;
+        m.result = result_dev;
+        if (key_out_dev) m.keys = key_out_dev;
+        AMS_REQUIRE(loss_dev && dlogits, "%s: null pointer", who);
+        RUN(launch_loss_mining(c, o, top_k, m, st));
+        c.teacher = labels_out_dev;
+    } else {
+        AMS_REQUIRE(labels_out_dev, "%s: null output (mined labels)", who);
+        AMS_REQUIRE(c.logits && c.teacher && loss_dev && dlogits && B >= 1 && H >= 1 && W >= 1, "%s: null pointer", who);
+        AMS_CHECK_HIP(hipMemcpyAsync(labels_out_dev, teacher, (size_t)B * H * W, hipMemcpyDeviceToDevice, st));
+    }
+    RUN(launch_ce_loss_grad(c, o, loss_dev, scratch, st));
+    return launch_ce_combine(c, loss_dev, scratch, dlogits, c.ld, st);
 }
 
 size_t ams_k_pointwise_wgrad_scratch(int64_t M, int32_t K, int32_t N) { return pointwise_wgrad_scratch(M, K, N); }

@@ -168,6 +168,11 @@ struct ams_student {
     // points at loss_cw once they are set).  The defaults are the reference's loss; the step runs objective_of_step(loss_objective)
     ams::LossObjective loss_objective;
     float loss_cw[32];
+    // hard-pixel mining (ams_student_set_loss_mining): the fraction kept, 1 = off (the step launches nothing extra); the CALLER's scratch block
+    // (loss_mining_buffers: key map, mined labels, histograms, result); whether a mined step has left a result in it
+    float mining_top_k = 1.f;
+    void* mining_scratch = nullptr;
+    bool mining_ran = false;
     const uint8_t* reg_mask = nullptr; int reg_nvars = 0; float reg_coef = 0.f;
     int nan_grads = 0;               // a batch without a valid pixel: NaN loss, ZERO gradients — what TensorFlow computes for utils/graph_utils.py:408
                                      // (reduce_mean over the empty boolean_mask: its gradient is an empty tensor, densified to zeros); 1 = NaN gradients (AMS_OPT_NAN_GRADS)

@@ -382,6 +382,23 @@ int loss_forward(ams_student* s, const uint8_t* teacher, int B, int32_t* labels,
     return launch_upsample_argmax(student_head_call(s, B, teacher), labels, s->conf_buf, s->loss_buf, st);
 }
 
+// Steps 1 - 3 of a mined step (k_loss_mining.hip) on the student's logits: *mined = the label map the loss and the backward then see, in the
+// caller's scratch block.  The objective is the step's own, so the keys rank the pixels by what the loss kernel is about to sum.
+static int mine_labels(ams_student* s, const uint8_t* teacher, int B, hipStream_t st, const uint8_t** mined) {
+    const ams_student_config& c = s->cfg;
+    const LossObjective o = objective_of_step(s->loss_objective);
+    AMS_REQUIRE(o.soft_teacher || o.conf_gamma == 0.f, "train_step: conf_gamma %g weights by the teacher's confidence: it needs soft_teacher (AMS_OPT_SOFT_TEACHER)",
+                (double)o.conf_gamma);
+    const MiningBuffers m = loss_mining_buffers(s->mining_scratch, c.max_batch, c.height, c.width);
+    const int64_t n = (int64_t)B * c.height * c.width;
+    RUNK(0, 4.0 * n, launch_mining_keys(student_head_call(s, B, teacher), o, s->mining_top_k, m, st));
+    RUNK(0, 12.0 * n, launch_mining_select(n, s->mining_top_k, m, st));
+    RUNK(0, 6.0 * n, launch_mining_relabel(teacher, n, m, st));
+    s->mining_ran = true;
+    *mined = m.labels;
+    return AMS_OK;
+}
+
 int train_step_impl(ams_student* s, const void* frames_dev, int32_t frames_dtype, const uint8_t* teacher_dev,
                            int32_t batch, int32_t global_batch, float lr, const uint8_t* mask_dev, double* loss_dev,
                            ams_allreduce_cb cb, void* user, ams_comm* comm, void* stream) {
@@ -393,9 +410,15 @@ int train_step_impl(ams_student* s, const void* frames_dev, int32_t frames_dtype
     AMS_REQUIRE(!s->loss_objective.soft_teacher || s->loss_objective.teacher_logits, "train_step: soft_teacher is on but no teacher logits are fed (ams_student_feed_teacher_logits)");
     hipStream_t st = (hipStream_t)stream;
     if (comm) cb = comm_as_cb;
+    // mining off (the default): nothing below differs from the step without it, launch for launch
+    const bool mined = s->mining_top_k < 1.f;
+    AMS_REQUIRE(!mined || !cb, "train_step: loss mining (top_k %g) on a step with an all-reduce callback or an RCCL communicator: a global threshold "
+                "needs the ranks' histograms summed (ams_student_set_loss_mining)", (double)s->mining_top_k);
+    AMS_REQUIRE(!mined || s->mining_scratch, "train_step: loss mining without a scratch block (ams_student_set_loss_mining)");
     SyncCtx sc{cb, user, s, comm};
     const SyncCtx* psc = cb ? &sc : nullptr;
     RUN(forward_live(s, frames_dev, frames_dtype, batch, global_batch, /*update_ema=*/true, psc, st));
+    if (mined) RUN(mine_labels(s, teacher_dev, batch, st, &teacher_dev));       // the loss and the backward see the mined map
     RUN(loss_forward(s, teacher_dev, batch, nullptr, st));
     RUN(sync_doubles(psc, s->loss_buf, 2, st));         // loss sum and valid-pixel count over all ranks
     RUN(backward(s, frames_dev, frames_dtype, teacher_dev, batch, global_batch, psc, st));

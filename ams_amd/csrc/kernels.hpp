@@ -420,6 +420,19 @@ int launch_upsample_confidence(const HeadCall& c, uint8_t* conf_u8, float* conf_
 int soft_metric_stats_len(int K);
 int launch_upsample_soft_metric(const HeadCall& c, const LossObjective& o, int64_t* stats, float* p_f32, float* ce_f32, hipStream_t st);
 
+// ---- k_loss_mining.hip : hard-pixel mining for the fine-tune loss: the key map, the key of rank k from the top, the mined label map ----
+// keys f32 [B][H][W], labels uint8 [B][H][W] (the mined map), hist: three histograms and the state words, result: 8-byte aligned; all on the device
+struct MiningBuffers { float* keys = nullptr; uint8_t* labels = nullptr; uint32_t* hist = nullptr; ams_mining_result* result = nullptr; };
+size_t loss_mining_scratch(int B, int H, int W);                        // bytes of a block that holds all four
+MiningBuffers loss_mining_buffers(void* scratch, int B, int H, int W);  // the four inside such a block (16-byte aligned)
+int mining_top_k_check(const char* who, float top_k);
+// c.teacher: the labels the map is mined from; o: the objective whose per-pixel value is the key.  Steps 1 - 3 of a mined step (the fourth is
+// launch_ce_loss_grad / launch_ce_combine on m.labels); the step's profiler times them one by one
+int launch_mining_keys(const HeadCall& c, const LossObjective& o, float top_k, const MiningBuffers& m, hipStream_t st);
+int launch_mining_select(int64_t n, float top_k, const MiningBuffers& m, hipStream_t st);
+int launch_mining_relabel(const uint8_t* labels, int64_t n, const MiningBuffers& m, hipStream_t st);
+int launch_loss_mining(const HeadCall& c, const LossObjective& o, float top_k, const MiningBuffers& m, hipStream_t st);
+
 // ---- k_replay.hip : the replay memory on the device: a mini-batch in one launch, cached teacher logits, the phi-score pairs ----
 // samples_host / pairs_host: the host copies of the device tables, checked before anything is launched
 int launch_replay_gather(const uint8_t* frame_slots, int64_t frame_stride, const uint8_t* label_slots, int64_t label_stride, int capacity, int Hs,

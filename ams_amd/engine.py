@@ -86,6 +86,7 @@ class StudentEngine:
         self.soft_teacher = False
         self.kd_temperature, self.kd_alpha = 1.0, 1.0
         self.loss_class_weights, self.conf_gamma = None, 0.0
+        self.loss_top_k, self._mining_scratch = 1.0, None
         self._reg_mask = self._teacher_logits_dev = None
         self._frames_b, self._frames_u8, self._frames_metric = 0, False, False
         self.class_indices = [int(c) for c in class_indices]
@@ -303,6 +304,33 @@ class StudentEngine:
         hip.check(self.lib.ams_student_set_loss_weights(self._h, cw.ctypes.data_as(C.POINTER(C.c_float)) if cw is not None else None,
                                                         int(cw.size) if cw is not None else 0, float(conf_gamma)), "ams_student_set_loss_weights")
         self.loss_class_weights, self.conf_gamma = cw, float(conf_gamma)
+
+    def set_loss_mining(self, top_k: float = 1.0) -> None:
+        """Hard-pixel mining (DeepLab's ``top_k_percent_pixels``; this project's own knob): a step's loss and gradient are those of the
+        objective over the fraction ``top_k`` in (0, 1] of the valid pixels whose own objective value is largest, ties at the threshold all
+        kept; the mean divides by what was kept.  ``1.0`` (the default) is the unmined step, launch for launch.  The scratch (key map, mined
+        labels, histograms, result) is a torch tensor of this engine's, allocated at the first ``top_k < 1``; the arena does not change."""
+        top_k = float(top_k)
+        if top_k < 1.0 and self._mining_scratch is None:
+            n = self.lib.ams_k_loss_mining_scratch(self.max_batch, self.height, self.width)
+            self._mining_scratch = torch.zeros(n, dtype=torch.uint8, device=self.device)
+        scr = self._mining_scratch
+        hip.check(self.lib.ams_student_set_loss_mining(self._h, top_k, C.c_void_p(scr.data_ptr() if scr is not None else 0),
+                                                       int(scr.numel()) if scr is not None else 0), "ams_student_set_loss_mining")
+        self.loss_top_k = top_k
+
+    def mining_result(self) -> dict:
+        """The last mined step's block: ``threshold`` (the k-th largest key), ``valid`` (n), ``rank`` (k) and ``kept``.  Synchronises."""
+        r = hip.MiningResult()
+        hip.check(self.lib.ams_student_mining_result(self._h, C.byref(r), self._stream()), "ams_student_mining_result")
+        return {"threshold": float(r.threshold), "valid": int(r.valid), "rank": int(r.rank), "kept": int(r.kept)}
+
+    def mined_labels(self, batch: int) -> torch.Tensor:
+        """The label map the last mined step of ``batch`` frames ran its loss on (uint8 [batch, H, W], a dropped pixel reads 255): a view of
+        the scratch, valid until the next mined step."""
+        n = self.max_batch * self.height * self.width
+        off = hip.MINING_KEYS_OFFSET + (4 * n + 15) // 16 * 16
+        return self._mining_scratch[off:off + batch * self.height * self.width].view(batch, self.height, self.width)
 
     def set_regularizer(self, on: bool, biases_only: bool = False, coef: float = 0.01) -> None:
         """create_student_v3(regularize=True[, train_biases_only=True]) (utils/graph_utils.py:451-456): loss += coef * mean over tvars of

@@ -85,6 +85,13 @@ class FirstBlockPlan(C.Structure):
                                          "interior_tiles", "interior_grid", "border_tiles", "border_grid", "border_walks")]
 
 
+class MiningResult(C.Structure):
+    """ams_mining_result: what a mined fine-tune step leaves (the k-th largest key, the valid pixels n, the rank k, the pixels kept)."""
+    _fields_ = [("threshold", C.c_float), ("valid", C.c_int64), ("rank", C.c_int64), ("kept", C.c_int64)]
+
+
+MINING_KEYS_OFFSET = 24832    # AMS_MINING_KEYS_OFFSET: the key map inside a mining scratch block; the mined labels follow it
+
 RENDER_VIEWS = tuple(f[0] for f in RenderOut._fields_)
 RENDER_TABLE_BYTES = 1120
 CONFIDENCE_BINS = 32          # AMS_CONFIDENCE_BINS
@@ -192,6 +199,11 @@ SIGNATURES = {
                                         _f32, _f32]),
     "ams_k_ce_loss_grad_weighted": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i32), _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _sz,
                                               _vp, _f32, _f32, C.POINTER(_f32), _f32]),
+    "ams_k_ce_loss_grad_mined": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i32), _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _sz,
+                                           _vp, _f32, _f32, C.POINTER(_f32), _f32, _f32, _vp, _vp, _vp, _vp, _sz]),
+    "ams_k_loss_mining_scratch": (_sz, [_i32, _i32, _i32]),
+    "ams_student_set_loss_mining": (C.c_int, [_vp, _f32, _vp, _sz]),
+    "ams_student_mining_result": (C.c_int, [_vp, _vp, _vp]),
     "ams_debug_launch_table_needs_attr": (C.c_int, [_i32, C.c_uint64, _sz]),
     "ams_debug_reload_knobs": (C.c_int, []),
     "ams_debug_phase_cycles": (C.c_int, [C.c_int32, C.POINTER(C.c_uint64), C.c_int32]),

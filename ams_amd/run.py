@@ -140,7 +140,14 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--kd_conf_gamma", type=float, default=None,
                    help="server: weight every pixel of the soft-teacher loss by the teacher's confidence (largest target probability) to this power "
                         "(extra flag; needs --soft_teacher; in [0, 8], default 0)")
-    p.add_argument("--horizon_k1s", default="16,32,64,128,256,512", help="horizon mode: training-window lengths in seconds (reference: hard-coded)")
+    p.add_argument("--loss_top_k", type=float, default=None,
+                   help="server: hard-pixel mining (extra flag; DeepLab's top_k_percent_pixels): every fine-tune step takes its loss over the hardest "
+                        "fraction F in (0, 1] of the valid pixels, chosen on the device.  Also writes <results>_mining.npy, one row (threshold, kept, "
+                        "valid) per training event from the phase's last iteration; evaluation stays unmined and every other file keeps its name")
+    p.add_argument("--loss_top_k_warmup", type=int, default=None,
+                   help="server: ease the mining in over the first N iterations of every phase (extra flag; needs --loss_top_k < 1; DeepLab's "
+                        "hard_example_mining_step): iteration it keeps min(1, it / N) F + (1 - min(1, it / N)), so iteration 0 is unmined")
+    p.add_argument("--horizon_k1s",default="16,32,64,128,256,512", help="horizon mode: training-window lengths in seconds (reference: hard-coded)")
     p.add_argument("--horizon_k2", type=int, default=256, help="horizon mode: evaluation window in seconds (reference: 256)")
     p.add_argument("--horizon_points", type=int, default=3, help="horizon mode: number of evaluation points (reference: 3)")
     return p
@@ -364,6 +371,8 @@ def train_model(ctx: Context, train_start, train_end, sampling_period, gpu_id, r
     fixed_weights = None if weights_flag is None or balanced else parse_loss_class_weights(weights_flag, int(class_weights(exp_num).sum()))
     conf_gamma = float(getattr(FLAGS, "kd_conf_gamma", None) or 0.0)
     loss_weights_log = []     # --loss_class_weights, per training phase: the K weights it ran under
+    mining_flag = getattr(FLAGS, "loss_top_k", None)
+    mining_log = []           # --loss_top_k, per training phase: (threshold, kept, valid) of its last iteration
     semantic_network = ctx.network_cls(meta_dir=FLAGS.student_checkpoint, class_weights_exp=class_weights(exp_num),
                                        height=FLAGS.height, gpu_id=gpu_id, scale=[1], mini_batch_size=FLAGS.batch_size,
                                        lr=FLAGS.lr, mem_frac=1, coord_frac=float(FLAGS.coord_fraction),
@@ -374,7 +383,8 @@ def train_model(ctx: Context, train_start, train_end, sampling_period, gpu_id, r
                                        **({"soft_teacher": True} if soft_teacher else {}),
                                        **{k: float(getattr(FLAGS, k)) for k in ("kd_temperature", "kd_alpha", "kd_conf_gamma")
                                           if getattr(FLAGS, k, None) is not None},
-                                       **({"loss_class_weights": fixed_weights} if fixed_weights is not None else {}))
+                                       **({"loss_class_weights": fixed_weights} if fixed_weights is not None else {}),
+                                       **{k: getattr(FLAGS, k) for k in ("loss_top_k", "loss_top_k_warmup") if getattr(FLAGS, k, None) is not None})
     save_dir = ctx.save_dir(run_label + "_%d" % train_start)
     semantic_network.save_to_frozen_graph(save_dir + "_final")
     print_process("Saved model to %s_final.pb" % save_dir, 0)
@@ -478,6 +488,9 @@ def train_model(ctx: Context, train_start, train_end, sampling_period, gpu_id, r
                 semantic_network.train_with_deque(frame_memory, label_memory, FLAGS.iter, FLAGS.train_strategy)
             train_ms.append(1000 * (time.time() - t1))
             print("Training for %d iterations took %d ms!!!" % (FLAGS.iter, train_ms[-1]))
+            if mining_flag is not None:
+                m = getattr(semantic_network, "last_mining", None)        # None: the phase's last iteration was unmined (a warm-up not yet over)
+                mining_log.append((m["threshold"], m["kept"], m["valid"]) if m else (np.nan, np.nan, np.nan))
             if soft_teacher:
                 # what the phase left: the soft loss and the probabilistic IoU of the model about to be published, over the whole memory
                 metric, _conf = semantic_network.evaluate_memory(device_memory)
@@ -516,6 +529,8 @@ def train_model(ctx: Context, train_start, train_end, sampling_period, gpu_id, r
     np.save(final_save_dir + '_control.npy', np.asarray(control_log, dtype=np.float64).reshape(-1, 5))
     if weights_flag is not None:
         np.save(final_save_dir + '_loss_weights.npy', np.asarray(loss_weights_log, dtype=np.float32).reshape(-1, int(class_weights(exp_num).sum())))
+    if mining_flag is not None:
+        np.save(final_save_dir + '_mining.npy', np.asarray(mining_log, dtype=np.float64).reshape(-1, 3))
     if soft_teacher:
         k = int(class_weights(exp_num).sum())
         np.save(final_save_dir + '_soft_eval.npy', np.asarray(soft_eval, dtype=np.float64).reshape(-1, 3 + k))
@@ -710,6 +725,12 @@ def parse_flags(argv: Optional[List[str]] = None):
             parser.error("--%s needs --soft_teacher: it shapes the loss against the teacher logits that flag caches" % name)
     problem = loss_knobs_problem(flags.soft_teacher, dash="--", **{name: getattr(flags, name) for name in ("kd_temperature", "kd_alpha", "kd_conf_gamma")
                                                                    if getattr(flags, name) is not None})
+    if problem:
+        parser.error(problem)
+    if flags.loss_top_k_warmup is not None and flags.loss_top_k is None:
+        parser.error("--loss_top_k_warmup needs --loss_top_k: it eases the mining in")
+    problem = loss_knobs_problem(True, dash="--", **{name: getattr(flags, name) for name in ("loss_top_k", "loss_top_k_warmup")
+                                                     if getattr(flags, name) is not None})
     if problem:
         parser.error(problem)
     if flags.loss_class_weights is not None and flags.loss_class_weights != "balanced":

@@ -44,7 +44,7 @@ from .engine import StudentEngine
 from .render import VIEWS as RENDER_VIEWS, DeviceRenderer
 from .replay import LOW_RES_LOGITS, SAMPLE_FIELDS, DeviceReplayMemory, draw_samples
 from .soft_metric import SoftMetric
-from .utils import calculate_miou, colormap, loss_knobs_problem
+from .utils import calculate_miou, colormap, loss_knobs_problem, mining_fraction
 from .weights import load_npy
 
 FROZEN_MAGIC = b"AMSF\x01"
@@ -156,11 +156,18 @@ class SemanticNetwork(object):
         # Evaluation stays unweighted, so that runs trained under different weights stay comparable
         self.loss_class_weights = kwargs.pop("loss_class_weights", None)
         self.kd_conf_gamma = float(kwargs.pop("kd_conf_gamma", 0.0))
+        # ... and hard-pixel mining (StudentEngine.set_loss_mining): a phase's iteration `it` keeps the fraction utils.mining_fraction(loss_top_k,
+        # loss_top_k_warmup, it) of the valid pixels.  Evaluation stays unmined, for the reason it stays unweighted
+        self.loss_top_k = float(kwargs.pop("loss_top_k", 1.0))
+        self.loss_top_k_warmup = kwargs.pop("loss_top_k_warmup", 0)
+        self.last_mining = None    # after a phase whose last iteration was mined: that step's threshold, valid, rank and kept
         if frozen:                 # the reference's frozen branch never calls create_student_v3: the kwargs are accepted and unused there too
             self.soft_teacher = self.regularize = self.train_biases_only = False
             self.kd_temperature = self.kd_alpha = 1.0
             self.loss_class_weights, self.kd_conf_gamma = None, 0.0
+            self.loss_top_k, self.loss_top_k_warmup = 1.0, 0
         self.loss_class_weights = self._checked_loss_weights(self.loss_class_weights, self.kd_conf_gamma)
+        self.loss_top_k_warmup = self._checked_mining(self.loss_top_k, self.loss_top_k_warmup)
         initial_variables = kwargs.pop("initial_variables", None)
         frozen_graph = kwargs.pop("frozen_graph", None)
         max_batch = kwargs.pop("max_batch", None)
@@ -561,6 +568,19 @@ class SemanticNetwork(object):
             self.engine.set_loss_weights(cw, float(conf_gamma))
         self.loss_class_weights, self.kd_conf_gamma = cw, float(conf_gamma)
 
+    def _checked_mining(self, top_k, warmup):
+        """The warm-up as an int, after the assertion that the two mining knobs can be served."""
+        problem = loss_knobs_problem(self.soft_teacher, self.kd_temperature, self.kd_alpha, loss_top_k=top_k, loss_top_k_warmup=warmup)
+        assert problem is None, problem
+        return int(warmup)
+
+    def set_loss_mining(self, top_k: float = 1.0, warmup: int = 0) -> None:
+        """Hard-pixel mining for the phases to come: iteration ``it`` of a phase keeps the hardest ``utils.mining_fraction(top_k, warmup, it)``
+        of the valid pixels (``StudentEngine.set_loss_mining``).  ``1.0`` is off.  Training only; evaluation stays unmined."""
+        assert not self.frozen, "Can't train frozen graph!!!"
+        warmup = self._checked_mining(float(top_k), warmup)
+        self.loss_top_k, self.loss_top_k_warmup = float(top_k), warmup
+
     def _host_feed(self) -> HostBatchFeed:
         """The helper threads and pinned staging ring of training from host deques (ams_amd/batch_feed.py), kept from phase to phase; made
         on first use and again when the instance's batch geometry changed since."""
@@ -608,13 +628,20 @@ class SemanticNetwork(object):
             _before, train_mask_ = self.get_train_mask(train_strategy)
             mask_dev = self._mask_to_device(train_mask_) if train_mask_ is not None else None
         losses = []
+        mined, frac = getattr(self, "loss_top_k", 1.0) < 1.0, 1.0          # (a subclass that skips __init__ trains unmined)
+        self.last_mining = None
         t_phase = time.time()
         for it in range(num_of_iterations):
             if feed is not None:
                 staged = feed.next_staged()
                 if staged is None:                  # a helper died: its exception is raised by train_with_deque
+                    if mined:
+                        self.engine.set_loss_mining(1.0)
                     return
             t1 = time.time()
+            if mined:                               # host code: the fraction this iteration keeps (iteration 0 of a warm-up is unmined)
+                frac = mining_fraction(self.loss_top_k, self.loss_top_k_warmup, it)
+                self.engine.set_loss_mining(frac)
             if plan is not None:
                 frames_dev, labels_dev, logits_dev = plan.batch(it)       # one launch on this stream into the resident batch buffer
             else:
@@ -659,8 +686,12 @@ class SemanticNetwork(object):
                     self._restore_dict(_combine)
                     self.mask = train_mask_
                     mask_dev = self._mask_to_device(train_mask_)
+        if mined:
+            if frac < 1.0:
+                self.last_mining = self.engine.mining_result()         # of the phase's last iteration
+            self.engine.set_loss_mining(1.0)                           # steps outside a phase (train_step) stay unmined
         stacked = torch.stack(losses).cpu().numpy() if losses else np.zeros((0, 2))
-        self.last_losses = [float(s / c) if c > 0 else float("nan") for s, c in stacked]
+        self.last_losses =[float(s / c) if c > 0 else float("nan") for s, c in stacked]
         self._last_train_ms = (time.time() - t_phase) * 1000.0
 
         if on_device:

@@ -227,10 +227,34 @@ def balanced_class_weights(counts):
     return cw.astype(np.float32)
 
 
-def loss_knobs_problem(soft_teacher, kd_temperature=1.0, kd_alpha=1.0, kd_conf_gamma=0.0, loss_class_weights=None, class_count=None, dash=""):
+def mining_rank(top_k, n):
+    """The rank hard-pixel mining keeps down to, among ``n`` valid pixels: ``max(1, floor(float64(float32(top_k)) n))`` — the rule the device
+    applies to the count its key pass produces (k_loss_mining.hip: mining_scan_kernel).  For tests and tools; the engine never calls it."""
+    return max(1, int(np.floor(np.float64(np.float32(top_k)) * np.float64(n))))
+
+
+def mining_fraction(top_k, warmup, it):
+    """The fraction of pixels iteration ``it`` (0-based) of a phase keeps under ``loss_top_k = top_k`` and ``loss_top_k_warmup = warmup``
+    (DeepLab's hard_example_mining_step): ``ratio = min(1, it / warmup)``, ``ratio top_k + (1 - ratio)``; iteration 0 is unmined whenever
+    ``warmup > 0``, and ``warmup = 0`` mines at ``top_k`` from the first iteration."""
+    if warmup <= 0:
+        return float(top_k)
+    ratio = min(1.0, it / float(warmup))
+    return float(ratio * top_k + (1.0 - ratio))
+
+
+def loss_knobs_problem(soft_teacher, kd_temperature=1.0, kd_alpha=1.0, kd_conf_gamma=0.0, loss_class_weights=None, class_count=None, dash="",
+                       loss_top_k=1.0, loss_top_k_warmup=0):
     """What is wrong with a setting of the fine-tune loss's knobs, in words, or None: the ranges the C library holds them to (head_common.hpp:
-    kd_params_check, loss_weights_check), and that the three KD knobs shape a loss which only ``soft_teacher`` computes.  ``loss_class_weights``:
-    ``class_count`` numbers or None.  ``dash``: what stands in front of a knob's name (run.py's parser passes "--")."""
+    kd_params_check, loss_weights_check; k_loss_mining.hip: mining_top_k_check), and that the three KD knobs shape a loss which only
+    ``soft_teacher`` computes.  ``loss_class_weights``: ``class_count`` numbers or None.  ``dash``: what stands in front of a knob's name
+    (run.py's parser passes "--")."""
+    if not (np.isfinite(loss_top_k) and 0.0 < loss_top_k <= 1.0):
+        return "%sloss_top_k must lie in (0, 1] (got %r)" % (dash, loss_top_k)
+    if not (np.isfinite(loss_top_k_warmup) and float(loss_top_k_warmup) == int(loss_top_k_warmup) and loss_top_k_warmup >= 0):
+        return "%sloss_top_k_warmup must be a whole number of iterations >= 0 (got %r)" % (dash, loss_top_k_warmup)
+    if loss_top_k_warmup > 0 and loss_top_k == 1.0:
+        return "%sloss_top_k_warmup needs %sloss_top_k < 1: it eases the mining in" % (dash, dash)
     if not (np.isfinite(kd_temperature) and kd_temperature > 0):
         return "%skd_temperature must be finite and > 0 (got %r)" % (dash, kd_temperature)
     if not 0.0 <= kd_alpha <= 1.0:

@@ -261,6 +261,37 @@ int ams_student_set_kd(ams_student* s, float temperature, float alpha);
  * with conf_gamma = 0 (the default) run the kernels that run without this call: the same bits.  Evaluation entries stay unweighted. */
 int ams_student_set_loss_weights(ams_student* s, const float* class_weights_host /* n_selected, or NULL = ones */, int32_t n, float conf_gamma);
 
+/* Hard-pixel mining (DeepLab's top_k_percent_pixels; the reference has none): the step's loss and gradient are those of the objective above over
+ * the fraction top_k of the valid pixels whose own objective value is largest.  Per pixel, in f32,
+ *   key = max(0, w_q pixel)            (pixel, w_q: as ams_student_set_kd and ams_student_set_loss_weights define them; a NaN counts as 0);
+ * a pixel is valid when its label is in the class subset and w_q > 0, n = the valid pixels of the batch, k = max(1, floor((double)top_k n)),
+ * threshold = the k-th largest key, kept = the valid pixels with key >= threshold: ties at the threshold are all kept (kept >= k) and nothing
+ * depends on an order.  The mean is over the kept pixels: loss_dev[1] is their number (their weight sum under weights).  n, k and the threshold
+ * are formed on the device: a memset pair and eight launches in front of the loss kernel (mining_key_kernel, three mining_hist_kernel +
+ * mining_scan_kernel passes of a radix select, mining_relabel_kernel), no host round trip.  The loss kernels are the unmined step's: they run
+ * on a label map in which every dropped pixel reads 255.
+ *
+ * scratch_dev: the caller's, 16-byte aligned, at least ams_k_loss_mining_scratch(max_batch, height, width) bytes (the key map, the mined labels,
+ * the histograms and the result); it stays referenced: keep it alive.  The student's arena does not change.  top_k = 1 switches mining off (NULL
+ * scratch allowed): the step then launches what it launches without this call, the same bits.  AMS_E_INVALID, the student keeping what it had:
+ * top_k outside (0, 1] or not finite; with top_k < 1 a scratch that is NULL, misaligned or too small, or a student whose size is outside the
+ * one-pass loss kernel (ams_k_ce_loss_grad).  Needs a trainable student.  A step with top_k < 1 and an all-reduce callback or an RCCL
+ * communicator is refused before anything is launched: a global threshold needs the ranks' histograms summed.  Evaluation stays unmined. */
+typedef struct ams_mining_result {
+    float threshold;         /* the k-th largest key (0 without a valid pixel) */
+    int64_t valid;           /* n */
+    int64_t rank;            /* k */
+    int64_t kept;            /* valid pixels with key >= threshold */
+} ams_mining_result;
+/* A scratch block for batches of up to B frames, n = B H W: the result at byte 0, the histograms behind it, the key map f32 [n] at
+ * AMS_MINING_KEYS_OFFSET and the mined labels uint8 [n] at AMS_MINING_KEYS_OFFSET + 4 n rounded up to 16 (a step of fewer frames fills the
+ * front of both maps). */
+#define AMS_MINING_KEYS_OFFSET 24832
+size_t ams_k_loss_mining_scratch(int32_t B, int32_t H, int32_t W);      /* bytes; 0 for a size < 1 */
+int ams_student_set_loss_mining(ams_student* s, float top_k, void* scratch_dev, size_t scratch_bytes);
+/* The result block of the last mined step, copied to the host after `stream` has drained.  AMS_E_STATE before the first mined step. */
+int ams_student_mining_result(ams_student* s, ams_mining_result* out_host, void* stream);
+
 /* ---- data-parallel split of the same step (one process per GPU) -------------------------
  * Callback form (any transport; what the gloo CPU tests and a host without RCCL use): `cb` is invoked on the host
  * whenever cross-rank sums are needed and must all-reduce (sum) `count` values of `dtype` at arena byte offset
@@ -904,6 +935,18 @@ int ams_k_ce_loss_grad_weighted(const float* logits, int32_t B, int32_t h, int32
                                 int32_t K, int32_t H, int32_t W, const uint8_t* teacher, const float* teacher_logits, int32_t th, int32_t tw,
                                 int32_t layout, double* loss_dev, float* dlogits, float* scratch, size_t scratch_floats, void* stream,
                                 float temperature, float alpha, const float* class_weights_host, float conf_gamma);
+/* The same over the hardest pixels alone (ams_student_set_loss_mining has the semantics): the key pass, the select and the relabel, then the two
+ * launches of ams_k_ce_loss_grad_weighted on labels_out_dev.  labels_out_dev: uint8 [B, H, W], the mined map (a dropped pixel reads 255);
+ * key_out_dev: f32 [B, H, W] or NULL (the keys then stay in the mining scratch), -1 at a pixel that is not valid; result_dev: 8-byte aligned;
+ * mining_scratch_dev: 16-byte aligned, ams_k_loss_mining_scratch(B, H, W) bytes.  top_k = 1: the unmined entry, labels_out_dev a copy of
+ * `teacher`, key_out_dev and result_dev untouched.  AMS_E_INVALID, nothing launched, nothing written: whatever ams_k_ce_loss_grad_weighted
+ * refuses, in its order; then top_k outside (0, 1] or not finite; the mining scratch NULL, misaligned or too small; a NULL output. */
+int ams_k_ce_loss_grad_mined(const float* logits, int32_t B, int32_t h, int32_t w, int32_t ld, int32_t NC, const int32_t* class_idx_host,
+                             int32_t K, int32_t H, int32_t W, const uint8_t* teacher, const float* teacher_logits, int32_t th, int32_t tw,
+                             int32_t layout, double* loss_dev, float* dlogits, float* scratch, size_t scratch_floats, void* stream,
+                             float temperature, float alpha, const float* class_weights_host, float conf_gamma, float top_k,
+                             uint8_t* labels_out_dev, float* key_out_dev, ams_mining_result* result_dev, void* mining_scratch_dev,
+                             size_t mining_scratch_bytes);
 
 /* K13: weight gradient of a 1x1 conv: dw[K,N] = x[M,K]^T @ dy[M,N]. scratch: >= ams_k_pointwise_wgrad_scratch floats */
 int ams_k_pointwise_wgrad(const float* x, const float* dy, int64_t M, int32_t K, int32_t N, float* dw,
