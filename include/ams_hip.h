@@ -712,13 +712,17 @@ int ams_k_depthwise3x3(const float* x, int32_t B, int32_t H, int32_t W, int32_t 
                        float* y, void* stream);
 
 /* K4: 1x1 conv as GEMM: y[M,N] = act((x[M,K] @ w[K,N] + img_bias[row/rows_per_img]) * scale + shift) + res.
- * Any of img_bias/scale/shift/res may be NULL.  trans_w != 0: w is given as [N,K] (dgrad). */
+ * Any of img_bias/scale/shift/res may be NULL.  trans_w != 0: w is given as [N,K] (dgrad).
+ * M <= 16 runs a kernel of its own (one row per block row, k summed in another order than the tiled and streaming kernels): wherever an entry
+ * below is called bit-identical to ams_k_pointwise, that holds for M > 16 rows; up to 16 rows the two agree to f32 rounding. */
 int ams_k_pointwise(const float* x, int64_t M, int32_t K, const float* w, int32_t N, int32_t trans_w,
                     const float* img_bias, int64_t rows_per_img, const float* scale, const float* shift,
                     int32_t act, const float* res, float* y, void* stream);
 
 /* K4, split-bf16 form (see AMS_MATMUL_SPLIT_BF16): y = act((x @ w) * scale + shift) + res with w [K,N] f32 split on the
- * fly into bf16 hi/lo panels held in `panels` (uint16, >= 2*N*roundup(K,32) elements).  K % 8 == 0. */
+ * fly into bf16 hi/lo panels held in `panels` (uint16, >= 2*N*roundup(K,32) elements).  K % 8 == 0.
+ * Scratch and panels of every ams_k_* entry: the caller need not zero them — an entry writes every element it later reads, the pad columns
+ * K .. roundup(K,32) of a weight panel included — and an entry refuses (AMS_E_INVALID, nothing launched) a size below the minimum it states. */
 int ams_k_pointwise_split(const float* x, int64_t M, int32_t K, const float* w, int32_t N, const float* scale,
                           const float* shift, int32_t act, const float* res, float* y, uint16_t* panels,
                           size_t panel_elems, void* stream);
@@ -752,7 +756,8 @@ int ams_k_block_fused(const float* x, int32_t B, int32_t H, int32_t W, int32_t C
 
 /* K4+K3 fused, streaming form for the stride-16 blocks (Cin in {64, 96, 160}, stride 1, rate 1|2, Cexp % 32 == 0): the same
  * result as ams_k_pointwise_split (parts = 2) / the three-part split (parts = 3) followed by ams_k_depthwise3x3, bit for bit,
- * without writing the expanded tensor.  panels: scratch of >= 3*Cexp*Cin uint16 (w_exp [Cin,Cexp] is split into it).
+ * without writing the expanded tensor.  panels: scratch of >= 3*Cexp*Cin uint16 (w_exp [Cin,Cexp] is split into it; three planes
+ * whatever `parts` is).  In all: ns * Cexp*Cin + (presplit ? ns * B*H*W*Cin : 0) with ns = 3 here and 2 for ams_k_expand_dw_stream_f16.
  * Cin in {16, 24, 32}: exact-f32 products instead (bit-identical to ams_k_pointwise + ams_k_depthwise3x3; parts / presplit /
  * panels unused), and rate = -2 selects the stride-2 depthwise conv (y [B,Ho,Wo,Cexp], SAME).
  * presplit != 0: x is first written as bf16 parts (what the project GEMM of the previous block leaves behind in the engine) and
@@ -840,7 +845,9 @@ int ams_k_global_mean(const float* x, int32_t B, int64_t HW, int32_t C, float* y
 size_t ams_k_global_mean_scratch(int32_t B, int32_t C);
 
 /* K9-K12: bilinear(align_corners) upsample of low-res logits to HxW fused with class gather, argmax and
- * (when teacher != NULL) confusion matrix + CE loss sums.  Full-resolution logits are never written. */
+ * (when teacher != NULL) confusion matrix + CE loss sums.  Full-resolution logits are never written.
+ * conf_mat int64 [K*K] and loss double[2] are accumulators: the call zeroes both itself (on `stream`, in front of its kernel) — the caller
+ * need not, and whatever they held is gone.  teacher == NULL: neither is touched. */
 int ams_k_upsample_argmax(const float* logits /*[B,h,w,NC]*/, int32_t B, int32_t h, int32_t w, int32_t NC,
                           const int32_t* class_idx_host, int32_t K, int32_t H, int32_t W, const uint8_t* teacher,
                           int32_t* labels_out, int64_t* conf_mat, double* loss, void* stream);
@@ -948,7 +955,14 @@ int ams_k_ce_loss_grad_mined(const float* logits, int32_t B, int32_t h, int32_t 
                              uint8_t* labels_out_dev, float* key_out_dev, ams_mining_result* result_dev, void* mining_scratch_dev,
                              size_t mining_scratch_bytes);
 
-/* K13: weight gradient of a 1x1 conv: dw[K,N] = x[M,K]^T @ dy[M,N]. scratch: >= ams_k_pointwise_wgrad_scratch floats */
+/* K13: weight gradient of a 1x1 conv: dw[K,N] = x[M,K]^T @ dy[M,N]; x and dy are packed (row strides K and N).
+ * scratch: the partial products of the row splits, written before they are summed (nothing to zero): splits * K * N floats, where
+ *   ams_k_pointwise_wgrad (exact f32):  splits = max(min(ceil(1024 / tiles), ceil(M / 256)), 1), tiles = ceil(K / 64) * ceil(N / 64);
+ *   ams_k_pointwise_wgrad_split (K13b): splits = max(min(ceil(512 / tiles), ceil(M / 256), 32), 1), tiles = ceil(K / (16 kt)) * ceil(N / (16 nw)),
+ *     kt = 8 for K > 64 and 4 up to there; with n16 = ceil(N / 16): nw = 4 | 5 | 6 | 8 | 10 for n16 <= 4 | 5 | 6 | 8 | 10, above that
+ *     10, 8 or 6 where it divides n16 (tried in that order) and 8 otherwise.
+ * Each entry refuses (AMS_E_INVALID) fewer floats than ITS formula gives; ams_k_pointwise_wgrad_scratch returns the larger of the two, which
+ * serves either entry and ams_k_pointwise_wgrad_xform with either value of split. */
 int ams_k_pointwise_wgrad(const float* x, const float* dy, int64_t M, int32_t K, int32_t N, float* dw,
                           float* scratch, size_t scratch_floats, void* stream);
 size_t ams_k_pointwise_wgrad_scratch(int64_t M, int32_t K, int32_t N);
@@ -958,7 +972,9 @@ size_t ams_k_pointwise_wgrad_scratch(int64_t M, int32_t K, int32_t N);
 int ams_k_pointwise_wgrad_split(const float* x, const float* dy, int64_t M, int32_t K, int32_t N, float* dw,
                                 float* scratch, size_t scratch_floats, void* stream);
 
-/* K13: depthwise backward: dx (input gradient) and dw[3,3,C,1]. */
+/* K13: depthwise backward: dx (input gradient) and dw[3,3,C,1].  ams_k_depthwise3x3_wgrad's scratch holds one 9 x C partial per block, each written
+ * whole before the second stage sums them (nothing to zero): scratch_floats >= blocks * 9 * C with items = B * ceil(Ho / 4) * Wo,
+ * slots = max(256 / (C / 4), 1), blocks = min(ceil(items / (2 * slots)), max(items * 2 / 9, 1), 1024); AMS_E_INVALID below that. */
 int ams_k_depthwise3x3_dgrad(const float* dy, int32_t B, int32_t H, int32_t W, int32_t C, const float* w,
                              int32_t stride, int32_t rate, float* dx, void* stream);
 int ams_k_depthwise3x3_wgrad(const float* x, const float* dy, int32_t B, int32_t H, int32_t W, int32_t C,
@@ -973,7 +989,8 @@ int ams_k_depthwise3x3_wgrad(const float* x, const float* dy, int32_t B, int32_t
  * split 1: the three-part bf16 kernel (panels: >= 3 N Kp bf16 scratch); split 2: the two-fp16-part kernel (mode 1 only: what the fine-tune step's
  * forward runs under AMS_MATMUL_SPLIT_F16; panels >= 2 N Kp); 0: the exact-f32 streaming kernel.  *rows_out = 0 means the kernel
  * chosen for this shape cannot fuse the reduction (y is then the plain product, + res): the caller runs the separate pass.
- * part_floats >= (M / 64 + 8 or 2048) * 2 N. */
+ * part_floats >= (M / 64 + 8 or 2048, whichever is larger) * 2 N; rows that would not fit make the launch run unfused (*rows_out = 0), no
+ * refusal.  The *rows_out rows are written whole; the rest of `part` is left alone.  Nothing in `part` or `panels` needs zeroing. */
 int ams_k_pointwise_red(const float* x, int64_t M, int32_t K, const float* w, int32_t N, int32_t trans_w, int32_t split, int32_t mode,
                         const float* center, const float* z, const float* scale, const float* shift, const float* mean, const float* rstd,
                         int32_t act, const float* res, float* y, float* part, size_t part_floats, int32_t* rows_out, uint16_t* panels,
