@@ -652,6 +652,102 @@ int ams_student_encode_delta(ams_student* s, const uint8_t* mask_dev, const ams_
                                payload_bytes_dev, st);
 }
 
+// ---- the q8 delta (k_delta_q8.hip) ---------------------------------------------------------------------------
+// What a q8 call can tell about its table without the handle: the variable count, the regions, the signs and the contiguous masks.
+// -> the mask section in bytes (has_stats: an entry lies in AMS_REGION_STATS), or -1 with the reason in the error.  The bounds inside
+// the arena are delta_mask_bytes' business, once the handle is known to be there.
+static int64_t delta_table_shape(const ams_delta_var* vars, int32_t n_vars, const char* what, bool* has_stats) {
+    if (!vars || n_vars < 1 || n_vars > AMS_DELTA_MAX_VARS) { set_error("%s: malformed table: %d variables (1 .. %d)", what, n_vars, AMS_DELTA_MAX_VARS); return -1; }
+    int64_t mask = 0;
+    *has_stats = false;
+    for (int32_t i = 0; i < n_vars; ++i) {
+        const ams_delta_var& d = vars[i];
+        if (d.region != AMS_REGION_PARAMS && d.region != AMS_REGION_STATS) {
+            set_error("%s: malformed table: variable %d: region %d is neither params nor stats", what, i, d.region);
+            return -1;
+        }
+        if (d.offset < 0 || d.count < 0 || d.count > ((int64_t)1 << 40)) {
+            set_error("%s: malformed table: variable %d: elements [%lld, +%lld)", what, i, (long long)d.offset, (long long)d.count);
+            return -1;
+        }
+        if (d.mask_offset != mask) {
+            set_error("%s: malformed table: variable %d: mask at byte %lld, the masks before it end at %lld", what, i, (long long)d.mask_offset,
+                      (long long)mask);
+            return -1;
+        }
+        *has_stats = *has_stats || d.region == AMS_REGION_STATS;
+        mask += (d.count + 7) / 8;
+    }
+    return mask;
+}
+
+size_t ams_student_encode_delta_q8_scratch(const ams_delta_var* vars_host, int32_t n_vars) {
+    const int64_t mask = delta_mask_sum(vars_host, n_vars);
+    return mask < 0 ? 0 : q8_encode_table_words(n_vars) + 1 + (size_t)delta_segments(mask);
+}
+
+// Order of refusal: null pointers; advance_base; the table's shape; the statistics' base; the scratch; the room; and only then the handle and
+// the table against its arena — so everything before it can be asked without a student.
+int ams_student_encode_delta_q8(ams_student* s, const uint8_t* mask_dev, const ams_delta_var* vars_host, int32_t n_vars, float* base_params_dev,
+                                float* base_stats_dev, int32_t advance_base, uint8_t* payload_dev, int64_t payload_cap, int64_t* payload_bytes_dev,
+                                int32_t* status_dev, int64_t* scratch_dev, size_t scratch_elems, void* stream) {
+    AMS_REQUIRE(base_params_dev && payload_dev && payload_bytes_dev && status_dev && scratch_dev, "encode_delta_q8: null pointer");
+    AMS_REQUIRE(advance_base == 0 || advance_base == 1, "encode_delta_q8: advance_base %d (0 or 1)", advance_base);
+    bool has_stats = false;
+    const int64_t shape = delta_table_shape(vars_host, n_vars, "encode_delta_q8", &has_stats);
+    if (shape < 0) return AMS_E_INVALID;
+    AMS_REQUIRE(base_stats_dev || !has_stats, "encode_delta_q8: null statistics base, and the table has variables in AMS_REGION_STATS");
+    const size_t table = q8_encode_table_words(n_vars);
+    const size_t need = table + 1 + (size_t)delta_segments(shape);
+    AMS_REQUIRE(scratch_elems >= need, "encode_delta_q8: scratch too small (need %zu int64)", need);
+    AMS_REQUIRE(payload_cap >= shape + 4 * (int64_t)n_vars, "encode_delta_q8: room for %lld bytes, the mask and scale sections alone have %lld",
+                (long long)payload_cap, (long long)(shape + 4 * (int64_t)n_vars));
+    AMS_REQUIRE(s, "encode_delta_q8: null handle");
+    const int64_t mask_bytes = delta_mask_bytes(s, vars_host, n_vars, "encode_delta_q8");
+    if (mask_bytes < 0) return AMS_E_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    // as in encode_delta: the table travels from a host copy the handle keeps; its tail, the per-variable maxima, travels as zeros
+    if (s->ev_encode) AMS_CHECK_HIP(hipEventSynchronize(s->ev_encode));
+    else RUN(create_sync_event(&s->ev_encode));
+    s->encode_table.assign(table, 0);
+    memcpy(s->encode_table.data(), vars_host, n_vars * sizeof(ams_delta_var));
+    int64_t first = 0;
+    for (int32_t i = 0; i < n_vars; ++i) { s->encode_table[4 * (size_t)n_vars + i] = first; first += vars_host[i].count; }
+    s->encode_table[5 * (size_t)n_vars] = first;
+    AMS_CHECK_HIP(hipMemcpyAsync(scratch_dev, s->encode_table.data(), table * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    AMS_CHECK_HIP(hipEventRecord(s->ev_encode, st));
+    return launch_encode_delta_q8(mask_dev, scratch_dev, n_vars, mask_bytes, s->params, s->stats, base_params_dev, base_stats_dev, advance_base,
+                                  scratch_dev + table, payload_dev, payload_cap, payload_bytes_dev, status_dev, st);
+}
+
+size_t ams_student_apply_delta_q8_scratch(const ams_delta_var* vars_host, int32_t n_vars) {
+    return ams_student_apply_delta_scratch(vars_host, n_vars);
+}
+
+int ams_student_apply_delta_q8(ams_student* s, const uint8_t* payload_dev, int64_t payload_bytes, const ams_delta_var* vars_host, int32_t n_vars,
+                               int64_t* n_applied_dev, int32_t* status_dev, int64_t* scratch_dev, size_t scratch_elems, void* stream) {
+    AMS_REQUIRE(n_applied_dev && status_dev && scratch_dev, "apply_delta_q8: null pointer");
+    AMS_REQUIRE(payload_bytes >= 0 && (payload_dev || payload_bytes == 0), "apply_delta_q8: %lld payload bytes at %p", (long long)payload_bytes,
+                (const void*)payload_dev);
+    bool has_stats = false;
+    const int64_t shape = delta_table_shape(vars_host, n_vars, "apply_delta_q8", &has_stats);
+    if (shape < 0) return AMS_E_INVALID;
+    const size_t need = 4 * (size_t)n_vars + (size_t)delta_segments(shape);
+    AMS_REQUIRE(scratch_elems >= need, "apply_delta_q8: scratch too small (need %zu int64)", need);
+    AMS_REQUIRE(s, "apply_delta_q8: null handle");
+    const int64_t mask_bytes = delta_mask_bytes(s, vars_host, n_vars, "apply_delta_q8");
+    if (mask_bytes < 0) return AMS_E_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    if (s->ev_delta) AMS_CHECK_HIP(hipEventSynchronize(s->ev_delta));
+    else RUN(create_sync_event(&s->ev_delta));
+    s->delta_vars.assign(vars_host, vars_host + n_vars);
+    ams_delta_var* vars_dev = reinterpret_cast<ams_delta_var*>(scratch_dev);
+    AMS_CHECK_HIP(hipMemcpyAsync(vars_dev, s->delta_vars.data(), n_vars * sizeof(ams_delta_var), hipMemcpyHostToDevice, st));
+    AMS_CHECK_HIP(hipEventRecord(s->ev_delta, st));
+    return launch_apply_delta_q8(payload_dev, payload_bytes, vars_dev, n_vars, mask_bytes, s->params, (int64_t)s->cfg.n_trainable, s->stats,
+                                 (int64_t)s->cfg.n_stats, scratch_dev + 4 * n_vars, n_applied_dev, status_dev, st);
+}
+
 // ---- kernel-level entry points -----------------------------------------------------------------------------
 int ams_k_stem_conv(const void* frames, int32_t frames_dtype, int32_t B, int32_t H, int32_t W, const float* w, int32_t cout,
                     const float* scale, const float* shift, int32_t act, float pixel_scale, float* y, void* stream) {

@@ -14,25 +14,11 @@
 #include "common.hpp"
 #include "kernels.hpp"
 #include "block_scan.hpp"
+#include "delta_walk.hpp"                                   // DELTA_THREADS, DELTA_SEG, mask_word: shared with k_delta_q8.hip
 
 #include <hip/hip_fp16.h>
 
 namespace ams {
-
-namespace {
-
-constexpr int DELTA_THREADS = BLOCK_SCAN_THREADS;
-constexpr int64_t DELTA_SEG = 8 * DELTA_THREADS;          // mask bytes per segment: 8 per thread
-
-// mask bytes [b, b + 8) clipped at e, as one word in element order: bit 63 = bit 7 of byte b
-__device__ inline uint64_t mask_word(const uint8_t* p, int64_t b, int64_t e) {
-    if (b + 8 <= e && ((uintptr_t)(p + b) & 7) == 0) return __builtin_bswap64(*reinterpret_cast<const uint64_t*>(p + b));
-    uint64_t w = 0;
-    for (int k = 0; k < 8; ++k) w = (w << 8) | (uint64_t)(b + k < e ? p[b + k] : 0);
-    return w;
-}
-
-}  // namespace
 
 __global__ void __launch_bounds__(DELTA_THREADS) delta_count_kernel(const uint8_t* payload, int64_t end, int64_t* counts) {
     __shared__ int64_t sh[DELTA_THREADS];
@@ -110,6 +96,13 @@ __global__ void __launch_bounds__(DELTA_THREADS) delta_apply_kernel(const uint8_
 }
 
 int64_t delta_segments(int64_t mask_bytes) { return mask_bytes > 0 ? cdiv64(mask_bytes, DELTA_SEG) : 1; }
+
+// the count pass alone, for the q8 decoder (k_delta_q8.hip): the mask section is the same
+int launch_delta_count(const uint8_t* payload, int64_t readable, int nseg, int64_t* counts, hipStream_t st) {
+    hipLaunchKernelGGL(delta_count_kernel, dim3(nseg), dim3(DELTA_THREADS), 0, st, payload, readable, counts);
+    AMS_CHECK_LAUNCH();
+    return AMS_OK;
+}
 
 // scratch (int64): [descriptor table: 4 per variable][segment counts -> offsets]
 int launch_apply_delta(const uint8_t* payload, int64_t payload_bytes, const ams_delta_var* vars_dev, int n_vars, int64_t mask_bytes,

@@ -372,6 +372,18 @@ int64_t delta_segments(int64_t mask_bytes);
 int launch_apply_delta(const uint8_t* payload, int64_t payload_bytes, const ams_delta_var* vars_dev, int n_vars, int64_t mask_bytes,
                        float* params, int64_t n_params, float* stats, int64_t n_stats, int64_t* counts, int64_t* n_applied, int32_t* status,
                        hipStream_t st);
+int launch_delta_count(const uint8_t* payload, int64_t readable, int nseg, int64_t* counts, hipStream_t st);
+// k_delta_q8.hip: the same delta as int8 codes of (current - base) with one f32 scale per variable, encoded and decoded
+// (ams_student_encode_delta_q8 / ams_student_apply_delta_q8).  Segments are delta_segments() on both sides.
+// table_dev (int64): [descriptors: 4 per variable][element starts: n_vars + 1][per-variable maxima, uint32, zeroed by the table copy];
+// work (int64): [payload size][segment counts -> offsets]
+size_t q8_encode_table_words(int n_vars);
+int launch_encode_delta_q8(const uint8_t* mask, int64_t* table_dev, int n_vars, int64_t mask_bytes, const float* params, const float* stats,
+                           float* base_params, float* base_stats, int advance_base, int64_t* work, uint8_t* payload, int64_t cap,
+                           int64_t* payload_bytes, int32_t* status, hipStream_t st);
+int launch_apply_delta_q8(const uint8_t* payload, int64_t payload_bytes, const ams_delta_var* vars_dev, int n_vars, int64_t mask_bytes,
+                          float* params, int64_t n_params, float* stats, int64_t n_stats, int64_t* counts, int64_t* n_applied, int32_t* status,
+                          hipStream_t st);
 // k_select.hip: the server half of a model update: coordinates chosen by their change, the roll-back, the downlink delta encoded
 size_t select_scratch();
 int launch_select_changed(const float* after, const float* before, int64_t n, int64_t k, ams_select_result* result, int64_t* scratch,

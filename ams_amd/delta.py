@@ -8,7 +8,9 @@ their configuration, decides which variables it covers.
   statistics interleaved), the key order of ``engine.get_variables()``.
 
 Bytes: per variable ``np.packbits(mask.flatten())`` (big-endian bits, each variable starting on a byte), then the masked values of every
-variable in the same order as little-endian fp16.  This module is the one place that knows the two orders; it holds no numerics.
+variable in the same order as little-endian fp16.  In the q8 format (``FORMATS``) the mask section is followed by one little-endian f32 scale
+per variable of the layout and one int8 code of (value - base) per masked element instead.  This module is the one place that knows the two
+orders; it holds no numerics.
 """
 from __future__ import annotations
 
@@ -19,6 +21,16 @@ from . import hip
 from .spec import StudentSpec
 
 TRAINABLE, ALL_VARIABLES = "trainable", "all_variables"
+# what follows the mask section: fp16 = the masked values as fp16 (the reference's payload); q8 = one f32 scale per variable of the layout,
+# then one int8 code of (value - base) per masked element (include/ams_hip.h: ams_student_encode_delta_q8)
+FP16, Q8 = "fp16", "q8"
+FORMATS = (FP16, Q8)
+
+
+def check_format(fmt: str) -> str:
+    if fmt not in FORMATS:
+        raise ValueError("delta format %r: one of %s" % (fmt, ", ".join(FORMATS)))
+    return fmt
 
 
 def layout_kind(train_strategy: str) -> str:
@@ -50,6 +62,14 @@ class DeltaLayout:
     def max_payload_bytes(self) -> int:
         """every element masked: the mask section plus two bytes per element"""
         return self.mask_bytes + 2 * self.n_elements
+
+    @property
+    def max_payload_bytes_q8(self) -> int:
+        """the q8 format, every element masked: the mask section, one f32 scale per variable, one byte per element"""
+        return self.mask_bytes + 4 * len(self.entries) + self.n_elements
+
+    def payload_limit(self, fmt: str) -> int:
+        return self.max_payload_bytes_q8 if check_format(fmt) == Q8 else self.max_payload_bytes
 
     def table(self):
         """the entries as a C array of ams_delta_var (built once)"""

@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import coord_masks, hip
+from .delta import check_format
 from .spec import (BN_DECAY, BN_EPS_FROZEN, PIXEL_SCALE, Layer, StudentSpec, build_spec)
 from . import weights as W
 
@@ -147,6 +148,10 @@ class StudentEngine:
         # server-side model updates (select_changed, encode_delta): scratch (created on first use), [a, b | NaN changes | kept | payload bytes]
         self._select_scratch = self._encode_scratch = None
         self._select_words = torch.zeros(4, dtype=torch.int64, device=self.device)
+        # the q8 delta: the base the encoder subtracts (set_delta_base: params / stats in arena order), its scratch, [payload bytes, status (int32)]
+        self._q8_base = None
+        self._q8_scratch = None
+        self._q8_words = torch.zeros(2, dtype=torch.int64, device=self.device)
         self.generation = 0
         for name, opt in _ENV_OPTIONS.items():
             if name in os.environ:
@@ -447,11 +452,16 @@ class StudentEngine:
         hip.check(self.lib.ams_student_f16_fallback_layers(self._h, C.byref(n)), "ams_student_f16_fallback_layers")
         return int(n.value)
 
-    def apply_delta(self, payload, layout) -> int:
+    def apply_delta(self, payload, layout, fmt: str = "fp16") -> int:
         """Decode a downlink delta (``SemanticNetwork.delta_payload`` bytes of ``layout``, an ``ams_amd.delta.DeltaLayout``) into the unfolded
         variables (``params`` / ``stats``) on the device; returns the number of values written.  ``payload``: bytes / uint8 array (through a
         pinned staging buffer) or a uint8 device tensor.  A malformed payload raises AmsHipError and changes nothing.  The frozen snapshot is
-        not touched: call ``freeze`` to serve the update.  Synchronises the stream once (the status word)."""
+        not touched: call ``freeze`` to serve the update.  Synchronises the stream once (the status word).
+
+        ``fmt="q8"``: the payload holds int8 codes of the change and one scale per variable (``ams_student_apply_delta_q8``); every masked
+        element becomes its current value plus scale x code, so the variables must hold the base the server encoded against."""
+        q8 = check_format(fmt) == "q8"
+        limit = layout.payload_limit(fmt)
         if isinstance(payload, torch.Tensor):
             assert payload.dtype == torch.uint8 and payload.device == self.arena.device, "payload: a uint8 tensor on the engine's device"
             dev = payload.contiguous().view(-1)
@@ -460,29 +470,35 @@ class StudentEngine:
             a = np.frombuffer(payload, dtype=np.uint8) if isinstance(payload, (bytes, bytearray, memoryview)) else \
                 np.ascontiguousarray(payload, dtype=np.uint8).reshape(-1)
             n = int(a.size)
-            if n > layout.max_payload_bytes:
-                raise hip.AmsHipError("delta payload rejected: %d bytes, the %s layout holds at most %d; the model is unchanged"
-                                      % (n, layout.kind, layout.max_payload_bytes))
-            if self._delta_host is None or self._delta_host.numel() < layout.max_payload_bytes:
-                self._delta_host = torch.empty(layout.max_payload_bytes, dtype=torch.uint8).pin_memory()
-                self._delta_dev = torch.empty(layout.max_payload_bytes, dtype=torch.uint8, device=self.device)
+            if n > limit:
+                raise hip.AmsHipError("delta payload rejected: %d bytes, the %s layout holds at most %d%s; the model is unchanged"
+                                      % (n, layout.kind, limit, " in the q8 format" if q8 else ""))
+            if self._delta_host is None or self._delta_host.numel() < limit:
+                room = max(layout.max_payload_bytes, layout.max_payload_bytes_q8)
+                self._delta_host = torch.empty(room, dtype=torch.uint8).pin_memory()
+                self._delta_dev = torch.empty(room, dtype=torch.uint8, device=self.device)
             np.copyto(self._delta_host[:n].numpy(), a)          # (the previous update's copy out of this buffer ended with its status read)
             self._delta_dev[:n].copy_(self._delta_host[:n], non_blocking=True)
             dev = self._delta_dev
         table = layout.table()
-        need = int(self.lib.ams_student_apply_delta_scratch(table, len(table)))
+        entry, scratch_of = (self.lib.ams_student_apply_delta_q8, self.lib.ams_student_apply_delta_q8_scratch) if q8 else \
+            (self.lib.ams_student_apply_delta, self.lib.ams_student_apply_delta_scratch)
+        need = int(scratch_of(table, len(table)))
         if self._delta_scratch is None or self._delta_scratch.numel() < need:
             self._delta_scratch = torch.empty(need, dtype=torch.int64, device=self.device)
         words = self._delta_words.data_ptr()
-        hip.check(self.lib.ams_student_apply_delta(self._h, C.c_void_p(dev.data_ptr()) if n else None, n, table, len(table),
-                                                   C.c_void_p(words), C.c_void_p(words + 8), C.c_void_p(self._delta_scratch.data_ptr()),
-                                                   self._delta_scratch.numel(), self._stream()), "ams_student_apply_delta")
+        hip.check(entry(self._h, C.c_void_p(dev.data_ptr()) if n else None, n, table, len(table), C.c_void_p(words), C.c_void_p(words + 8),
+                        C.c_void_p(self._delta_scratch.data_ptr()), self._delta_scratch.numel(), self._stream()),
+                  "ams_student_apply_delta_q8" if q8 else "ams_student_apply_delta")
         w = self._delta_words.cpu().numpy()
         applied, status = int(w[0]), int(w[1:].view(np.int32)[0])
         if status != hip.DELTA_OK:
-            why = {hip.DELTA_BAD_SIZE: "its size does not match its mask (%d mask bytes + 2 per set bit): truncated, over-long or corrupted"
-                   % layout.mask_bytes, hip.DELTA_BAD_PADDING: "a padding bit after a variable's last element is set"}.get(status, "status %d" % status)
-            raise hip.AmsHipError("delta payload rejected (%d bytes, %s layout): %s; the model is unchanged" % (n, layout.kind, why))
+            size_rule = "%d mask bytes + 4 per variable + 1 per set bit" % layout.mask_bytes if q8 else "%d mask bytes + 2 per set bit" % layout.mask_bytes
+            why = {hip.DELTA_BAD_SIZE: "its size does not match its mask (%s): truncated, over-long or corrupted" % size_rule,
+                   hip.DELTA_BAD_PADDING: "a padding bit after a variable's last element is set",
+                   hip.DELTA_BAD_SCALE: "a variable's scale is NaN, infinite, negative or denormal"}.get(status, "status %d" % status)
+            raise hip.AmsHipError("delta payload rejected (%d bytes, %s layout%s): %s; the model is unchanged"
+                                  % (n, layout.kind, ", q8" if q8 else "", why))
         if applied:
             self._updated_since_freeze = True
         return applied
@@ -516,13 +532,66 @@ class StudentEngine:
                                             C.c_void_p(mask.data_ptr()), C.c_void_p(words.data_ptr() + 16), self._stream()), "ams_select_apply")
         return mask, words[2:3].clone()
 
-    def encode_delta(self, layout, mask: Optional[torch.Tensor] = None, cap: Optional[int] = None) -> torch.Tensor:
+    def set_delta_base(self, variables: Optional[Dict[str, np.ndarray]]) -> None:
+        """The model the q8 encoder takes the change against: a device copy of ``variables`` in arena order (params and stats), uploaded once
+        per call; a variable the dict does not name keeps the engine's current value, so its change is zero.  A pair of f32 device tensors
+        (params, stats) of the arena's sizes is taken as it is, and ``advance_base`` then writes into it.  None drops the base."""
+        if variables is None:
+            self._q8_base = None
+            return
+        if isinstance(variables, tuple):
+            p, s = variables
+            assert p.dtype == s.dtype == torch.float32 and p.numel() == self.params.numel() and s.numel() == self.stats.numel()
+            assert p.device == s.device == self.arena.device and p.is_contiguous() and s.is_contiguous()
+            self._q8_base = (p, s)
+            return
+        tr = self.params.cpu().numpy()
+        st = self.stats.cpu().numpy()
+        W.fill_flat(tr, [v for v in self.spec.trainable if v.name in variables], variables)
+        W.fill_flat(st, [v for v in self.spec.stats if v.name in variables], variables)
+        self._q8_base = (torch.from_numpy(tr).to(self.device), torch.from_numpy(st).to(self.device))
+
+    def _encode_delta_q8(self, layout, mask, cap, advance_base) -> torch.Tensor:
+        if self._q8_base is None:
+            raise hip.AmsHipError("encode_delta(fmt='q8'): no base; call set_delta_base with the model the receiver holds")
+        base_p, base_s = self._q8_base
+        table = layout.table()
+        need = int(self.lib.ams_student_encode_delta_q8_scratch(table, len(table)))
+        if self._q8_scratch is None or self._q8_scratch.numel() < need:
+            self._q8_scratch = torch.empty(need, dtype=torch.int64, device=self.device)
+        cap = layout.max_payload_bytes_q8 if cap is None else int(cap)
+        out = torch.empty(cap, dtype=torch.uint8, device=self.device)
+        words = self._q8_words.data_ptr()
+        hip.check(self.lib.ams_student_encode_delta_q8(self._h, C.c_void_p(mask.data_ptr()) if mask is not None else None, table, len(table),
+                                                       C.c_void_p(base_p.data_ptr()), C.c_void_p(base_s.data_ptr()), int(bool(advance_base)),
+                                                       C.c_void_p(out.data_ptr()), cap, C.c_void_p(words), C.c_void_p(words + 8),
+                                                       C.c_void_p(self._q8_scratch.data_ptr()), self._q8_scratch.numel(), self._stream()),
+                  "ams_student_encode_delta_q8")
+        w = self._q8_words.cpu().numpy()
+        nbytes, status = int(w[0]), int(w[1:].view(np.int32)[0])
+        if status == hip.DELTA_Q8_NONFINITE:
+            raise hip.AmsHipError("encode_delta(fmt='q8'): a masked change (variable - base) is NaN or infinite; nothing was written")
+        if status != hip.DELTA_OK:
+            raise hip.AmsHipError("encode_delta(fmt='q8'): status %d" % status)
+        if nbytes > cap:
+            raise hip.AmsHipError("encode_delta: the payload has %d bytes, the buffer %d; nothing was written" % (nbytes, cap))
+        return out[:nbytes]
+
+    def encode_delta(self, layout, mask: Optional[torch.Tensor] = None, cap: Optional[int] = None, fmt: str = "fp16",
+                     advance_base: bool = False) -> torch.Tensor:
         """The downlink delta of ``layout`` (an ``ams_amd.delta.DeltaLayout``) encoded on the device from the current variables: the bytes of
         ``SemanticNetwork.delta_payload`` as a uint8 device tensor (what ``apply_delta`` accepts).  ``mask``: uint8 on the device, one entry per
         element in layout order (the trainable layout: arena order), None = every element.  ``cap``: bytes of the output buffer (default: the
-        layout's largest payload); a payload beyond it raises AmsHipError with nothing written.  Synchronises once (the payload's size)."""
+        layout's largest payload); a payload beyond it raises AmsHipError with nothing written.  Synchronises once (the payload's size).
+
+        ``fmt="q8"``: int8 codes of the change against the base of ``set_delta_base`` with one f32 scale per variable
+        (``ams_student_encode_delta_q8``); a NaN or infinite masked change raises AmsHipError with nothing written.  ``advance_base=True``
+        also moves the base's masked elements to what the receiver decodes, so that the next payload starts from the receiver's model."""
         if mask is not None:
             assert mask.dtype == torch.uint8 and mask.numel() == layout.n_elements and mask.device == self.arena.device
+        if check_format(fmt) == "q8":
+            return self._encode_delta_q8(layout, mask, cap, advance_base)
+        assert not advance_base, "advance_base belongs to the q8 format: an fp16 payload carries values, not changes"
         table = layout.table()
         need = int(self.lib.ams_student_encode_delta_scratch(table, len(table)))
         if self._encode_scratch is None or self._encode_scratch.numel() < need:

@@ -96,7 +96,7 @@ RENDER_VIEWS = tuple(f[0] for f in RenderOut._fields_)
 RENDER_TABLE_BYTES = 1120
 CONFIDENCE_BINS = 32          # AMS_CONFIDENCE_BINS
 
-DELTA_OK, DELTA_BAD_SIZE, DELTA_BAD_PADDING = 0, 1, 2
+DELTA_OK, DELTA_BAD_SIZE, DELTA_BAD_PADDING, DELTA_BAD_SCALE, DELTA_Q8_NONFINITE = 0, 1, 2, 3, 4
 DELTA_MAX_VARS = 1024
 
 ALLREDUCE_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int32)
@@ -162,6 +162,10 @@ SIGNATURES = {
     "ams_select_apply": (C.c_int, [_vp, _vp, _i64, _f32, _vp, _vp, _vp]),
     "ams_student_encode_delta": (C.c_int, [_vp, _vp, C.POINTER(DeltaVar), _i32, _vp, _i64, _vp, _vp, _sz, _vp]),
     "ams_student_encode_delta_scratch": (_sz, [C.POINTER(DeltaVar), _i32]),
+    "ams_student_encode_delta_q8": (C.c_int, [_vp, _vp, C.POINTER(DeltaVar), _i32, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "ams_student_encode_delta_q8_scratch": (_sz, [C.POINTER(DeltaVar), _i32]),
+    "ams_student_apply_delta_q8": (C.c_int, [_vp, _vp, _i64, C.POINTER(DeltaVar), _i32, _vp, _vp, _vp, _sz, _vp]),
+    "ams_student_apply_delta_q8_scratch": (_sz, [C.POINTER(DeltaVar), _i32]),
     "ams_k_stem_conv": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _f32, _vp, _vp]),
     "ams_k_depthwise3x3": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp]),
     "ams_k_pointwise": (C.c_int, [_vp, _i64, _i32, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp]),

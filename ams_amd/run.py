@@ -100,6 +100,11 @@ def build_parser() -> argparse.ArgumentParser:
                    help="score the edge model the downlink payload produces (extra flag): the server also writes each event's raw payload "
                         "(<label>_<second>_delta.bin), and the edge keeps its network and applies that payload to the initial model "
                         "(--no_restore: to its previous model) on the device instead of reloading the server's full f32 model")
+    p.add_argument("--delta_format", default="fp16", choices=["fp16", "q8"],
+                   help="what the downlink payload carries behind its mask bits (extra flag): fp16 = the masked values as fp16 (the reference's "
+                        "format), q8 = one f32 scale per variable and one int8 code per masked element of the CHANGE against the model both ends "
+                        "hold (the initial model; with --no_restore the edge's previous model, which the server tracks).  _mask.dat, _mask.dat.gz, "
+                        "_delta.bin and the downlink accounting carry the chosen format; --edge_from_delta decodes it")
     p.add_argument("--device_masks", action="store_true",
                    help="server: choose coord_desc_auto's coordinates, keep the masks and encode the downlink payload on the device (extra "
                         "flag; same files and numbers)")
@@ -497,7 +502,10 @@ def train_model(ctx: Context, train_start, train_end, sampling_period, gpu_id, r
                 soft_eval.append([float(second), metric.loss_soft, metric.soft_miou] + [float(v) for v in metric.soft_iou])
                 print_process("Soft-teacher loss over the memory %.4f, probabilistic mIoU %.1f%%" % (metric.loss_soft, 100 * metric.soft_miou), second)
             # model delta on the downlink: packed mask bits + masked parameters as fp16, gzip -9 (run.py:316-336)
-            payload = semantic_network.delta_payload()          # value part gathered + cast to fp16 on the device
+            if getattr(FLAGS, "delta_format", "fp16") == "q8":  # int8 codes of the change; continual training follows the edge's model
+                payload = semantic_network.delta_payload(fmt="q8", track_edge=bool(FLAGS.no_restore))
+            else:
+                payload = semantic_network.delta_payload()      # value part gathered + cast to fp16 on the device
             if getattr(FLAGS, "device_masks", False):          # the same number from the layout: curr_mask stays on the device
                 full_size = delta_layout(semantic_network.engine.spec, FLAGS.train_strategy).n_elements
             else:
@@ -629,7 +637,8 @@ def infer_output(ctx: Context, inf_start, inf_end, gpu_id, run_label, gt_path, e
                     with open(save_dir + "_delta.bin", "rb") as f:
                         payload = f.read()
                     t0 = time.time()
-                    semantic_network.apply_delta(payload, FLAGS.train_strategy, None if FLAGS.no_restore else base_variables)
+                    semantic_network.apply_delta(payload, FLAGS.train_strategy, None if FLAGS.no_restore else base_variables,
+                                                 **({"fmt": "q8"} if getattr(FLAGS, "delta_format", "fp16") == "q8" else {}))
                     update_s.append(time.time() - t0)
             else:
                 if semantic_network is not None:
@@ -683,7 +692,8 @@ def infer_output(ctx: Context, inf_start, inf_end, gpu_id, run_label, gt_path, e
     if semantic_network is not None:
         semantic_network.close_model()
     n = max(1, inf_end_frame - inf_start * fps)
-    summary = {"frames": n, "frames_per_sec": n / max(t_infer, 1e-9), "mean_miou": float(np.nanmean(miou_s))}
+    summary = {"frames": n, "frames_per_sec": n / max(t_infer, 1e-9), "mean_miou": float(np.nanmean(miou_s)),
+               "delta_format": getattr(FLAGS, "delta_format", "fp16")}
     if from_delta:
         summary["edge_updates"] = len(update_s)
         summary["edge_update_ms"] = 1000.0 * float(np.mean(update_s)) if update_s else float("nan")

@@ -38,7 +38,7 @@ from . import coord_masks, hip
 from .batch_feed import HostBatchFeed
 from .confidence import Confidence, ConfidenceStats
 from . import weights as W
-from .delta import delta_layout
+from .delta import check_format, delta_layout
 from .edge_pipeline import EdgePipeline
 from .engine import StudentEngine
 from .render import VIEWS as RENDER_VIEWS, DeviceRenderer
@@ -226,6 +226,7 @@ class SemanticNetwork(object):
         self._confidence_host = None       # pinned block the statistics rows of a synchronous pass leave through, on first use
         self._soft_host = None             # the same for the rows of the soft-teacher metric
         self._held = None                  # device_masks: what the last phase left on the device (_hold_phase)
+        self._q8_tracked = False           # delta_payload(fmt="q8", track_edge=True) has run: the engine's delta base follows the edge's model
         self._auto_mask_dev = None         # device_masks: coord_desc_auto's selection, kept for keep_mask=True
         self._feed = None                  # training from host deques: the helper threads and their pinned ring (_host_feed)
         # frozen with pipeline_depth >= 2: predict_with_metric_async / collect.  Every synchronous pass drains it first (one output block).
@@ -735,7 +736,29 @@ class SemanticNetwork(object):
                                flip=self.flip)
         return memory.plan(samples, crop[0], crop[1])
 
-    def delta_payload(self, device: bool = False):
+    def _delta_payload_q8(self, device, base_variables, track_edge):
+        """delta_payload(fmt="q8"): always encoded on the device, whichever path the phase took."""
+        eng = self.engine
+        held = self._held
+        with self.process_lock:
+            if held is not None:
+                layout, mask = delta_layout(eng.spec, held["strategy"]), held["mask"]
+            else:
+                assert self.curr_mask is not None, "no training phase has run yet"
+                layout = delta_layout(eng.spec, "coord_desc_rand" if len(self.curr_mask) == len(eng.spec.trainable) else "full_model")
+                assert [m.size for m in self.curr_mask] == [e.count for e in layout.entries], "curr_mask does not follow a delta layout"
+                flat = np.concatenate([np.asarray(m).reshape(-1) for m in self.curr_mask]).astype(np.uint8)
+                mask = None if flat.all() else torch.from_numpy(flat).to(eng.device)          # NULL = every element
+            if base_variables is not None:
+                eng.set_delta_base(base_variables)
+                self._q8_tracked = False
+            elif not self._q8_tracked:
+                eng.set_delta_base({k: v for k, v in self._initial.items() if self.filter(k) is not None})
+            dev = eng.encode_delta(layout, mask, fmt="q8", advance_base=track_edge)
+            self._q8_tracked = self._q8_tracked or bool(track_edge)
+            return dev if device else dev.cpu().numpy().tobytes()
+
+    def delta_payload(self, device: bool = False, fmt: str = "fp16", base_variables=None, track_edge: bool = False):
         """The downlink model delta of reference run.py:316-336 as bytes: per variable ``np.packbits(mask.flatten())``, then
         per variable the masked parameters as fp16.  Under the coordinate-descent strategies (``train_params`` = the
         trainable variables, in arena order) the value part is gathered and cast on the device by ``ams_pack_masked_fp16``;
@@ -743,7 +766,16 @@ class SemanticNetwork(object):
 
         After a ``device_masks=True`` phase the whole payload, mask bits included, is encoded on the device from the phase's device mask and the
         engine's current variables (``ams_student_encode_delta``; call it before the model changes again, as run.py does) and comes to the
-        host in one copy.  ``device=True`` returns the payload as a uint8 device tensor instead, which ``apply_delta`` accepts."""
+        host in one copy.  ``device=True`` returns the payload as a uint8 device tensor instead, which ``apply_delta`` accepts.
+
+        ``fmt="q8"`` (an addition; fp16 is the reference's format and the default): after the same mask bits, one f32 scale per variable and one
+        int8 code of (value - base) per masked element, always encoded on the device (``ams_student_encode_delta_q8``).  The base is
+        ``base_variables``, by default the checkpoint ``restore_initial`` loads.  ``track_edge=True`` serves continual training (run.py
+        --no_restore): after encoding, the base's masked elements become what the edge decodes, and later calls encode against that
+        tracked base, so each update's quantisation error is carried into the next instead of accumulating on the edge."""
+        if check_format(fmt) == "q8":
+            return self._delta_payload_q8(device, base_variables, track_edge)
+        assert base_variables is None and not track_edge, "base_variables / track_edge belong to the q8 format"
         held = self._held
         if held is not None:
             with self.process_lock:
@@ -768,7 +800,7 @@ class SemanticNetwork(object):
                 payload += p_[m_].astype(np.float16).tobytes()
         return bytes(payload)
 
-    def apply_delta(self, payload, train_strategy, base_variables=None) -> int:
+    def apply_delta(self, payload, train_strategy, base_variables=None, fmt: str = "fp16") -> int:
         """The edge half of the downlink (an addition: the reference's edge reloads the server's full model, run.py:401-411): decode a
         ``delta_payload`` of a server running ``train_strategy`` into this network's variables on the device and, on a frozen instance,
         re-freeze (which repeats the fp16 range check).  ``base_variables`` (a {name: array} dict, e.g. the initial model's) are loaded
@@ -776,7 +808,9 @@ class SemanticNetwork(object):
         values applied.  A malformed payload raises AmsHipError and leaves the model as it was (including a base loaded for it).
 
         Frames submitted with ``predict_with_metric_async`` before this call are answered by the old model, frames submitted after it by the
-        new one: the queued ones are launched and fetched first."""
+        new one: the queued ones are launched and fetched first.
+
+        ``fmt="q8"``: the payload carries changes, added to the base (``base_variables``, or the current model when None)."""
         layout = delta_layout(self.engine.spec, train_strategy)
         with self.process_lock:
             self._pipeline.flush()
@@ -787,7 +821,7 @@ class SemanticNetwork(object):
                 eng.load_variables(base_variables)
                 eng._updated_since_freeze = True
             try:
-                n = eng.apply_delta(payload, layout)
+                n = eng.apply_delta(payload, layout, fmt)
             except hip.AmsHipError:
                 if saved is not None:
                     eng.params.copy_(saved[0])

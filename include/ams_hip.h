@@ -466,11 +466,13 @@ typedef struct ams_delta_var {
 
 #define AMS_DELTA_MAX_VARS 1024
 
-/* status word written by ams_student_apply_delta */
+/* status word written by ams_student_apply_delta, ams_student_apply_delta_q8 and ams_student_encode_delta_q8 */
 enum {
     AMS_DELTA_OK = 0,
     AMS_DELTA_BAD_SIZE = 1,      /* payload bytes != mask bytes + 2 x set mask bits (truncated, over-long or a corrupted mask) */
-    AMS_DELTA_BAD_PADDING = 2    /* a padding bit after a variable's last element is set */
+    AMS_DELTA_BAD_PADDING = 2,   /* a padding bit after a variable's last element is set */
+    AMS_DELTA_BAD_SCALE = 3,     /* q8 payload: a variable's scale is NaN, inf, negative, or nonzero below 2^-126 */
+    AMS_DELTA_Q8_NONFINITE = 4   /* q8 encoder: a masked change (current - base) is NaN or +-inf; nothing was written */
 };
 
 /* Decodes payload_dev (payload_bytes device bytes, any alignment) into the student's unfolded variables: every masked element gets
@@ -523,6 +525,44 @@ int ams_student_encode_delta(ams_student* s, const uint8_t* mask_dev, const ams_
                              int64_t payload_cap, int64_t* payload_bytes_dev, int64_t* scratch_dev, size_t scratch_elems, void* stream);
 /* int64 elements of device scratch ams_student_encode_delta needs for this table (0 if the table is malformed) */
 size_t ams_student_encode_delta_scratch(const ams_delta_var* vars_host, int32_t n_vars);
+
+/* ---- the same delta in 8 bits (q8): both ends hold the model the update starts from, so the change travels, not the value --------------
+ * Payload, over the same descriptor table, no header and no padding between sections:
+ *   [mask section]   as above: per variable np.packbits(mask)
+ *   [scale section]  n_vars little-endian f32, one per variable of the layout in layout order (unaligned: read and written as bytes)
+ *   [code section]   one int8 per set mask bit, in mask order
+ * so payload bytes = mask bytes + 4 x n_vars + set bits.
+ *
+ * Encoder, all f32, one rounding per operation: d = current - base; amax_v = max |d| over the masked elements of variable v (0 if none);
+ * scale_v = amax_v / 127, set to 0 if below 2^-126; q = 0 if scale_v == 0, else clamp(rintf(d / scale_v), -127, 127) (ties to even).
+ * The student's params / stats are the current values; base_params_dev / base_stats_dev hold the base in the same element order
+ * (n_trainable / n_stats floats; base_stats_dev may be NULL only if no table entry lies in AMS_REGION_STATS).  mask_dev as above.
+ * *status_dev (int32) = AMS_DELTA_OK, or AMS_DELTA_Q8_NONFINITE if a masked d is NaN or +-inf: then *payload_bytes_dev = 0 and neither
+ * the payload nor the base is written.  Otherwise *payload_bytes_dev (int64) = the payload's size; beyond payload_cap nothing is written
+ * either and the caller sees payload_bytes > payload_cap.  advance_base = 1: the write pass also stores f32(base + f32(scale_v * q)) —
+ * what the decoder makes of the element — into the base of every masked element, so that the next payload is relative to the model the
+ * edge really holds (continual training); 0 leaves the base alone.
+ * Refused on the host with AMS_E_INVALID and nothing launched: a null pointer, advance_base outside 0 / 1, a malformed table, scratch
+ * below ams_student_encode_delta_q8_scratch, payload_cap below mask section + scale section.
+ * Three launches (q8_amax_kernel, q8_encode_scan_kernel, q8_encode_write_kernel) after a copy of the table, which also zeroes the
+ * per-variable maxima; no allocation, no synchronisation. */
+int ams_student_encode_delta_q8(ams_student* s, const uint8_t* mask_dev, const ams_delta_var* vars_host, int32_t n_vars,
+                                float* base_params_dev, float* base_stats_dev, int32_t advance_base, uint8_t* payload_dev,
+                                int64_t payload_cap, int64_t* payload_bytes_dev, int32_t* status_dev, int64_t* scratch_dev,
+                                size_t scratch_elems, void* stream);
+/* int64 elements of device scratch ams_student_encode_delta_q8 needs for this table (0 if the table is malformed) */
+size_t ams_student_encode_delta_q8_scratch(const ams_delta_var* vars_host, int32_t n_vars);
+
+/* Decodes a q8 payload in place: every masked element becomes f32(element + f32(scale_v * q)), two roundings (the element's current
+ * value is the base: load the base first); every other element keeps its bits; a code of -128 (never produced) decodes as -128.
+ * Validated on the device first, all or nothing: size (AMS_DELTA_BAD_SIZE), padding bits (AMS_DELTA_BAD_PADDING), then the scales
+ * (AMS_DELTA_BAD_SCALE).  *status_dev / *n_applied_dev, the table and the scratch as for ams_student_apply_delta.  Three launches
+ * (delta_count_kernel, q8_delta_scan_kernel, q8_delta_apply_kernel) after a copy of the table; no allocation, no synchronisation. */
+int ams_student_apply_delta_q8(ams_student* s, const uint8_t* payload_dev, int64_t payload_bytes, const ams_delta_var* vars_host,
+                               int32_t n_vars, int64_t* n_applied_dev, int32_t* status_dev, int64_t* scratch_dev, size_t scratch_elems,
+                               void* stream);
+/* int64 elements of device scratch ams_student_apply_delta_q8 needs for this table (0 if the table is malformed) */
+size_t ams_student_apply_delta_q8_scratch(const ams_delta_var* vars_host, int32_t n_vars);
 
 /* ---- the server's replay memory on the device (replaces run.py:136-137 frame_memory / label_memory, two host deques, and the sampling of
  * utils/utils.py:129-185 mini_batch from them).  The memory is a ring of `capacity` slots the caller owns: slot p of the frames is uint8
