@@ -1005,6 +1005,26 @@ int ams_k_expand_dw_stream_f16(const float* x, int32_t B, int32_t H, int32_t W, 
                                   panel_elems, 2, presplit, y_h2i, stream);
 }
 
+// The steps of the launch ams_k_expand_dw_stream[_f16] would make for these arguments (the launchers' own geometry functions, the kernels' own
+// step rule): host arithmetic, no GPU call.  Checked as the launch entries check their shape.
+int ams_k_expand_dw_steps(int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cexp, int32_t rate, int32_t f16, int32_t presplit, int32_t* out, size_t n) {
+    const bool f32 = !f16 && Cin <= 32;
+    const bool wreg = !f32 && presplit == 2;
+    BlockCall c;
+    c.B = B; c.H = H; c.W = W; c.Cin = Cin; c.Cexp = Cexp; c.rate = rate;
+    if (f32 && rate < 0) { c.stride = -rate; c.rate = 1; }
+    AMS_REQUIRE(B > 0 && H > 0 && W > 0, "expand_dw_steps: no pixels: B=%d, %d x %d", B, H, W);
+    AMS_REQUIRE(expand_dw_stream_supported(Cin, Cexp, c.stride, c.rate) && (!f16 || Cin >= 64), "expand_dw_steps: unsupported shape Cin=%d Cexp=%d rate=%d",
+                Cin, Cexp, rate);
+    AMS_REQUIRE(out && n >= 10, "expand_dw_steps: out needs at least 10 elements");
+    const int np = f32 ? 0 : (f16 ? 2 : 3);         // parts as staged: the bf16 entry is counted with its three parts
+    XdwGeom g;
+    const bool fits = wreg ? expand_dw_wreg_geom(B, H, W, Cin, Cexp, c.rate, np, &g) : expand_dw_stream_geom(B, H, W, Cin, Cexp, c.rate, np, &g);
+    AMS_REQUIRE(fits, "expand_dw_steps: no segment geometry fits LDS (W=%d rate=%d)", W, rate);
+    expand_dw_steps(g, H, W, c.rate, out, n);
+    return AMS_OK;
+}
+
 int ams_k_global_mean(const float* x, int32_t B, int64_t HW, int32_t C, float* y, float* scratch, size_t scratch_floats,
                       void* stream) {
     AMS_REQUIRE(scratch && scratch_floats >= image_colsum_scratch(B, C), "global_mean: scratch too small (need %zu floats)",

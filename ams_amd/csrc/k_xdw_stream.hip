@@ -19,6 +19,7 @@
 #include "pw_common.hpp"
 #include "split_bf16.hpp"
 #include "block_call.hpp"
+#include "xdw_steps.hpp"
 
 namespace ams {
 
@@ -161,8 +162,12 @@ __global__ __launch_bounds__(64 * (NWE + NWD)) void xdw_stream_kernel(XdsArgs a,
             const bool live = i0 < Hs && j0 < Ws;                    // a segment past the end of a smaller sub-image: barriers only
             // operand source of a pixel: f32 activations (split here) or, PRE, the bf16 parts the producing GEMM wrote beside them
             const int64_t frame0 = (int64_t)b * a.H * a.W * a.Cin + (F32 ? 0 : 8 * q);
-            int e_row, e_col;
-            { const int e0 = 16 * wave + l15; e_row = e0 / Wp; e_col = e0 - e_row * Wp; }
+            // the item's steps (xdw_steps.hpp): only the steps from the first to the last that holds a pixel of the feature map load operands and
+            // multiply; the others write the zeros a stored centre will read (the pad rows), or nothing; the item ends with its last stored centre
+            const XdwItemSteps steps = xdw_item_steps(Wp, STEP, a.SH, Hs, Ws, i0, j0);
+            XdwWalk ew = xdw_e_start();
+            int e_row, e_col;                                        // the lane's pixel of the next compute step: the walker starts at the first one
+            { const int e0 = steps.inside.t0 * STEP + 16 * wave + l15; e_row = e0 / Wp; e_col = e0 - e_row * Wp; }
             float4 raw[(PRE || F32) ? 1 : KS][2];
             u32x4 rawp[PRE ? KS : 1][NP];
             float4 rawf[F32 ? KS : 1];                                // F32: k = 16c + 4q .. + 3 of the lane's pixel
@@ -186,21 +191,53 @@ __global__ __launch_bounds__(64 * (NWE + NWD)) void xdw_stream_kernel(XdsArgs a,
                     raw[s][1] = ld4(a.x + off + 32 * s + 4);
                 }
             };
-            {
+            if (steps.T_item > 0) {                                   // operands of the first compute step
                 const int64_t p = next_pixel();
 #pragma unroll
                 for (int s = 0; s < KS; ++s) load_stage(p, s);
             }
-            for (int t = 0; t < a.T; ++t) {
+            auto end_step = [&]() {
+                sbase += STEP;
+                if (sbase == R) sbase = 0;
+                lap(0);
+                __syncthreads();
+                lap(1);
+                ++nstep;
+            };
+            // a step that computes nothing: zeros where stored centres read it (the depthwise conv's padding: the pad rows), or nothing at all
+            auto other_step = [&](int t) {
+                if (xdw_e_class(t, ew, steps) == XDW_E_ZERO) {
+                    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+                    float* dst = ring + sbase * PITCH + ring_lane;
+                    const bool mirror = sbase == 0 && 16 * wave + l15 < MIRROR;
+#pragma unroll
+                    for (int tt = 0; tt < NT; ++tt) {
+                        st4(dst + 16 * tt, z);
+                        if (mirror) st4(dst + R * PITCH + 16 * tt, z);
+                    }
+                }
+                xdw_advance(ew, steps);
+                end_step();
+            };
+            // The compute steps of an item follow each other (xdw_steps.hpp) and run in a loop of their own, the loop this kernel always had:
+            // each requests the operands of the next inside its MFMA loop (the last one loads a clamped pixel for nothing).  Measured and not
+            // kept: one loop over all steps with the compute step as a branch of its body — hipcc then keeps the operands requested for the
+            // next step apart from the ones in use and copies them behind the loads, which waits for them within the step: 49 -> 62 us on the
+            // 64 -> 384 layer.
+            int t = 0;
+            for (; t < steps.inside.t0 && t < steps.T_item; ++t) other_step(t);
+            for (; t <= steps.inside.t1 && t < steps.T_item; ++t) {
+                xdw_advance(ew, steps);
+                {
                 const bool inside = in_next;
+                e_row += qS; e_col += rS;
+                if (e_col >= Wp) { e_col -= Wp; ++e_row; }
+                const int64_t pn = next_pixel();                      // pixel of the next compute step
                 f32x4 acc[NT], accx[H16 ? NT : 1];
 #pragma unroll
                 for (int tt = 0; tt < NT; ++tt) acc[tt] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int tt = 0; tt < (H16 ? NT : 1); ++tt) accx[tt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-                e_row += qS; e_col += rS;
-                if (e_col >= Wp) { e_col -= Wp; ++e_row; }
-                const int64_t pn = next_pixel();                      // pixel of step t + 1
                 // Operands are split stage by stage (12 registers live instead of 12 * KS) and a stage's registers are refilled
                 // with the next step's operands as soon as they are split: those loads have the rest of the step to land.
                 // Products in the order of pw_gemm_bf16x3_l per accumulator; consecutive MFMAs go to different accumulators (see there:
@@ -286,13 +323,10 @@ __global__ __launch_bounds__(64 * (NWE + NWD)) void xdw_stream_kernel(XdsArgs a,
                         if (mirror) st4(dst + R * PITCH + 16 * tt, v);
                     }
                 }
-                sbase += STEP;
-                if (sbase == R) sbase = 0;
-                lap(0);
-                __syncthreads();
-                lap(1);
-                ++nstep;
+                }
+                end_step();
             }
+            for (; t < steps.T_item; ++t) other_step(t);
             __syncthreads();                                          // the D-waves finish the item (their step T - 1)
         }
         flush(0);
@@ -332,8 +366,15 @@ __global__ __launch_bounds__(64 * (NWE + NWD)) void xdw_stream_kernel(XdsArgs a,
             int d_row, d_col;                                        // first centre of this thread at step 0: -Wp - 1 + pt * PX
             { const int c0 = Wp - 1 + pt * PX; d_row = c0 / Wp; d_col = c0 - d_row * Wp; d_row -= 2; }
             __syncthreads();                                          // E-step 0
-            for (int t = 0; t < a.T; ++t) {
-                // D-step t: the STEP centres whose neighbourhood is complete after E-step t
+            const XdwItemSteps steps = xdw_item_steps(Wp, STEP, a.SH, Hs, Ws, i0, j0);
+            XdwWalk dw = xdw_d_start(Wp);
+            for (int t = 0; t < steps.T_item; ++t) {
+                // D-step t: the STEP centres whose neighbourhood is complete after E-step t.  A step without a stored centre goes straight to
+                // the barrier (xdw_steps.hpp; at stride 2 the rule counts every position of the item's rows and columns as a centre, and the
+                // ballot below then drops the pairs and steps that hold none); the walkers advance all the same
+                const bool d_act = xdw_d_active(t, dw, steps);
+                xdw_advance(dw, steps);
+                if (d_act) {
                 if constexpr (S == 2) {
                     // stride 2: the window centres sit on every other row and column of the input, so of a thread's pair of adjacent
                     // positions at most one is a centre, and whole steps fall on rows without any (wave-uniform skip)
@@ -431,6 +472,7 @@ __global__ __launch_bounds__(64 * (NWE + NWD)) void xdw_stream_kernel(XdsArgs a,
                         }
                     }
                 }
+                }
                 d_row += qS; d_col += rS;
                 if (d_col >= Wp) { d_col -= Wp; ++d_row; }
                 cb += STEP;
@@ -521,6 +563,50 @@ static bool xds_plan(int B, int H, int W, int Cin, int Cexp, int rate, int np, X
     return xds_plan_try(B, H, W, Cin, Cexp, rate, np, 2, 4, 4, nsy_force, 0, groups_force, p);
 }
 
+bool expand_dw_stream_geom(int B, int H, int W, int Cin, int Cexp, int rate, int np, XdwGeom* g) {
+    XdsPlan p;
+    if (!xds_plan(B, H, W, Cin, Cexp, rate, np, &p)) return false;
+    const int step = 16 * p.nwe;
+    g->step = step; g->SH = p.SH; g->SW = p.SW; g->Wp = p.SW + 2; g->T = ((p.SH + 2) * g->Wp + step - 1) / step; g->ring = p.ring;
+    g->nsy = p.nsy; g->nsx = p.nsx; g->cgroups = (Cexp + 16 * p.nt - 1) / (16 * p.nt);
+    g->items = B * rate * rate * p.nsy * p.nsx; g->groups = p.groups;
+    g->nt = p.nt; g->nwe = p.nwe; g->nwd = p.nwd; g->nrg = 1; g->lds = p.lds;
+    return true;
+}
+
+// the host's walk over the items of a launch, step by step with the kernels' own rule (item order of the kernels: column strip, row
+// segment, sub-image, frame)
+void expand_dw_steps(const XdwGeom& g, int H, int W, int rate, int32_t* out, size_t n) {
+    const size_t per_item = 10, per_step = per_item + 5 * (size_t)g.items;
+    const bool items_out = n >= per_step, steps_out = n >= per_step + (size_t)g.T * g.items;
+    int64_t sum[5] = {0, 0, 0, 0, 0};
+    for (int item = 0; item < g.items; ++item) {
+        int u1 = item;
+        const int segx = u1 % g.nsx; u1 /= g.nsx;
+        const int segy = u1 % g.nsy; u1 /= g.nsy;
+        const int sub = u1 % (rate * rate);
+        const int sy = sub / rate, sx = sub - sy * rate;
+        const int Hs = (H - sy + rate - 1) / rate, Ws = (W - sx + rate - 1) / rate;
+        const XdwItemSteps s = xdw_item_steps(g.Wp, g.step, g.SH, Hs, Ws, segy * g.SH, segx * g.SW);
+        XdwWalk e = xdw_e_start(), d = xdw_d_start(g.Wp);
+        int cnt[5] = {s.T_item, 0, 0, 0, 0};
+        for (int t = 0; t < g.T; ++t) {
+            const int cls = xdw_e_class(t, e, s);
+            const bool act = xdw_d_active(t, d, s);
+            xdw_advance(e, s);
+            xdw_advance(d, s);
+            if (t < s.T_item) { cnt[1] += cls == XDW_E_COMPUTE; cnt[2] += cls == XDW_E_ZERO; cnt[3] += act; cnt[4] += cls == XDW_E_COMPUTE && act; }
+            if (steps_out) out[per_step + (size_t)item * g.T + t] = cls + 4 * act + 8 * (t < s.T_item);
+        }
+        for (int k = 0; k < 5; ++k) {
+            sum[k] += cnt[k];
+            if (items_out) out[per_item + 5 * (size_t)item + k] = cnt[k];
+        }
+    }
+    out[0] = g.step; out[1] = g.Wp; out[2] = g.SH; out[3] = g.T; out[4] = g.items;
+    for (int k = 0; k < 5; ++k) out[5 + k] = (int32_t)sum[k];
+}
+
 // Cin 16 / 24 / 32: exact-f32 products (the early blocks); 64 / 96 / 160: split-bf16 products (the stride-16 section)
 bool expand_dw_stream_supported(int Cin, int Cexp, int stride, int rate) {
     if (rate != 1 && rate != 2) return false;
@@ -588,8 +674,10 @@ int launch_expand_dw_stream(const BlockCall& c, hipStream_t st) {
     const bool h16 = !f32 && c.expand.np == AMS_NP_F16;       // two fp16 parts
     const int np = f32 ? 0 : h16 ? 2 : c.expand.np;
     AMS_REQUIRE((int64_t)H * W * Cexp * 4 < 0x7fffffffLL, "expand_dw_stream: a frame of the output exceeds 2 GiB");
-    XdsPlan p;
-    AMS_REQUIRE(xds_plan(B, H, W, Cin, Cexp, rate, np, &p), "expand_dw_stream: no segment geometry fits LDS (W=%d rate=%d)", W, rate);
+    XdwGeom g;
+    AMS_REQUIRE(expand_dw_stream_geom(B, H, W, Cin, Cexp, rate, np, &g), "expand_dw_stream: no segment geometry fits LDS (W=%d rate=%d)", W, rate);
+    XdsPlan p{};
+    p.nt = g.nt; p.nwe = g.nwe; p.nwd = g.nwd; p.lds = g.lds;      // what the launch dispatch reads
     XdsArgs a;
     memset(&a, 0, sizeof(a));
     a.x = c.x; a.xs = f32 ? nullptr : c.x_parts; a.xs_plane = c.x_plane; a.wf = c.expand.w; a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.wp = c.expand.panels; a.plane = c.expand.plane;
@@ -602,10 +690,9 @@ int launch_expand_dw_stream(const BlockCall& c, hipStream_t st) {
         same_pad(W, 3, 2, 1, &a.Wo, &pl);
         a.cy0 = 1 - pt; a.cx0 = 1 - pl;
     }
-    const int step = 16 * p.nwe;
-    a.SH = p.SH; a.SW = p.SW; a.Wp = p.SW + 2; a.T = ((p.SH + 2) * a.Wp + step - 1) / step; a.ring = p.ring;
-    a.nsy = p.nsy; a.nsx = p.nsx; a.chunks = (Cexp + 16 * p.nt - 1) / (16 * p.nt);
-    a.items = B * rate * rate * p.nsy * p.nsx; a.groups = p.groups;
+    a.SH = g.SH; a.SW = g.SW; a.Wp = g.Wp; a.T = g.T; a.ring = g.ring;
+    a.nsy = g.nsy; a.nsx = g.nsx; a.chunks = g.cgroups;
+    a.items = g.items; a.groups = g.groups;
     a.y_fmt = c.y_fmt;
     a.timed = knobs().xwr_timed;
     if (h16) {

@@ -14,6 +14,7 @@
 #include "pw_common.hpp"
 #include "split_bf16.hpp"
 #include "block_call.hpp"
+#include "xdw_steps.hpp"
 
 namespace ams {
 
@@ -172,18 +173,30 @@ __global__ __launch_bounds__(64 * (NWE + NWD)) void xdw_wreg_kernel(XwrArgs a, u
 #pragma unroll
                 for (int k = 0; k < LPT; ++k) sA[buf * AUNITS + pdst[k]] = piece[k];
             };
+            // the item's steps (xdw_steps.hpp): a step that meets no pixel of the feature map loads nothing and multiplies nothing — it writes the
+            // zeros a stored centre will read (the pad rows), or nothing at all; the item ends with its last stored centre
+            const XdwItemSteps steps = xdw_item_steps(Wp, STEP, a.SH, Hs, Ws, i0, j0);
+            XdwWalk ew = xdw_e_start();
+            int cls_next = xdw_e_class(0, ew, steps);
             // prologue of the item: operand tile of step 0
-            load_pieces(loader_pixel());
-            store_pieces(par);
+            if (cls_next == XDW_E_COMPUTE) {
+                load_pieces(loader_pixel());
+                store_pieces(par);
+            }
             __syncthreads();                                          // (A) tile 0 visible; pairs with the D-waves' first barrier
-            for (int t = 0; t < a.T; ++t) {
+            for (int t = 0; t < steps.T_item; ++t) {
+                const int cls = cls_next;
 #pragma unroll
                 for (int rg = 0; rg < NRG; ++rg) {
                     in_cur[rg] = inside_of(rg);
                     e_row[rg] += qS; e_col[rg] += rS;
                     if (e_col[rg] >= Wp) { e_col[rg] -= Wp; ++e_row[rg]; }
                 }
-                if constexpr (!(ABL & 1)) load_pieces(loader_pixel());        // tile of step t + 1: lands during the MFMAs
+                xdw_advance(ew, steps);
+                cls_next = xdw_e_class(t + 1, ew, steps);
+                const bool load_next = cls_next == XDW_E_COMPUTE && !(ABL & 1);
+                if (load_next) load_pieces(loader_pixel());          // tile of step t + 1: lands during the MFMAs
+                if (cls == XDW_E_COMPUTE) {
                 // The accumulators start at zero INSIDE the active branch (there the first MFMA of each takes the constant 0 as its C operand); a wave of
                 // a short last channel group skips the products and the ring stores alike — nothing valid reads its ring columns (the D-threads of
                 // those channels store nothing) — so no path needs 32 zeroed registers (they were 32 v_mov per step on every path)
@@ -274,7 +287,21 @@ __global__ __launch_bounds__(64 * (NWE + NWD)) void xdw_wreg_kernel(XwrArgs a, u
                         }
                     }
                 }
-                store_pieces(par ^ 1);
+                } else if (cls == XDW_E_ZERO && active && !(ABL & 16)) {
+                    // nothing of the step is inside the feature map, but stored centres read it: the depthwise conv's zero padding
+                    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+                    for (int rg = 0; rg < NRG; ++rg) {
+                        float* dst = ring + (sbase + 16 * rg) * PITCH + ring_lane;
+                        const bool mirror = sbase == 0 && rg == 0 && l15 < MIRROR;
+#pragma unroll
+                        for (int tt = 0; tt < 2; ++tt) {
+                            st4(dst + 16 * tt, z);
+                            if (mirror) st4(dst + R * PITCH + 16 * tt, z);
+                        }
+                    }
+                }
+                if (cls_next == XDW_E_COMPUTE) store_pieces(par ^ 1);
                 par ^= 1;
                 sbase += STEP;
                 if (sbase == R) sbase = 0;
@@ -382,7 +409,17 @@ __global__ __launch_bounds__(64 * (NWE + NWD)) void xdw_wreg_kernel(XwrArgs a, u
                     }
                 }
             };
-            for (int t = 0; t < a.T; ++t) {
+            const XdwItemSteps steps = xdw_item_steps(Wp, STEP, a.SH, Hs, Ws, i0, j0);
+            XdwWalk dw = xdw_d_start(Wp);
+            for (int t = 0; t < steps.T_item; ++t) {
+                // a step without a stored centre goes straight to the barrier (xdw_steps.hpp); the walkers advance all the same
+                const bool d_act = xdw_d_active(t, dw, steps);
+                xdw_advance(dw, steps);
+                const int row0 = d_row, col0 = d_col, off0c = d_off;     // the step's first centre; the next ones follow by increments
+                d_row += qS; d_col += rS; d_off += stepdelta;
+                if (d_col >= Wp) { d_col -= Wp; ++d_row; d_off += wrapdelta; }
+                const int cb_next = cb + STEP >= R ? cb + STEP - R : cb + STEP;
+                if (d_act) {
                 load_row(0);
                 load_row(1);
                 load_row(2);
@@ -406,11 +443,6 @@ __global__ __launch_bounds__(64 * (NWE + NWD)) void xdw_wreg_kernel(XwrArgs a, u
                                 AMS_DW_FMA4(acc4[hh][u], vv, w4);
                             }
                 }
-                const int row0 = d_row, col0 = d_col, off0c = d_off;     // the step's first centre; the next ones follow by increments
-                d_row += qS; d_col += rS; d_off += stepdelta;
-                if (d_col >= Wp) { d_col -= Wp; ++d_row; d_off += wrapdelta; }
-                cb += STEP;
-                if (cb >= R) cb -= R;
                 if constexpr (TIMED) {                                // [5]: the FMAs are done
 #pragma unroll
                     for (int hh = 0; hh < NH; ++hh)
@@ -419,6 +451,8 @@ __global__ __launch_bounds__(64 * (NWE + NWD)) void xdw_wreg_kernel(XwrArgs a, u
                     lap(3);
                 }
                 epilogue(acc4, row0, col0, off0c);
+                }
+                cb = cb_next;
                 lap(0);
                 __syncthreads();
                 lap(1);
@@ -487,12 +521,8 @@ static int launch_xwr_w(const XwrArgs& a, int nwe, int nrg, size_t lds, hipStrea
 
 // the weight-register form; c.x_parts is required (bf16 parts of the input, np of them).  AMS_XWR_FORCE = "E-waves (4|8),row
 // segments,column strips,blocks per channel group,row groups per E-wave and step (1|2; 2 only with 4 E-waves)" (0 = automatic).
-int launch_expand_dw_wreg(const BlockCall& c, hipStream_t st) {
-    RUN_RC(block_call_check("expand_dw_wreg", BK_WREG, c));
-    const int B = c.B, H = c.H, W = c.W, Cin = c.Cin, Cexp = c.Cexp, rate = c.rate;
-    const bool h16 = c.expand.np == AMS_NP_F16;      // two fp16 parts (split_bf16.hpp)
-    const int np = h16 ? 2 : c.expand.np;
-    AMS_REQUIRE((int64_t)H * W * Cexp * 4 < 0x7fffffffLL, "expand_dw_wreg: a frame of the output exceeds 2 GiB");
+// The launch geometry, for the launcher and for the step count of ams_k_expand_dw_steps alike (np: parts as staged, 2 for the fp16 form)
+bool expand_dw_wreg_geom(int B, int H, int W, int Cin, int Cexp, int rate, int np, XdwGeom* g) {
     int nwe = 4, nsy_force = 0, nsx_force = 0, groups_force = 0, nrg = 2;
     if (knobs().xwr_set) { const int* f = knobs().xwr; nwe = f[0]; nsy_force = f[1]; nsx_force = f[2]; groups_force = f[3]; nrg = f[4]; }
     if (nwe != 4 && nwe != 8) nwe = 4;
@@ -507,25 +537,43 @@ int launch_expand_dw_wreg(const BlockCall& c, hipStream_t st) {
         ring = (2 * (SW + 2) + 2 + 2 * step + step - 1) / step * step;
         if (xwr_lds(Cin, np, nwe, nrg, ring) <= budget || SW <= 1) break;
     }
-    AMS_REQUIRE(xwr_lds(Cin, np, nwe, nrg, ring) <= budget, "expand_dw_wreg: no segment geometry fits LDS (W=%d rate=%d)", W, rate);
+    if (xwr_lds(Cin, np, nwe, nrg, ring) > budget) return false;
     nsx = (Ws + SW - 1) / SW;
     const int cgroups = (Cexp + 32 * nwe - 1) / (32 * nwe);
     int nsy = 1;
     if (nsy_force > 0) nsy = nsy_force;
     else
         while ((int64_t)B * rate * rate * cgroups * nsx * nsy < 512 && (Hs + nsy - 1) / nsy > 8) ++nsy;
+    g->nt = 2; g->nwe = nwe; g->nwd = 4; g->nrg = nrg; g->step = step;
+    g->SH = (Hs + nsy - 1) / nsy; g->SW = SW; g->Wp = SW + 2; g->T = ((g->SH + 2) * g->Wp + step - 1) / step; g->ring = ring;
+    g->nsy = nsy; g->nsx = nsx; g->cgroups = cgroups;
+    g->items = B * rate * rate * nsy * nsx;
+    int64_t groups = groups_force > 0 ? groups_force : (512 + cgroups - 1) / cgroups;      // one block per CU (LDS), twice over
+    if (groups > g->items) groups = g->items;
+    g->groups = (int)groups;
+    g->lds = xwr_lds(Cin, np, nwe, nrg, ring);
+    return true;
+}
+
+int launch_expand_dw_wreg(const BlockCall& c, hipStream_t st) {
+    RUN_RC(block_call_check("expand_dw_wreg", BK_WREG, c));
+    const int B = c.B, H = c.H, W = c.W, Cin = c.Cin, Cexp = c.Cexp, rate = c.rate;
+    const bool h16 = c.expand.np == AMS_NP_F16;      // two fp16 parts (split_bf16.hpp)
+    const int np = h16 ? 2 : c.expand.np;
+    AMS_REQUIRE((int64_t)H * W * Cexp * 4 < 0x7fffffffLL, "expand_dw_wreg: a frame of the output exceeds 2 GiB");
+    XdwGeom g;
+    AMS_REQUIRE(expand_dw_wreg_geom(B, H, W, Cin, Cexp, rate, np, &g), "expand_dw_wreg: no segment geometry fits LDS (W=%d rate=%d)", W, rate);
+    const int nwe = g.nwe, nrg = g.nrg;
     XwrArgs a;
     memset(&a, 0, sizeof(a));
     a.xs = c.x_parts; a.xs_plane = c.x_plane; a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.wp = c.expand.panels; a.plane = c.expand.plane; a.sc_e = c.expand.scale;
     a.sh_e = c.expand.shift; a.act_e = c.expand.act; a.Cexp = Cexp; a.w_dw = c.dw.w; a.sc_d = c.dw.scale; a.sh_d = c.dw.shift; a.act_d = c.dw.act; a.y = c.y; a.rate = rate;
-    a.SH = (Hs + nsy - 1) / nsy; a.SW = SW; a.Wp = SW + 2; a.T = ((a.SH + 2) * a.Wp + step - 1) / step; a.ring = ring;
-    a.nsy = nsy; a.nsx = nsx; a.cgroups = cgroups;
-    a.items = B * rate * rate * nsy * nsx;
+    a.SH = g.SH; a.SW = g.SW; a.Wp = g.Wp; a.T = g.T; a.ring = g.ring;
+    a.nsy = g.nsy; a.nsx = g.nsx; a.cgroups = g.cgroups;
+    a.items = g.items;
     a.y_fmt = c.y_fmt;
-    int64_t groups = groups_force > 0 ? groups_force : (512 + cgroups - 1) / cgroups;      // one block per CU (LDS), twice over
-    if (groups > a.items) groups = a.items;
-    a.groups = (int)groups;
-    const size_t lds = xwr_lds(Cin, np, nwe, nrg, ring);
+    a.groups = g.groups;
+    const size_t lds = g.lds;
     if (h16) {
         switch (Cin / 32) {
             case 2: return launch_xwr_w<2, 2, true>(a, nwe, nrg, lds, st);

@@ -291,6 +291,17 @@ int launch_expand_dw_stream(const BlockCall& c, hipStream_t st);
 
 // ---- k_xdw_wreg.hip : the streaming fusion with the expand weights in registers and the operand staged in LDS (160 -> 960)
 int launch_expand_dw_wreg(const BlockCall& c, hipStream_t st);
+// The geometry the two streaming launchers pick for a call (AMS_XDS_FORCE / AMS_XWR_FORCE honoured) — the launchers take it from these
+// functions, and so does expand_dw_steps: step = pixels per step, items = work items per chunk / channel group (cgroups of them), groups =
+// blocks per chunk.  np: parts as staged (0: the exact-f32 form, 2 for the fp16 form).  false: nothing fits LDS.
+struct XdwGeom { int step, SH, SW, Wp, T, ring, nsy, nsx, cgroups, items, groups, nt, nwe, nwd, nrg; size_t lds; };
+bool expand_dw_stream_geom(int B, int H, int W, int Cin, int Cexp, int rate, int np, XdwGeom* g);
+bool expand_dw_wreg_geom(int B, int H, int W, int Cin, int Cexp, int rate, int np, XdwGeom* g);
+// The steps of every item of such a launch by the rule of xdw_steps.hpp (what the kernels' step loops execute), no GPU call.  out[0 .. 9]: step,
+// Wp, SH, T, items; summed over the items: steps executed, E compute steps, E zero steps, active D-steps, steps (loop index) with an E compute and
+// an active D-step.  n >= 10 + 5 * items: then per item T_item and its four counts; n >= 10 + (5 + T) * items: then per item and step t < T the
+// code E class (0 idle, 1 zero, 2 compute) + 4 * (D-step active) + 8 * (t < T_item).  H x W: the input (rate 1 | 2, stride 1 or 2).
+void expand_dw_steps(const XdwGeom& g, int H, int W, int rate, int32_t* out, size_t n);
 // c.expand.np of the two streaming launchers: 1 .. 3 bf16 parts, or AMS_NP_F16 = the two fp16 parts of split_bf16.hpp (hi | lo 2^11; planes as
 // for np = 2).  c.y_fmt 1 (fp16 form only): the result as fp16 pairs interleaved per 8 channels (PwArgs::x_fmt 1) instead of f32
 

@@ -183,6 +183,7 @@ SIGNATURES = {
                                     C.POINTER(FirstBlockPlan), _vp]),
     "ams_k_first_block_tiles": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ams_k_first_block_plan": (C.c_int, [_i32, _i32, _i32, _i32, _i32, C.POINTER(_i32), C.POINTER(FirstBlockPlan)]),
+    "ams_k_expand_dw_steps": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i32), _sz]),
     "ams_k_expand_dw": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ams_k_expand_dw_stream": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _sz, _i32, _i32, _vp]),
     "ams_k_global_mean": (C.c_int, [_vp, _i32, _i64, _i32, _vp, _vp, _sz, _vp]),

@@ -870,6 +870,19 @@ int ams_k_first_block_tiles(const void* frames, int32_t frames_dtype, int32_t B,
 /* The plan ams_k_first_block would hand back, without a launch.  occupancy NULL: the blocks per CU of the two walking kernels and the CU count are
  * asked of the current device; else {interior blocks per CU, border blocks per CU, CUs}: pure host arithmetic, no GPU needed. */
 int ams_k_first_block_plan(int32_t frames_dtype, int32_t B, int32_t H, int32_t W, int32_t form, const int32_t* occupancy, ams_first_block_plan* plan_out);
+/* The steps that ams_k_expand_dw_stream (f16 == 0; Cin > 32: counted with three parts) or ams_k_expand_dw_stream_f16 (f16 != 0) would run for
+ * these arguments (presplit 2: the weight-register form; rate -2 as there), without a launch: the launchers' own geometry (AMS_XDS_FORCE /
+ * AMS_XWR_FORCE honoured) walked with the kernels' own step rule (csrc/xdw_steps.hpp).  Host arithmetic, no GPU needed.  A work item is a
+ * segment of a sub-image; its roles walk it in steps of STEP positions: the E-waves expand, the D-waves run the depthwise conv one row behind.
+ * out[0 .. 4]: STEP, Wp (row pitch of a segment), SH (its rows), T (steps of a whole segment: what every item ran before steps were
+ *   skipped), items per channel chunk.
+ * out[5 .. 9], summed over the items: steps executed, E-steps that compute, E-steps that only write zeros, D-steps with a stored centre,
+ *   loop steps in which the E-step computes and the D-step is active.
+ * n >= 10 + 5 * items: out[10 + 5 i ..] the same five figures of item i (the first is its T_item).
+ * n >= 10 + (5 + T) * items: out[10 + 5 items + T i + t] = E class of step t of item i (0 idle, 1 zero, 2 compute) + 4 (D-step t active)
+ *   + 8 (t < T_item: the step is executed). */
+int ams_k_expand_dw_steps(int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cexp, int32_t rate, int32_t f16, int32_t presplit, int32_t* out,
+                          size_t n);
 
 /* Frame ingest (reference run.py:179-183, :415-421: cv2.resize of the decoded frame to [H, 2H] + BGR->RGB; INTER_NEAREST for
  * the teacher label map).  src [Hs,Ws,C] uint8 -> dst [H,W,C] uint8, both device memory.  mode AMS_RESIZE_NEAREST |
