@@ -23,10 +23,12 @@ import torch
 from . import hip
 
 
-def init_from_env(backend: Optional[str] = None, device: Optional[torch.device] = None):
+def init_from_env(backend: Optional[str] = None, device: Optional[torch.device] = None, timeout=None):
     """Join the job described by RANK / WORLD_SIZE / LOCAL_RANK / MASTER_ADDR / MASTER_PORT (torchrun's contract).
 
-    Returns (rank, world_size, local_rank).  With WORLD_SIZE unset or 1 no process group is created."""
+    Returns (rank, world_size, local_rank).  With WORLD_SIZE unset or 1 no process group is created.  ``timeout``: a
+    ``datetime.timedelta`` for the group's rendezvous and collectives (None: torch's default), after which a rank whose
+    peer died raises instead of waiting."""
     import torch.distributed as dist
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -38,6 +40,8 @@ def init_from_env(backend: Optional[str] = None, device: Optional[torch.device] 
         kwargs = {}
         if backend == "nccl" and device is not None:
             kwargs["device_id"] = device
+        if timeout is not None:
+            kwargs["timeout"] = timeout
         dist.init_process_group(backend, rank=rank, world_size=world, **kwargs)
     return rank, world, local_rank
 

@@ -58,6 +58,15 @@ autograd call per bit), and EVERY quantity that depends on the mask (dgamma, dbe
 input gradient) is then compared under that one assignment: no element is left out or given slack.  More than 64 ambiguous elements in a
 layer, more than 1e-4 of its elements or more than 8 in one channel fail the run.
 
+THE DATA-PARALLEL STEP (tests/test_gpu_dp_links.py) is held by the same links.  With an all-reduce the engine takes other launches (the
+reductions' second stages stop at the f64 sums, the cross-rank sum, then separate finalize / coefficient kernels; dgamma / dbeta from
+the local sums) and mixes local row counts with global ones.  One rank with a reduce function that does nothing (or a one-rank RCCL
+communicator) is such a step whose run is a plain run.  Two ranks each leave a run of their own shard: z, a, dz, da, logits of their
+frames, but grads, moving statistics and loss of the whole batch, the same bits on every rank.  ``join_rank_runs`` asserts that
+invariant and concatenates the shards into the run of the global batch, and the links then close over it exactly as over a
+single-process run: F2 / F3 / B2 fail on statistics or coefficients formed from one rank's rows, B1 and dgamma / dbeta on gradients
+that were not summed, or summed twice.  The bars are the f32 CPU oracle's at the GLOBAL size, by the same rule.
+
 ERROR MEASURES (no others).  Elementwise tensors (z, a, dz, da, dlogits): max|got - ref| / max|ref| over the tensor.  Reduced quantities
 (every GRADS slice, moving statistics, the CE sum): max_e |got_e - ref_e| / max_e S_e with S_e the f64 sum of the absolute values of the
 terms of element e (sum |dy| for dbeta, sum |x||dz| for a weight gradient, ...) — dbeta of a project layer in front of a training-mode BN
@@ -689,6 +698,34 @@ def oracle_run(W: Dict[str, np.ndarray], class_indices, frames, labels, dtype, t
 
 def copy_run(run: dict) -> dict:
     return {k: (dict(v) if isinstance(v, dict) else v) for k, v in run.items()}
+
+
+def join_rank_runs(runs: List[dict], identical: bool = True) -> dict:
+    """The runs of the ranks of ONE data-parallel step, each on its own shard of the batch, as the run of the whole batch: frames, labels,
+    teacher logits, logits and every z / a / dz / da (dlogits, y, dy where the runs keep them) concatenated along the batch in rank order;
+    params and stats_before from rank 0.  grads, stats_after and loss are what the step leaves AFTER its cross-rank sums, so every rank
+    must hold the same bits (identical Adam input on every rank is the data-parallel invariant): asserted, with the name of the first
+    tensor that differs, and taken once.  ``identical`` False takes rank 0's without looking (un-synchronised stand-ins on the CPU)."""
+    r0 = runs[0]
+    if identical:
+        for k, r in enumerate(runs[1:], 1):
+            for key in ("grads", "stats_after"):
+                assert list(r[key]) == list(r0[key]), "rank %d names other %s than rank 0" % (k, key)
+                for name, t in r0[key].items():
+                    assert torch.equal(r[key][name], t), "%s of %s on rank %d is not rank 0's, bit for bit (worst |difference| %.3e)" % (
+                        key, name, k, float((r[key][name] - t).abs().max()))
+            assert tuple(r["loss"]) == tuple(r0["loss"]), "loss (CE sum, valid count) on rank %d %r is not rank 0's %r" % (k, r["loss"], r0["loss"])
+    out = copy_run(r0)
+    for key in ("frames", "logits", "dlogits"):
+        if r0.get(key) is not None:
+            out[key] = torch.cat([r[key] for r in runs], dim=0)
+    for key in ("labels", "teacher_logits"):
+        if r0.get(key) is not None:
+            out[key] = np.concatenate([np.asarray(r[key]) for r in runs], axis=0)
+    for kind in ("z", "a", "dz", "da", "y", "dy"):
+        if kind in r0:
+            out[kind] = {i: torch.cat([r[kind][i] for r in runs], dim=0) for i in r0[kind]}
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------------

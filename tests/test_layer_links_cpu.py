@@ -8,9 +8,14 @@
 (d) The default step: the same runs with every tensor the default (fused) step does not store withheld (LL.default_step_stored).  Both
     plans together close to 1e-10 across the withheld tensors; the f32 run gives the levels of the composite links and the band of every
     withheld activation; six more wrong wires and two planted mask bits fail or pass as they must.
+(e) The data-parallel step (LL.join_rank_runs, tests/test_gpu_dp_links.py): the f32 oracle's step of 4 frames cut into the runs of two ranks
+    (3 + 1 frames) and joined is the original and passes every link; un-synchronised BN (each rank's own oracle step), gradients that
+    were not summed over the ranks, dgamma / dbeta summed twice each fail the links they belong to, and moving statistics that differ
+    between the ranks stop the join.
 
-Sizes: 64x128 x 2 frames and 62x124 x 3 frames (even and odd block inputs pad differently under SAME).
+Sizes: 64x128 x 2 frames and 62x124 x 3 frames (even and odd block inputs pad differently under SAME); 62x124 x 4 frames for (e).
 """
+import numpy as np
 import pytest
 import torch
 
@@ -328,3 +333,153 @@ def test_mask_controls(runs64, composite, bars, H, B):
     # ... and without the band the same run fails: the bit is no rounding
     bands[e.idx] = 0.0
     assert _failing(planted(near), composite, bars, e, bands=bands, plan=plan)[0]
+
+
+# ---------------------------------------------------------------------------------------------------------
+# the data-parallel step: runs of the ranks joined into the run of the whole batch (LL.join_rank_runs)
+# ---------------------------------------------------------------------------------------------------------
+DP_CASE = (62, 4)                          # odd maps; 4 frames over two ranks (case A of tests/test_gpu_dp_links.py)
+DP_SHARDS = ((0, 3), (3, 4))               # uneven: local and global row counts differ on every layer
+
+
+@pytest.fixture(scope="module")
+def dp():
+    """the f32 CPU oracle's step of the whole batch as the stand-in for a synchronised step, and the bars of its own size"""
+    return LL.f32_run(*DP_CASE), LL.bars_from_levels(LL.f32_levels((DP_CASE,)))
+
+
+def _rank_slice(run, lo, hi):
+    """What the rank that holds frames lo .. hi - 1 leaves of a synchronised step: its rows of every batched tensor, and the whole
+    batch's gradients, moving statistics and loss."""
+    out = LL.copy_run(run)
+    for key in ("frames", "labels", "logits", "dlogits"):
+        out[key] = run[key][lo:hi]
+    for kind in ("z", "a", "dz", "da", "y", "dy"):
+        out[kind] = {i: t[lo:hi] for i, t in run[kind].items()}
+    return out
+
+
+def _same(a, b):
+    if isinstance(a, dict):
+        return a.keys() == b.keys() and all(_same(a[k], b[k]) for k in a)
+    if torch.is_tensor(a):
+        return torch.equal(a, b)
+    if isinstance(a, np.ndarray):
+        return np.array_equal(a, b)
+    return a == b
+
+
+def _backward_plan(links):
+    plan = []
+    for l in links.spec.layers:
+        plan.append(("B1", l.idx))
+        if l.bn_eps is not None:
+            plan.append(("B2", l.idx))
+        if l.residual_from is not None:
+            plan.append(("DA", l.idx))
+    return plan
+
+
+def _rank_grads(links, lo, hi):
+    """What frames lo .. hi - 1 alone add to every gradient of the run's step: the f64 links B1 and B2 (statistics, mask and cotangent of
+    the WHOLE batch) summed over those rows only.  The engine forms exactly this on a rank before the gradient all-reduce."""
+    g = {}
+    for l in links.spec.layers:
+        x, dz = links.x_in(l).detach()[lo:hi], links.dz(l.idx)[lo:hi]
+        w = LL._leaf(links.P(l.weight_name))
+        g[l.weight_name] = torch.autograd.grad((links.conv(l, x, w) * dz).sum(), w)[0]
+        if l.bn_eps is None:
+            g[l.scope + "/biases:0"] = dz.sum(dim=(0, 2, 3))
+            continue
+        gamma, beta = (LL._leaf(t) for t in links._gb(l))
+        y, _, _ = links._bn(l, links.z(l.idx), gamma, beta)
+        dg, db = torch.autograd.grad((y * links.mask(l) * links.cot_a(l.idx))[lo:hi].sum(), [gamma, beta])
+        g[l.scope + "/BatchNorm/gamma:0"], g[l.scope + "/BatchNorm/beta:0"] = dg, db
+    return g
+
+
+def _grad_names(spec):
+    w = {l.weight_name for l in spec.layers} | {spec.layers[-1].scope + "/biases:0"}
+    dg = {l.scope + "/BatchNorm/gamma:0" for l in spec.layers if l.bn_eps is not None}
+    db = {l.scope + "/BatchNorm/beta:0" for l in spec.layers if l.bn_eps is not None}
+    assert len(w | dg | db) == 164
+    return w, dg, db
+
+
+def test_rank_runs_joined_are_the_run_of_the_whole_batch(dp):
+    """(a) of the data-parallel proofs: cut into 3 + 1 frames and joined, the run is the original, tensor for tensor, and passes every link"""
+    run, bars = dp
+    ranks = [_rank_slice(run, lo, hi) for lo, hi in DP_SHARDS]
+    assert [r["frames"].shape[0] for r in ranks] == [3, 1]
+    joined = LL.join_rank_runs(ranks)
+    assert _same(joined, run)
+    res = LL.Links(joined).close()
+    assert {r.kind for r in res} == set(LL.KINDS) and len(res) == 3 + 55 + 56 + 54 + 2 * 54 + (3 * 54 - 1) + 10
+    assert not LL.failures(res, bars)
+    # rank order matters: the shards the other way round are another batch, and the loss no longer belongs to it
+    swapped = LL.join_rank_runs(ranks[::-1])
+    assert not _same(swapped["z"], run["z"])
+
+
+def test_unsynchronised_batch_norm_fails_its_links(dp):
+    """(b): each rank's own oracle step normalises with the statistics of its own rows.  The ranks then disagree on gradients and
+    statistics (the join refuses them); taken as one run anyway, BN + activation, the moving statistics and the BN backward of every
+    layer fail, the convolutions (frame by frame the same operation) do not."""
+    _, bars = dp
+    frames, labels = LL.case_clip(*DP_CASE)
+    ranks = [LL.oracle_run(LL.case_weights(), LL.CI, frames[lo:hi], labels[lo:hi], torch.float32) for lo, hi in DP_SHARDS]
+    with pytest.raises(AssertionError, match="grads of MobilenetV2/Conv/weights:0 on rank 1"):
+        LL.join_rank_runs(ranks)
+    links = LL.Links(LL.join_rank_runs(ranks, identical=False))
+    bad = LL.failures(links.close(), bars)
+    bn = [l for l in links.spec.layers if l.bn_eps is not None]
+    assert {r.name for r in bad if r.link == "F2"} == {l.scope for l in bn}
+    # every moving variance; a moving mean may survive: behind a project layer without a skip each rank's own BN leaves the same mean (beta),
+    # so the expand layer's batch mean is the same on every rank
+    assert {r.name for r in bad if r.link == "F3"} >= {n for n in links.r["stats_after"] if n.endswith("moving_variance:0")}
+    assert len(links.r["stats_after"]) == 108
+    assert {r.name for r in bad if r.link == "B2" and r.kind == "dz"} == {l.scope for l in bn if l is not links.lp}
+    assert {r.name for r in bad if r.kind == "dgamma"} == {l.scope + "/BatchNorm/gamma:0" for l in bn}
+    assert not [r for r in bad if r.link == "F1"]
+
+
+def test_gradients_not_summed_or_summed_twice_fail_their_links(dp):
+    """(c) and (d): the step's gradients replaced by what rank 0's frames alone add to them (the gradient all-reduce left out) fail the
+    weight-gradient link and the dgamma / dbeta links of every layer and nothing else; dgamma / dbeta formed from the sums AFTER their
+    cross-rank sum and then added up by the gradient all-reduce come out twice as large, and fail.  The two ranks' shares added up
+    pass: the shares are the step's own."""
+    run, bars = dp
+    joined = LL.join_rank_runs([_rank_slice(run, lo, hi) for lo, hi in DP_SHARDS])
+    links = LL.Links(joined)
+    plan = _backward_plan(links)
+    weights, dgamma, dbeta = _grad_names(links.spec)
+    share = [_rank_grads(links, lo, hi) for lo, hi in DP_SHARDS]
+
+    def failing(grads):
+        bad = LL.copy_run(joined)
+        bad["grads"] = grads
+        return {r.name for r in LL.failures(LL.Links(bad).close(plan), bars)}
+
+    assert not failing({k: share[0][k] + share[1][k] for k in share[0]})
+    assert failing(share[0]) == weights | dgamma | dbeta                         # (c): every gradient tensor, no dz and no da
+    twice = dict(joined["grads"])
+    for k in dgamma | dbeta:
+        twice[k] = 2.0 * joined["grads"][k]
+    got = failing(twice)                                                        # (d)
+    # dbeta of a project layer is 0 in real arithmetic (the training-mode BN behind it removes a constant), and so is twice it
+    zero = {l.scope + "/BatchNorm/beta:0" for l in links.backbone if l.act == "none"}
+    assert dgamma | (dbeta - zero) <= got <= dgamma | dbeta, (dgamma | dbeta) - got
+
+
+def test_join_refuses_ranks_that_disagree(dp):
+    """(e): one moving statistic one ulp off on one rank, and the loss: the join names what differs"""
+    run, _ = dp
+    ranks = [_rank_slice(run, lo, hi) for lo, hi in DP_SHARDS]
+    name = "MobilenetV2/expanded_conv_9/depthwise/BatchNorm/moving_variance:0"
+    ranks[1]["stats_after"][name] = torch.nextafter(run["stats_after"][name], torch.full_like(run["stats_after"][name], 1e30))
+    with pytest.raises(AssertionError, match="stats_after of " + name + " on rank 1"):
+        LL.join_rank_runs(ranks)
+    ranks = [_rank_slice(run, lo, hi) for lo, hi in DP_SHARDS]
+    ranks[1]["loss"] = (run["loss"][0] * (1 + 1e-12), run["loss"][1])
+    with pytest.raises(AssertionError, match="loss"):
+        LL.join_rank_runs(ranks)
