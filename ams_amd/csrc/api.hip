@@ -1382,6 +1382,154 @@ int ams_k_xdw_dwe(const float* G1, const float* xx_g0, int32_t Cin, int32_t Cexp
     return launch_xdw_dwe(G1, xx_g0, Cin, Cexp, w_exp, cA, cB, cC, dw_exp, (hipStream_t)stream);
 }
 
+// ---- the BN pieces of k_elementwise.hip: column reductions, second stages over partial rows, per-channel arithmetic, apply passes, plain folds ----
+int ams_k_col_plan(int64_t M, int32_t groups, int32_t C, int32_t* out) {
+    AMS_REQUIRE(out, "col_plan: null output");
+    return col_plan(M, groups, C, out);
+}
+size_t ams_k_colstats_scratch(int64_t M, int32_t C) { return colstats_scratch(M, C); }
+int ams_k_colstats(const float* z, int64_t M, int32_t C, const float* center, double* sums, float* scratch, size_t scratch_floats, void* stream) {
+    AMS_REQUIRE(z && sums && scratch, "colstats: null pointer");
+    AMS_REQUIRE(M > 0 && C > 0 && scratch_floats >= colstats_scratch(M, C), "colstats: no rows (M=%lld C=%d) or scratch too small (need %zu floats)",
+                (long long)M, C, colstats_scratch(M, C));
+    return launch_colstats(z, M, C, center, sums, scratch, (hipStream_t)stream);
+}
+int ams_k_colstats_f64(const float* z, int64_t M, int32_t C, const float* center, double* sums, void* stream) {
+    AMS_REQUIRE(z && sums, "colstats_f64: null pointer");
+    AMS_REQUIRE(M > 0 && C > 0, "colstats_f64: no rows (M=%lld C=%d)", (long long)M, C);
+    return launch_colstats_f64(z, M, C, center, sums, (hipStream_t)stream);
+}
+int ams_k_colstats_bn(const float* z, int64_t M, int32_t C, const float* center, double* sums, float* scratch, size_t scratch_floats, double n,
+                      const float* gamma, const float* beta, float eps, float one_minus_decay, float* moving_mean, float* moving_var, float* scale,
+                      float* shift, float* save_mean, float* save_rstd, void* stream) {
+    AMS_REQUIRE(z && sums && scratch && gamma && beta && scale && shift, "colstats_bn: null pointer");
+    AMS_REQUIRE(!moving_mean == !moving_var && !save_mean == !save_rstd, "colstats_bn: moving_mean / moving_var and save_mean / save_rstd come in pairs");
+    AMS_REQUIRE(M > 0 && C > 0 && n >= 1.0 && scratch_floats >= colstats_scratch(M, C),
+                "colstats_bn: no rows (M=%lld C=%d n=%g) or scratch too small (need %zu floats)", (long long)M, C, n, colstats_scratch(M, C));
+    return launch_colstats_bn(z, M, C, center, sums, scratch, n, gamma, beta, eps, one_minus_decay, moving_mean, moving_var, scale, shift, save_mean,
+                              save_rstd, (hipStream_t)stream);
+}
+int ams_k_bn_finalize(const double* sums, double n, int32_t C, const float* center, const float* gamma, const float* beta, float eps,
+                      float one_minus_decay, float* moving_mean, float* moving_var, float* scale, float* shift, float* save_mean, float* save_rstd,
+                      void* stream) {
+    AMS_REQUIRE(sums && gamma && beta && scale && shift, "bn_finalize: null pointer");
+    AMS_REQUIRE(!moving_mean == !moving_var && !save_mean == !save_rstd, "bn_finalize: moving_mean / moving_var and save_mean / save_rstd come in pairs");
+    AMS_REQUIRE(C > 0 && n >= 1.0, "bn_finalize: C=%d n=%g", C, n);
+    return launch_bn_finalize(sums, n, C, center, gamma, beta, eps, one_minus_decay, moving_mean, moving_var, scale, shift, save_mean, save_rstd,
+                              (hipStream_t)stream);
+}
+// partial rows [rows][2][C], row_stride floats apart (0: dense, 2 * C)
+static int partials_shape(const char* who, int rows, int64_t row_stride, int C) {
+    AMS_REQUIRE(rows > 0 && C > 0 && (row_stride == 0 || row_stride >= 2 * (int64_t)C), "%s: rows=%d C=%d row_stride=%lld (0 or at least 2 * C)", who, rows,
+                C, (long long)row_stride);
+    return AMS_OK;
+}
+int ams_k_bn_fwd_partials(const float* part, int32_t rows, int64_t row_stride, int32_t C, double* sums, double n, const float* center,
+                          const float* gamma, const float* beta, float eps, float one_minus_decay, float* moving_mean, float* moving_var, float* scale,
+                          float* shift, float* save_mean, float* save_rstd, void* stream) {
+    AMS_REQUIRE(part && sums && gamma && beta && scale && shift, "bn_fwd_partials: null pointer");
+    AMS_REQUIRE(!moving_mean == !moving_var && !save_mean == !save_rstd, "bn_fwd_partials: moving_mean / moving_var and save_mean / save_rstd come in pairs");
+    AMS_REQUIRE(n >= 1.0, "bn_fwd_partials: n=%g", n);
+    if (int rc = partials_shape("bn_fwd_partials", rows, row_stride, C)) return rc;
+    return launch_bn_fwd_finalize_partials(part, rows, row_stride, C, sums, n, center, gamma, beta, eps, one_minus_decay, moving_mean, moving_var, scale,
+                                           shift, save_mean, save_rstd, (hipStream_t)stream);
+}
+int ams_k_partials_to_sums(const float* part, int32_t rows, int64_t row_stride, int32_t C, double* sums, void* stream) {
+    AMS_REQUIRE(part && sums, "partials_to_sums: null pointer");
+    if (int rc = partials_shape("partials_to_sums", rows, row_stride, C)) return rc;
+    return launch_partials_to_sums(part, rows, row_stride, C, sums, (hipStream_t)stream);
+}
+int ams_k_bn_bwd_reduce(const float* da, const float* z, int64_t M, int32_t C, const float* scale, const float* shift, int32_t act, const float* mean,
+                        const float* rstd, double* sums, float* scratch, size_t scratch_floats, void* stream) {
+    AMS_REQUIRE(da && z && scale && shift && mean && rstd && sums && scratch, "bn_bwd_reduce: null pointer");
+    AMS_REQUIRE(M > 0 && C > 0 && scratch_floats >= colstats_scratch(M, C), "bn_bwd_reduce: no rows (M=%lld C=%d) or scratch too small (need %zu floats)",
+                (long long)M, C, colstats_scratch(M, C));
+    return launch_bn_bwd_reduce(da, z, M, C, scale, shift, act, mean, rstd, sums, scratch, (hipStream_t)stream);
+}
+int ams_k_bn_bwd_reduce_coef(const float* da, const float* z, int64_t M, int32_t C, const float* scale, const float* shift, int32_t act,
+                             const float* mean, const float* rstd, double* sums, float* scratch, size_t scratch_floats, double n, const float* gamma,
+                             float* coefA, float* coefB, float* coefC, float* dgamma, float* dbeta, void* stream) {
+    AMS_REQUIRE(da && z && scale && shift && mean && rstd && sums && scratch && gamma && coefA && coefB && coefC && dgamma && dbeta,
+                "bn_bwd_reduce_coef: null pointer");
+    AMS_REQUIRE(M > 0 && C > 0 && n >= 1.0 && scratch_floats >= colstats_scratch(M, C),
+                "bn_bwd_reduce_coef: no rows (M=%lld C=%d n=%g) or scratch too small (need %zu floats)", (long long)M, C, n, colstats_scratch(M, C));
+    return launch_bn_bwd_reduce_coef(da, z, M, C, scale, shift, act, mean, rstd, sums, scratch, n, gamma, coefA, coefB, coefC, dgamma, dbeta,
+                                     (hipStream_t)stream);
+}
+int ams_k_bn_bwd_partials(const float* part, int32_t rows, int64_t row_stride, int32_t C, double* sums, double n, const float* gamma, const float* mean,
+                          const float* rstd, float* coefA, float* coefB, float* coefC, float* dgamma, float* dbeta, void* stream) {
+    AMS_REQUIRE(part && sums && gamma && mean && rstd && coefA && coefB && coefC && dgamma && dbeta, "bn_bwd_partials: null pointer");
+    AMS_REQUIRE(n >= 1.0, "bn_bwd_partials: n=%g", n);
+    if (int rc = partials_shape("bn_bwd_partials", rows, row_stride, C)) return rc;
+    return launch_bn_bwd_finalize_partials(part, rows, row_stride, C, sums, n, gamma, mean, rstd, coefA, coefB, coefC, dgamma, dbeta, (hipStream_t)stream);
+}
+int ams_k_bn_bwd_coef(const double* sums, double n, int32_t C, const float* gamma, const float* mean, const float* rstd, float* coefA, float* coefB,
+                      float* coefC, float* dgamma, float* dbeta, void* stream) {
+    AMS_REQUIRE(sums && gamma && mean && rstd && coefA && coefB && coefC, "bn_bwd_coef: null pointer");
+    AMS_REQUIRE(!dgamma == !dbeta, "bn_bwd_coef: dgamma and dbeta come as a pair");
+    AMS_REQUIRE(C > 0 && n >= 1.0, "bn_bwd_coef: C=%d n=%g", C, n);
+    return launch_bn_bwd_coef(sums, n, C, gamma, mean, rstd, coefA, coefB, coefC, dgamma, dbeta, (hipStream_t)stream);
+}
+int ams_k_bn_param_grads(const double* sums, int32_t C, float* dgamma, float* dbeta, void* stream) {
+    AMS_REQUIRE(sums && dgamma && dbeta, "bn_param_grads: null pointer");
+    AMS_REQUIRE(C > 0, "bn_param_grads: C=%d", C);
+    return launch_bn_param_grads(sums, C, dgamma, dbeta, (hipStream_t)stream);
+}
+int ams_k_bn_act(const float* z, int64_t M, int32_t C, const float* scale, const float* shift, int32_t act, const float* res, float* a, void* stream) {
+    AMS_REQUIRE(z && scale && shift && a, "bn_act: null pointer");
+    AMS_REQUIRE(M > 0 && C > 0 && act >= AMS_ACT_NONE && act <= AMS_ACT_RELU6, "bn_act: M=%lld C=%d act=%d", (long long)M, C, act);
+    return launch_bn_act(z, M, C, scale, shift, act, res, a, (hipStream_t)stream);
+}
+int ams_k_bn_bwd_apply(const float* da, const float* z, int64_t M, int32_t C, const float* scale, const float* shift, int32_t act, const float* coefA,
+                       const float* coefB, const float* coefC, float* dz, void* stream) {
+    AMS_REQUIRE(da && z && scale && shift && coefA && coefB && coefC && dz, "bn_bwd_apply: null pointer");
+    AMS_REQUIRE(M > 0 && C > 0 && act >= AMS_ACT_NONE && act <= AMS_ACT_RELU6, "bn_bwd_apply: M=%lld C=%d act=%d", (long long)M, C, act);
+    return launch_bn_bwd_apply(da, z, M, C, scale, shift, act, coefA, coefB, coefC, dz, (hipStream_t)stream);
+}
+int ams_k_bn_fold(const float* gamma, const float* beta, const float* mean, const float* var, float eps, int32_t C, float* scale, float* shift,
+                  void* stream) {
+    AMS_REQUIRE(gamma && beta && mean && var && scale && shift, "bn_fold: null pointer");
+    AMS_REQUIRE(C > 0, "bn_fold: C=%d", C);
+    return launch_bn_fold(gamma, beta, mean, var, eps, C, scale, shift, (hipStream_t)stream);
+}
+int ams_k_reduce_splits(const float* part, int32_t splits, int64_t n, int64_t stride, float* out, void* stream) {
+    AMS_REQUIRE(part && out, "reduce_splits: null pointer");
+    AMS_REQUIRE(splits > 0 && n > 0 && stride >= n, "reduce_splits: splits=%d n=%lld stride=%lld (at least n)", splits, (long long)n, (long long)stride);
+    return launch_reduce_splits(part, splits, n, out, (hipStream_t)stream, stride);
+}
+int ams_k_reduce_batch(const float* const* part, const int32_t* splits, const int64_t* count, const int64_t* stride, float* const* out, int32_t n_jobs,
+                       void* stream) {
+    AMS_REQUIRE(part && splits && count && stride && out, "reduce_batch: null pointer");
+    AMS_REQUIRE(n_jobs > 0 && n_jobs <= ReduceJobs::kMax, "reduce_batch: %d jobs (1..%d)", n_jobs, ReduceJobs::kMax);
+    ReduceJobs jobs;
+    for (int j = 0; j < n_jobs; ++j) {
+        AMS_REQUIRE(part[j] && out[j] && splits[j] > 0 && count[j] > 0 && stride[j] >= count[j], "reduce_batch: job %d: null pointer, or splits=%d count=%lld stride=%lld",
+                    j, splits[j], (long long)count[j], (long long)stride[j]);
+        jobs.add(part[j], splits[j], count[j], out[j], stride[j]);
+    }
+    return launch_reduce_batch(jobs, (hipStream_t)stream);
+}
+size_t ams_k_colsum_scratch(int32_t C) { return colsum_scratch(C); }
+int ams_k_colsum(const float* x, int64_t M, int32_t C, int32_t ldx, float* out, float* scratch, size_t scratch_floats, void* stream) {
+    AMS_REQUIRE(x && out && scratch, "colsum: null pointer");
+    AMS_REQUIRE(M > 0 && C > 0 && ldx >= C && scratch_floats >= colsum_scratch(C), "colsum: M=%lld C=%d ldx=%d, or scratch too small (need %zu floats)",
+                (long long)M, C, ldx, colsum_scratch(C));
+    return launch_colsum(x, M, C, ldx, out, scratch, (hipStream_t)stream);
+}
+size_t ams_k_image_colsum_scratch(int32_t B, int32_t C) { return image_colsum_scratch(B, C); }
+int ams_k_image_colsum(const float* x, int32_t B, int64_t HW, int32_t C, int32_t ldx, float* out, float* scratch, size_t scratch_floats, void* stream) {
+    AMS_REQUIRE(x && out && scratch, "image_colsum: null pointer");
+    AMS_REQUIRE(B > 0 && HW > 0 && C > 0 && ldx >= C && scratch_floats >= image_colsum_scratch(B, C),
+                "image_colsum: B=%d HW=%lld C=%d ldx=%d, or scratch too small (need %zu floats)", B, (long long)HW, C, ldx, image_colsum_scratch(B, C));
+    return launch_image_colsum(x, B, HW, C, ldx, out, scratch, (hipStream_t)stream);
+}
+
+int ams_k_l2_regularizer(const float* params, float* grads, const uint8_t* mask, int64_t n, int32_t n_vars, float coef, double* scratch,
+                         size_t scratch_doubles, double* loss, void* stream) {
+    AMS_REQUIRE(n > 0 && scratch_doubles >= 256, "l2_regularizer: n=%lld, or scratch too small (need 256 doubles)", (long long)n);
+    return launch_l2_regularizer(params, grads, mask, n, n_vars, coef, scratch, loss, (hipStream_t)stream);
+}
+
 int ams_k_adam(float* params, const float* grads, float* m, float* v, const uint8_t* mask, int64_t n, float lr_t, float beta1,
                float beta2, float eps, void* stream) {
     return launch_adam(params, grads, m, v, mask, n, lr_t, beta1, beta2, eps, (hipStream_t)stream);

@@ -201,6 +201,16 @@ static int run_col_reduce(Op op, int64_t rows_per_group, int groups, int C, int 
 }
 
 size_t colstats_scratch(int64_t M, int C) { (void)M; return (size_t)kMaxChunks * 2 * C; }
+size_t colsum_scratch(int C) { return (size_t)kMaxChunks * C; }
+
+// {CG, slots, chunks, rows_per_chunk} of the launch run_col_reduce / run_col_reduce_bn make for these rows (host arithmetic, no GPU call)
+int col_plan(int64_t rows_per_group, int groups, int C, int32_t out[4]) {
+    AMS_REQUIRE(rows_per_group > 0 && groups > 0, "col_plan: no rows: %lld x %d", (long long)rows_per_group, groups);
+    AMS_REQUIRE(C > 0 && C % 4 == 0 && C / 4 <= 256, "column reduce: C=%d must be a multiple of 4 (<= 1024)", C);
+    const ColGeom g = col_geom(rows_per_group, groups, C, C, kMaxChunks);
+    out[0] = g.CG; out[1] = g.slots; out[2] = g.chunks; out[3] = (int32_t)g.rows_per_chunk;
+    return AMS_OK;
+}
 
 int launch_colstats(const float* z, int64_t M, int C, const float* center, double* sums, float* scratch, hipStream_t st) {
     OpStats op{z, center, {}};

@@ -315,6 +315,9 @@ int launch_image_colsum(const float* x, int B, int64_t HW, int C, int ldx, float
 
 // per-channel shifted sums over rows: sums[0][c] = sum(z - center[c]), sums[1][c] = sum((z-center[c])^2)  (f64)
 size_t colstats_scratch(int64_t M, int C);
+size_t colsum_scratch(int C);           // launch_colsum's scratch, floats
+// the geometry the column reductions launch with: out = {CG, slots, chunks, rows_per_chunk}
+int col_plan(int64_t rows_per_group, int groups, int C, int32_t out[4]);
 int launch_colstats(const float* z, int64_t M, int C, const float* center, double* sums /*[2][C]*/, float* scratch,
                     hipStream_t st);
 // ... formed in f64 throughout by one thread per channel: for layers of a few rows whose variance is small against the centre's distance

@@ -243,6 +243,29 @@ SIGNATURES = {
     "ams_k_xdw_bwd_reduce_stem": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _sz,
                                            C.POINTER(_i32), C.POINTER(_i64), _vp]),
     "ams_k_xdw_dwe": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ams_k_col_plan": (C.c_int, [_i64, _i32, _i32, C.POINTER(_i32)]),
+    "ams_k_colstats_scratch": (_sz, [_i64, _i32]),
+    "ams_k_colstats": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "ams_k_colstats_f64": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _vp]),
+    "ams_k_bn_finalize": (C.c_int, [_vp, C.c_double, _i32, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ams_k_colstats_bn": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _sz, C.c_double, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ams_k_bn_fwd_partials": (C.c_int, [_vp, _i32, _i64, _i32, _vp, C.c_double, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ams_k_bn_bwd_partials": (C.c_int, [_vp, _i32, _i64, _i32, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ams_k_partials_to_sums": (C.c_int, [_vp, _i32, _i64, _i32, _vp, _vp]),
+    "ams_k_bn_bwd_reduce": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ams_k_bn_bwd_coef": (C.c_int, [_vp, C.c_double, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ams_k_bn_param_grads": (C.c_int, [_vp, _i32, _vp, _vp, _vp]),
+    "ams_k_bn_bwd_reduce_coef": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _sz, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ams_k_bn_act": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "ams_k_bn_bwd_apply": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "ams_k_bn_fold": (C.c_int, [_vp, _vp, _vp, _vp, _f32, _i32, _vp, _vp, _vp]),
+    "ams_k_reduce_splits": (C.c_int, [_vp, _i32, _i64, _i64, _vp, _vp]),
+    "ams_k_reduce_batch": (C.c_int, [C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_vp), _i32, _vp]),
+    "ams_k_colsum_scratch": (_sz, [_i32]),
+    "ams_k_colsum": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _sz, _vp]),
+    "ams_k_image_colsum_scratch": (_sz, [_i32, _i32]),
+    "ams_k_image_colsum": (C.c_int, [_vp, _i32, _i64, _i32, _i32, _vp, _vp, _sz, _vp]),
+    "ams_k_l2_regularizer": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _f32, _vp, _sz, _vp, _vp]),
     "ams_k_adam": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _vp]),
 }
 

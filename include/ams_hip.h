@@ -1132,6 +1132,84 @@ int ams_k_xdw_bwd_reduce_stem(const void* frames, int32_t frames_dtype, int32_t 
 int ams_k_xdw_dwe(const float* G1, const float* xx_g0, int32_t Cin, int32_t Cexp, const float* w_exp, const float* cA, const float* cB,
                   const float* cC, float* dw_exp, void* stream);
 
+/* ---- The BN pieces of the fine-tune step (k_elementwise.hip), each alone.  What FusedBatchNormV3(is_training=True), its gradient, Relu6 / Relu6Grad
+ * and the reductions behind them are to the reference's graph.  All tensors f32, [M, C] dense unless an ld is given; sums are f64 [2][C].
+ *
+ * The column reductions run in two stages.  ams_k_col_plan gives the geometry of the first: CG = C / 4 lanes along the channels, slots = max(1, 256 / CG)
+ * rows per block step, chunks = min(1024, ceil(M / (16 * slots))) blocks per group, rows_per_chunk = ceil(M / chunks) rows each (chunk k owns rows
+ * [k * rows_per_chunk, min(M, (k + 1) * rows_per_chunk)); with the cap in force trailing chunks can be empty).  out = {CG, slots, chunks, rows_per_chunk}.
+ * Host arithmetic: no GPU call.  C must be a multiple of 4, at most 1024.
+ * Scratch sizes (floats), independent of M: the first stage leaves one row of NQ * C partial sums per chunk, and at most 1024 chunks run:
+ *   ams_k_colstats_scratch(M, C)       = 1024 * 2 * C    (ams_k_colstats, ams_k_colstats_bn, ams_k_bn_bwd_reduce, ams_k_bn_bwd_reduce_coef: NQ = 2)
+ *   ams_k_colsum_scratch(C)            = 1024 * C        (NQ = 1)
+ *   ams_k_image_colsum_scratch(B, C)   = B * 1024 * C    (one group per image; the same as ams_k_global_mean_scratch)
+ * The second stage adds the chunks' rows in f64 in a fixed order: results are the same bits from run to run. */
+int ams_k_col_plan(int64_t M, int32_t groups, int32_t C, int32_t* out /* [4] */);
+/* sums[0][c] = sum_m (z[m,c] - center[c]), sums[1][c] = sum_m (z[m,c] - center[c])^2; center == NULL: 0.  The differences, squares and the sums within
+ * a chunk are f32 (ams_k_colstats), or everything is f64 with one thread per channel (ams_k_colstats_f64: layers of a few rows). */
+size_t ams_k_colstats_scratch(int64_t M, int32_t C);
+int ams_k_colstats(const float* z, int64_t M, int32_t C, const float* center, double* sums, float* scratch, size_t scratch_floats, void* stream);
+int ams_k_colstats_f64(const float* z, int64_t M, int32_t C, const float* center, double* sums, void* stream);
+/* the per-channel arithmetic from such sums over n elements: d1 = sums[0] / n, var = max(0, sums[1] / n - d1^2) (f64); mean = f32(center + d1),
+ * rstd = 1 / sqrtf(f32(var) + eps), scale = gamma * rstd, shift = beta - mean * scale (f32).  With moving_mean != NULL (then moving_var too):
+ * moving -= (moving - stat) * one_minus_decay in f32, stat = mean and the UNBIASED variance f32(var * n / (n - 1)) (n = 1: var).  save_mean / save_rstd
+ * may be NULL together. */
+int ams_k_bn_finalize(const double* sums, double n, int32_t C, const float* center, const float* gamma, const float* beta, float eps,
+                      float one_minus_decay, float* moving_mean, float* moving_var, float* scale, float* shift, float* save_mean, float* save_rstd,
+                      void* stream);
+/* ams_k_colstats + ams_k_bn_finalize in two launches (the single-process step): the second stage does the per-channel arithmetic.  Also writes sums. */
+int ams_k_colstats_bn(const float* z, int64_t M, int32_t C, const float* center, double* sums, float* scratch, size_t scratch_floats, double n,
+                      const float* gamma, const float* beta, float eps, float one_minus_decay, float* moving_mean, float* moving_var, float* scale,
+                      float* shift, float* save_mean, float* save_rstd, void* stream);
+/* The second stages alone, over partial rows part [rows][2][C] that a fused kernel left (ams_k_pointwise_red, ams_k_depthwise3x3_*_bn*, ams_k_xdw_*),
+ * row_stride floats apart (0: dense = 2 * C): sums[q][c] = sum_r part[r * row_stride + q * C + c] in f64, then the arithmetic of ams_k_bn_finalize
+ * (ams_k_bn_fwd_partials), of ams_k_bn_bwd_coef with dgamma and dbeta (ams_k_bn_bwd_partials), or none (ams_k_partials_to_sums: the data-parallel
+ * step all-reduces the sums first).  Nothing but those rows * 2 * C floats is read. */
+int ams_k_bn_fwd_partials(const float* part, int32_t rows, int64_t row_stride, int32_t C, double* sums, double n, const float* center,
+                          const float* gamma, const float* beta, float eps, float one_minus_decay, float* moving_mean, float* moving_var, float* scale,
+                          float* shift, float* save_mean, float* save_rstd, void* stream);
+int ams_k_bn_bwd_partials(const float* part, int32_t rows, int64_t row_stride, int32_t C, double* sums, double n, const float* gamma, const float* mean,
+                          const float* rstd, float* coefA, float* coefB, float* coefC, float* dgamma, float* dbeta, void* stream);
+int ams_k_partials_to_sums(const float* part, int32_t rows, int64_t row_stride, int32_t C, double* sums, void* stream);
+/* backward sums: dy = da * mask, mask = act'(y) of y = f32(f32(z * scale) + shift) (RELU6: 0 < y < 6, RELU: y > 0, NONE: 1);
+ * sums[0][c] = sum_m dy, sums[1][c] = sum_m (dy * (z - mean)) * rstd, terms in f32.  Scratch: ams_k_colstats_scratch. */
+int ams_k_bn_bwd_reduce(const float* da, const float* z, int64_t M, int32_t C, const float* scale, const float* shift, int32_t act, const float* mean,
+                        const float* rstd, double* sums, float* scratch, size_t scratch_floats, void* stream);
+/* from those sums over n elements, in f64 rounded once: A = gamma * rstd, k = A * (sums[1] / n) * rstd, coefA = A, coefC = -k,
+ * coefB = -A * (sums[0] / n) + k * mean, so that dz = A dy + B + C z; dgamma = sums[1], dbeta = sums[0] (may be NULL together in ams_k_bn_bwd_coef;
+ * ams_k_bn_param_grads writes only these two: a data-parallel rank's own share). */
+int ams_k_bn_bwd_coef(const double* sums, double n, int32_t C, const float* gamma, const float* mean, const float* rstd, float* coefA, float* coefB,
+                      float* coefC, float* dgamma, float* dbeta, void* stream);
+int ams_k_bn_param_grads(const double* sums, int32_t C, float* dgamma, float* dbeta, void* stream);
+/* ams_k_bn_bwd_reduce + ams_k_bn_bwd_coef in two launches (the single-process step). */
+int ams_k_bn_bwd_reduce_coef(const float* da, const float* z, int64_t M, int32_t C, const float* scale, const float* shift, int32_t act,
+                             const float* mean, const float* rstd, double* sums, float* scratch, size_t scratch_floats, double n, const float* gamma,
+                             float* coefA, float* coefB, float* coefC, float* dgamma, float* dbeta, void* stream);
+/* apply passes, one IEEE f32 operation at a time (nothing fused): a = act(f32(f32(z * scale) + shift)) (+ res when res != NULL);
+ * dz = ((coefA * (da * mask)) + coefB) + (coefC * z), mask as in ams_k_bn_bwd_reduce; dz may be da (in place).  C a multiple of 4. */
+int ams_k_bn_act(const float* z, int64_t M, int32_t C, const float* scale, const float* shift, int32_t act, const float* res, float* a, void* stream);
+int ams_k_bn_bwd_apply(const float* da, const float* z, int64_t M, int32_t C, const float* scale, const float* shift, int32_t act, const float* coefA,
+                       const float* coefB, const float* coefC, float* dz, void* stream);
+/* frozen coefficients: scale = gamma * (1 / sqrtf(var + eps)), shift = beta - mean * scale (f32) */
+int ams_k_bn_fold(const float* gamma, const float* beta, const float* mean, const float* var, float eps, int32_t C, float* scale, float* shift,
+                  void* stream);
+/* plain folds: out[i] = f32(sum_k part[k * stride + i]) for i < n, k < splits, in f64 in a fixed order (stride >= n).  ams_k_reduce_batch does up to 32
+ * such folds in one launch (arrays of n_jobs entries, host memory); more jobs are refused before anything is launched.  No scratch. */
+int ams_k_reduce_splits(const float* part, int32_t splits, int64_t n, int64_t stride, float* out, void* stream);
+int ams_k_reduce_batch(const float* const* part, const int32_t* splits, const int64_t* count, const int64_t* stride, float* const* out, int32_t n_jobs,
+                       void* stream);
+/* column sums of x [M, ldx] (the first C columns): out[c] = sum_m x[m, c]; per image: x [B, HW, ldx], out [B, C].  ldx a multiple of 4. */
+size_t ams_k_colsum_scratch(int32_t C);
+int ams_k_colsum(const float* x, int64_t M, int32_t C, int32_t ldx, float* out, float* scratch, size_t scratch_floats, void* stream);
+size_t ams_k_image_colsum_scratch(int32_t B, int32_t C);
+int ams_k_image_colsum(const float* x, int32_t B, int64_t HW, int32_t C, int32_t ldx, float* out, float* scratch, size_t scratch_floats, void* stream);
+
+/* regularize=True over a flat arena with a byte mask of the regularised entries: grads[i] = grads[i] + (coef / n_vars) * params[i] where mask[i] != 0
+ * (f32, two operations; the others untouched), and loss[0] += 0.5 * coef / n_vars * sum_mask params^2 * loss[1] with the sum and the update in f64
+ * (loss = {CE sum, valid pixels}, as the loss kernels leave it).  Scratch: 256 doubles (one per block). */
+int ams_k_l2_regularizer(const float* params, float* grads, const uint8_t* mask, int64_t n, int32_t n_vars, float coef, double* scratch,
+                         size_t scratch_doubles, double* loss, void* stream);
+
 /* K14-K16: fused Adam + coordinate-descent mask over a flat arena (TF1 Adam, Appendix C.10). */
 int ams_k_adam(float* params, const float* grads, float* m, float* v, const uint8_t* mask, int64_t n, float lr_t,
                float beta1, float beta2, float eps, void* stream);
