@@ -2,6 +2,7 @@
 // the profiler read-out, and the kernel-level entry points (ams_k_*) the parity tests drive.
 #include "engine.hpp"
 #include "head_common.hpp"
+#include "entry_check.hpp"
 
 using namespace ams;
 
@@ -749,75 +750,136 @@ int ams_student_apply_delta_q8(ams_student* s, const uint8_t* payload_dev, int64
 }
 
 // ---- kernel-level entry points -----------------------------------------------------------------------------
+// The GEMM, depthwise / stem and recompute entries describe their call to entry_check (entry_check.hpp) and launch nothing before it has
+// passed: no pixels or rows; the shape rule; scratch or panels; scale without shift; null pointers.  The launchers keep their own checks.
+static bool sizes3(int B, int H, int W) { return B > 0 && H > 0 && W > 0; }
+
 int ams_k_stem_conv(const void* frames, int32_t frames_dtype, int32_t B, int32_t H, int32_t W, const float* w, int32_t cout,
                     const float* scale, const float* shift, int32_t act, float pixel_scale, float* y, void* stream) {
+    EntryCall c;
+    c.who = "stem_conv";
+    c.describe("B=%d, %d x %d, cout=%d, dtype=%d", B, H, W, cout, frames_dtype);
+    c.sizes = sizes3(B, H, W) && cout > 0;
+    c.shape = cout % 8 == 0 && cout <= 256 && frame_dtype_ok(frames_dtype);
+    c.scale_without_shift = scale && !shift;
+    c.ptrs = frames && w && y;
+    RUN(entry_check(c));
     return launch_stem(frames, frames_dtype, B, H, W, w, cout, scale, shift, act, pixel_scale, y, (hipStream_t)stream);
+}
+
+// the depthwise entries: B, H, W, C > 0; C % 4 == 0 and <= 1024, stride 1 | 2, rate 1 | 2, not both 2
+static EntryCall dw_entry(const char* who, int B, int H, int W, int C, int stride, int rate) {
+    EntryCall c;
+    c.who = who;
+    c.describe("B=%d, %d x %d, C=%d, stride=%d, rate=%d", B, H, W, C, stride, rate);
+    c.sizes = sizes3(B, H, W) && C > 0;
+    c.shape = dw_entry_shape(C, stride, rate);
+    return c;
 }
 
 int ams_k_depthwise3x3(const float* x, int32_t B, int32_t H, int32_t W, int32_t C, const float* w, int32_t stride, int32_t rate,
                        const float* scale, const float* shift, int32_t act, float* y, void* stream) {
+    EntryCall c = dw_entry("depthwise3x3", B, H, W, C, stride, rate);
+    c.scale_without_shift = scale && !shift;
+    c.ptrs = x && w && y;
+    RUN(entry_check(c));
     return launch_depthwise(x, B, H, W, C, w, stride, rate, scale, shift, act, y, (hipStream_t)stream);
+}
+
+// the forward GEMM entries: M, K, N > 0; k_mult divides K (4: exact f32, 8: the part kernels)
+static EntryCall pw_entry(const char* who, int64_t M, int K, int N, int k_mult) {
+    EntryCall c;
+    c.who = who;
+    c.describe("M=%lld K=%d N=%d", (long long)M, K, N);
+    c.sizes = M > 0 && K > 0 && N > 0;
+    c.shape = K % k_mult == 0;
+    return c;
+}
+static void pw_entry_panels(EntryCall* c, const uint16_t* panels, size_t panel_elems, int planes, int K, int N) {
+    c->scratch_what = "panel scratch"; c->scratch = panels; c->have = panel_elems;
+    if (c->shaped()) c->need = (size_t)planes * N * ((K + 31) / 32 * 32);
 }
 
 int ams_k_pointwise(const float* x, int64_t M, int32_t K, const float* w, int32_t N, int32_t trans_w, const float* img_bias,
                     int64_t rows_per_img, const float* scale, const float* shift, int32_t act, const float* res, float* y,
                     void* stream) {
+    EntryCall c = pw_entry("pointwise", M, K, N, 4);
+    c.scale_without_shift = scale && !shift;
+    c.ptrs = x && w && y;
+    RUN(entry_check(c));
     PwArgs a = pw_args(x, M, K, K, w, N, y, N);
     if (trans_w) { a.w_sk = 1; a.w_sn = K; }
     a.img_bias = img_bias; a.rows_per_img = rows_per_img > 0 ? rows_per_img : 1;
     a.scale = scale; a.shift = shift; a.act = act; a.res = res; a.ldr = N;
-    if (scale && !shift) { set_error("pointwise: scale without shift"); return AMS_E_INVALID; }
     return launch_pointwise(a, (hipStream_t)stream);
 }
 
 int ams_k_pointwise_split(const float* x, int64_t M, int32_t K, const float* w, int32_t N, const float* scale, const float* shift,
                           int32_t act, const float* res, float* y, uint16_t* panels, size_t panel_elems, void* stream) {
+    EntryCall c = pw_entry("pointwise_split", M, K, N, 8);
+    pw_entry_panels(&c, panels, panel_elems, 2, K, N);
+    c.scale_without_shift = scale && !shift;
+    c.ptrs = x && w && y;
+    RUN(entry_check(c));
     const int Kp = (K + 31) / 32 * 32;
-    AMS_REQUIRE(panels && panel_elems >= (size_t)2 * N * Kp, "pointwise_split: panel scratch too small (need %zu)", (size_t)2 * N * Kp);
     hipStream_t st = (hipStream_t)stream;
     uint16_t* hi = panels;
     uint16_t* lo = panels + (size_t)N * Kp;
     RUN(launch_split_weights(w, N, 1, K, N, Kp, hi, lo, st));
     PwArgs a = pw_args(x, M, K, K, w, N, y, N);
     a.scale = scale; a.shift = shift; a.act = act; a.res = res; a.ldr = N;
-    if (scale && !shift) { set_error("pointwise_split: scale without shift"); return AMS_E_INVALID; }
     return launch_pointwise_split(a, hi, lo, Kp, st);
 }
 
 int ams_k_pointwise_split3(const float* x, int64_t M, int32_t K, const float* w, int32_t N, const float* scale, const float* shift,
                            int32_t act, const float* res, float* y, uint16_t* panels, size_t panel_elems, void* stream) {
+    EntryCall c = pw_entry("pointwise_split3", M, K, N, 8);
+    pw_entry_panels(&c, panels, panel_elems, 3, K, N);
+    c.scale_without_shift = scale && !shift;
+    c.ptrs = x && w && y;
+    RUN(entry_check(c));
     const int Kp = (K + 31) / 32 * 32;
     const size_t plane = (size_t)N * Kp;
-    AMS_REQUIRE(panels && panel_elems >= 3 * plane, "pointwise_split3: panel scratch too small (need %zu)", 3 * plane);
     hipStream_t st = (hipStream_t)stream;
     RUN(launch_split_weights3(w, N, 1, K, N, Kp, panels, panels + plane, panels + 2 * plane, st));
     PwArgs a = pw_args(x, M, K, K, w, N, y, N);
     a.scale = scale; a.shift = shift; a.act = act; a.res = res; a.ldr = N;
-    if (scale && !shift) { set_error("pointwise_split3: scale without shift"); return AMS_E_INVALID; }
     return launch_pointwise_split3(a, panels, panels + plane, panels + 2 * plane, Kp, st);
 }
 
-int ams_k_pack_h2i(const float* x, int64_t M, int32_t Cn, float* out, void* stream) { return launch_pack_h2i(x, M, Cn, out, (hipStream_t)stream); }
+int ams_k_pack_h2i(const float* x, int64_t M, int32_t Cn, float* out, void* stream) {
+    EntryCall c;
+    c.who = "pack_h2i";
+    c.describe("M=%lld C=%d", (long long)M, Cn);
+    c.sizes = M > 0 && Cn > 0;
+    c.shape = Cn % 8 == 0;
+    c.ptrs = x && out;
+    RUN(entry_check(c));
+    return launch_pack_h2i(x, M, Cn, out, (hipStream_t)stream);
+}
 
 int ams_k_pointwise_split_f16(const float* x, int64_t M, int32_t K, const float* w, int32_t N, const float* scale, const float* shift, int32_t act,
                               const float* res, float* y, uint16_t* panels, size_t panel_elems, float* x_h2i, uint16_t* y_parts, void* stream) {
-    const int Kp = (K + 31) / 32 * 32;
-    const size_t plane = (size_t)N * Kp;
-    AMS_REQUIRE(panels && panel_elems >= 2 * plane, "pointwise_split_f16: panel scratch too small (need %zu)", 2 * plane);
-    hipStream_t st = (hipStream_t)stream;
-    RUN(launch_split_weights_f16(w, N, 1, K, N, Kp, panels, panels + plane, st));
     PwArgs a = pw_args(x, M, K, K, w, N, y, N);
     a.scale = scale; a.shift = shift; a.act = act; a.res = res; a.ldr = N;
-    if (scale && !shift) { set_error("pointwise_split_f16: scale without shift"); return AMS_E_INVALID; }
+    EntryCall c = pw_entry("pointwise_split_f16", M, K, N, 8);
+    // the fp16 form's own rule (K >= 32), and part planes only from a vector epilogue (N % 4 == 0)
+    c.shape = c.sizes && pointwise_f16_applies(a) && (!y_parts || pointwise_split_writes_parts(a));
+    pw_entry_panels(&c, panels, panel_elems, 2, K, N);
+    c.scale_without_shift = scale && !shift;
+    c.ptrs = x && w && y;
+    RUN(entry_check(c));
+    const int Kp = (K + 31) / 32 * 32;
+    const size_t plane = (size_t)N * Kp;
+    hipStream_t st = (hipStream_t)stream;
+    RUN(launch_split_weights_f16(w, N, 1, K, N, Kp, panels, panels + plane, st));
     if (x_h2i) {                                   // the operand as fp16 pairs, as the streaming expand + depthwise kernels leave it
         if (x_h2i != x) RUN(launch_pack_h2i(x, M, K, x_h2i, st));      // x_h2i == x: x IS the packed operand already (tools/bench_kernel.py)
         a.x = x_h2i; a.x_fmt = 1;
     }
     if (y_parts) {                                 // the result also as two fp16 part planes [2][M][N] (the next block's operand)
-        AMS_REQUIRE(pointwise_split_writes_parts(a), "pointwise_split_f16: this shape has no vector epilogue to write parts from");
         a.ysplit = y_parts; a.ysplit_plane = M * (int64_t)N; a.ysplit_np = 2; a.ysplit_fmt = 1;
     }
-    AMS_REQUIRE(pointwise_f16_applies(a), "pointwise_split_f16: unsupported shape M=%lld K=%d", (long long)M, K);
     return launch_pointwise_split_f16(a, panels, (int64_t)plane, Kp, st);
 }
 
@@ -1176,11 +1238,29 @@ int ams_k_ce_loss_grad_mined(const float* logits, int32_t B, int32_t h, int32_t 
     return launch_ce_combine(c, loss_dev, scratch, dlogits, c.ld, st);
 }
 
-size_t ams_k_pointwise_wgrad_scratch(int64_t M, int32_t K, int32_t N) { return pointwise_wgrad_scratch(M, K, N); }
+size_t ams_k_pointwise_wgrad_scratch(int64_t M, int32_t K, int32_t N) {
+    return AMS_ENTRY_SCRATCH(M > 0 && K > 0 && N > 0, pointwise_wgrad_scratch(M, K, N));
+}
+
+// the weight-gradient entries: M, K, N > 0; split: the three-part kernel's rule (pointwise_wgrad_x6_applies); scratch: the floats of the kernel
+// the entry runs (the exact-f32 kernel's where split == 0 or the three-part kernel does not apply)
+static EntryCall wg_entry(const char* who, int64_t M, int K, int N, int split, bool split_required, const float* scratch, size_t scratch_floats) {
+    EntryCall c;
+    c.who = who;
+    c.describe("M=%lld K=%d N=%d", (long long)M, K, N);
+    c.sizes = M > 0 && K > 0 && N > 0;
+    const bool x6 = c.sizes && split && pointwise_wgrad_x6_applies(M, K, N, K, N);
+    c.shape = !(split && split_required) || x6;
+    c.scratch_what = "scratch"; c.scratch = scratch; c.have = scratch_floats;
+    if (c.shaped()) c.need = (size_t)(x6 ? wgrad_x6_splits(M, K, N) : wgrad_f32_splits(M, K, N)) * K * N;
+    return c;
+}
 
 int ams_k_pointwise_wgrad_split(const float* x, const float* dy, int64_t M, int32_t K, int32_t N, float* dw, float* scratch,
                                 size_t scratch_floats, void* stream) {
-    if (!pointwise_wgrad_x6_applies(M, K, N, K, N)) { set_error("pointwise_wgrad_split: shape M=%lld K=%d N=%d not supported", (long long)M, K, N); return AMS_E_INVALID; }
+    EntryCall c = wg_entry("pointwise_wgrad_split", M, K, N, 1, true, scratch, scratch_floats);
+    c.ptrs = x && dy && dw;
+    RUN(entry_check(c));
     WgArgs a;
     a.x = x; a.ldx = K; a.K = K; a.dy = dy; a.ldy = N; a.N = N; a.M = M; a.dw = dw; a.scratch = scratch; a.scratch_floats = scratch_floats; a.allow_split = 1;
     return launch_pointwise_wgrad(a, (hipStream_t)stream);
@@ -1188,6 +1268,9 @@ int ams_k_pointwise_wgrad_split(const float* x, const float* dy, int64_t M, int3
 
 int ams_k_pointwise_wgrad(const float* x, const float* dy, int64_t M, int32_t K, int32_t N, float* dw, float* scratch,
                           size_t scratch_floats, void* stream) {
+    EntryCall c = wg_entry("pointwise_wgrad", M, K, N, 0, false, scratch, scratch_floats);
+    c.ptrs = x && dy && dw;
+    RUN(entry_check(c));
     WgArgs a;
     a.x = x; a.ldx = K; a.K = K; a.dy = dy; a.ldy = N; a.N = N; a.M = M; a.dw = dw; a.scratch = scratch; a.scratch_floats = scratch_floats; a.allow_split = 0;
     return launch_pointwise_wgrad(a, (hipStream_t)stream);
@@ -1195,11 +1278,19 @@ int ams_k_pointwise_wgrad(const float* x, const float* dy, int64_t M, int32_t K,
 
 int ams_k_depthwise3x3_dgrad(const float* dy, int32_t B, int32_t H, int32_t W, int32_t C, const float* w, int32_t stride, int32_t rate,
                              float* dx, void* stream) {
+    EntryCall c = dw_entry("depthwise3x3_dgrad", B, H, W, C, stride, rate);
+    c.ptrs = dy && w && dx;
+    RUN(entry_check(c));
     return launch_depthwise_dgrad(dy, B, H, W, C, w, stride, rate, dx, (hipStream_t)stream);
 }
 
 int ams_k_depthwise3x3_wgrad(const float* x, const float* dy, int32_t B, int32_t H, int32_t W, int32_t C, int32_t stride, int32_t rate,
                              float* dw, float* scratch, size_t scratch_floats, void* stream) {
+    EntryCall c = dw_entry("depthwise3x3_wgrad", B, H, W, C, stride, rate);
+    c.scratch_what = "scratch"; c.scratch = scratch; c.have = scratch_floats;
+    if (c.shaped()) c.need = depthwise_wgrad_scratch(B, H, W, C, stride, rate);
+    c.ptrs = x && dy && dw;
+    RUN(entry_check(c));
     return launch_depthwise_wgrad(x, dy, B, H, W, C, stride, rate, dw, scratch, scratch_floats, (hipStream_t)stream);
 }
 
@@ -1207,8 +1298,6 @@ int ams_k_pointwise_red(const float* x, int64_t M, int32_t K, const float* w, in
                         const float* center, const float* z, const float* scale, const float* shift, const float* mean, const float* rstd,
                         int32_t act, const float* res, float* y, float* part, size_t part_floats, int32_t* rows_out, uint16_t* panels,
                         size_t panel_elems, void* stream) {
-    AMS_REQUIRE(x && w && y && part && rows_out && (mode == 1 || mode == 2), "pointwise_red: bad arguments");
-    AMS_REQUIRE(mode == 1 || (z && scale && shift && mean && rstd), "pointwise_red: mode 2 needs z, scale, shift, mean, rstd");
     hipStream_t st = (hipStream_t)stream;
     PwArgs a = pw_args(x, M, K, K, w, N, y, N);
     if (trans_w) { a.w_sk = 1; a.w_sn = K; }
@@ -1217,17 +1306,22 @@ int ams_k_pointwise_red(const float* x, int64_t M, int32_t K, const float* w, in
     a.red_act = act; a.red_part = part; a.red_part_floats = part_floats;         // rows that would not fit: the launch runs unfused, *rows_out = 0
     int rows = 0;
     a.red_rows_out = &rows;
+    // M, K, N > 0; mode 1 | 2; split 0: K % 4 == 0, split 1: K % 8 == 0 and 3 panel planes, split 2: the fp16 form's rule (mode 1, K >= 32, K % 8
+    // == 0) and 2 planes; mode 2 reads z, scale, shift, mean, rstd
+    EntryCall c = pw_entry("pointwise_red", M, K, N, split ? 8 : 4);
+    c.shape = c.shape && (mode == 1 || mode == 2) && (split != 2 || (c.sizes && pointwise_f16_applies(a)));
+    if (split) pw_entry_panels(&c, panels, panel_elems, split == 2 ? 2 : 3, K, N);
+    c.ptrs = x && w && y && part && rows_out && (mode == 1 || (z && scale && shift && mean && rstd));
+    RUN(entry_check(c));
     int rc;
     if (split == 2) {                              // two fp16 parts (mode 1 only: the forward statistics)
         const int Kp = (K + 31) / 32 * 32;
         const size_t plane = (size_t)N * Kp;
-        AMS_REQUIRE(panels && panel_elems >= 2 * plane && pointwise_f16_applies(a), "pointwise_red: fp16 form needs mode 1, K %% 8 == 0 and %zu panel elements", 2 * plane);
         RUN(launch_split_weights_f16(w, a.w_sk, a.w_sn, K, N, Kp, panels, panels + plane, st));
         rc = launch_pointwise_split_f16(a, panels, (int64_t)plane, Kp, st);
     } else if (split) {
         const int Kp = (K + 31) / 32 * 32;
         const size_t plane = (size_t)N * Kp;
-        AMS_REQUIRE(panels && panel_elems >= 3 * plane && K % 8 == 0, "pointwise_red: panel scratch too small (need %zu) or K %% 8", 3 * plane);
         RUN(launch_split_weights3(w, a.w_sk, a.w_sn, K, N, Kp, panels, panels + plane, panels + 2 * plane, st));
         rc = launch_pointwise_split3(a, panels, panels + plane, panels + 2 * plane, Kp, st);
     } else {
@@ -1240,22 +1334,27 @@ int ams_k_pointwise_red(const float* x, int64_t M, int32_t K, const float* w, in
 int ams_k_pointwise_xform(const float* x, int64_t M, int32_t K, const float* w, int32_t N, int32_t trans_w, int32_t split, int32_t x_mode,
                           int32_t x_act, const float* v0, const float* v1, const float* v2, const float* x2, float* y, float* x_tmp,
                           uint16_t* panels, size_t panel_elems, void* stream) {
-    AMS_REQUIRE(x && w && y && v0 && v1 && (x_mode == 1 || (x_mode == 2 && v2 && x2)), "pointwise_xform: bad arguments");
     hipStream_t st = (hipStream_t)stream;
     PwArgs a = pw_args(x, M, K, K, w, N, y, N);
     if (trans_w) { a.w_sk = 1; a.w_sn = K; }
     a.x_mode = x_mode; a.x_act = x_act; a.x_v0 = v0; a.x_v1 = v1; a.x_v2 = v2; a.x2 = x2; a.x_tmp = x_tmp;
+    // M, K, N > 0; x_mode 1 | 2; split 0: K % 4 == 0, split 1: K % 8 == 0 and 3 panel planes, split 2: the fp16 form's rule (x_mode 1, 32 <= K <=
+    // 1024, K % 8 == 0, a plain vector epilogue) and 2 planes; x_mode 2 reads v2 and x2
+    EntryCall c = pw_entry("pointwise_xform", M, K, N, split ? 8 : 4);
+    const bool vecs = v0 && v1 && (x_mode != 2 || (v2 && x2));
+    c.shape = c.shape && (x_mode == 1 || x_mode == 2) && (split != 2 || !vecs || (c.sizes && pointwise_f16_applies(a)));      // (the fp16 rule looks at v0, v1: without them the call ends at 5)
+    if (split) pw_entry_panels(&c, panels, panel_elems, split == 2 ? 2 : 3, K, N);
+    c.ptrs = x && w && y && vecs;
+    RUN(entry_check(c));
     if (split == 2) {                              // two fp16 parts (x_mode 1 only)
         const int Kp = (K + 31) / 32 * 32;
         const size_t plane = (size_t)N * Kp;
-        AMS_REQUIRE(panels && panel_elems >= 2 * plane && pointwise_f16_applies(a), "pointwise_xform: fp16 form needs x_mode 1, K %% 8 == 0, K <= 1024 and %zu panel elements", 2 * plane);
         RUN(launch_split_weights_f16(w, a.w_sk, a.w_sn, K, N, Kp, panels, panels + plane, st));
         return launch_pointwise_split_f16(a, panels, (int64_t)plane, Kp, st);
     }
     if (split) {
         const int Kp = (K + 31) / 32 * 32;
         const size_t plane = (size_t)N * Kp;
-        AMS_REQUIRE(panels && panel_elems >= 3 * plane && K % 8 == 0, "pointwise_xform: panel scratch too small (need %zu) or K %% 8", 3 * plane);
         RUN(launch_split_weights3(w, a.w_sk, a.w_sn, K, N, Kp, panels, panels + plane, panels + 2 * plane, st));
         return launch_pointwise_split3(a, panels, panels + plane, panels + 2 * plane, Kp, st);
     }
@@ -1265,8 +1364,10 @@ int ams_k_pointwise_xform(const float* x, int64_t M, int32_t K, const float* w, 
 int ams_k_pointwise_wgrad_xform(const float* x, const float* dy, int64_t M, int32_t K, int32_t N, int32_t split, int32_t x_mode, int32_t x_act,
                                 const float* v0, const float* v1, int32_t dy_mode, const float* d0, const float* d1, const float* d2,
                                 const float* dy2, float* dw, float* scratch, size_t scratch_floats, void* stream) {
-    AMS_REQUIRE(x && dy && dw && scratch, "pointwise_wgrad_xform: null pointer");
-    if (split && !pointwise_wgrad_x6_applies(M, K, N, K, N)) { set_error("pointwise_wgrad_xform: shape M=%lld K=%d N=%d outside the split kernel", (long long)M, K, N); return AMS_E_INVALID; }
+    EntryCall c = wg_entry("pointwise_wgrad_xform", M, K, N, split, true, scratch, scratch_floats);
+    c.shape = c.shape && (x_mode == 0 || x_mode == 1) && (dy_mode == 0 || dy_mode == 2);
+    c.ptrs = x && dy && dw && (x_mode != 1 || (v0 && v1)) && (dy_mode != 2 || (d0 && d1 && d2 && dy2));
+    RUN(entry_check(c));
     WgArgs a;
     a.x = x; a.ldx = K; a.K = K; a.dy = dy; a.ldy = N; a.N = N; a.M = M; a.dw = dw; a.scratch = scratch; a.scratch_floats = scratch_floats;
     a.allow_split = split != 0;
@@ -1275,73 +1376,132 @@ int ams_k_pointwise_wgrad_xform(const float* x, const float* dy, int64_t M, int3
     return launch_pointwise_wgrad(a, (hipStream_t)stream);
 }
 
-size_t ams_k_depthwise3x3_fwd_bn_scratch(int32_t B, int32_t H, int32_t W, int32_t C, int32_t rate) { return depthwise_fwd_bn_scratch(B, H, W, C, rate); }
+// the four one-kernel fine-tune forms: stride 1; the depthwise rule (dw_entry); fwd_bn_tiles: an image of fewer than 2^31 elements
+static EntryCall dw_bn_entry(const char* who, int B, int H, int W, int C, int rate, const float* scratch, size_t scratch_floats) {
+    EntryCall c = dw_entry(who, B, H, W, C, 1, rate);
+    c.scratch_what = "scratch"; c.scratch = scratch; c.have = scratch_floats;
+    return c;
+}
+static bool dw_bn_accepts(int B, int H, int W, int C, int rate) { return sizes3(B, H, W) && C > 0 && dw_entry_shape(C, 1, rate); }
+
+size_t ams_k_depthwise3x3_fwd_bn_scratch(int32_t B, int32_t H, int32_t W, int32_t C, int32_t rate) {
+    return AMS_ENTRY_SCRATCH(dw_bn_accepts(B, H, W, C, rate), depthwise_fwd_bn_scratch(B, H, W, C, rate));
+}
 int ams_k_depthwise3x3_fwd_bn(const float* ze, int32_t B, int32_t H, int32_t W, int32_t C, const float* w, int32_t rate, const float* scale,
                               const float* shift, int32_t act, const float* center, float* zd, float* scratch, size_t scratch_floats,
                               int32_t* rows_out, void* stream) {
-    AMS_REQUIRE(ze && w && scale && shift && zd && scratch && rows_out, "depthwise3x3_fwd_bn: null pointer");
-    AMS_REQUIRE(scratch_floats >= depthwise_fwd_bn_scratch(B, H, W, C, rate), "depthwise3x3_fwd_bn: scratch too small");
+    EntryCall c = dw_bn_entry("depthwise3x3_fwd_bn", B, H, W, C, rate, scratch, scratch_floats);
+    if (c.shaped()) c.need = depthwise_fwd_bn_scratch(B, H, W, C, rate);
+    c.ptrs = ze && w && scale && shift && zd && rows_out;
+    RUN(entry_check(c));
     int rows = 0;
     int rc = launch_depthwise_fwd_bn(ze, B, H, W, C, w, rate, scale, shift, act, center, zd, scratch, &rows, (hipStream_t)stream);
     *rows_out = rows;
     return rc;
 }
-size_t ams_k_depthwise3x3_dgrad_bn_scratch(int32_t B, int32_t H, int32_t W, int32_t C) { return depthwise_dgrad_bn_scratch(B, H, W, C); }
+size_t ams_k_depthwise3x3_dgrad_bn_scratch(int32_t B, int32_t H, int32_t W, int32_t C) {
+    return AMS_ENTRY_SCRATCH(dw_bn_accepts(B, H, W, C, 1), depthwise_dgrad_bn_scratch(B, H, W, C));
+}
 int ams_k_depthwise3x3_dgrad_bn(const float* dz, int32_t B, int32_t H, int32_t W, int32_t C, const float* w, int32_t rate, const float* z_prev,
                                 const float* scale, const float* shift, int32_t act, const float* mean, const float* rstd, float* out,
                                 float* scratch, size_t scratch_floats, int32_t* rows_out, void* stream) {
-    AMS_REQUIRE(dz && w && z_prev && scale && shift && mean && rstd && out && scratch && rows_out, "depthwise3x3_dgrad_bn: null pointer");
-    AMS_REQUIRE(rate == 1 || rate == 2, "depthwise3x3_dgrad_bn: rate %d", rate);
-    AMS_REQUIRE(scratch_floats >= depthwise_dgrad_bn_scratch(B, H, W, C), "depthwise3x3_dgrad_bn: scratch too small");
+    EntryCall c = dw_bn_entry("depthwise3x3_dgrad_bn", B, H, W, C, rate, scratch, scratch_floats);
+    if (c.shaped()) c.need = depthwise_dgrad_bn_scratch(B, H, W, C);
+    c.ptrs = dz && w && z_prev && scale && shift && mean && rstd && out && rows_out;
+    RUN(entry_check(c));
     int rows = 0;
     int rc = launch_depthwise_dgrad_bn(dz, B, H, W, C, w, rate, z_prev, scale, shift, act, mean, rstd, out, scratch, &rows, (hipStream_t)stream);
     *rows_out = rows;
     return rc;
 }
 
-size_t ams_k_depthwise3x3_fwd_bn_tiles_scratch(int32_t B, int32_t H, int32_t W, int32_t C, int32_t rate) { return depthwise_fwd_bn2_scratch(B, H, W, C, rate); }
+size_t ams_k_depthwise3x3_fwd_bn_tiles_scratch(int32_t B, int32_t H, int32_t W, int32_t C, int32_t rate) {
+    return AMS_ENTRY_SCRATCH(dw_bn_accepts(B, H, W, C, rate) && (int64_t)H * W * C < 0x7fffffffLL, depthwise_fwd_bn2_scratch(B, H, W, C, rate));
+}
 int ams_k_depthwise3x3_fwd_bn_tiles(const float* ze, int32_t B, int32_t H, int32_t W, int32_t C, const float* w, int32_t rate, const float* scale,
                                     const float* shift, int32_t act, const float* center, float* zd, float* scratch, size_t scratch_floats,
                                     int32_t* rows_out, void* stream) {
-    AMS_REQUIRE(ze && w && scale && shift && zd && scratch && rows_out, "depthwise3x3_fwd_bn_tiles: null pointer");
-    AMS_REQUIRE(scratch_floats >= depthwise_fwd_bn2_scratch(B, H, W, C, rate), "depthwise3x3_fwd_bn_tiles: scratch too small");
+    EntryCall c = dw_bn_entry("depthwise3x3_fwd_bn_tiles", B, H, W, C, rate, scratch, scratch_floats);
+    c.shape = c.shape && (int64_t)H * W * C < 0x7fffffffLL;
+    if (c.shaped()) c.need = depthwise_fwd_bn2_scratch(B, H, W, C, rate);
+    c.ptrs = ze && w && scale && shift && zd && rows_out;
+    RUN(entry_check(c));
     int rows = 0;
     int rc = launch_depthwise_fwd_bn2(ze, B, H, W, C, w, rate, scale, shift, act, center, zd, scratch, &rows, (hipStream_t)stream);
     *rows_out = rows;
     return rc;
 }
 
-size_t ams_k_depthwise3x3_dgrad_bn_apply_scratch(int32_t B, int32_t H, int32_t W, int32_t C, int32_t rate) { return depthwise_dgrad_bn2_scratch(B, H, W, C, rate); }
+size_t ams_k_depthwise3x3_dgrad_bn_apply_scratch(int32_t B, int32_t H, int32_t W, int32_t C, int32_t rate) {
+    return AMS_ENTRY_SCRATCH(dw_bn_accepts(B, H, W, C, rate), depthwise_dgrad_bn2_scratch(B, H, W, C, rate));
+}
 int ams_k_depthwise3x3_dgrad_bn_apply(const float* dy, const float* zd, const float* cA, const float* cB, const float* cC, int32_t B, int32_t H, int32_t W,
                                       int32_t C, const float* w, int32_t rate, const float* z_prev, const float* scale, const float* shift, int32_t act,
                                       const float* mean, const float* rstd, float* out, float* scratch, size_t scratch_floats, int32_t* rows_out,
                                       void* stream) {
-    AMS_REQUIRE(dy && zd && cA && cB && cC && w && z_prev && scale && shift && mean && rstd && out && scratch && rows_out, "depthwise3x3_dgrad_bn_apply: null pointer");
-    AMS_REQUIRE(rate == 1 || rate == 2, "depthwise3x3_dgrad_bn_apply: rate %d", rate);
-    AMS_REQUIRE(scratch_floats >= depthwise_dgrad_bn2_scratch(B, H, W, C, rate), "depthwise3x3_dgrad_bn_apply: scratch too small");
+    EntryCall c = dw_bn_entry("depthwise3x3_dgrad_bn_apply", B, H, W, C, rate, scratch, scratch_floats);
+    if (c.shaped()) c.need = depthwise_dgrad_bn2_scratch(B, H, W, C, rate);
+    c.ptrs = dy && zd && cA && cB && cC && w && z_prev && scale && shift && mean && rstd && out && rows_out;
+    RUN(entry_check(c));
     int rows = 0;
     int rc = launch_depthwise_dgrad_bn2(dy, zd, cA, cB, cC, B, H, W, C, w, rate, z_prev, scale, shift, act, mean, rstd, out, scratch, &rows, (hipStream_t)stream);
     *rows_out = rows;
     return rc;
 }
 
-size_t ams_k_xx_gram_scratch(int64_t M, int32_t Cin) { return xx_stats_scratch_doubles(M, Cin); }
+size_t ams_k_xx_gram_scratch(int64_t M, int32_t Cin) { return AMS_ENTRY_SCRATCH(M > 0 && xx_gram_shape(Cin), xx_stats_scratch_doubles(M, Cin)); }
 int ams_k_xx_gram(const float* x, int64_t M, int32_t Cin, double* scratch, size_t scratch_doubles, double* xx64, float* xx32, void* stream) {
-    AMS_REQUIRE(scratch_doubles >= xx_stats_scratch_doubles(M, Cin), "xx_gram: scratch too small");
+    EntryCall c;
+    c.who = "xx_gram";
+    c.describe("M=%lld Cin=%d", (long long)M, Cin);
+    c.sizes = M > 0 && Cin > 0;
+    c.shape = xx_gram_shape(Cin);
+    c.scratch_what = "scratch"; c.scratch = scratch; c.have = scratch_doubles;
+    if (c.shaped()) c.need = xx_stats_scratch_doubles(M, Cin);
+    c.ptrs = x && xx64;
+    RUN(entry_check(c));
     return launch_xx_gram(x, M, Cin, scratch, xx64, xx32, (hipStream_t)stream);
 }
 int ams_k_expand_stats(const double* xx64, int32_t Cin, const float* w_exp, int32_t Cexp, double n, const float* center, const float* gamma,
                        const float* beta, float eps, float one_minus_decay, float* moving_mean, float* moving_var, float* scale, float* shift,
                        float* save_mean, float* save_rstd, double* sums, void* stream) {
+    EntryCall c;
+    c.who = "expand_stats";
+    c.describe("Cin=%d Cexp=%d n=%g", Cin, Cexp, n);
+    c.sizes = Cin > 0 && Cexp > 0 && n > 0;
+    c.shape = xx_gram_shape(Cin);
+    // the saved statistics and the moving averages each come as a pair or not at all
+    c.ptrs = xx64 && w_exp && gamma && beta && scale && shift && (save_mean == nullptr) == (save_rstd == nullptr) &&
+             (moving_mean == nullptr) == (moving_var == nullptr);
+    RUN(entry_check(c));
     return launch_expand_stats(xx64, Cin, w_exp, Cexp, n, center, gamma, beta, eps, one_minus_decay, moving_mean, moving_var, scale, shift, save_mean,
                                save_rstd, sums, (hipStream_t)stream);
 }
 
-size_t ams_k_xdw_train_scratch(int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cexp) { return xdw_train_scratch(B, H, W, Cin, Cexp); }
+// the recompute entries of an early block: B, H, W, Cin, Cexp > 0; xdw_train_supported (Cin % 4 == 0 in 8..32, Cexp % 16 == 0 in 32..192, stride
+// 1 | 2) and an image the kernels' 32-bit element offsets cover
+static EntryCall xdw_entry(const char* who, int B, int H, int W, int Cin, int Cexp, int stride) {
+    EntryCall c;
+    c.who = who;
+    c.describe("B=%d, %d x %d, Cin=%d Cexp=%d stride=%d", B, H, W, Cin, Cexp, stride);
+    c.sizes = sizes3(B, H, W) && Cin > 0 && Cexp > 0;
+    c.shape = xdw_train_supported(Cin, Cexp, stride, 1) && xdw_image_ok(H, W, Cin, Cexp);
+    return c;
+}
+static void xdw_entry_scratch(EntryCall* c, const float* scratch, size_t scratch_floats, int B, int H, int W, int Cin, int Cexp) {
+    c->scratch_what = "scratch"; c->scratch = scratch; c->have = scratch_floats;
+    if (c->shaped()) c->need = xdw_train_scratch(B, H, W, Cin, Cexp);
+}
+
+size_t ams_k_xdw_train_scratch(int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cexp) {
+    return AMS_ENTRY_SCRATCH(xdw_entry("", B, H, W, Cin, Cexp, 1).shaped(), xdw_train_scratch(B, H, W, Cin, Cexp));
+}
 int ams_k_xdw_fwd_stats(const float* x, int32_t B, int32_t H, int32_t W, int32_t Cin, const float* w_exp, int32_t Cexp, const float* center,
                         float* scratch, size_t scratch_floats, int32_t* rows_out, int64_t* stride_out, void* stream) {
-    AMS_REQUIRE(x && w_exp && scratch && rows_out && stride_out, "xdw_fwd_stats: null pointer");
-    AMS_REQUIRE(xdw_train_supported(Cin, Cexp, 1, 1) && scratch_floats >= xdw_train_scratch(B, H, W, Cin, Cexp), "xdw_fwd_stats: shape or scratch");
+    EntryCall c = xdw_entry("xdw_fwd_stats", B, H, W, Cin, Cexp, 1);
+    xdw_entry_scratch(&c, scratch, scratch_floats, B, H, W, Cin, Cexp);
+    c.ptrs = x && w_exp && rows_out && stride_out;
+    RUN(entry_check(c));
     int rows = 0;
     int rc = launch_xdw_fwd_stats(x, B, H, W, Cin, w_exp, Cexp, center, scratch, &rows, stride_out, (hipStream_t)stream);
     *rows_out = rows;
@@ -1350,8 +1510,10 @@ int ams_k_xdw_fwd_stats(const float* x, int32_t B, int32_t H, int32_t W, int32_t
 int ams_k_xdw_bwd_reduce(const float* x, int32_t B, int32_t H, int32_t W, int32_t Cin, const float* w_exp, int32_t Cexp, const float* sc_e,
                          const float* sh_e, const float* mean_e, const float* rstd_e, int32_t act_e, const float* w_dw, int32_t stride,
                          const float* dz_d, float* scratch, size_t scratch_floats, int32_t* rows_out, int64_t* stride_out, void* stream) {
-    AMS_REQUIRE(x && w_exp && sc_e && sh_e && mean_e && rstd_e && w_dw && dz_d && scratch && rows_out && stride_out, "xdw_bwd_reduce: null pointer");
-    AMS_REQUIRE(xdw_train_supported(Cin, Cexp, stride, 1) && scratch_floats >= xdw_train_scratch(B, H, W, Cin, Cexp), "xdw_bwd_reduce: shape or scratch");
+    EntryCall c = xdw_entry("xdw_bwd_reduce", B, H, W, Cin, Cexp, stride);
+    xdw_entry_scratch(&c, scratch, scratch_floats, B, H, W, Cin, Cexp);
+    c.ptrs = x && w_exp && sc_e && sh_e && mean_e && rstd_e && w_dw && dz_d && rows_out && stride_out;
+    RUN(entry_check(c));
     int rows = 0;
     int rc = launch_xdw_bwd_reduce(x, B, H, W, Cin, w_exp, Cexp, sc_e, sh_e, mean_e, rstd_e, act_e, w_dw, stride, dz_d, scratch, &rows, stride_out,
                                    (hipStream_t)stream);
@@ -1361,15 +1523,26 @@ int ams_k_xdw_bwd_reduce(const float* x, int32_t B, int32_t H, int32_t W, int32_
 int ams_k_xdw_bwd_dx(const float* x, int32_t B, int32_t H, int32_t W, int32_t Cin, const float* w_exp, int32_t Cexp, const float* sc_e,
                      const float* sh_e, int32_t act_e, const float* w_dw, int32_t stride, const float* dz_d, const float* cA, const float* cB,
                      const float* cC, const float* res, float* dx, void* stream) {
-    AMS_REQUIRE(x && w_exp && sc_e && sh_e && w_dw && dz_d && cA && cB && cC && dx, "xdw_bwd_dx: null pointer");
+    EntryCall c = xdw_entry("xdw_bwd_dx", B, H, W, Cin, Cexp, stride);
+    c.ptrs = x && w_exp && sc_e && sh_e && w_dw && dz_d && cA && cB && cC && dx;
+    RUN(entry_check(c));
     return launch_xdw_bwd_dx(x, B, H, W, Cin, w_exp, Cexp, sc_e, sh_e, act_e, w_dw, stride, dz_d, cA, cB, cC, res, dx, (hipStream_t)stream);
 }
-size_t ams_k_xdw_stem_scratch(int32_t B, int32_t fH, int32_t fW) { return xdw_stem_scratch(B, fH, fW); }
+size_t ams_k_xdw_stem_scratch(int32_t B, int32_t fH, int32_t fW) {
+    return AMS_ENTRY_SCRATCH(sizes3(B, fH, fW) && (int64_t)fH * fW * 3 < 0x7fffffffLL, xdw_stem_scratch(B, fH, fW));
+}
 int ams_k_xdw_bwd_reduce_stem(const void* frames, int32_t frames_dtype, int32_t B, int32_t fH, int32_t fW, float pixel_scale, const float* w_stem,
                               const float* sc_e, const float* sh_e, const float* mean_e, const float* rstd_e, int32_t act_e, const float* w_dw,
                               const float* dz_d, float* scratch, size_t scratch_floats, int32_t* rows_out, int64_t* stride_out, void* stream) {
-    AMS_REQUIRE(frames && w_stem && sc_e && sh_e && mean_e && rstd_e && w_dw && dz_d && scratch && rows_out && stride_out, "xdw_bwd_reduce_stem: null pointer");
-    AMS_REQUIRE(scratch_floats >= xdw_stem_scratch(B, fH, fW), "xdw_bwd_reduce_stem: scratch too small");
+    EntryCall c;
+    c.who = "xdw_bwd_reduce_stem";
+    c.describe("B=%d, frames %d x %d, dtype=%d", B, fH, fW, frames_dtype);
+    c.sizes = sizes3(B, fH, fW);
+    c.shape = frame_dtype_ok(frames_dtype) && (int64_t)fH * fW * 3 < 0x7fffffffLL;
+    c.scratch_what = "scratch"; c.scratch = scratch; c.have = scratch_floats;
+    if (c.shaped()) c.need = xdw_stem_scratch(B, fH, fW);
+    c.ptrs = frames && w_stem && sc_e && sh_e && mean_e && rstd_e && w_dw && dz_d && rows_out && stride_out;
+    RUN(entry_check(c));
     int rows = 0;
     int rc = launch_xdw_bwd_reduce_stem(frames, frames_dtype, B, fH, fW, pixel_scale, w_stem, sc_e, sh_e, mean_e, rstd_e, act_e, w_dw, dz_d, scratch,
                                         &rows, stride_out, (hipStream_t)stream);
@@ -1378,7 +1551,13 @@ int ams_k_xdw_bwd_reduce_stem(const void* frames, int32_t frames_dtype, int32_t 
 }
 int ams_k_xdw_dwe(const float* G1, const float* xx_g0, int32_t Cin, int32_t Cexp, const float* w_exp, const float* cA, const float* cB,
                   const float* cC, float* dw_exp, void* stream) {
-    AMS_REQUIRE(G1 && xx_g0 && w_exp && cA && cB && cC && dw_exp, "xdw_dwe: null pointer");
+    EntryCall c;
+    c.who = "xdw_dwe";
+    c.describe("Cin=%d Cexp=%d", Cin, Cexp);
+    c.sizes = Cin > 0 && Cexp > 0;
+    c.shape = xdw_dwe_shape(Cin, Cexp);
+    c.ptrs = G1 && xx_g0 && w_exp && cA && cB && cC && dw_exp;
+    RUN(entry_check(c));
     return launch_xdw_dwe(G1, xx_g0, Cin, Cexp, w_exp, cA, cB, cC, dw_exp, (hipStream_t)stream);
 }
 

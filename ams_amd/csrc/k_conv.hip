@@ -179,7 +179,8 @@ __global__ __launch_bounds__(256) void stem_mfma_kernel(const TIn* __restrict__ 
 
 int launch_stem(const void* frames, int dtype, int B, int H, int W, const float* w, int cout, const float* scale,
                 const float* shift, int act, float pixel_scale, float* y, hipStream_t st) {
-    AMS_REQUIRE(cout % 8 == 0 && cout <= 256, "stem: cout %d must be a multiple of 8", cout);
+    AMS_REQUIRE(B > 0 && H > 0 && W > 0, "stem: no pixels: B=%d, %d x %d", B, H, W);
+    AMS_REQUIRE(cout >= 8 && cout % 8 == 0 && cout <= 256, "stem: cout %d must be a multiple of 8 in 8 .. 256", cout);
     AMS_REQUIRE(dtype == AMS_DT_U8 || dtype == AMS_DT_F32, "stem: frames must be uint8 or float32");
     AMS_REQUIRE((scale == nullptr) == (shift == nullptr), "stem: scale and shift come together");
     int Ho, Wo, pt, pl;
@@ -272,7 +273,8 @@ struct DwGeom {
 };
 
 static int dw_geom(int B, int H, int W, int C, int stride, int rate, bool over_input, DwGeom* g) {
-    AMS_REQUIRE(C % 4 == 0 && C / 4 <= 256, "depthwise: C=%d must be a multiple of 4 and <= 1024", C);
+    AMS_REQUIRE(B > 0 && H > 0 && W > 0, "depthwise: no pixels: B=%d, %d x %d", B, H, W);
+    AMS_REQUIRE(C >= 4 && C % 4 == 0 && C / 4 <= 256, "depthwise: C=%d must be a multiple of 4 in 4 .. 1024", C);      // (C / 4 divides below)
     AMS_REQUIRE((stride == 1 || stride == 2) && (rate == 1 || rate == 2) && !(stride == 2 && rate == 2),
                 "depthwise: unsupported stride %d / rate %d", stride, rate);
     g->B = B; g->H = H; g->W = W; g->C = C; g->flip = 0;
@@ -654,6 +656,10 @@ __global__ __launch_bounds__(256) void dw3x3_dgrad_bn_kernel(const float* __rest
 
 // A strip per image is too few blocks on the narrow layers: the walk down an image is split into bands of row tiles until the launch has
 // ~`target` blocks (one partial row per block either way).
+static bool dw_walk_ok(int B, int H, int W, int C, int rate) {
+    return B > 0 && H > 0 && W > 0 && C >= 4 && C % 4 == 0 && C / 4 <= 256 && (rate == 1 || rate == 2);
+}
+// (callers check dw_walk_ok first: dw_geom then cannot refuse)
 static void dw_walk_plan(int B, int H, int W, int C, int rate, int target, DwGeom* f, int* bands, int* tpb) {
     dw_geom(B, H, W, C, 1, rate, false, f);
     f->tiles_y = rate == 2 ? 2 * cdiv(f->Ho, 8) : cdiv(f->Ho, 4);
@@ -668,7 +674,7 @@ static void dw_walk_plan(int B, int H, int W, int C, int rate, int target, DwGeo
 constexpr int kDgradBnBlocks = 1;
 
 size_t depthwise_dgrad_bn_scratch(int B, int H, int W, int C) {
-    if (C % 4 != 0 || C / 4 > 256) return (size_t)-1;
+    if (!dw_walk_ok(B, H, W, C, 1)) return (size_t)-1;
     DwGeom f; int bands, tpb;
     // (the rate does not change the count: tiles_y only caps the bands, and both rates have >= 8 row tiles wherever bands are wanted)
     dw_walk_plan(B, H, W, C, 1, kDgradBnBlocks, &f, &bands, &tpb);
@@ -794,7 +800,7 @@ __global__ __launch_bounds__(256) void dw3x3_fwd_bn_kernel(const float* __restri
 
 size_t depthwise_fwd_bn_scratch(int B, int H, int W, int C, int rate) {
     DwGeom f; int bands, tpb;
-    if (C % 4 != 0 || C / 4 > 256) return (size_t)-1;
+    if (!dw_walk_ok(B, H, W, C, rate)) return (size_t)-1;
     dw_walk_plan(B, H, W, C, rate, 1024, &f, &bands, &tpb);
     return (size_t)f.tiles_x * bands * B * 2 * C;
 }
@@ -804,7 +810,7 @@ int launch_depthwise_fwd_bn(const float* ze, int B, int H, int W, int C, const f
                             const float* center, float* zd, float* scratch, int* rows_out, hipStream_t st) {
     DwGeom f;
     int bands, tpb;
-    AMS_REQUIRE(C % 4 == 0 && C / 4 <= 256 && (rate == 1 || rate == 2), "depthwise_fwd_bn: C=%d rate=%d", C, rate);
+    AMS_REQUIRE(dw_walk_ok(B, H, W, C, rate), "depthwise_fwd_bn: B=%d, %d x %d, C=%d rate=%d", B, H, W, C, rate);
     dw_walk_plan(B, H, W, C, rate, 1024, &f, &bands, &tpb);
     const unsigned nb = (unsigned)f.tiles_x * bands * B;
     *rows_out = (int)nb;
@@ -914,6 +920,7 @@ static int dw_wgrad_blocks(int64_t total_items, int C) {
 }
 
 size_t depthwise_wgrad_scratch(int B, int H, int W, int C, int stride, int rate) {
+    if (!dw_walk_ok(B, H, W, C, rate) || (stride != 1 && stride != 2)) return (size_t)-1;      // (dw_wgrad_blocks divides by C / 4)
     int Ho, Wo, p;
     same_pad(H, 3, stride, rate, &Ho, &p);
     same_pad(W, 3, stride, rate, &Wo, &p);

@@ -225,6 +225,8 @@ static int wgrad_splits(int64_t M, int K, int N) {
     return (int)want;
 }
 
+int wgrad_f32_splits(int64_t M, int K, int N) { return wgrad_splits(M, K, N); }
+
 size_t pointwise_wgrad_scratch(int64_t M, int K, int N) {
     const size_t f32 = (size_t)wgrad_splits(M, K, N) * K * N, x6 = (size_t)wgrad_x6_splits(M, K, N) * K * N;
     return f32 > x6 ? f32 : x6;

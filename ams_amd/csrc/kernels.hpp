@@ -169,6 +169,7 @@ bool dw_project_supported(int C, int N, int stride, int rate);
 int launch_dw_project(const BlockCall& c, hipStream_t st);
 bool pointwise_wgrad_x6_applies(int64_t M, int K, int N, int ldx, int ldy);
 int wgrad_x6_splits(int64_t M, int K, int N);
+int wgrad_f32_splits(int64_t M, int K, int N);             // the exact-f32 kernel's row splits (K, N > 0)
 int launch_pointwise_wgrad_x6(const WgArgs& a, int splits, hipStream_t st);
 size_t pointwise_wgrad_scratch(int64_t M, int K, int N);
 int launch_pointwise_wgrad(const WgArgs& a, hipStream_t st);

@@ -740,13 +740,30 @@ int ams_render_views(const uint8_t* frames_dev, const void* student_dev, int32_t
  * check each against the oracle (SURVEY.md §4 test pyramid level 1).  x/y/... are device pointers.
  * ===================================================================================================== */
 
+/* The entries of the GEMM family (ams_k_pointwise, _split, _split3, _split_f16, _wgrad, _wgrad_split, _red, _xform, _wgrad_xform,
+ * ams_k_pack_h2i), of the depthwise and stem family (ams_k_depthwise3x3, _dgrad, _wgrad, _fwd_bn, _dgrad_bn, _fwd_bn_tiles, _dgrad_bn_apply,
+ * ams_k_stem_conv) and of the recompute family (ams_k_xdw_fwd_stats, _bwd_reduce, _bwd_dx, _bwd_reduce_stem, _dwe, ams_k_xx_gram,
+ * ams_k_expand_stats) refuse with AMS_E_INVALID, in this order and in front of their first launch (a weight split is a launch); the message
+ * starts with the entry's name without its prefix ("depthwise3x3_wgrad: ..."):
+ *   1. no pixels or rows — B, H, W, M, K, N, C, Cin, Cexp, cout or n <= 0                                  "empty problem"
+ *   2. the entry's shape rule, stated as "Accepts:" at its prototype                                        "unsupported shape"
+ *   3. scratch or panels NULL, or fewer elements than the entry states                                      "too small (need N)"
+ *   4. scale without shift                                                                                  "scale without shift"
+ *   5. NULL among the pointers the entry reads or writes ("Reads:"; what is not listed may be NULL)         "null pointer"
+ * The *_scratch() functions of these entries return 0 for sizes <= 0 and for a shape their entry refuses at 1 or 2.  The launchers behind the
+ * entries keep their own conditions (alignment, grid and LDS limits), which follow. */
+
 /* K1+K2: pad(127.5) -> x/127.5-1 -> dense 3x3 stride 2 SAME (3 -> cout) -> y*scale+shift -> act.
- * scale/shift NULL: raw conv output.  stats_dev != NULL: also emit per-channel shifted (sum, sumsq) partials. */
+ * scale/shift NULL: raw conv output.
+ * Accepts: B, H, W, cout > 0; cout % 8 == 0 and <= 256, frames_dtype AMS_DT_U8 | AMS_DT_F32 (cout == 32 runs the MFMA form, every other width the
+ * generic kernel).  Reads: frames, w, y. */
 int ams_k_stem_conv(const void* frames, int32_t frames_dtype, int32_t B, int32_t H, int32_t W, const float* w /*[3,3,3,cout]*/,
                     int32_t cout, const float* scale, const float* shift, int32_t act, float pixel_scale,
                     float* y /*[B,Ho,Wo,cout]*/, void* stream);
 
-/* K3: depthwise 3x3, NHWC, SAME, stride 1|2, rate 1|2 -> y*scale+shift -> act (scale NULL: raw). */
+/* K3: depthwise 3x3, NHWC, SAME, stride 1|2, rate 1|2 -> y*scale+shift -> act (scale NULL: raw).
+ * Accepts (every ams_k_depthwise3x3* entry): B, H, W, C > 0; C % 4 == 0 and 4 <= C <= 1024; stride 1 | 2, rate 1 | 2, not both 2 (the four
+ * one-kernel fine-tune forms have stride 1).  Reads: x, w, y. */
 int ams_k_depthwise3x3(const float* x, int32_t B, int32_t H, int32_t W, int32_t C, const float* w /*[3,3,C,1]*/,
                        int32_t stride, int32_t rate, const float* scale, const float* shift, int32_t act,
                        float* y, void* stream);
@@ -754,7 +771,8 @@ int ams_k_depthwise3x3(const float* x, int32_t B, int32_t H, int32_t W, int32_t 
 /* K4: 1x1 conv as GEMM: y[M,N] = act((x[M,K] @ w[K,N] + img_bias[row/rows_per_img]) * scale + shift) + res.
  * Any of img_bias/scale/shift/res may be NULL.  trans_w != 0: w is given as [N,K] (dgrad).
  * M <= 16 runs a kernel of its own (one row per block row, k summed in another order than the tiled and streaming kernels): wherever an entry
- * below is called bit-identical to ams_k_pointwise, that holds for M > 16 rows; up to 16 rows the two agree to f32 rounding. */
+ * below is called bit-identical to ams_k_pointwise, that holds for M > 16 rows; up to 16 rows the two agree to f32 rounding.
+ * Accepts: M, K, N > 0; K % 4 == 0 (any N >= 1).  Reads: x, w, y. */
 int ams_k_pointwise(const float* x, int64_t M, int32_t K, const float* w, int32_t N, int32_t trans_w,
                     const float* img_bias, int64_t rows_per_img, const float* scale, const float* shift,
                     int32_t act, const float* res, float* y, void* stream);
@@ -762,7 +780,8 @@ int ams_k_pointwise(const float* x, int64_t M, int32_t K, const float* w, int32_
 /* K4, split-bf16 form (see AMS_MATMUL_SPLIT_BF16): y = act((x @ w) * scale + shift) + res with w [K,N] f32 split on the
  * fly into bf16 hi/lo panels held in `panels` (uint16, >= 2*N*roundup(K,32) elements).  K % 8 == 0.
  * Scratch and panels of every ams_k_* entry: the caller need not zero them — an entry writes every element it later reads, the pad columns
- * K .. roundup(K,32) of a weight panel included — and an entry refuses (AMS_E_INVALID, nothing launched) a size below the minimum it states. */
+ * K .. roundup(K,32) of a weight panel included — and an entry refuses (AMS_E_INVALID, nothing launched) a size below the minimum it states.
+ * Accepts (this entry and ams_k_pointwise_split3): M, K, N > 0; K % 8 == 0 (any N >= 1); panels as stated.  Reads: x, w, y. */
 int ams_k_pointwise_split(const float* x, int64_t M, int32_t K, const float* w, int32_t N, const float* scale,
                           const float* shift, int32_t act, const float* res, float* y, uint16_t* panels,
                           size_t panel_elems, void* stream);
@@ -810,10 +829,12 @@ int ams_k_expand_dw_stream(const float* x, int32_t B, int32_t H, int32_t W, int3
 /* The two-fp16-part forms (AMS_MATMUL_SPLIT_F16; k_pw_f16.hip, split_bf16.hpp): every operand x ~ hi + lo 2^-11 with hi = f16(x),
  * lo = f16((x - hi) 2^11); products hi hi + 2^-11 (hi lo + lo hi), 3 MFMAs per 32 k, f32 accumulate.
  * ams_k_pack_h2i: f32 [M][C] (C % 8 == 0) -> "H2I": per 8 channels 16 bytes of hi then 16 bytes of lo, 4 C bytes per row (what the streaming
- *   kernels write with y_h2i and the GEMM reads with x_h2i).
+ *   kernels write with y_h2i and the GEMM reads with x_h2i).  Accepts: M, C > 0; C % 8 == 0.  Reads: x, out.
  * ams_k_pointwise_split_f16: as ams_k_pointwise_split3 (K4; replaces the Conv2D nodes of model.meta `expanded_conv_N/project`, `aspp0`, ...);
  *   panels >= 2*N*Kp uint16; x_h2i (optional, M*K floats of scratch): x is first packed into H2I and the GEMM loads its operand from there —
  *   same result, bit for bit (x_h2i == x: x is taken as packed already); y_parts (optional, 2*M*N uint16): the result also as two fp16 part planes.
+ *   Accepts: M, K, N > 0; K % 8 == 0 and K >= 32 (any N >= 1); with y_parts, N % 4 == 0 (the vector epilogue writes the planes); panels as
+ *   stated.  Reads: x, w, y.
  * ams_k_expand_dw_stream_f16: as ams_k_expand_dw_stream with the fp16 parts (Cin 64 / 96 / 160); presplit 1 | 2 as there (2 = the
  *   weight-register form; panels then needs 2*B*H*W*Cin more elements); y_h2i != 0: y is written in H2I instead of f32.  Bit-identical to
  *   ams_k_pointwise_split_f16 followed by ams_k_depthwise3x3. */
@@ -1015,19 +1036,22 @@ int ams_k_ce_loss_grad_mined(const float* logits, int32_t B, int32_t h, int32_t 
  *     kt = 8 for K > 64 and 4 up to there; with n16 = ceil(N / 16): nw = 4 | 5 | 6 | 8 | 10 for n16 <= 4 | 5 | 6 | 8 | 10, above that
  *     10, 8 or 6 where it divides n16 (tried in that order) and 8 otherwise.
  * Each entry refuses (AMS_E_INVALID) fewer floats than ITS formula gives; ams_k_pointwise_wgrad_scratch returns the larger of the two, which
- * serves either entry and ams_k_pointwise_wgrad_xform with either value of split. */
+ * serves either entry and ams_k_pointwise_wgrad_xform with either value of split.
+ * Accepts (ams_k_pointwise_wgrad): M, K, N > 0, any K and N (the launcher picks one of nine vector-width pairs <VA, VB>: 1 up to 16 channels, at
+ * most 2 up to 32, else the widest of 4 / 2 / 1 that divides the count).  Reads: x, dy, dw. */
 int ams_k_pointwise_wgrad(const float* x, const float* dy, int64_t M, int32_t K, int32_t N, float* dw,
                           float* scratch, size_t scratch_floats, void* stream);
 size_t ams_k_pointwise_wgrad_scratch(int64_t M, int32_t K, int32_t N);
 /* K13b: the same on the bf16 matrix pipe with both operands split into three bf16 parts (six products, f32-level
- * accuracy): the kernel the fine-tune step uses for its late layers (few pixels, many channel pairs).  Requires
- * 1024 <= M <= 32768, K and N multiples of 4, K*N >= 4096 (AMS_E_INVALID otherwise). */
+ * accuracy): the kernel the fine-tune step uses for its late layers (few pixels, many channel pairs).
+ * Accepts: M, K, N > 0; 1024 <= M <= 32768, K and N multiples of 4, K*N >= 4096.  Reads: x, dy, dw. */
 int ams_k_pointwise_wgrad_split(const float* x, const float* dy, int64_t M, int32_t K, int32_t N, float* dw,
                                 float* scratch, size_t scratch_floats, void* stream);
 
 /* K13: depthwise backward: dx (input gradient) and dw[3,3,C,1].  ams_k_depthwise3x3_wgrad's scratch holds one 9 x C partial per block, each written
  * whole before the second stage sums them (nothing to zero): scratch_floats >= blocks * 9 * C with items = B * ceil(Ho / 4) * Wo,
- * slots = max(256 / (C / 4), 1), blocks = min(ceil(items / (2 * slots)), max(items * 2 / 9, 1), 1024); AMS_E_INVALID below that. */
+ * slots = max(256 / (C / 4), 1), blocks = min(ceil(items / (2 * slots)), max(items * 2 / 9, 1), 1024); AMS_E_INVALID below that.
+ * Accepts: as ams_k_depthwise3x3.  Reads: dy, w, dx (dgrad); x, dy, dw (wgrad). */
 int ams_k_depthwise3x3_dgrad(const float* dy, int32_t B, int32_t H, int32_t W, int32_t C, const float* w,
                              int32_t stride, int32_t rate, float* dx, void* stream);
 int ams_k_depthwise3x3_wgrad(const float* x, const float* dy, int32_t B, int32_t H, int32_t W, int32_t C,
@@ -1043,7 +1067,9 @@ int ams_k_depthwise3x3_wgrad(const float* x, const float* dy, int32_t B, int32_t
  * forward runs under AMS_MATMUL_SPLIT_F16; panels >= 2 N Kp); 0: the exact-f32 streaming kernel.  *rows_out = 0 means the kernel
  * chosen for this shape cannot fuse the reduction (y is then the plain product, + res): the caller runs the separate pass.
  * part_floats >= (M / 64 + 8 or 2048, whichever is larger) * 2 N; rows that would not fit make the launch run unfused (*rows_out = 0), no
- * refusal.  The *rows_out rows are written whole; the rest of `part` is left alone.  Nothing in `part` or `panels` needs zeroing. */
+ * refusal.  The *rows_out rows are written whole; the rest of `part` is left alone.  Nothing in `part` or `panels` needs zeroing.
+ * Accepts: M, K, N > 0; mode 1 | 2; split 0: K % 4 == 0; split 1: K % 8 == 0; split 2: mode 1, K % 8 == 0 and K >= 32; panels as stated.
+ * Reads: x, w, y, part, rows_out, and with mode 2 z, scale, shift, mean, rstd. */
 int ams_k_pointwise_red(const float* x, int64_t M, int32_t K, const float* w, int32_t N, int32_t trans_w, int32_t split, int32_t mode,
                         const float* center, const float* z, const float* scale, const float* shift, const float* mean, const float* rstd,
                         int32_t act, const float* res, float* y, float* part, size_t part_floats, int32_t* rows_out, uint16_t* panels,
@@ -1057,7 +1083,11 @@ int ams_k_pointwise_red(const float* x, int64_t M, int32_t K, const float* w, in
  *     x2 = the BN layer's raw output).  split 1: the three-part bf16 kernel (panels >= 3 N Kp), split 2 (x_mode 1 only): the two-fp16-part kernel, else the exact-f32 kernels.  A kernel that
  *     cannot transform on load writes x' into x_tmp [M,K] first (may be NULL: then such shapes fail with AMS_E_INVALID).
  *   ams_k_pointwise_wgrad_xform: dw [K,N] = x'^T . dy' with x' as x_mode 1 (x_mode 0: x' = x) and dy' = d0[n] * dy + d1[n] + d2[n] * dy2
- *     (dy_mode 2; dy_mode 0: dy' = dy); split != 0 the six-product bf16 kernel (shapes as ams_k_pointwise_wgrad_split). */
+ *     (dy_mode 2; dy_mode 0: dy' = dy); split != 0 the six-product bf16 kernel (shapes as ams_k_pointwise_wgrad_split).
+ * Accepts (xform): M, K, N > 0; x_mode 1 | 2; split 0: K % 4 == 0; split 1: K % 8 == 0; split 2: x_mode 1, K % 8 == 0, 32 <= K <= 1024, N % 4 == 0;
+ *   panels as stated.  Reads: x, w, y, v0, v1, and with x_mode 2 v2, x2.
+ * Accepts (wgrad_xform): M, K, N > 0; x_mode 0 | 1, dy_mode 0 | 2; split != 0: the shapes of ams_k_pointwise_wgrad_split; scratch as the entry of
+ *   the same split.  Reads: x, dy, dw, with x_mode 1 v0, v1, with dy_mode 2 d0, d1, d2, dy2. */
 int ams_k_pointwise_xform(const float* x, int64_t M, int32_t K, const float* w, int32_t N, int32_t trans_w, int32_t split, int32_t x_mode,
                           int32_t x_act, const float* v0, const float* v1, const float* v2, const float* x2, float* y, float* x_tmp,
                           uint16_t* panels, size_t panel_elems, void* stream);
@@ -1071,7 +1101,9 @@ int ams_k_pointwise_wgrad_xform(const float* x, const float* dy, int64_t M, int3
  *            [rows][2][C] of sum(zd - center), sum((zd - center)^2) (center may be NULL) in scratch; *rows_out = rows;
  *   backward: out [B,H,W,C] = dwconv3x3^T(dz, w) * act'(z_prev * scale + shift), and partial rows [rows][11][C] of sum(out),
  *            sum(out * (z_prev - mean) * rstd) and the nine taps of the depthwise weight gradient sum(act(z_prev * scale + shift) . dz).
- * scratch_floats must be at least the matching *_scratch(). */
+ * scratch_floats must be at least the matching *_scratch().
+ * Accepts (all four, and the two tile forms below): as ams_k_depthwise3x3 with stride 1; ams_k_depthwise3x3_fwd_bn_tiles: H * W * C < 2^31.
+ * Reads: every tensor and vector but center (NULL: sums about zero), and rows_out. */
 size_t ams_k_depthwise3x3_fwd_bn_scratch(int32_t B, int32_t H, int32_t W, int32_t C, int32_t rate);
 int ams_k_depthwise3x3_fwd_bn(const float* ze, int32_t B, int32_t H, int32_t W, int32_t C, const float* w, int32_t rate,
                               const float* scale, const float* shift, int32_t act, const float* center, float* zd, float* scratch,
@@ -1101,12 +1133,20 @@ int ams_k_depthwise3x3_dgrad_bn_apply(const float* dy, const float* zd, const fl
  *               partial rows  S [2][Cexp] = sum dy_e, sum dy_e xhat_e | dWd [9][Cexp] (depthwise weight gradient) | G1 [KP][Cexp] = x^T dy_e
  *   bwd_dx    : dx [B,H,W,Cin] = (cA dy_e + cB + cC z_e) . w_exp^T (+ res)
  *   dwe       : dw_exp [Cin][Cexp] = cA G1 + g0^T cB + cC (XX . w_exp) from the REDUCED rows (G1; XX | g0 contiguous)
- * rows of *stride_out floats, *rows_out of them, in scratch (>= ams_k_xdw_train_scratch floats). */
+ * rows of *stride_out floats, *rows_out of them, in scratch (>= ams_k_xdw_train_scratch floats).
+ * Accepts (fwd_stats, bwd_reduce, bwd_dx): B, H, W, Cin, Cexp > 0; Cin % 4 == 0 in 8 .. 32, Cexp % 16 == 0 in 32 .. 192, stride 1 | 2 (fwd_stats has
+ *   none), H * W * max(Cin, Cexp) < 2^31.  Reads: every tensor and vector but center and res (NULL: none), rows_out, stride_out.
+ * Accepts (bwd_reduce_stem): B, fH, fW > 0; frames_dtype AMS_DT_U8 | AMS_DT_F32, fH * fW * 3 < 2^31.  Reads: all its pointers.
+ * Accepts (dwe): Cin, Cexp > 0; Cin <= 32 (the stem's 27 taps included: rows of KP = Cin rounded up to 16), Cexp % 16 == 0 in 32 .. 192.
+ *   Reads: all its pointers. */
 /* BN statistics of an early block's expand layer from the Gram matrix of the block input (AMS_OPT_TRAIN_RECOMPUTE = 2, k_xx_stats.hip; what
  * FusedBatchNormV3's reduction over z_e = x . W_e is to the reference's graph): ams_k_xx_gram forms XX = x^T x [KP][KP] and g0 = sum x [KP]
  * (KP = Cin rounded up to 16, Cin <= 32) over the M rows of x [M, Cin] on the f64 matrix pipe — xx64: KP KP + KP doubles, xx32 (may be NULL) the
  * same as floats; ams_k_expand_stats turns them into scale / shift / saved mean / rstd (and the moving averages, sums [2][Cexp] about
- * `center`, both optional) of the BN over n pixels: sum z = g0 . w, sum z^2 = w^T XX w per channel, in f64. */
+ * `center`, both optional) of the BN over n pixels: sum z = g0 . w, sum z^2 = w^T XX w per channel, in f64.
+ * Accepts (xx_gram): M, Cin > 0; 4 <= Cin <= 32.  Reads: x, xx64 (xx32 optional); scratch >= ams_k_xx_gram_scratch doubles.
+ * Accepts (expand_stats): Cin, Cexp, n > 0; 4 <= Cin <= 32.  Reads: xx64, w_exp, gamma, beta, scale, shift; save_mean and save_rstd, and
+ *   moving_mean and moving_var, each as a pair or both NULL; center and sums optional. */
 size_t ams_k_xx_gram_scratch(int64_t M, int32_t Cin);
 int ams_k_xx_gram(const float* x, int64_t M, int32_t Cin, double* scratch, size_t scratch_doubles, double* xx64, float* xx32, void* stream);
 int ams_k_expand_stats(const double* xx64, int32_t Cin, const float* w_exp, int32_t Cexp, double n, const float* center, const float* gamma,
