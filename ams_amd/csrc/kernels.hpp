@@ -399,6 +399,18 @@ int launch_encode_delta_q8(const uint8_t* mask, int64_t* table_dev, int n_vars, 
 int launch_apply_delta_q8(const uint8_t* payload, int64_t payload_bytes, const ams_delta_var* vars_dev, int n_vars, int64_t mask_bytes,
                           float* params, int64_t n_params, float* stats, int64_t n_stats, int64_t* counts, int64_t* n_applied, int32_t* status,
                           hipStream_t st);
+// k_uplink.hip: the uplink frame codec AUC1 (ams_uplink_*).  Blocks and slices of the planes Y, Cb, Cr of an H x W frame; the scratch
+// layouts are stated at the top of k_uplink.hip.  The launchers take sizes uplink_shape_ok accepts and 16-byte aligned scratch.
+struct UplinkGeom { int H, W, nb[3], ns[3], nblocks, nslices; };
+bool uplink_shape_ok(int H, int W);
+UplinkGeom uplink_geom(int H, int W);
+int64_t uplink_max_bytes(int H, int W);
+size_t uplink_encode_scratch_bytes(int H, int W);
+size_t uplink_decode_scratch_bytes(int H, int W);
+int launch_uplink_transform(const uint8_t* frame, int H, int W, void* scratch, hipStream_t st);
+int launch_uplink_size_table(void* scratch, int H, int W, int64_t* sizes, hipStream_t st);
+int launch_uplink_encode(void* scratch, int H, int W, int q, uint8_t* payload, int64_t cap, int64_t* bytes_out, int32_t* status, hipStream_t st);
+int launch_uplink_decode(const uint8_t* payload, int64_t bytes, int H, int W, uint8_t* frame, int32_t* status, void* scratch, hipStream_t st);
 // k_select.hip: the server half of a model update: coordinates chosen by their change, the roll-back, the downlink delta encoded
 size_t select_scratch();
 int launch_select_changed(const float* after, const float* before, int64_t n, int64_t k, ams_select_result* result, int64_t* scratch,

@@ -25,8 +25,16 @@ committed; the defects listed in SURVEY.md Appendix D are resolved towards their
     hold the overlays.  The reference rewrites ``<results>_<second>_*.png`` at every frame (``second = i / fps`` after ``i`` advanced), so only
     the last frame of each label survives; here only those frames are painted and written.  ``cross_ignore`` raises IndexError on a teacher id
     from the class count on (255 = unlabelled in the synthetic clips); the pictures count such a pixel as ignored, as the metric does.
-Out of scope (networking emulation / reporting): H.264 uplink through ffmpeg (``--compress_uplink``
-is rejected), PNG-exact uplink byte counts (zlib-deflated frame size is logged instead), the matplotlib plots.
+  * ``--compress_uplink`` (run.py:177-266 there: sampled frames at twice the network size through ffmpeg/libx264 at a bitrate the flag
+    ``uplink_bw`` is read for but never defined): there is no ffmpeg here, so the lossy leg is an intra-frame transform codec of the project's own
+    (``ams_amd.uplink``, format AUC1), encoded and decoded on the device.  A sampled frame is resized to 2H x 4H, encoded at the largest of the
+    100 qualities whose payload fits the frame's budget, decoded, resized to H x 2H and only then stored: the server trains on what the decoder
+    gives back, and ``*_bw_uplink.npy`` counts the payload bytes.  Budget rule: with ``--uplink_bw`` in kbit/s (added flag, default 200: a
+    choice, not a measurement) an upload of n frames gives each floor(uplink_bw * 1000 / 8 * period / n) bytes, period = the upload period of
+    the loop in seconds.  The byte counts are this codec's, NOT H.264's: no inter-frame prediction, no byte parity.
+    ``<results>_uplink_quality.npy`` has one row per upload: second, frames, bytes, budget per frame, min q, mean q, frames that did not fit;
+Out of scope (networking emulation / reporting): H.264 byte parity of the uplink, PNG-exact uplink byte counts without
+``--compress_uplink`` (zlib-deflated frame size is logged instead), the matplotlib plots.
 Video comes from a ``FrameSource``: there is no OpenCV here (pictures are written by ``ams_amd.png``), so ``--input_video`` is either
 ``synthetic:<NUM>-<name>[:seconds=S][:fps=F]`` (procedural clip) or a directory holding
 ``frame_%06d.npy`` (RGB uint8) and ``gt_%06d.npy`` files, with ``--soft_teacher`` also ``logits_%06d.npy`` (the teacher's logits, f32
@@ -73,7 +81,13 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--send_period", type=int, default=30)
     p.add_argument("--train_period", type=int, default=10)
     p.add_argument("--only_results", action="store_true")
-    p.add_argument("--compress_uplink", action="store_true")
+    p.add_argument("--compress_uplink", action="store_true",
+                   help="uplink: sampled frames travel at twice the network size through the lossy frame codec of ams_amd.uplink at the byte "
+                        "budget --uplink_bw gives (needs a GPU and --height a multiple of 8); the server trains on the decoded frames and the "
+                        "uplink is counted in payload bytes.  The reference's H.264 leg in mechanism, not in byte counts")
+    p.add_argument("--uplink_bw", type=float, default=200.0,
+                   help="--compress_uplink: the uplink's rate in kbit/s (extra flag; the reference reads an undefined flag of this name); an "
+                        "upload of n frames gives each floor(uplink_bw * 1000 / 8 * upload period / n) bytes")
     p.add_argument("--no_restore", action="store_true")
     p.add_argument("--save_pic", action="store_true")
     p.add_argument("--gpu_ingest", action="store_true",
@@ -255,6 +269,24 @@ def _to_size(frame: np.ndarray, label: np.ndarray, size: List[int], ingest=None)
     return frame, label
 
 
+def uplink_budget(uplink_bw: float, period: int, n: int) -> int:
+    """--compress_uplink: the bytes each of the ``n`` frames of an upload may take, ``period`` seconds after the previous upload."""
+    return int(uplink_bw * 1000 / 8 * period // n)
+
+
+def _through_uplink(fr, codec, budget: int, size: List[int], ingest=None):
+    """--compress_uplink: the sampled frame as the server receives it.  Resized to twice the network size, encoded at the budget and decoded on
+    the device, resized to the network size by the same rule (both on the device with ``ingest``, else ``resize_linear`` on the host)
+    -> (frame, payload bytes, quality, fits)."""
+    H2, W2 = 2 * size[0], 2 * size[1]
+    if fr.shape[:2] != (H2, W2):
+        fr = ingest.frame(fr, H2, W2) if ingest is not None else resize_linear(_host(fr), W2, H2)
+    payload, quality, fits = codec.encode_to_budget(fr, budget)
+    decoded = codec.decode(payload, (H2, W2))
+    fr = ingest.frame(decoded, size[0], size[1]) if ingest is not None else resize_linear(_host(decoded), size[1], size[0])
+    return fr, int(payload.numel()), quality, fits
+
+
 def _batch1(x):
     """np.expand_dims(x, 0) for host arrays and device tensors alike."""
     return x.unsqueeze(0) if hasattr(x, "unsqueeze") else np.expand_dims(x, axis=0)
@@ -330,7 +362,11 @@ def train_model(ctx: Context, train_start, train_end, sampling_period, gpu_id, r
     a frozen model after each (reference run.py:78-361)."""
     FLAGS = ctx.flags
     assert train_end - train_start != 0, "There should be at least one set of data points"
-    assert not FLAGS.compress_uplink, "H.264 uplink emulation (ffmpeg) is out of scope for this build"
+    uplink_codec = None
+    if getattr(FLAGS, "compress_uplink", False):
+        from .uplink import UplinkCodec
+        uplink_codec = UplinkCodec("cuda:%s" % gpu_id)
+    uplink_log = []           # --compress_uplink, per upload: (second, frames, bytes, budget per frame, min q, mean q, frames that did not fit)
     save_range = list(save_range)
     fps = ctx.source.fps
     train_end_frame = min(train_end * fps, len(ctx.source))
@@ -411,11 +447,17 @@ def train_model(ctx: Context, train_start, train_end, sampling_period, gpu_id, r
         if second % sample_send_period == 0:
             frames_chosen, labels_chosen = choose_frames(frame_label_bucket, min(1.0, send_rate / fps if per_second else send_rate))
             size_images = 0.0
+            budget = uplink_budget(FLAGS.uplink_bw, sample_send_period, len(frames_chosen)) if uplink_codec is not None and frames_chosen else 0
+            sent = []         # --compress_uplink: (bytes, quality, fits) per frame of this upload
             for fr, label in zip(frames_chosen, labels_chosen):
                 logits = None
                 if soft_teacher:
                     label, index = label
                     logits = source_logits(ctx.source, index)
+                if uplink_codec is not None:
+                    # the frame goes through the lossy leg before anything else sees it; its label does not travel (the teacher is the server's)
+                    fr, *info = _through_uplink(fr, uplink_codec, budget, ctx.size, ctx.ingest)
+                    sent.append(info)
                 if labels_from_logits:
                     # the server never touches the source's label map: no resize, no upload; the slot's labels are the argmax of the
                     # logits' upsample, formed on the device
@@ -435,11 +477,18 @@ def train_model(ctx: Context, train_start, train_end, sampling_period, gpu_id, r
                         label_resized = map_coco[label_resized]
                     frame_memory.append(fr)
                     label_memory.append(label_resized)
-                size_images += len(zlib.compress(fr.tobytes(), 6)) / 1024     # stand-in for the PNG size
+                if uplink_codec is not None:
+                    size_images += sent[-1][0] / 1024                         # the payload that travelled
+                else:
+                    size_images += len(zlib.compress(fr.tobytes(), 6)) / 1024     # stand-in for the PNG size
             frame_label_bucket.clear()
             sample_per_period.append(len(frames_chosen))
             num_unseen_frames += len(frames_chosen)
             up_bw_per_period.append(size_images * 8)
+            if uplink_codec is not None:
+                qs = [q for _, q, _ in sent]
+                uplink_log.append((second, len(sent), sum(n for n, _, _ in sent), budget, min(qs) if qs else np.nan,
+                                   float(np.mean(qs)) if qs else np.nan, sum(1 for _, _, fits in sent if not fits)))
 
         n_memory = len(device_memory) if device_memory is not None else len(frame_memory)
         if second in save_range and n_memory == 0:
@@ -535,6 +584,8 @@ def train_model(ctx: Context, train_start, train_end, sampling_period, gpu_id, r
     np.save(final_save_dir + '_model_update_times.npy', model_save_times)
     np.save(final_save_dir + '_train_ms.npy', train_ms)
     np.save(final_save_dir + '_control.npy', np.asarray(control_log, dtype=np.float64).reshape(-1, 5))
+    if uplink_codec is not None:
+        np.save(final_save_dir + '_uplink_quality.npy', np.asarray(uplink_log, dtype=np.float64).reshape(-1, 7))
     if weights_flag is not None:
         np.save(final_save_dir + '_loss_weights.npy', np.asarray(loss_weights_log, dtype=np.float32).reshape(-1, int(class_weights(exp_num).sum())))
     if mining_flag is not None:
@@ -737,6 +788,17 @@ def parse_flags(argv: Optional[List[str]] = None):
                                                                    if getattr(flags, name) is not None})
     if problem:
         parser.error(problem)
+    if flags.compress_uplink:
+        import torch
+        if not torch.cuda.is_available():
+            parser.error("--compress_uplink needs a GPU: the uplink frame codec runs on the device and has no host fallback")
+        if flags.height < 8 or flags.height % 8 != 0:
+            parser.error("--compress_uplink needs --height to be a multiple of 8 (got %d): the codec takes frames of 2 x height by 4 x height "
+                         "in macroblocks of 16 x 16" % flags.height)
+        if flags.height > 1024:
+            parser.error("--compress_uplink takes --height up to 1024 (got %d): the codec's frames are at most 4096 wide" % flags.height)
+        if not (np.isfinite(flags.uplink_bw) and flags.uplink_bw > 0):
+            parser.error("--uplink_bw must be finite and > 0 kbit/s (got %r)" % flags.uplink_bw)
     if flags.loss_top_k_warmup is not None and flags.loss_top_k is None:
         parser.error("--loss_top_k_warmup needs --loss_top_k: it eases the mining in")
     problem = loss_knobs_problem(True, dash="--", **{name: getattr(flags, name) for name in ("loss_top_k", "loss_top_k_warmup")

@@ -564,6 +564,63 @@ int ams_student_apply_delta_q8(ams_student* s, const uint8_t* payload_dev, int64
 /* int64 elements of device scratch ams_student_apply_delta_q8 needs for this table (0 if the table is malformed) */
 size_t ams_student_apply_delta_q8_scratch(const ams_delta_var* vars_host, int32_t n_vars);
 
+/* ---- the uplink frame codec (k_uplink.hip; run.py --compress_uplink): an intra-frame transform codec of the project's own, format AUC1.
+ * It stands for the reference's H.264 leg (lossy frames at a byte budget, counted bytes); its byte counts are NOT H.264's.  All arithmetic
+ * is integer (>> is an arithmetic shift), so tests/uplink_ref.py restates both ends byte for byte.
+ *
+ * Frame: RGB uint8 [H, W, 3], H and W multiples of 16 in 16 .. 4096.
+ * Colour, JFIF full range in 16-bit fixed point, every result clamped to 0 .. 255:
+ *   Y = (19595 R + 38470 G + 7471 B + 32768) >> 16;  Cb = ((-11059 R - 21709 G + 32768 B + 32768) >> 16) + 128;
+ *   Cr = ((32768 R - 27439 G - 5329 B + 32768) >> 16) + 128;  chroma 4:2:0: (a + b + c + d + 2) >> 2 over each 2 x 2.
+ *   Back, chroma replicated 2 x 2: R = Y + ((91881 (Cr - 128) + 32768) >> 16);  B = Y + ((116130 (Cb - 128) + 32768) >> 16);
+ *   G = Y - ((22554 (Cb - 128) + 46802 (Cr - 128) + 32768) >> 16).
+ * Transform: 8 x 8 blocks of pixel - 128; M = rint(2^13 C), C the orthonormal 8-point DCT-II matrix.  Forward: along the rows
+ *   t = (M x + 512) >> 10, then along the columns c = (M t + 32768) >> 16.  Inverse: the same two shifts with M transposed, columns
+ *   first, then + 128 and the clamp; the decoder clamps every dequantised coefficient to [-2047, 2047] first.
+ * Quantisation: the JPEG Annex K luminance / chrominance tables with libjpeg's quality scaling, q in 1 .. 100: s = q < 50 ? 5000 / q :
+ *   200 - 2 q;  qt = clamp((base s + 50) / 100, 1, 255);  level = sign(c) ((|c| + qt / 2) / qt);  dequantised level x qt.
+ * Entropy code: Exp-Golomb of order 0, bits MSB first: ue(v) = floor(log2(v + 1)) zero bits, then v + 1 in binary; se(v) = ue(v > 0 ?
+ *   2 v - 1 : -2 v).  A block in JPEG zig-zag order: se(dc - pred); per non-zero AC ue(run + 1), se(level), run = the zeros since the
+ *   previous coded coefficient; ue(0) ends every block.
+ * Slices: planes in the order Y, Cb, Cr, blocks in raster order within a plane; every 32 consecutive blocks of a plane are a slice (a
+ *   plane's last may be shorter); pred = the previous block's quantised DC within the slice, 0 for its first; zero bits pad a slice to a byte.
+ * Payload, little-endian, no alignment assumed: 16-byte header "AUC1", u16 H, u16 W, u8 q, three zero bytes, u32 total payload bytes;
+ *   one u16 byte length per slice; the slices. */
+enum {
+    AMS_UPLINK_OK = 0,
+    AMS_UPLINK_BAD_HEADER = 1,      /* magic, H or W (against the call's), q, the reserved bytes or the total (against the bytes handed in) */
+    AMS_UPLINK_BAD_TABLE = 2,       /* header + table + the table's lengths != the total */
+    AMS_UPLINK_BAD_SLICE_END = 3,   /* a slice's last block ends before the slice's last byte, or a padding bit is set */
+    AMS_UPLINK_BAD_POSITION = 4,    /* a run leads past coefficient 63 */
+    AMS_UPLINK_BAD_ZERO_LEVEL = 5,  /* an AC level of 0 */
+    AMS_UPLINK_BAD_LEVEL = 6,       /* |level| > 2047 (an Exp-Golomb prefix of more than 16 zero bits counts as one) */
+    AMS_UPLINK_BAD_OVERRUN = 7,     /* a code runs past the end of its slice */
+    AMS_UPLINK_NO_ROOM = 8          /* encoder: the payload is larger than payload_cap; nothing was written */
+};
+/* Every ams_uplink_* entry refuses on the host, AMS_E_INVALID and nothing launched, in this order: H or W <= 0; H or W no multiple of 16
+ * in 16 .. 4096 (the encoder: or q outside 1 .. 100); scratch NULL or below the entry's _scratch bytes; a null pointer; scratch
+ * not 16-byte aligned; a negative payload_cap / payload_bytes.  No handle, no allocation, no synchronisation. */
+/* the largest payload of an H x W frame: header + table + 208 bytes per block; 0 for a size the entries refuse */
+int64_t ams_uplink_max_bytes(int32_t H, int32_t W);
+/* BYTES of device scratch of the encoder entries (transform, size_table, encode share one block) and of the decoder; 0 for a refused size */
+size_t ams_uplink_encode_scratch(int32_t H, int32_t W);
+size_t ams_uplink_decode_scratch(int32_t H, int32_t W);
+/* Colour, 4:2:0 and the forward transform of frame_dev: int16 coefficients, zig-zag order per block, into the scratch (one launch). */
+int ams_uplink_transform(const uint8_t* frame_dev, int32_t H, int32_t W, void* scratch_dev, size_t scratch_bytes, void* stream);
+/* From the coefficients ams_uplink_transform left in the scratch: sizes_dev[q - 1] (int64 x 100) = the exact payload bytes at quality q
+ * (two launches: per (quality, slice) byte counts, then the 100 totals). */
+int ams_uplink_size_table(void* scratch_dev, size_t scratch_bytes, int32_t H, int32_t W, int64_t* sizes_dev, void* stream);
+/* Writes the payload at quality q from the coefficients in the scratch.  *bytes_dev (int64) = the payload's size; *status_dev (int32) =
+ * AMS_UPLINK_OK, or AMS_UPLINK_NO_ROOM if that size exceeds payload_cap: then no byte of payload_dev is written.  Three launches: slice
+ * lengths, their scan with header and table, the slices' bits. */
+int ams_uplink_encode(void* scratch_dev, size_t scratch_bytes, int32_t H, int32_t W, int32_t q, uint8_t* payload_dev, int64_t payload_cap,
+                      int64_t* bytes_dev, int32_t* status_dev, void* stream);
+/* Decodes payload_dev[0, payload_bytes) to RGB uint8 [H, W, 3].  Validated on the device, all or nothing: *status_dev (int32) = AMS_UPLINK_*
+ * (several malformed slices: the largest of their codes), and frame_out_dev is written only under AMS_UPLINK_OK.  No byte outside
+ * [0, payload_bytes) is read.  Three launches: header, table and scan; one slice per thread into int16 levels; reconstruction. */
+int ams_uplink_decode(const uint8_t* payload_dev, int64_t payload_bytes, int32_t H, int32_t W, uint8_t* frame_out_dev, int32_t* status_dev,
+                      void* scratch_dev, size_t scratch_bytes, void* stream);
+
 /* ---- the server's replay memory on the device (replaces run.py:136-137 frame_memory / label_memory, two host deques, and the sampling of
  * utils/utils.py:129-185 mini_batch from them).  The memory is a ring of `capacity` slots the caller owns: slot p of the frames is uint8
  * [src_h, src_w, 3] at frame_slots_dev + p * frame_slot_stride, of the labels uint8 [src_h, src_w] at label_slots_dev + p * label_slot_stride
