@@ -750,8 +750,10 @@ int ams_student_apply_delta_q8(ams_student* s, const uint8_t* payload_dev, int64
 }
 
 // ---- the uplink frame codec (k_uplink.hip) ------------------------------------------------------------------
-// One description for the four entries, refused in entry_check's order; then what only some of them take (a negative byte count).
-static int uplink_entry(const char* who, int32_t H, int32_t W, bool q_ok, int32_t q, const void* scratch, size_t have, bool decoder, bool ptrs) {
+// One description for the entries of both payload kinds, refused in entry_check's order; then what only some of them take (a negative byte
+// count).  need = the entry's scratch bytes for a size the shape rule accepts.
+static int uplink_entry(const char* who, int32_t H, int32_t W, bool q_ok, int32_t q, const void* scratch, size_t have, size_t (*need)(int, int),
+                        bool ptrs) {
     EntryCall c;
     c.who = who;
     c.describe("%d x %d, q=%d", H, W, q);
@@ -760,7 +762,7 @@ static int uplink_entry(const char* who, int32_t H, int32_t W, bool q_ok, int32_
     c.scratch_what = "scratch";
     c.scratch = scratch;
     c.have = have;
-    if (c.shaped()) c.need = decoder ? uplink_decode_scratch_bytes(H, W) : uplink_encode_scratch_bytes(H, W);
+    if (c.shaped()) c.need = need(H, W);
     c.ptrs = ptrs;
     RUN_RC(entry_check(c));
     AMS_REQUIRE(((uintptr_t)scratch & 15) == 0, "%s: scratch at %p is not 16-byte aligned", who, scratch);
@@ -772,28 +774,65 @@ size_t ams_uplink_encode_scratch(int32_t H, int32_t W) { return AMS_ENTRY_SCRATC
 size_t ams_uplink_decode_scratch(int32_t H, int32_t W) { return AMS_ENTRY_SCRATCH(uplink_shape_ok(H, W), uplink_decode_scratch_bytes(H, W)); }
 
 int ams_uplink_transform(const uint8_t* frame_dev, int32_t H, int32_t W, void* scratch_dev, size_t scratch_bytes, void* stream) {
-    RUN_RC(uplink_entry("uplink_transform", H, W, true, 0, scratch_dev, scratch_bytes, false, frame_dev != nullptr));
+    RUN_RC(uplink_entry("uplink_transform", H, W, true, 0, scratch_dev, scratch_bytes, uplink_encode_scratch_bytes, frame_dev != nullptr));
     return launch_uplink_transform(frame_dev, H, W, scratch_dev, (hipStream_t)stream);
 }
 
 int ams_uplink_size_table(void* scratch_dev, size_t scratch_bytes, int32_t H, int32_t W, int64_t* sizes_dev, void* stream) {
-    RUN_RC(uplink_entry("uplink_size_table", H, W, true, 0, scratch_dev, scratch_bytes, false, sizes_dev != nullptr));
+    RUN_RC(uplink_entry("uplink_size_table", H, W, true, 0, scratch_dev, scratch_bytes, uplink_encode_scratch_bytes, sizes_dev != nullptr));
     return launch_uplink_size_table(scratch_dev, H, W, sizes_dev, (hipStream_t)stream);
 }
 
 int ams_uplink_encode(void* scratch_dev, size_t scratch_bytes, int32_t H, int32_t W, int32_t q, uint8_t* payload_dev, int64_t payload_cap,
                       int64_t* bytes_dev, int32_t* status_dev, void* stream) {
-    RUN_RC(uplink_entry("uplink_encode", H, W, q >= 1 && q <= 100, q, scratch_dev, scratch_bytes, false, payload_dev && bytes_dev && status_dev));
+    RUN_RC(uplink_entry("uplink_encode", H, W, q >= 1 && q <= 100, q, scratch_dev, scratch_bytes, uplink_encode_scratch_bytes,
+                        payload_dev && bytes_dev && status_dev));
     AMS_REQUIRE(payload_cap >= 0, "uplink_encode: room for %lld bytes", (long long)payload_cap);
     return launch_uplink_encode(scratch_dev, H, W, q, payload_dev, payload_cap, bytes_dev, status_dev, (hipStream_t)stream);
 }
 
 int ams_uplink_decode(const uint8_t* payload_dev, int64_t payload_bytes, int32_t H, int32_t W, uint8_t* frame_out_dev, int32_t* status_dev,
                       void* scratch_dev, size_t scratch_bytes, void* stream) {
-    RUN_RC(uplink_entry("uplink_decode", H, W, true, 0, scratch_dev, scratch_bytes, true,
+    RUN_RC(uplink_entry("uplink_decode", H, W, true, 0, scratch_dev, scratch_bytes, uplink_decode_scratch_bytes,
                         frame_out_dev && status_dev && (payload_dev || payload_bytes <= 0)));
     AMS_REQUIRE(payload_bytes >= 0, "uplink_decode: %lld payload bytes", (long long)payload_bytes);
     return launch_uplink_decode(payload_dev, payload_bytes, H, W, frame_out_dev, status_dev, scratch_dev, (hipStream_t)stream);
+}
+
+// ---- the predicted frame AUP1 (k_uplink_inter.hip): the same description; the reference stands with the other pointers
+int64_t ams_uplink_inter_max_bytes(int32_t H, int32_t W) { return uplink_shape_ok(H, W) ? uplink_inter_max_bytes(H, W) : 0; }
+size_t ams_uplink_inter_encode_scratch(int32_t H, int32_t W) {
+    return AMS_ENTRY_SCRATCH(uplink_shape_ok(H, W), uplink_inter_encode_scratch_bytes(H, W));
+}
+size_t ams_uplink_inter_decode_scratch(int32_t H, int32_t W) {
+    return AMS_ENTRY_SCRATCH(uplink_shape_ok(H, W), uplink_inter_decode_scratch_bytes(H, W));
+}
+
+int ams_uplink_inter_transform(const uint8_t* frame_dev, const uint8_t* ref_dev, int32_t H, int32_t W, void* scratch_dev, size_t scratch_bytes,
+                               void* stream) {
+    RUN_RC(uplink_entry("uplink_inter_transform", H, W, true, 0, scratch_dev, scratch_bytes, uplink_inter_encode_scratch_bytes, frame_dev && ref_dev));
+    return launch_uplink_inter_transform(frame_dev, ref_dev, H, W, scratch_dev, (hipStream_t)stream);
+}
+
+int ams_uplink_inter_size_table(void* scratch_dev, size_t scratch_bytes, int32_t H, int32_t W, int64_t* sizes_dev, void* stream) {
+    RUN_RC(uplink_entry("uplink_inter_size_table", H, W, true, 0, scratch_dev, scratch_bytes, uplink_inter_encode_scratch_bytes, sizes_dev != nullptr));
+    return launch_uplink_inter_size_table(scratch_dev, H, W, sizes_dev, (hipStream_t)stream);
+}
+
+int ams_uplink_inter_encode(void* scratch_dev, size_t scratch_bytes, int32_t H, int32_t W, int32_t q, uint8_t* payload_dev, int64_t payload_cap,
+                            int64_t* bytes_dev, int32_t* status_dev, void* stream) {
+    RUN_RC(uplink_entry("uplink_inter_encode", H, W, q >= 1 && q <= 100, q, scratch_dev, scratch_bytes, uplink_inter_encode_scratch_bytes,
+                        payload_dev && bytes_dev && status_dev));
+    AMS_REQUIRE(payload_cap >= 0, "uplink_inter_encode: room for %lld bytes", (long long)payload_cap);
+    return launch_uplink_inter_encode(scratch_dev, H, W, q, payload_dev, payload_cap, bytes_dev, status_dev, (hipStream_t)stream);
+}
+
+int ams_uplink_inter_decode(const uint8_t* payload_dev, int64_t payload_bytes, const uint8_t* ref_dev, int32_t H, int32_t W, uint8_t* frame_out_dev,
+                            int32_t* status_dev, void* scratch_dev, size_t scratch_bytes, void* stream) {
+    RUN_RC(uplink_entry("uplink_inter_decode", H, W, true, 0, scratch_dev, scratch_bytes, uplink_inter_decode_scratch_bytes,
+                        ref_dev && frame_out_dev && status_dev && (payload_dev || payload_bytes <= 0)));
+    AMS_REQUIRE(payload_bytes >= 0, "uplink_inter_decode: %lld payload bytes", (long long)payload_bytes);
+    return launch_uplink_inter_decode(payload_dev, payload_bytes, ref_dev, H, W, frame_out_dev, status_dev, scratch_dev, (hipStream_t)stream);
 }
 
 // ---- kernel-level entry points -----------------------------------------------------------------------------

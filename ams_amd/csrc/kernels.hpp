@@ -411,6 +411,18 @@ int launch_uplink_transform(const uint8_t* frame, int H, int W, void* scratch, h
 int launch_uplink_size_table(void* scratch, int H, int W, int64_t* sizes, hipStream_t st);
 int launch_uplink_encode(void* scratch, int H, int W, int q, uint8_t* payload, int64_t cap, int64_t* bytes_out, int32_t* status, hipStream_t st);
 int launch_uplink_decode(const uint8_t* payload, int64_t bytes, int H, int W, uint8_t* frame, int32_t* status, void* scratch, hipStream_t st);
+
+// k_uplink_inter.hip: the predicted frame AUP1 (ams_uplink_inter_*): one vector per macroblock against a reference frame of the same size,
+// the residual through AUC1's transform and block code (uplink_common.hpp), motion slices in front of the residual slices.  Scratch layouts
+// at the top of k_uplink_inter.hip.
+int64_t uplink_inter_max_bytes(int H, int W);
+size_t uplink_inter_encode_scratch_bytes(int H, int W);
+size_t uplink_inter_decode_scratch_bytes(int H, int W);
+int launch_uplink_inter_transform(const uint8_t* frame, const uint8_t* ref, int H, int W, void* scratch, hipStream_t st);
+int launch_uplink_inter_size_table(void* scratch, int H, int W, int64_t* sizes, hipStream_t st);
+int launch_uplink_inter_encode(void* scratch, int H, int W, int q, uint8_t* payload, int64_t cap, int64_t* bytes_out, int32_t* status, hipStream_t st);
+int launch_uplink_inter_decode(const uint8_t* payload, int64_t bytes, const uint8_t* ref, int H, int W, uint8_t* frame, int32_t* status, void* scratch,
+                               hipStream_t st);
 // k_select.hip: the server half of a model update: coordinates chosen by their change, the roll-back, the downlink delta encoded
 size_t select_scratch();
 int launch_select_changed(const float* after, const float* before, int64_t n, int64_t k, ams_select_result* result, int64_t* scratch,

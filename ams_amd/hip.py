@@ -100,7 +100,7 @@ DELTA_OK, DELTA_BAD_SIZE, DELTA_BAD_PADDING, DELTA_BAD_SCALE, DELTA_Q8_NONFINITE
 DELTA_MAX_VARS = 1024
 # AMS_UPLINK_*: the status word of ams_uplink_encode / ams_uplink_decode
 (UPLINK_OK, UPLINK_BAD_HEADER, UPLINK_BAD_TABLE, UPLINK_BAD_SLICE_END, UPLINK_BAD_POSITION, UPLINK_BAD_ZERO_LEVEL, UPLINK_BAD_LEVEL,
- UPLINK_BAD_OVERRUN, UPLINK_NO_ROOM) = range(9)
+ UPLINK_BAD_OVERRUN, UPLINK_NO_ROOM, UPLINK_BAD_VECTOR, UPLINK_BAD_ZERO_SLICE) = range(11)
 
 ALLREDUCE_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int32)
 
@@ -176,6 +176,13 @@ SIGNATURES = {
     "ams_uplink_size_table": (C.c_int, [_vp, _sz, _i32, _i32, _vp, _vp]),
     "ams_uplink_encode": (C.c_int, [_vp, _sz, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp]),
     "ams_uplink_decode": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "ams_uplink_inter_max_bytes": (_i64, [_i32, _i32]),
+    "ams_uplink_inter_encode_scratch": (_sz, [_i32, _i32]),
+    "ams_uplink_inter_decode_scratch": (_sz, [_i32, _i32]),
+    "ams_uplink_inter_transform": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _sz, _vp]),
+    "ams_uplink_inter_size_table": (C.c_int, [_vp, _sz, _i32, _i32, _vp, _vp]),
+    "ams_uplink_inter_encode": (C.c_int, [_vp, _sz, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp]),
+    "ams_uplink_inter_decode": (C.c_int, [_vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
     "ams_k_stem_conv": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _f32, _vp, _vp]),
     "ams_k_depthwise3x3": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp]),
     "ams_k_pointwise": (C.c_int, [_vp, _i64, _i32, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp]),

@@ -31,8 +31,14 @@ committed; the defects listed in SURVEY.md Appendix D are resolved towards their
     100 qualities whose payload fits the frame's budget, decoded, resized to H x 2H and only then stored: the server trains on what the decoder
     gives back, and ``*_bw_uplink.npy`` counts the payload bytes.  Budget rule: with ``--uplink_bw`` in kbit/s (added flag, default 200: a
     choice, not a measurement) an upload of n frames gives each floor(uplink_bw * 1000 / 8 * period / n) bytes, period = the upload period of
-    the loop in seconds.  The byte counts are this codec's, NOT H.264's: no inter-frame prediction, no byte parity.
+    the loop in seconds.  The byte counts are this codec's, NOT H.264's: no byte parity, and no inter-frame prediction unless
+    ``--uplink_gop`` asks for it.
     ``<results>_uplink_quality.npy`` has one row per upload: second, frames, bytes, budget per frame, min q, mean q, frames that did not fit;
+    ``--uplink_gop N`` (added flag, default 1 = all of the above unchanged): the frames of one upload travel as the reference's one clip per
+    upload does, frame k with k % N != 0 predicted from the decoded frame k - 1 where that is the better payload (format AUP1, motion search
+    on the device; the choice per frame is exact, from the sizes of both kinds), frame k of n at (upload bytes - spent) // (n - k) bytes; the
+    budget column stays the even split; ``<results>_uplink_kinds.npy``: per upload second, intra frames, inter frames, zero-length slices,
+    all slices;
 Out of scope (networking emulation / reporting): H.264 byte parity of the uplink, PNG-exact uplink byte counts without
 ``--compress_uplink`` (zlib-deflated frame size is logged instead), the matplotlib plots.
 Video comes from a ``FrameSource``: there is no OpenCV here (pictures are written by ``ams_amd.png``), so ``--input_video`` is either
@@ -85,6 +91,11 @@ def build_parser() -> argparse.ArgumentParser:
                    help="uplink: sampled frames travel at twice the network size through the lossy frame codec of ams_amd.uplink at the byte "
                         "budget --uplink_bw gives (needs a GPU and --height a multiple of 8); the server trains on the decoded frames and the "
                         "uplink is counted in payload bytes.  The reference's H.264 leg in mechanism, not in byte counts")
+    p.add_argument("--uplink_gop", type=int, default=1,
+                   help="--compress_uplink: within one upload, frame k with k %% N != 0 may travel predicted from the decoded frame k - 1 "
+                        "(format AUP1: motion search and residual on the device), chosen per frame against intra from the exact sizes; frame k "
+                        "of n gets (upload bytes - spent) // (n - k).  1 = every frame intra.  <results>_uplink_kinds.npy: per upload second, "
+                        "intra frames, inter frames, zero-length slices, all slices")
     p.add_argument("--uplink_bw", type=float, default=200.0,
                    help="--compress_uplink: the uplink's rate in kbit/s (extra flag; the reference reads an undefined flag of this name); an "
                         "upload of n frames gives each floor(uplink_bw * 1000 / 8 * upload period / n) bytes")
@@ -274,13 +285,33 @@ def uplink_budget(uplink_bw: float, period: int, n: int) -> int:
     return int(uplink_bw * 1000 / 8 * period // n)
 
 
-def _through_uplink(fr, codec, budget: int, size: List[int], ingest=None):
+def uplink_upload_bytes(uplink_bw: float, period: int) -> int:
+    """--uplink_gop > 1: the bytes of one upload, ``period`` seconds after the previous one; frame k of n gets (these - spent) // (n - k)."""
+    return int(uplink_bw * 1000 / 8 * period)
+
+
+def _through_uplink(fr, codec, budget: int, size: List[int], ingest=None, chain=None):
     """--compress_uplink: the sampled frame as the server receives it.  Resized to twice the network size, encoded at the budget and decoded on
     the device, resized to the network size by the same rule (both on the device with ``ingest``, else ``resize_linear`` on the host)
-    -> (frame, payload bytes, quality, fits)."""
+    -> (frame, payload bytes, quality, fits).
+
+    ``chain`` (--uplink_gop > 1) is the upload's state: under "reference" the decoded frame in front of this one, or None where this frame
+    must be intra; the call offers it to the encoder, leaves its own decoded frame there and appends (kind, zero-length slices, slices)
+    to "frames"."""
     H2, W2 = 2 * size[0], 2 * size[1]
     if fr.shape[:2] != (H2, W2):
         fr = ingest.frame(fr, H2, W2) if ingest is not None else resize_linear(_host(fr), W2, H2)
+    if chain is not None:
+        from .uplink import INTER, kind_of, table_lengths
+        reference = chain["reference"]
+        payload, quality, fits = codec.encode_to_budget(fr, budget, reference=reference)
+        kind = kind_of(payload)
+        decoded = codec.decode(payload, reference=reference) if kind == INTER else codec.decode(payload, (H2, W2))
+        lens = table_lengths(payload, H2, W2)
+        chain["reference"] = decoded
+        chain["frames"].append((kind, int((lens == 0).sum()), len(lens)))
+        fr = ingest.frame(decoded, size[0], size[1]) if ingest is not None else resize_linear(_host(decoded), size[1], size[0])
+        return fr, int(payload.numel()), quality, fits
     payload, quality, fits = codec.encode_to_budget(fr, budget)
     decoded = codec.decode(payload, (H2, W2))
     fr = ingest.frame(decoded, size[0], size[1]) if ingest is not None else resize_linear(_host(decoded), size[1], size[0])
@@ -367,6 +398,8 @@ def train_model(ctx: Context, train_start, train_end, sampling_period, gpu_id, r
         from .uplink import UplinkCodec
         uplink_codec = UplinkCodec("cuda:%s" % gpu_id)
     uplink_log = []           # --compress_uplink, per upload: (second, frames, bytes, budget per frame, min q, mean q, frames that did not fit)
+    uplink_gop = getattr(FLAGS, "uplink_gop", 1)
+    uplink_kinds = []         # --uplink_gop > 1, per upload: (second, intra frames, inter frames, zero-length slices, all slices)
     save_range = list(save_range)
     fps = ctx.source.fps
     train_end_frame = min(train_end * fps, len(ctx.source))
@@ -449,12 +482,22 @@ def train_model(ctx: Context, train_start, train_end, sampling_period, gpu_id, r
             size_images = 0.0
             budget = uplink_budget(FLAGS.uplink_bw, sample_send_period, len(frames_chosen)) if uplink_codec is not None and frames_chosen else 0
             sent = []         # --compress_uplink: (bytes, quality, fits) per frame of this upload
-            for fr, label in zip(frames_chosen, labels_chosen):
+            # --uplink_gop N > 1: within this upload frame k with k % N != 0 is offered the decoded frame k - 1; no reference crosses uploads
+            chain = dict(reference=None, frames=[]) if uplink_codec is not None and uplink_gop > 1 else None
+            upload_bytes = uplink_upload_bytes(FLAGS.uplink_bw, sample_send_period) if chain is not None else 0
+            for k, (fr, label) in enumerate(zip(frames_chosen, labels_chosen)):
                 logits = None
                 if soft_teacher:
                     label, index = label
                     logits = source_logits(ctx.source, index)
-                if uplink_codec is not None:
+                if chain is not None:
+                    if k % uplink_gop == 0:
+                        chain["reference"] = None
+                    # what prediction saved so far goes to the frames that follow
+                    fr, *info = _through_uplink(fr, uplink_codec, (upload_bytes - sum(n for n, _, _ in sent)) // (len(frames_chosen) - k), ctx.size,
+                                                ctx.ingest, chain)
+                    sent.append(info)
+                elif uplink_codec is not None:
                     # the frame goes through the lossy leg before anything else sees it; its label does not travel (the teacher is the server's)
                     fr, *info = _through_uplink(fr, uplink_codec, budget, ctx.size, ctx.ingest)
                     sent.append(info)
@@ -489,6 +532,10 @@ def train_model(ctx: Context, train_start, train_end, sampling_period, gpu_id, r
                 qs = [q for _, q, _ in sent]
                 uplink_log.append((second, len(sent), sum(n for n, _, _ in sent), budget, min(qs) if qs else np.nan,
                                    float(np.mean(qs)) if qs else np.nan, sum(1 for _, _, fits in sent if not fits)))
+            if chain is not None:
+                inter = sum(1 for kind, _, _ in chain["frames"] if kind == "AUP1")
+                uplink_kinds.append((second, len(chain["frames"]) - inter, inter, sum(z for _, z, _ in chain["frames"]),
+                                     sum(n for _, _, n in chain["frames"])))
 
         n_memory = len(device_memory) if device_memory is not None else len(frame_memory)
         if second in save_range and n_memory == 0:
@@ -586,6 +633,8 @@ def train_model(ctx: Context, train_start, train_end, sampling_period, gpu_id, r
     np.save(final_save_dir + '_control.npy', np.asarray(control_log, dtype=np.float64).reshape(-1, 5))
     if uplink_codec is not None:
         np.save(final_save_dir + '_uplink_quality.npy', np.asarray(uplink_log, dtype=np.float64).reshape(-1, 7))
+        if uplink_gop > 1:
+            np.save(final_save_dir + '_uplink_kinds.npy', np.asarray(uplink_kinds, dtype=np.float64).reshape(-1, 5))
     if weights_flag is not None:
         np.save(final_save_dir + '_loss_weights.npy', np.asarray(loss_weights_log, dtype=np.float32).reshape(-1, int(class_weights(exp_num).sum())))
     if mining_flag is not None:
@@ -788,6 +837,10 @@ def parse_flags(argv: Optional[List[str]] = None):
                                                                    if getattr(flags, name) is not None})
     if problem:
         parser.error(problem)
+    if flags.uplink_gop < 1:
+        parser.error("--uplink_gop must be at least 1 (got %d)" % flags.uplink_gop)
+    if flags.uplink_gop > 1 and not flags.compress_uplink:
+        parser.error("--uplink_gop needs --compress_uplink: predicted frames are a payload kind of the uplink frame codec")
     if flags.compress_uplink:
         import torch
         if not torch.cuda.is_available():

@@ -595,7 +595,9 @@ enum {
     AMS_UPLINK_BAD_ZERO_LEVEL = 5,  /* an AC level of 0 */
     AMS_UPLINK_BAD_LEVEL = 6,       /* |level| > 2047 (an Exp-Golomb prefix of more than 16 zero bits counts as one) */
     AMS_UPLINK_BAD_OVERRUN = 7,     /* a code runs past the end of its slice */
-    AMS_UPLINK_NO_ROOM = 8          /* encoder: the payload is larger than payload_cap; nothing was written */
+    AMS_UPLINK_NO_ROOM = 8,         /* encoder: the payload is larger than payload_cap; nothing was written */
+    AMS_UPLINK_BAD_VECTOR = 9,      /* AUP1: a vector component beyond +-15, or a 16 x 16 luma window that leaves the frame */
+    AMS_UPLINK_BAD_ZERO_SLICE = 10  /* AUP1: a slice of nothing but zero levels (a motion slice: zero vectors) sent with bytes */
 };
 /* Every ams_uplink_* entry refuses on the host, AMS_E_INVALID and nothing launched, in this order: H or W <= 0; H or W no multiple of 16
  * in 16 .. 4096 (the encoder: or q outside 1 .. 100); scratch NULL or below the entry's _scratch bytes; a null pointer; scratch
@@ -620,6 +622,57 @@ int ams_uplink_encode(void* scratch_dev, size_t scratch_bytes, int32_t H, int32_
  * [0, payload_bytes) is read.  Three launches: header, table and scan; one slice per thread into int16 levels; reconstruction. */
 int ams_uplink_decode(const uint8_t* payload_dev, int64_t payload_bytes, int32_t H, int32_t W, uint8_t* frame_out_dev, int32_t* status_dev,
                       void* scratch_dev, size_t scratch_bytes, void* stream);
+
+/* ---- the predicted frame of the uplink codec (k_uplink_inter.hip; run.py --uplink_gop), format AUP1: a frame coded as a prediction from a
+ * reference frame plus a residual.  Everything not stated here is AUC1's, above; tests/uplink_inter_ref.py restates both ends byte for byte.
+ *
+ * Reference: RGB uint8 [H, W, 3] of the frame's size, what the decoder produced for the previous frame (closed loop).  Both ends take it to
+ *   Y and 4:2:0 Cb, Cr with the AUC1 colour equations.
+ * Motion: one vector (dy, dx) per 16 x 16 macroblock (my, mx), full luma pels, each component in -15 .. 15.  Legal are the vectors whose
+ *   luma window lies in the frame: 0 <= y0 = 16 my + dy <= H - 16 and 0 <= x0 = 16 mx + dx <= W - 16.  Luma prediction: that window.
+ *   Chroma prediction: the 8 x 8 window of the reference's chroma plane at (8 my + (dy >> 1), 8 mx + (dx >> 1)) = (y0 >> 1, x0 >> 1); an odd
+ *   component averages each sample with its successor along that axis, (a + b + 1) >> 1; two odd components average the four,
+ *   (a + b + c + d + 2) >> 2.
+ *   Those reads stay in the plane for every legal luma vector: along y (x alike) the first row read is y0 >> 1 >= 0.  For an even y0 the
+ *   last is y0 / 2 + 7 <= (H - 16) / 2 + 7 = H / 2 - 1.  For an odd y0 it is (y0 - 1) / 2 + 8, and H - 16 is even, so y0 <= H - 17 and
+ *   the row is at most (H - 18) / 2 + 8 = H / 2 - 1.
+ * Residual: current - prediction per 8 x 8 block, without the - 128, through the AUC1 forward transform, tables, quality scale, level rule,
+ *   zig-zag and block code, DC prediction within a slice included.  |coefficient| <= 2047 holds for residuals in +-255: with A = the largest
+ *   row sum of |C| = 8 / sqrt(8) (row 0 and row 4; the others are smaller), the real coefficient is at most 255 A^2 = 2040, and the two
+ *   rounded passes add less than FWD_BOUND's terms at twice the range: 1/2 + A e_t / 8 + R1 (2048 A + e_t) / 65536 with e_t = 1/2 + 255 R1 /
+ *   1024, about 1.1 (tests/test_uplink_inter_ref_cpu.py computes it and runs the extremes).  So the level rule's numerator stays below 4096
+ *   and the coefficients fit int16.  The decoder adds the inverse transform, without the + 128, to the prediction and clamps to 0 .. 255.
+ * Slices: the motion slices come first, each 32 consecutive raster macroblocks (the last may be shorter): per macroblock se(dy - pdy)
+ *   se(dx - pdx) against the previous macroblock's vector in the slice, (0, 0) for its first, zero bits to a whole byte.  The Y, Cb, Cr
+ *   residual slices follow as AUC1 cuts them.  A table length of 0 means: every level of the slice is zero (a motion slice: every vector),
+ *   and no byte follows.  A slice of that content MUST be written so: the long form is refused, one frame has one payload.
+ * Payload: "AUP1", u16 H, u16 W, u8 q, three zero bytes, u32 total payload bytes; one u16 byte length per slice; the slices.
+ * Each decoder refuses the other kind's payload with AMS_UPLINK_BAD_HEADER.
+ *
+ * The encoder's choices (not the format's: the decoder takes any legal vector): an exhaustive search over the legal vectors for the least
+ *   SAD_luma + 128 [vector != 0]; ties go to the smaller |dy| + |dx|, then the smaller dy, then the smaller dx.
+ *
+ * The entries refuse on the host as the ams_uplink_* entries above do, in the same order; ref_dev is one of the pointers. */
+/* the largest payload: header + table + 208 bytes per block + 3 bytes per macroblock; 0 for a size the entries refuse */
+int64_t ams_uplink_inter_max_bytes(int32_t H, int32_t W);
+/* BYTES of device scratch of the encoder entries (transform, size_table, encode share one block) and of the decoder; 0 for a refused size */
+size_t ams_uplink_inter_encode_scratch(int32_t H, int32_t W);
+size_t ams_uplink_inter_decode_scratch(int32_t H, int32_t W);
+/* The motion search of frame_dev in ref_dev, then prediction and the residual's forward transform: vectors and int16 coefficients, zig-zag
+ * order per block, into the scratch (two launches). */
+int ams_uplink_inter_transform(const uint8_t* frame_dev, const uint8_t* ref_dev, int32_t H, int32_t W, void* scratch_dev, size_t scratch_bytes,
+                               void* stream);
+/* From what ams_uplink_inter_transform left in the scratch: sizes_dev[q - 1] (int64 x 100) = the exact AUP1 payload bytes at quality q; the
+ * (quality, slice) count of an all-zero slice is 0 (two launches). */
+int ams_uplink_inter_size_table(void* scratch_dev, size_t scratch_bytes, int32_t H, int32_t W, int64_t* sizes_dev, void* stream);
+/* Writes the AUP1 payload at quality q from the scratch; *bytes_dev, *status_dev and payload_cap as in ams_uplink_encode (three launches). */
+int ams_uplink_inter_encode(void* scratch_dev, size_t scratch_bytes, int32_t H, int32_t W, int32_t q, uint8_t* payload_dev, int64_t payload_cap,
+                            int64_t* bytes_dev, int32_t* status_dev, void* stream);
+/* Decodes an AUP1 payload against ref_dev (RGB uint8 [H, W, 3]) to RGB uint8 [H, W, 3].  Validated on the device, all or nothing, as
+ * ams_uplink_decode: the largest status of the malformed slices stands, frame_out_dev is written only under AMS_UPLINK_OK, and no byte outside
+ * the payload or the reference is read: the vectors are validated before the reconstruction reads through them (three launches). */
+int ams_uplink_inter_decode(const uint8_t* payload_dev, int64_t payload_bytes, const uint8_t* ref_dev, int32_t H, int32_t W, uint8_t* frame_out_dev,
+                            int32_t* status_dev, void* scratch_dev, size_t scratch_bytes, void* stream);
 
 /* ---- the server's replay memory on the device (replaces run.py:136-137 frame_memory / label_memory, two host deques, and the sampling of
  * utils/utils.py:129-185 mini_batch from them).  The memory is a ring of `capacity` slots the caller owns: slot p of the frames is uint8
