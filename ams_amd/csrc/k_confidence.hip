@@ -89,7 +89,7 @@ __global__ __launch_bounds__(256) void upsample_confidence_kernel(const float* _
             }
         }
         const float p = 1.f / ssum;                   // softmax of the largest logit: exp(zmax - zmax) / ssum
-        if (conf_u8) conf_u8[pix] = (uint8_t)rintf(p * 255.f);
+        if (conf_u8) conf_u8[pix] = p == p ? (uint8_t)rintf(p * 255.f) : (uint8_t)0;      // a NaN p is stored as 0 (no conversion of a NaN to an integer)
         if (conf_f32) conf_f32[pix] = p;
         if (!want_stats) continue;
         int bin = (int)(p * (float)kConfNB);

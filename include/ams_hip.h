@@ -1031,7 +1031,13 @@ size_t ams_k_global_mean_scratch(int32_t B, int32_t C);
 /* K9-K12: bilinear(align_corners) upsample of low-res logits to HxW fused with class gather, argmax and
  * (when teacher != NULL) confusion matrix + CE loss sums.  Full-resolution logits are never written.
  * conf_mat int64 [K*K] and loss double[2] are accumulators: the call zeroes both itself (on `stream`, in front of its kernel) — the caller
- * need not, and whatever they held is gone.  teacher == NULL: neither is touched. */
+ * need not, and whatever they held is gone.  teacher == NULL: neither is touched.
+ * The argmax is a strict `>` scan from class 0 in the order of class_idx_host over the K interpolated values: ties, and -0.0 against +0.0, take
+ * the lower index; a NaN wins only in class 0 (a NaN there keeps label 0, a NaN elsewhere is never the label).  ams_k_upsample_confidence and
+ * ams_k_upsample_soft_metric derive the same label, bit for bit.  A pixel whose teacher label is ignored (outside the subset) contributes
+ * nothing to conf_mat and loss, whatever its logits hold.  A valid pixel whose loss is not finite (a NaN or an infinite logit among its taps,
+ * a tap of weight 0 included) makes loss[0] non-finite; it is still counted in loss[1] and in conf_mat, under the label of the rule.  Frames
+ * do not affect each other's labels or counts.  The loss of a pixel enters loss[0] rounded to a multiple of 2^-20. */
 int ams_k_upsample_argmax(const float* logits /*[B,h,w,NC]*/, int32_t B, int32_t h, int32_t w, int32_t NC,
                           const int32_t* class_idx_host, int32_t K, int32_t H, int32_t W, const uint8_t* teacher,
                           int32_t* labels_out, int64_t* conf_mat, double* loss, void* stream);
@@ -1048,7 +1054,8 @@ int ams_k_upsample_argmax(const float* logits /*[B,h,w,NC]*/, int32_t B, int32_t
  *            whose argmax is the teacher's class, bin_sum their summed rint(p * 2^20); sel_cnt[k] the valid pixels whose teacher class OR
  *            argmax is k (once when both are), sel_sum[k] their summed rint(CE * 2^20).  All integers: a frame's row does not depend on the
  *            batch it is computed in.  A pixel whose logits hold a NaN is counted in bin 0 and adds 0 to bin_sum and sum_all; a pixel
- *            loss that is not finite is counted in sel_cnt and adds 0 to sel_sum. */
+ *            loss that is not finite is counted in sel_cnt and adds 0 to sel_sum.  Such a pixel's conf_f32 is a NaN and its conf_u8 is 0.
+ *            p == 1 (every other class underflows) is counted in the last bin.  A pixel the teacher ignores enters hist and sum_all alone. */
 #define AMS_CONFIDENCE_BINS 32
 int ams_k_upsample_confidence(const float* logits /*[B,h,w,NC]*/, int32_t B, int32_t h, int32_t w, int32_t NC,
                               const int32_t* class_idx_host, int32_t K, int32_t H, int32_t W, const uint8_t* teacher,
@@ -1085,7 +1092,10 @@ size_t ams_soft_metric_stats_len(int32_t K);    /* 2 + 2 K K; 0 for K outside 1.
 
 /* K11 backward: d loss / d low-res logits (zeros for unselected classes); loss_and_count_dev: the double[2]
  * written by ams_k_upsample_argmax ([1] = number of valid pixels, the mean's denominator).
- * class_idx_host (here and above): HOST array of the K selected class ids; it travels by value. */
+ * class_idx_host (here and above): HOST array of the K selected class ids; it travels by value.
+ * A pixel whose teacher label is ignored contributes nothing, whatever its logits hold (it is skipped, not multiplied by 0).  A valid pixel
+ * with a non-finite logit among its taps makes non-finite only the cells it is interpolated from: every other cell, every other frame
+ * among them, holds the bits it holds without that pixel. */
 int ams_k_ce_grad(const float* logits, int32_t B, int32_t h, int32_t w, int32_t NC, const int32_t* class_idx_host,
                   int32_t K, int32_t H, int32_t W, const uint8_t* teacher, const double* loss_and_count_dev,
                   float* dlogits, void* stream);
@@ -1094,7 +1104,12 @@ int ams_k_ce_grad(const float* logits, int32_t B, int32_t h, int32_t w, int32_t 
  * gradient): loss_dev[0] = CE sum over valid pixels, loss_dev[1] = their number, dlogits [B*h*w, NC] = d(mean CE) / d low-res
  * logits (zeros for unselected classes).  Every pixel's softmax is evaluated once; no atomics touch the gradient (run-to-run
  * identical).  scratch: >= ams_k_ce_loss_grad_scratch floats.  AMS_E_INVALID when one source column spans more than ~20 output
- * columns (callers then use ams_k_upsample_argmax + ams_k_ce_grad). */
+ * columns (callers then use ams_k_upsample_argmax + ams_k_ce_grad).
+ * Here and in the _soft, _kd, _weighted and _mined forms: a pixel whose teacher label is ignored contributes nothing to loss_dev or dlogits,
+ * whatever its logits hold (it is skipped, not multiplied by 0).  A valid pixel whose loss is not finite (a NaN or an infinite logit among its
+ * taps, a tap of weight 0 included) makes loss_dev[0] non-finite and is still counted in loss_dev[1]; it makes non-finite only the cells of
+ * dlogits that one of its four taps names: every other cell, every other frame among them, holds the bits it holds without that pixel.
+ * The loss of a pixel enters loss_dev[0] rounded to a multiple of 2^-20: a pixel loss below 2^-21 (a saturated, correct student) adds 0. */
 int ams_k_ce_loss_grad(const float* logits, int32_t B, int32_t h, int32_t w, int32_t NC, const int32_t* class_idx_host,
                        int32_t K, int32_t H, int32_t W, const uint8_t* teacher, double* loss_dev, float* dlogits,
                        float* scratch, size_t scratch_floats, void* stream);
